@@ -34,6 +34,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes written at most
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -195,8 +196,38 @@ def scene_setup(np, capi, synth, cfg_name, rank, local_rank, args, with_ekf, dow
     return cfg, world, lap, ctx, frames, host
 
 
+def dump_outputs(np, out_dir, ctx, slots, with_ekf):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 / float64 .npy files in out_dir.
+    det_*: the detections of the step's frames in stream order (det_count markers per frame; ids, corners, rvecs, tvecs
+    concatenated); with the EKF, ekf_frame_stats (per frame: markers, landmarks appended, corrections fused, stationary no-ops)
+    and the filter after the step: ekf_mu, ekf_landmark_ids and ekf_sigma, or a fixed seeded sample of Sigma's entries
+    (ekf_sigma_sample at the row-major flat indices ekf_sigma_sample_index) where the whole matrix would pass DUMP_LIMIT"""
+    dets = [ctx.get_slot_detections(s) for s in slots]
+    out = {"det_count": np.array([len(d[0]) for d in dets], np.float64),
+           "det_ids": np.concatenate([d[0] for d in dets]).astype(np.float64),
+           "det_corners": np.concatenate([d[1] for d in dets]).astype(np.float32),
+           "det_rvecs": np.concatenate([d[2] for d in dets]).astype(np.float64),
+           "det_tvecs": np.concatenate([d[3] for d in dets]).astype(np.float64)}
+    if with_ekf:
+        out["ekf_frame_stats"] = np.concatenate([ctx.get_slot_ekf_stats(s, 1) for s in slots]).astype(np.float64)
+        mu, sigma = ctx.get_state()
+        out["ekf_mu"] = mu.astype(np.float64)
+        out["ekf_landmark_ids"] = ctx.get_landmark_ids().astype(np.float64)
+        room = DUMP_LIMIT - sum(a.nbytes for a in out.values())
+        if sigma.nbytes <= room:
+            out["ekf_sigma"] = sigma.astype(np.float64)
+        else:
+            idx = np.sort(np.random.RandomState(0).choice(sigma.size, room // 16, replace=False))
+            out["ekf_sigma_sample_index"] = idx.astype(np.float64)
+            out["ekf_sigma_sample"] = sigma.reshape(-1)[idx].astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_config(mods, args, cfg_name, steps, warmup, batch, with_ekf, rank, local_rank, world_size, cpu_frames, want_gather,
-               detector="scene", qualify=True):
+               detector="scene", qualify=True, dump_dir=None):
     np, torch, dist, capi, synth, MapGather = mods
     cfg, world, lap, ctx, frames, host = scene_setup(np, capi, synth, cfg_name, rank, local_rank, args, with_ekf,
                                                      cpu_frames if rank == 0 else 0, detector=detector, qualify=qualify)
@@ -253,6 +284,8 @@ def run_config(mods, args, cfg_name, steps, warmup, batch, with_ekf, rank, local
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:               # the last timed step covered the B slots before `pos`
+        dump_outputs(np, dump_dir, ctx, [(pos[0] - B + i) % (2 * lap) for i in range(B)], with_ekf)
 
     # ---- every slot's last pass: M detections, M corrections fused, nothing appended, no stationary no-op
     plan = ctx.plan_stats() if with_ekf else None
@@ -429,7 +462,7 @@ def host_fed_rate(np, run, H=100):
     return out
 
 
-def cfg5_run(np, capi, synth, args, steps):
+def cfg5_run(np, capi, synth, args, steps, dump_dir=None):
     """BASELINE configs[4]: 64 x 640x480 frames per step, 4 markers each, detect + PnP only"""
     rows, cols, f, n = 480, 640, 450.0, 64
     K = synth.camera_matrix(rows, cols, f)
@@ -449,6 +482,8 @@ def cfg5_run(np, capi, synth, args, steps):
         ctx.run_staged((s & 1) * n, n, with_ekf=False)
     ctx.sync()
     el = time.perf_counter() - t0
+    if dump_dir is not None:
+        dump_outputs(np, dump_dir, ctx, [((steps - 1) & 1) * n + i for i in range(n)], False)
     found = sum(len(ctx.get_slot_detections(i)[0]) for i in range(2 * n))
     assert found == 2 * n * 4, f"cfg5: {found} of {2 * n * 4} markers found"
     ctx.profile_enable(True)
@@ -526,9 +561,13 @@ def main():
     ap.add_argument("--waves", type=int, default=0, help="wavefronts of the work-queue kernels (0 = library default)")
     ap.add_argument("--force-gather", action="store_true", help="run the (pipelined) map gather even with one rank (development check)")
     ap.add_argument("--reserve", type=int, default=0, help="CUs per XCD kept free of detection beside the EKF chain (0 = library default 16, <0 = off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step (rank 0) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--emu-check", action="store_true", help=argparse.SUPPRESS)   # tests/test_dist_gloo.py: launcher + rank plumbing on CPU
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker)
@@ -554,7 +593,7 @@ def main():
     if world > 1 or (args.force_gather and "RANK" in os.environ):
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
     if args.config == "cfg5":                      # BASELINE configs[4] on its own (profiling runs): detect + PnP only
-        r5, _, _ = cfg5_run(np, capi, synth, args, steps=args.steps)
+        r5, _, _ = cfg5_run(np, capi, synth, args, steps=args.steps, dump_dir=args.dump_outputs)
         print(json.dumps({"metric": "frames/s (detect+pose) cfg5", "value": r5["value"], "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
                           "warmup": 3, "ms_per_step": r5["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                           "dtype": "u8/f64", "data": "synthetic", "config": {"workload": r5["workload"], "asserted": r5["asserted"]},
@@ -565,7 +604,7 @@ def main():
 
     head, run = run_config(mods, args, args.config, args.steps, args.warmup, args.batch, with_ekf, rank, local_rank, world,
                            (max(args.cpu_sample, 400 if extras_on else 0) if args.cpu_sample > 0 else 0),
-                           want_gather=(world > 1 or args.force_gather))
+                           want_gather=(world > 1 or args.force_gather), dump_dir=args.dump_outputs)
     cpu = None
     extra = None
     if rank == 0 and args.cpu_sample > 0:

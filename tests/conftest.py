@@ -46,3 +46,11 @@ def pytest_collection_modifyitems(config, items):
 @pytest.fixture(scope="session")
 def on_emulation():
     return os.environ.get("ARUCO_SLAM_LIB") == EMU_LIB
+
+
+@pytest.fixture(scope="session")
+def emu_lib():
+    """the CPU emulation build, for tests that run it whatever library the session uses (a session on a GPU box does not
+    build it in pytest_configure)"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hipemu")])
+    return EMU_LIB

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE — a minimal, functional stand-in for the ROS 1 / OpenCV / tf2 / cv_bridge / image_transport headers
-// that include/aruco_slam/aruco_slam.h, include/aruco_slam/map_loader.h and the reference's own node source
-// (src/aruco_slam_node.cpp, compiled in place in the build container) use.  Not a ROS implementation: one process, no
+// that include/aruco_slam/aruco_slam.h, include/aruco_slam/map_loader.h and a node source such as
+// tests/cpp/node_harness.cpp use.  Not a ROS implementation: one process, no
 // transport.  `ros::spin()` replays a scripted scenario (directory named by $ASLAM_STUB_SCENARIO):
 //   params.txt   "<key> <value>" lines of the parameter server; "tf <target> <source> tx ty tz qx qy qz qw" transforms
 //   events.txt   "caminfo fx fy cx cy nD d0 .."  |  "enc <t> <wl> <wr>"  |  "img <t> <file> <rows> <cols> <channels>"

@@ -19,20 +19,27 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(aslam_[a-z_0-9]+)\s*\(", src)))
 
 
+def load_real():
+    """the gfx950 build, bound to the same HIP runtime as torch, as capi.load() binds it: a bare CDLL would map a second
+    runtime, and torch / RCCL later in the same session would find no device"""
+    capi._share_hip_runtime(REAL)
+    return ctypes.CDLL(REAL)
+
+
 def test_header_and_binding_agree():
     assert set(declared_symbols()) == set(capi.EXPORTED_SYMBOLS)
 
 
 @pytest.mark.skipif(not os.path.exists(REAL), reason="library not built (run __graft_entry__.build())")
 def test_library_exports_every_declared_symbol():
-    lib = ctypes.CDLL(REAL)
+    lib = load_real()
     for name in declared_symbols():
         assert hasattr(lib, name), f"{name} missing from libaruco_slam_hip.so"
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd") or not os.path.exists(REAL), reason="only meaningful without a GPU")
 def test_create_fails_loudly_without_a_device():
-    lib = ctypes.CDLL(REAL)
+    lib = load_real()
     lib.aslam_default_init.argtypes = [ctypes.POINTER(capi.AslamInit)]
     lib.aslam_create.argtypes = [ctypes.POINTER(capi.AslamInit), ctypes.POINTER(ctypes.c_void_p)]
     init = capi.AslamInit()

@@ -17,12 +17,12 @@ def test_two_rank_map_gather_gloo():
     assert "rank 0 ok" in r.stdout and "rank 1 ok" in r.stdout
 
 
-def test_bench_launcher_starts_n_ranks():
+def test_bench_launcher_starts_n_ranks(emu_lib):
     """`python bench.py --gpus 2` with no torchrun environment must start the two ranks itself (BASELINE config 4 is driven
     that way); rehearsed on the CPU emulation build with gloo through the hidden --emu-check mode of the very same launcher"""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    env["ARUCO_SLAM_LIB"] = os.path.join(ROOT, "tests", "hipemu", "_build", "libaruco_slam_emu.so")
+    env["ARUCO_SLAM_LIB"] = emu_lib
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--emu-check"], env=env,
                        capture_output=True, text=True, timeout=600)

@@ -1,13 +1,8 @@
 """The drop-in boundary as a ROS node would use it (SURVEY §8 b, f1): include/aruco_slam/aruco_slam.h keeps the reference's
-class surface signature for signature, so
-
-  * tests/cpp/node_harness.cpp (our own node-shaped driver) and
-  * the reference's OWN node source, /root/reference/src/aruco_slam_node.cpp, compiled IN PLACE and unchanged (build
-    container only: the reference does not travel to the GPU box and is never copied)
-
-are compiled against that header plus the scripted single-process ROS stand-in of tests/ros_stubs, linked with the library
-(the gfx950 build on a GPU box, the CPU emulation build here), run over a synthetic scenario, and everything they publish
-(pose, detected_markers, detected_map, real_map, marked image) is compared with the ctypes path on the same inputs."""
+class surface signature for signature, so tests/cpp/node_harness.cpp (our own node-shaped driver) is compiled against that
+header plus the scripted single-process ROS stand-in of tests/ros_stubs, linked with the library (the gfx950 build on a GPU
+box, the CPU emulation build here), run over a synthetic scenario, and everything it publishes (pose, detected_markers,
+detected_map, real_map, marked image) is compared with the ctypes path on the same inputs."""
 import os
 import subprocess
 
@@ -17,7 +12,6 @@ import pytest
 from aruco_slam_amd import capi, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_NODE = "/root/reference/src/aruco_slam_node.cpp"
 ROWS, COLS, F = 240, 320, 225.0
 R2C = (0.18, -0.1, 0.05, 0.5, -0.5, 0.5, -0.5)          # base_link <- camera_optical: translation, quaternion (x, y, z, w)
 
@@ -143,10 +137,3 @@ def test_harness_node_on_the_device(tmp_path):
     """the same C++ program linked with -laruco_slam_hip on the MI355X box"""
     assert capi.lib_path().endswith("libaruco_slam_hip.so")
     _dropin(tmp_path, os.path.join(ROOT, "tests", "cpp", "node_harness.cpp"), "harness/gpu")
-
-
-@pytest.mark.skipif(not os.path.exists(REF_NODE), reason="the reference checkout exists only in the build container")
-def test_reference_node_source_compiles_unchanged_and_runs(tmp_path):
-    """src/aruco_slam_node.cpp of the reference, in place and unmodified, against include/aruco_slam/{aruco_slam,map_loader}.h"""
-    _dropin(tmp_path, REF_NODE, "reference node")
-
