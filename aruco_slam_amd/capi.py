@@ -65,6 +65,28 @@ class DetectorParams(C.Structure):
     ]
 
 
+MAX_CAMERAS = 8
+
+
+class Camera(C.Structure):
+    """mirror of aslam_camera: one camera of a rig (K row-major, plumb-bob D, planar mount in base_link)"""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 5), ("nD", C.c_int), ("pad", C.c_int),
+                ("mount_x", C.c_double), ("mount_y", C.c_double), ("mount_yaw", C.c_double)]
+
+    @classmethod
+    def make(cls, K, D=None, mount=(0.0, 0.0, 0.0)):
+        c = cls()
+        K = np.asarray(K, np.float64).reshape(9)
+        D = np.zeros(0) if D is None else np.asarray(D, np.float64).reshape(-1)
+        for i in range(9):
+            c.K[i] = K[i]
+        for i in range(min(D.size, 5)):
+            c.D[i] = D[i]
+        c.nD = int(D.size)
+        c.mount_x, c.mount_y, c.mount_yaw = (float(v) for v in mount)
+        return c
+
+
 class PoseMsg(C.Structure):
     _fields_ = [("position", C.c_double * 3), ("orientation", C.c_double * 4), ("covariance", C.c_double * 36)]
 
@@ -121,6 +143,11 @@ _SIGS = {
     "aslam_get_slot_detections": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _fp, _dp, _dp]),
     "aslam_get_slot_raw_observations": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _dp, _dp]),
     "aslam_get_slot_ekf_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
+    "aslam_set_camera_rig": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "aslam_add_images": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_void_p), C.c_int, C.c_int, C.c_int, _P(C.c_size_t)]),
+    "aslam_run_staged_rig": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "aslam_get_rig_observations": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _ip, _ip, _dp, _dp]),
+    "aslam_get_rig_step_ekf_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
     "aslam_detect_batch": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                      C.c_int, _ip, _ip, _fp, _dp, _dp]),
     "aslam_export_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -202,7 +229,8 @@ def default_init(**over):
 
 
 class Context:
-    """One camera stream: thin RAII wrapper over aslam_ctx (mirrors the `ArucoSlam` class surface)."""
+    """One filter fed by one camera stream (set_camera) or by a camera rig (set_camera_rig): thin RAII wrapper over aslam_ctx
+    (mirrors the `ArucoSlam` class surface)."""
 
     def __init__(self, init=None, **over):
         self.lib = load()
@@ -408,6 +436,45 @@ class Context:
     def run_staged(self, first, count, with_ekf=True):
         """with_ekf: False/0 detection + pose only, True/1 full path, 2 EKF steps only (injected observations)"""
         self._ck(self.lib.aslam_run_staged(self.h, int(first), int(count), int(with_ekf)))
+
+    # -- camera rig: C cameras, one EKF step per rig step ---------------------------------------------
+    def set_camera_rig(self, cams):
+        """cams: Camera structs, or (K, D, (mount_x, mount_y, mount_yaw)) tuples"""
+        cams = [c if isinstance(c, Camera) else Camera.make(*c) for c in cams]
+        arr = (Camera * max(len(cams), 1))(*cams)
+        self._ck(self.lib.aslam_set_camera_rig(self.h, len(cams), arr))
+
+    def add_images(self, imgs):
+        """one rig step: one image per camera (all of one size), after the step's add_encoder"""
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise ValueError("the images of a rig step must all have the same size and channels")
+        rows, cols = imgs[0].shape[:2]
+        ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
+        ptrs = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        steps = (C.c_size_t * len(imgs))(*[im.strides[0] for im in imgs])
+        self._ck(self.lib.aslam_add_images(self.h, len(imgs), ptrs, rows, cols, ch, steps))
+
+    def run_staged_rig(self, first, n_steps, with_ekf=True):
+        """n_steps rig steps from slot `first`: slot first + s * C + c holds camera c's frame of step s"""
+        self._ck(self.lib.aslam_run_staged_rig(self.h, int(first), int(n_steps), int(with_ekf)))
+
+    def get_rig_observations(self):
+        """get_observations of the last rig step plus the camera of each popped observation: ids, idx, action, cam, xyth, Rdiag"""
+        n = C.c_int()
+        ids = np.zeros(MARKER_MAX, np.int32); idx = np.zeros(MARKER_MAX, np.int32); act = np.zeros(MARKER_MAX, np.int32)
+        cam = np.zeros(MARKER_MAX, np.int32); xyth = np.zeros((MARKER_MAX, 3)); R = np.zeros((MARKER_MAX, 3))
+        self._ck(self.lib.aslam_get_rig_observations(self.h, C.byref(n), _ptr(ids, _ip), _ptr(idx, _ip), _ptr(act, _ip), _ptr(cam, _ip),
+                                                     _ptr(xyth, _dp), _ptr(R, _dp)))
+        k = n.value
+        return ids[:k].copy(), idx[:k].copy(), act[:k].copy(), cam[:k].copy(), xyth[:k].copy(), R[:k].copy()
+
+    def get_rig_step_ekf_stats(self, first, count):
+        """count x 4 ints per rig step (step s of a call from slot `first` is step first + s): markers detected over all cameras,
+        landmarks appended, corrections fused, stationary no-ops"""
+        st = np.zeros((int(count), 4), np.int32)
+        self._ck(self.lib.aslam_get_rig_step_ekf_stats(self.h, int(first), int(count), _ptr(st, _ip)))
+        return st
 
     def inject_observations(self, slot, ids, valid, xyth, Rdiag):
         ids = np.ascontiguousarray(ids, dtype=np.int32); valid = np.ascontiguousarray(valid, dtype=np.int32)

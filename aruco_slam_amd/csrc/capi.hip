@@ -60,6 +60,15 @@ struct aslam_ctx {
     bool have_cam = false;
     CamParams cam{};
     SlamParams sp{};
+    // camera rig (aslam_set_camera_rig): the rig calls detect C frames per step and run one EKF step on the merged list.  The EKF
+    // works on slots [0, 2 max_batch): frame slots below max_batch, and the merged list of step s of a rig call that started at frame
+    // slot `first` at slot max_batch + first + s (its inputs: d_obs / d_nmarkers / d_enc / h_obs / h_nm / enc_host there)
+    int rig_n = 0;
+    PoseCams rig{};
+    bool rig_last = false;                // the last detection / EKF call was a rig call
+    int rig_last_slot0 = 0, rig_last_n = 0;   // frame slot of camera 0 of its last step, cameras
+    int merge_lo = 0, merge_hi = 0;       // frame slots the last merge read (its encoder samples, lists)
+    std::vector<unsigned long long> slot_shape;   // per frame slot: rows, cols, channels it was staged with (rig steps must agree)
 
     // staged batch
     int rows = 0, cols = 0, channels = 0;
@@ -288,6 +297,12 @@ int configure_frames(aslam_ctx* c, int rows, int cols, int channels) {
     return ASLAM_OK;
 }
 
+unsigned long long frame_shape(const aslam_ctx* c) { return ((unsigned long long)c->rows << 32) | ((unsigned long long)c->cols << 8) | (unsigned)c->channels; }
+void note_slot_shape(aslam_ctx* c, int slot0, int n) {
+    c->slot_shape.resize(c->max_batch, 0ull);
+    for (int i = slot0; i < slot0 + n; i++) c->slot_shape[i] = frame_shape(c);
+}
+
 int check_slot_range(aslam_ctx* c, int first, int count) {
     if (first < 0 || count <= 0 || first + count > c->max_batch) return fail(c, ASLAM_E_INVALID, "slot range outside [0, max_batch)");
     return ASLAM_OK;
@@ -306,13 +321,30 @@ int quiesce_slots(aslam_ctx* c, int slot0, int n) {
         c->ekf_count = 0;
     }
     if (c->last_detect && slot0 < c->last_first + c->last_count && c->last_first < slot0 + n) HIP_TRY(c, hipEventSynchronize(c->ev_detect));
+    if (c->merge_hi > c->merge_lo && slot0 < c->merge_hi && c->merge_lo < slot0 + n) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_detect));     // a rig merge still reads these slots' lists / encoder samples
+        c->merge_hi = c->merge_lo;
+    }
     return ASLAM_OK;
 }
 
-// detection + pose for `count` staged frames starting at slot `first` (asynchronous on the stream)
-int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipEvent_t wait_before = nullptr) {
+// the single-camera configuration as a camera table: aslam_set_camera's intrinsics, mounted at (r2c.x, r2c.y) looking forward
+PoseCams single_camera(const aslam_ctx* c) {
+    PoseCams pc{};
+    pc.n = 1;
+    pc.e[0].cam = c->cam;
+    pc.e[0].mx = c->sp.r2c_tx; pc.e[0].my = c->sp.r2c_ty;
+    pc.e[0].cpsi = 1.0; pc.e[0].spsi = 0.0; pc.e[0].psi = 0.0;
+    return pc;
+}
+
+// detection + pose for `count` staged frames starting at slot `first` (asynchronous on the stream).  rig: frame first + i is camera
+// i % rig->n of the rig (nullptr: the single camera); latency: the configuration of a one-frame call (one rig step)
+int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipEvent_t wait_before = nullptr, const PoseCams* rig = nullptr,
+               bool latency = false) {
     if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
-    if (!c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    if (!rig && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    PoseCams cams = rig ? *rig : single_camera(c);
     // the CU-masked stream only pays off while an EKF chain is actually in flight beside this detection; the first batch after
     // a synchronisation gets the whole GPU
     hipStream_t st = (beside_ekf && c->stream_part && (c->ekf_count > 0 || c->pend.active)) ? c->stream_part : c->stream;
@@ -322,7 +354,7 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
     DetectCfg g = c->cfg;
     // one frame (the drop-in call): a finer cut lattice - its longest segment sets the latency of k_seg / k_trace_write, and the extra nodes
     // (x 1.6) still fit k_link's LDS image for frames up to a megapixel or so
-    g.cut_mask = (count == 1 && (size_t)g.rows * g.cols <= (size_t)1200 * 1000 ? kCutGridSingle : kCutGrid) - 1;
+    g.cut_mask = ((count == 1 || latency) && (size_t)g.rows * g.cols <= (size_t)1200 * 1000 ? kCutGridSingle : kCutGrid) - 1;
     const size_t frame_px = (size_t)g.rows * g.cols;
     const bool alias_gray = c->channels == 1;              // staged gray frames are tight: the detector reads them in place
     c->last_first = first;
@@ -379,8 +411,9 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
         launch_identify(st, c->nwaves, g, c->d_ctr, gray, c->d_finals + (size_t)f0 * kCandMax, c->d_work, c->d_dict);
         prof_end(c);
         prof_begin(c, P_POSE, st);
+        cams.cam0 = (f0 - first) % cams.n;
         launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
-                    c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, c->cam, c->sp, c->d_ctr,
+                    c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr,
                     RefineCfg{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
                               g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
                               c->d_refine_mask, gray});
@@ -474,6 +507,13 @@ int sync_and_check(aslam_ctx* c) {
         snprintf(buf, sizeof(buf), "device list overflow (mask 0x%x: 1 starts, 2 contours, 4 points, 8 candidates, 16 markers, 32 landmarks, 64 fused updates > max_updates_per_frame)", h.overflow);
         return fail(c, ASLAM_E_CAPACITY, buf);
     }
+    return ASLAM_OK;
+}
+
+// the four per-step counts k_ekf_plan / the window chain left at EKF slots [slot, slot + count)
+int read_ekf_stats(aslam_ctx* c, int slot, int count, int* stats) {
+    { int rs = sync_streams(c); if (rs) return rs; }
+    HIP_TRY(c, hipMemcpy(stats, c->ekf.d_slot_stat + (size_t)4 * slot, sizeof(int) * 4 * count, hipMemcpyDeviceToHost));
     return ASLAM_OK;
 }
 
@@ -578,9 +618,9 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
     ok = ok && dalloc(&c->d_nfinal, B) == hipSuccess;
     ok = ok && dalloc(&c->d_work, (size_t)kCandMax * B) == hipSuccess;
     ok = ok && dalloc(&c->d_markers, (size_t)kMarkerMax * B) == hipSuccess;
-    ok = ok && dalloc(&c->d_nmarkers, B) == hipSuccess;
-    ok = ok && dalloc(&c->d_obs, (size_t)kMarkerMax * B) == hipSuccess;
-    ok = ok && dalloc(&c->d_enc, (size_t)3 * B) == hipSuccess;
+    ok = ok && dalloc(&c->d_nmarkers, 2 * B) == hipSuccess;              // frame slots, then the rig steps' merged lists
+    ok = ok && dalloc(&c->d_obs, (size_t)kMarkerMax * 2 * B) == hipSuccess;
+    ok = ok && dalloc(&c->d_enc, (size_t)3 * 2 * B) == hipSuccess;
     ok = ok && dalloc(&c->d_synth, 256) == hipSuccess;
     std::vector<unsigned long long> codes;
     aslam_default_detector_params(&c->dp);
@@ -591,19 +631,19 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
     ok = ok && hipMemset(c->d_nstarts, 0, sizeof(unsigned) * B) == hipSuccess;
     ok = ok && hipMemset(c->d_ncontours, 0, sizeof(unsigned) * B) == hipSuccess;
     ok = ok && hipMemset(c->d_npoints, 0, sizeof(unsigned) * B) == hipSuccess;
-    ok = ok && hipMemset(c->d_nmarkers, 0, sizeof(unsigned) * B) == hipSuccess;
+    ok = ok && hipMemset(c->d_nmarkers, 0, sizeof(unsigned) * 2 * B) == hipSuccess;
     ok = ok && hipMemset(c->d_nfinal, 0, sizeof(unsigned) * B) == hipSuccess;
     ok = ok && hipMemset(c->d_ncand, 0, sizeof(unsigned) * B) == hipSuccess;
-    ok = ok && hipMemset(c->d_enc, 0, sizeof(double) * 3 * B) == hipSuccess;
-    ok = ok && ekf_alloc(c->ekf, init->max_landmarks, init->max_batch, init->max_updates_per_frame) == hipSuccess;
+    ok = ok && hipMemset(c->d_enc, 0, sizeof(double) * 3 * 2 * B) == hipSuccess;
+    ok = ok && ekf_alloc(c->ekf, init->max_landmarks, 2 * init->max_batch, init->max_updates_per_frame) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_obs[0], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_obs[1], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_idx, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipStreamCreateWithPriority(&c->stream_win, hipStreamNonBlocking, prio_hi) == hipSuccess;
     for (int i = 0; i < 64; i++) ok = ok && hipEventCreateWithFlags(&c->ev_win[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_obs), (size_t)B * kMarkerMax * sizeof(ObsRaw), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_nm), (size_t)B * sizeof(unsigned), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_win_frames), (size_t)B * sizeof(WinFrame), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_obs), (size_t)2 * B * kMarkerMax * sizeof(ObsRaw), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_nm), (size_t)2 * B * sizeof(unsigned), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_win_frames), (size_t)2 * B * sizeof(WinFrame), hipHostMallocDefault) == hipSuccess;
     if (!ok) { aslam_destroy(c); return ASLAM_E_NO_DEVICE; }
     *out = c;
     return ASLAM_OK;
@@ -668,6 +708,7 @@ int aslam_stage_frames(aslam_ctx* c, int slot0, const uint8_t* frames, int nfram
     r = quiesce_slots(c, slot0, nframes);
     if (r) return r;
     c->in_frame_bytes = (size_t)rows * cols * channels;
+    note_slot_shape(c, slot0, nframes);
     const bool tight = step == (size_t)cols * channels;        // (a plain copy for tight rows: the 2-D path goes row by row for pageable memory)
     if (tight && (nframes == 1 || frame_stride == c->in_frame_bytes)) {
         HIP_TRY(c, hipMemcpyAsync(c->d_in + (size_t)slot0 * c->in_frame_bytes, frames, c->in_frame_bytes * nframes, hipMemcpyHostToDevice, c->stream));
@@ -695,7 +736,7 @@ int aslam_stage_encoders(aslam_ctx* c, int slot0, int n, const double* wl, const
     std::vector<double> h((size_t)3 * n);
     for (int i = 0; i < n; i++) { h[3 * i] = wl[i]; h[3 * i + 1] = wr[i]; h[3 * i + 2] = dt[i]; }
     HIP_TRY(c, hipMemcpy(c->d_enc + (size_t)3 * slot0, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    c->enc_host.resize((size_t)3 * c->max_batch);
+    c->enc_host.resize((size_t)3 * 2 * c->max_batch);
     std::memcpy(&c->enc_host[(size_t)3 * slot0], h.data(), h.size() * sizeof(double));
     return ASLAM_OK;
 }
@@ -998,6 +1039,8 @@ int finalize_pending(aslam_ctx* c) {
     return ASLAM_OK;
 }
 
+int schedule_ekf(aslam_ctx* c, int first, int count);
+
 int run_staged(aslam_ctx* c, int first, int count, int with_ekf, hipEvent_t wait_before) {
     int r = check_slot_range(c, first, count);
     if (r) return r;
@@ -1014,7 +1057,14 @@ int run_staged(aslam_ctx* c, int first, int count, int with_ekf, hipEvent_t wait
         c->last_detect = c->stream;
         HIP_TRY(c, hipEventRecord(c->ev_detect, c->stream));
     }
+    c->rig_last = false;
     if (!with_ekf) return ASLAM_OK;
+    return schedule_ekf(c, first, count);
+}
+
+// the EKF steps of EKF slots [first, first + count) (frames, or rig steps' merged lists), behind the detection that produced them
+int schedule_ekf(aslam_ctx* c, int first, int count) {
+    int r = ASLAM_OK;
     if (!c->win_enabled) {                     // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
@@ -1050,6 +1100,152 @@ int aslam_run_staged(aslam_ctx* c, int first, int count, int with_ekf) {
     return run_staged(c, first, count, with_ekf, nullptr);
 }
 
+// ---- camera rig (include/aruco_slam_hip.h): C frames per step, one batched detection pass, one EKF step per rig step ---------
+int aslam_set_camera_rig(aslam_ctx* c, int n_cams, const aslam_camera* cams) {
+    if (!c) return ASLAM_E_INVALID;
+    if (n_cams < 1 || n_cams > ASLAM_MAX_CAMERAS || !cams) return fail(c, ASLAM_E_INVALID, "a rig has 1..ASLAM_MAX_CAMERAS cameras");
+    if (n_cams > c->max_batch) return fail(c, ASLAM_E_INVALID, "a rig step (one frame per camera) must fit into max_batch slots");
+    const double PI = 3.14159265358979323846;
+    PoseCams pc{};
+    pc.n = n_cams;
+    for (int k = 0; k < n_cams; k++) {
+        const aslam_camera& a = cams[k];
+        if (a.nD < 0 || a.nD > 5) return fail(c, ASLAM_E_INVALID, "camera distortion: 0..5 plumb-bob coefficients");
+        if (!(a.mount_yaw > -PI && a.mount_yaw <= PI) || !std::isfinite(a.mount_x) || !std::isfinite(a.mount_y))
+            return fail(c, ASLAM_E_INVALID, "camera mount: finite (x, y) and a heading in (-pi, pi]");
+        RigCam& e = pc.e[k];
+        e.cam.fx = a.K[0]; e.cam.fy = a.K[4]; e.cam.cx = a.K[2]; e.cam.cy = a.K[5];
+        e.cam.nD = a.nD;
+        for (int i = 0; i < 5; i++) e.cam.k[i] = i < a.nD ? a.D[i] : 0.0;
+        e.mx = a.mount_x; e.my = a.mount_y;
+        e.psi = a.mount_yaw; e.cpsi = std::cos(a.mount_yaw); e.spsi = std::sin(a.mount_yaw);
+    }
+    c->rig = pc;                               // taken by value at every launch: batches already submitted keep their cameras
+    c->rig_n = n_cams;
+    return ASLAM_OK;
+}
+
+namespace {
+// the EKF slot of rig step s of a call whose frames start at slot `first`
+int rig_step_slot(const aslam_ctx* c, int first, int s) { return c->max_batch + first + s; }
+
+// observation lists of n_steps rig steps (frames from slot `first`) merged into their step slots, behind the detection on its stream
+int merge_rig_steps(aslam_ctx* c, int first, int n_steps) {
+    const int C = c->rig_n, e0 = rig_step_slot(c, first, 0);
+    hipStream_t st = c->last_detect ? c->last_detect : c->stream;
+    if (c->ekf_count > 0 && e0 < c->ekf_hi && c->ekf_lo < e0 + n_steps) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));   // EKF work in flight still reads these step lists
+    launch_rig_merge(st, n_steps, c->d_obs, c->d_nmarkers, c->d_enc, first, C, e0, c->d_ctr);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_detect, st));
+    c->last_detect = st;
+    c->merge_lo = first; c->merge_hi = first + n_steps * C;
+    c->enc_host.resize((size_t)3 * 2 * c->max_batch);
+    for (int s = 0; s < n_steps; s++)
+        std::memcpy(&c->enc_host[(size_t)3 * (e0 + s)], &c->enc_host[(size_t)3 * (first + s * C)], 3 * sizeof(double));
+    c->rig_last_slot0 = first + (n_steps - 1) * C;
+    c->rig_last_n = C;
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_add_images(aslam_ctx* c, int n_cams, const uint8_t* const* px, int rows, int cols, int channels, const size_t* step) {
+    if (!c || !px || !step) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->rig_n == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
+    if (n_cams != c->rig_n) return fail(c, ASLAM_E_INVALID, "one image per camera of the rig");
+    for (int k = 0; k < n_cams; k++) if (!px[k]) return fail(c, ASLAM_E_INVALID, "null image");
+    int r = finalize_pending(c);
+    if (r) return r;
+    if (!c->is_init) return ASLAM_OK;        // aruco_slam.cpp:84-85: nothing happens before the first encoder message
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    c->mirror_dirty = true;                  // planned on the device: the host's copy of the tables is stale afterwards
+    for (int k = 0; k < n_cams; k++) {
+        r = aslam_stage_frames(c, k, px[k], 1, rows, cols, channels, step[k], 0);
+        if (r) return r;
+    }
+    const auto t1 = clk::now();
+    r = run_detect(c, 0, n_cams, false, nullptr, &c->rig, true);      // one batched pass over the step's frames, latency configuration
+    if (r) return r;
+    c->rig_last = true;
+    r = merge_rig_steps(c, 0, 1);
+    if (r) return r;
+    const auto t2 = clk::now();
+    HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+    r = run_ekf_frame(c, rig_step_slot(c, 0, 0), 0, 0, 0, false);     // the prediction came with aslam_add_encoder
+    if (r) return r;
+    const auto t3 = clk::now();
+    r = sync_streams(c);
+    const auto t4 = clk::now();
+    if (!r) r = sync_and_check(c);
+    const auto t5 = clk::now();
+    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
+    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
+    return r;
+}
+
+int aslam_run_staged_rig(aslam_ctx* c, int first, int n_steps, int with_ekf) {
+    if (!c) return ASLAM_E_INVALID;
+    const int C = c->rig_n;
+    if (C == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
+    if (n_steps <= 0) return fail(c, ASLAM_E_INVALID, "at least one rig step");
+    const int count = n_steps * C;
+    int r = check_slot_range(c, first, count);
+    if (r) return r;
+    if (with_ekf && c->enc_host.size() < (size_t)3 * (first + count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
+    if (with_ekf != 2) {
+        for (int i = first; i < first + count; i++)
+            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+                return fail(c, ASLAM_E_INVALID, "the frames of a rig call must all be staged with the same rows, cols and channels");
+    }
+    const int e0 = rig_step_slot(c, first, 0);
+    if (c->pend.active && ((first < c->pend.first + c->pend.count && c->pend.first < first + count) ||
+                           (e0 < c->pend.first + c->pend.count && c->pend.first < e0 + n_steps))) {
+        r = finalize_pending(c);               // the pending batch still needs the observations in these slots
+        if (r) return r;
+    }
+    if (with_ekf != 2) {
+        r = run_detect(c, first, count, with_ekf == 1, nullptr, &c->rig, n_steps == 1);
+        if (r) return r;
+    } else {
+        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
+        c->last_detect = c->stream;
+    }
+    c->rig_last = true;
+    c->rig_last_slot0 = first + (n_steps - 1) * C;
+    c->rig_last_n = C;
+    if (!with_ekf) return ASLAM_OK;
+    r = merge_rig_steps(c, first, n_steps);
+    if (r) return r;
+    return schedule_ekf(c, e0, n_steps);
+}
+
+int aslam_get_rig_observations(aslam_ctx* c, int* n_out, int* ids, int* idx, int* action, int* cam, double* xyth, double* Rdiag) {
+    if (!c || !n_out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was not a camera-rig call");
+    int r = aslam_get_observations(c, n_out, ids, idx, action, xyth, Rdiag);
+    if (r || !cam) return r;
+    // camera of every popped observation: its position in the step's merged list against the per-camera list sizes
+    const int n = *n_out, C = c->rig_last_n;
+    std::vector<PopRec> h(std::max(n, 1));
+    if (n) HIP_TRY(c, hipMemcpy(h.data(), c->ekf.d_pop, n * sizeof(PopRec), hipMemcpyDeviceToHost));
+    std::vector<unsigned> nm(C);
+    HIP_TRY(c, hipMemcpy(nm.data(), c->d_nmarkers + c->rig_last_slot0, C * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        int k = 0, end = (int)std::min(nm[0], (unsigned)kMarkerMax);
+        while (k + 1 < C && h[i].det >= end) end += (int)std::min(nm[++k], (unsigned)kMarkerMax);
+        cam[i] = k;
+    }
+    return ASLAM_OK;
+}
+
+int aslam_get_rig_step_ekf_stats(aslam_ctx* c, int first_step, int count, int* stats) {
+    if (!c || !stats) return fail(c, ASLAM_E_INVALID, "null argument");
+    int r = check_slot_range(c, first_step, count);
+    if (r) return r;
+    return read_ekf_stats(c, rig_step_slot(c, first_step, 0), count, stats);
+}
+
 // ---- host-fed stream: pinned ring, asynchronous upload (include/aruco_slam_hip.h) --------------------------------------
 int ring_submit(aslam_ctx* c) {
     const int n = c->ring_fill, h = c->ring_half, H = c->ring_H;
@@ -1065,7 +1261,7 @@ int ring_submit(aslam_ctx* c) {
     HIP_TRY(c, hipMemcpyAsync(c->d_in + (size_t)slot0 * fb, c->h_ring + (size_t)slot0 * fb, (size_t)n * fb, hipMemcpyHostToDevice, c->stream_copy));
     HIP_TRY(c, hipEventRecord(c->ev_up[h], c->stream_copy));
     c->ev_up_set[h] = true;
-    c->enc_host.resize((size_t)3 * c->max_batch);
+    c->enc_host.resize((size_t)3 * 2 * c->max_batch);
     std::memcpy(&c->enc_host[(size_t)3 * slot0], c->ring_enc.data(), (size_t)3 * n * sizeof(double));
     int r = run_staged(c, slot0, n, 1, c->ev_up[h]);
     if (r) return r;
@@ -1263,6 +1459,7 @@ int aslam_add_image(aslam_ctx* c, const uint8_t* px, int rows, int cols, int cha
     r = run_detect(c, 0, 1);
     if (r) return r;
     const auto t2 = clk::now();
+    c->rig_last = false;
     HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
     r = run_ekf_frame(c, 0, 0, 0, 0, false);
     if (r) return r;
@@ -1425,6 +1622,7 @@ int aslam_get_map_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) 
 
 int aslam_get_detected_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) {   // detected_markers_, aruco_slam.cpp:325-347
     if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: detected-marker messages describe one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
     if (r) return r;
@@ -1475,6 +1673,7 @@ void draw_line(uint8_t* img, int rows, int cols, size_t step, int x0, int y0, in
 
 int aslam_draw_detected_markers(aslam_ctx* c, uint8_t* bgr, int rows, int cols, size_t step) {
     if (!c || !bgr || rows <= 0 || cols <= 0 || step < (size_t)cols * 3) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: the overlay describes one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
     if (r) return r;
@@ -1649,9 +1848,7 @@ int aslam_get_slot_ekf_stats(aslam_ctx* c, int first, int count, int* stats) {
     if (!c || !stats) return fail(c, ASLAM_E_INVALID, "null argument");
     int r = check_slot_range(c, first, count);
     if (r) return r;
-    { int rs = sync_streams(c); if (rs) return rs; }
-    HIP_TRY(c, hipMemcpy(stats, c->ekf.d_slot_stat + (size_t)4 * first, sizeof(int) * 4 * count, hipMemcpyDeviceToHost));
-    return ASLAM_OK;
+    return read_ekf_stats(c, first, count, stats);
 }
 
 int aslam_get_landmark_ids(aslam_ctx* c, int* L, int* ids) {
@@ -1673,6 +1870,7 @@ int aslam_detect_batch(aslam_ctx* c, const uint8_t* frames, int nframes, int row
         if (r) return r;
         r = run_detect(c, 0, nb);
         if (r) return r;
+        c->rig_last = false;
         r = sync_and_check(c);
         if (r) return r;
         for (int i = 0; i < nb; i++) {
@@ -1988,6 +2186,7 @@ int aslam_synth_render(aslam_ctx* c, int slot, int rows, int cols, const double 
     c->in_frame_bytes = (size_t)rows * cols;
     r = quiesce_slots(c, slot, 1);
     if (r) return r;
+    note_slot_shape(c, slot, 1);
     const int nc = c->dict_ms + 2;
     std::vector<SynthMarker> mk(n_markers);
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];

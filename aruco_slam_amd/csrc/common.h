@@ -139,6 +139,20 @@ struct CamParams {
     int pad;
 };
 
+// Camera rigs: up to kMaxCameras cameras, each with its own intrinsics and planar mount (mx, my, psi) in base_link.  k_pose gets
+// the table by value; frame f of a launch uses entry (cam0 + f) % n.  The single-camera configuration is the table
+// {aslam_set_camera, (r2c.x, r2c.y), psi = 0} with n = 1: cos 0 = 1 and sin 0 = 0 are exact, so its observations do not move.
+constexpr int kMaxCameras = 8;
+struct RigCam {
+    CamParams cam;
+    double mx, my;                    // mount translation in base_link
+    double cpsi, spsi, psi;           // optical axis heading: cos, sin (host libm) and the angle itself
+};
+struct PoseCams {
+    RigCam e[kMaxCameras];
+    int n, cam0;
+};
+
 struct SlamParams {
     double Q_k, R_x, R_y, R_theta, kl, kr, b, marker_length;
     double r2c_tx, r2c_ty;

@@ -8,7 +8,7 @@ namespace aslam {
 constexpr int kIdTableSize = 1024;     // marker id -> landmark index (std::map<int,int> aruco_id_map, aruco_slam.h:164)
 
 struct PopRec {                        // one popped observation (aruco_slam.cpp:92-95) and what was done with it
-    int id, index, action, pad;        // action: 0 augment, 1 update, 2 stationary no-op
+    int id, index, action, det;        // action: 0 augment, 1 update, 2 stationary no-op; det: position in the frame's observation list
     double z[3];
     double r[3];
 };

@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void k_ekf_plan(EkfState E, SlamParams sp, dou
         const ObsRaw o = sObs[slot];
         const int index = sIndex[slot];
         PopRec pr;
-        pr.id = o.id; pr.index = index; pr.action = sAction[q]; pr.pad = 0;
+        pr.id = o.id; pr.index = index; pr.action = sAction[q]; pr.det = slot;
         pr.z[0] = o.x; pr.z[1] = o.y; pr.z[2] = o.th;
         pr.r[0] = o.r[0]; pr.r[1] = o.r[1]; pr.r[2] = o.r[2];
         E.d_pop[q] = pr;

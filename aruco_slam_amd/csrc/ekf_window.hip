@@ -385,7 +385,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                         const ObsRaw o = obs[(size_t)slot * kMarkerMax + fr.pdet[lane]];
                         const bool upd = fr.pact[lane] == 1;
                         PopRec pr;
-                        pr.id = o.id; pr.index = fr.pidx[lane]; pr.action = upd ? 1 : 2; pr.pad = 0;
+                        pr.id = o.id; pr.index = fr.pidx[lane]; pr.action = upd ? 1 : 2; pr.det = fr.pdet[lane];
                         pr.z[0] = o.x; pr.z[1] = o.y; pr.z[2] = o.th;
                         pr.r[0] = o.r[0]; pr.r[1] = o.r[1]; pr.r[2] = o.r[2];
                         E.d_pop[lane] = pr;

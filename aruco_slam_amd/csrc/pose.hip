@@ -402,7 +402,7 @@ __device__ void corner_sub_pix_one(const uint8_t* gray, int rows, int cols, cons
 
 __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ finals, const unsigned* __restrict__ n_final,
                                               Marker* __restrict__ markers, unsigned* __restrict__ n_markers,
-                                              ObsRaw* __restrict__ obs, CamParams cam, SlamParams sp, Counters* ctr, RefineCfg rf) {
+                                              ObsRaw* __restrict__ obs, PoseCams cams, SlamParams sp, Counters* ctr, RefineCfg rf) {
     __shared__ float sC[kMarkerMax][8];
     __shared__ int sId[kMarkerMax];
     __shared__ unsigned char sRem[kMarkerMax];
@@ -410,6 +410,8 @@ __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ fina
     __shared__ int sN, sM;
     const int tid = threadIdx.x;
     const int f = blockIdx.x;
+    const RigCam& rc = cams.e[(cams.cam0 + f) % cams.n];          // this frame's camera: intrinsics and mount
+    const CamParams& cam = rc.cam;
     const FinalCand* fin = finals + (size_t)f * kCandMax;
     const int nF = (int)min(n_final[f], (unsigned)kCandMax);
 
@@ -498,9 +500,14 @@ __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ fina
         if (dist > sp.useful_distance_threshold) o.valid = 0;                    // aruco_slam.cpp:327-333
         double R[9];
         rodrigues_fwd(mk.rvec, R, nullptr);
-        o.x = t[2] + sp.r2c_tx;                                                  // aruco_slam.cpp:359
-        o.y = -t[0] + sp.r2c_ty;                                                 // aruco_slam.cpp:360
-        o.th = atan2(-R[2], R[8]);                                               // aruco_slam.cpp:361
+        // aruco_slam.cpp:359-361 in the camera's own frame, then rotated by the mount's heading psi and moved by its translation
+        // (psi = 0: the reference's t_z + r2c.x, -t_x + r2c.y, atan2(-R02, R22) to the bit)
+        const double x0 = t[2], y0 = -t[0];
+        double th0 = atan2(-R[2], R[8]);
+        wrap_once(th0);
+        o.x = (rc.cpsi * x0 - rc.spsi * y0) + rc.mx;
+        o.y = (rc.spsi * x0 + rc.cpsi * y0) + rc.my;
+        o.th = th0 + rc.psi;
         wrap_once(o.th);
         // CalculateCovariance (aruco_slam.cpp:437-471): reprojection error of the 4 corners (points stored as float)
         double par[6] = {mk.rvec[0], mk.rvec[1], mk.rvec[2], t[0], t[1], t[2]};
@@ -525,8 +532,38 @@ __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ fina
 }
 
 void launch_pose(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers,
-                 unsigned* n_markers, ObsRaw* obs, const CamParams& cam, const SlamParams& sp, Counters* ctr, const RefineCfg& rf) {
-    hipLaunchKernelGGL(k_pose, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, cam, sp, ctr, rf);
+                 unsigned* n_markers, ObsRaw* obs, const PoseCams& cams, const SlamParams& sp, Counters* ctr, const RefineCfg& rf) {
+    hipLaunchKernelGGL(k_pose, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, cams, sp, ctr, rf);
+}
+
+// One rig step = the observation lists of its C frames (slots frame0 + s C + c) concatenated in camera order into one list at
+// slot step0 + s, with the step's encoder sample (that of its camera-0 slot); the EKF kernels then run on step lists exactly as on
+// frame lists.  More than kMarkerMax observations in a step: the first kMarkerMax are kept and the markers-overflow bit is raised.
+__global__ __launch_bounds__(128) void k_rig_merge(ObsRaw* __restrict__ obs, unsigned* __restrict__ n_markers, double* __restrict__ enc,
+                                                   int frame0, int n_cams, int step0, Counters* ctr) {
+    __shared__ int sOff[kMaxCameras + 1];
+    const int tid = threadIdx.x;
+    const int s = blockIdx.x;
+    const int f0 = frame0 + s * n_cams;
+    if (tid == 0) {
+        int off = 0;
+        for (int c = 0; c < n_cams; c++) { sOff[c] = off; off += (int)min(n_markers[f0 + c], (unsigned)kMarkerMax); }
+        sOff[n_cams] = off;
+        if (off > kMarkerMax) atomicOr(&ctr->overflow, (unsigned)kOvfMarkers);
+        n_markers[step0 + s] = (unsigned)min(off, kMarkerMax);
+    }
+    if (tid < 3) enc[(size_t)3 * (step0 + s) + tid] = enc[(size_t)3 * f0 + tid];
+    __syncthreads();
+    ObsRaw* dst = obs + (size_t)(step0 + s) * kMarkerMax;
+    for (int c = 0; c < n_cams; c++) {
+        const int base = sOff[c], n = sOff[c + 1] - base;
+        const ObsRaw* src = obs + (size_t)(f0 + c) * kMarkerMax;
+        for (int i = tid; i < n && base + i < kMarkerMax; i += 128) dst[base + i] = src[i];
+    }
+}
+
+void launch_rig_merge(hipStream_t st, int n_steps, ObsRaw* obs, unsigned* n_markers, double* enc, int frame0, int n_cams, int step0, Counters* ctr) {
+    hipLaunchKernelGGL(k_rig_merge, dim3(n_steps), dim3(128), 0, st, obs, n_markers, enc, frame0, n_cams, step0, ctr);
 }
 
 } // namespace aslam

@@ -294,6 +294,35 @@ class RingWorld:
         return Frame(ids=self.ids[sel].copy(), poses=poses, wl=wl, wr=wr, dt=cfg.dt, true_pose=(px, py, norm_angle(phi)),
                      landmark_index=sel)
 
+    def rig_frame(self, index, mounts):
+        """rig step `index`: one Frame per camera of a rig, mounts = [(mount_x, mount_y, mount_yaw), ...] in base_link (cfg.r2c is
+        not used).  Camera c sits at the robot pose moved by its mount and looks along heading + mount_yaw; it sees the markers whose
+        ring angle lies within half a window of that direction.  Every Frame carries the step's encoder sample."""
+        cfg = self.cfg
+        i = index % self.lap_length()
+        px, py, phi = self.pose[i]
+        wl, wr = (0.0, 0.0) if index == 0 else (self.wl, self.wr)
+        out = []
+        for mx, my, myaw in mounts:
+            cx = px + math.cos(phi) * mx - math.sin(phi) * my
+            cy = py + math.sin(phi) * mx + math.cos(phi) * my
+            h = phi + myaw
+            u = np.array([math.cos(h), math.sin(h)])
+            n = np.array([-math.sin(h), math.cos(h)])
+            rel = (self.alpha - h + math.pi) % (2 * math.pi) - math.pi
+            sel = np.nonzero(np.abs(rel) < self.half_window)[0]
+            poses = np.zeros((len(sel), 12))
+            for a, li in enumerate(sel):
+                d = self.pos[li] - np.array([cx, cy])
+                zx, zy = float(d @ u), float(d @ n)
+                psi = (h + math.pi - self.theta_w[li] + math.pi) % (2 * math.pi) - math.pi
+                R, t = marker_pose((-zy, -self.height[li], zx), psi)
+                poses[a, :9] = R.reshape(-1)
+                poses[a, 9:] = t
+            out.append(Frame(ids=self.ids[sel].copy(), poses=poses, wl=wl, wr=wr, dt=cfg.dt, true_pose=(px, py, norm_angle(phi)),
+                             landmark_index=sel))
+        return out
+
 
 def make_world(cfg: SceneConfig):
     return RingWorld(cfg) if cfg.kind == "ring" else PanelWorld(cfg)

@@ -154,6 +154,30 @@ int aslam_get_slot_raw_observations(aslam_ctx* ctx, int slot, int* n, int* ids, 
  * that no observation was lost to the range / covariance gates (aruco_slam.cpp:327-333, :367-368). */
 int aslam_get_slot_ekf_stats(aslam_ctx* ctx, int first, int count, int* stats);
 
+/* ---- camera rig: several cameras on one robot feeding one filter (no reference counterpart) --------------
+ * Camera c has its own K / D and a planar mount (mount_x, mount_y, mount_yaw) in base_link: optical axis horizontal, pointing at
+ * heading mount_yaw in (-pi, pi], optical frame as in the reference (x right, y down, z forward).  A marker seen by camera c is
+ * observed at x = cos(yaw) x0 - sin(yaw) y0 + mount_x, y = sin(yaw) x0 + cos(yaw) y0 + mount_y, theta = normAngle(theta0 + yaw),
+ * where (x0, y0, theta0) = (t_z, -t_x, normAngle(atan2(-R02, R22))) is the reference's forward-camera observation
+ * (aruco_slam.cpp:359-361); the gates and the diagonal covariance are the reference's.  A rig step = one encoder sample, then
+ * one image per camera, all taken at the same instant: one EKF step whose queue receives camera 0's observations in detection
+ * order, then camera 1's, and so on.  The single-camera configuration (aslam_set_camera, r2c_t) is untouched; only the calls
+ * below use the rig.  Rig calls leave aslam_get_detected_markers / aslam_draw_detected_markers refusing with ASLAM_E_STATE. */
+#define ASLAM_MAX_CAMERAS 8
+typedef struct { double K[9]; double D[5]; int nD; int pad; double mount_x, mount_y, mount_yaw; } aslam_camera;
+/* the rig's cameras (1..ASLAM_MAX_CAMERAS and at most max_batch, nD <= 5, mount_yaw in (-pi, pi]); may be called again between calls */
+int aslam_set_camera_rig(aslam_ctx* ctx, int n_cams, const aslam_camera* cams);
+/* aslam_add_image for a rig step: px[c] (borrowed, step_bytes[c]) is camera c's image, all of one size; one batched detection pass
+ * over slots 0..n_cams-1, then one EKF step; synchronous, a no-op before the first encoder sample.  Detections: aslam_get_slot_detections(c) */
+int aslam_add_images(aslam_ctx* ctx, int n_cams, const uint8_t* const* px, int rows, int cols, int channels, const size_t* step_bytes);
+/* aslam_run_staged for n_steps rig steps: slot first + s*C + c holds camera c's frame of step s, the encoder sample staged in slot
+ * first + s*C is the step's (the other slots' samples are ignored); n_steps*C <= max_batch, same with_ekf values, asynchrony and re-staging rules */
+int aslam_run_staged_rig(aslam_ctx* ctx, int first, int n_steps, int with_ekf);
+/* aslam_get_observations of the last rig step, plus the camera each popped observation came from */
+int aslam_get_rig_observations(aslam_ctx* ctx, int* n, int* ids, int* idx, int* action, int* cam, double* xyth, double* Rdiag);
+/* the 4 counts of aslam_get_slot_ekf_stats per rig step (all cameras together); step s of a call that started at slot first is step first + s */
+int aslam_get_rig_step_ekf_stats(aslam_ctx* ctx, int first_step, int count, int* stats);
+
 /* ---- what the node publishes (aruco_slam_node.cpp:99-118), as plain data for the adapter to wrap in ROS messages ----
  * aslam_get_pose_msg = ArucoSlam::toRosPose (aruco_slam.cpp:378-410): frame "world", z = 0.1, yaw-only quaternion
  * (x, y, z, w) and the 6x6 row-major covariance with sigma_(0..2, 0..2) scattered to rows/columns 0, 1, 5.

@@ -1,0 +1,374 @@
+"""Camera rigs: C cameras with their own K / D and planar mounts feeding one filter (aslam_set_camera_rig, aslam_add_images,
+aslam_run_staged_rig).  The reference has one camera, so the rig reference here is the numpy restatement of the reference's EKF
+(oracle.ekf_literal.LiteralSlam) with the per-camera observation model of include/aruco_slam_hip.h, fed by the CPU oracle's
+detection and pose of every image with that image's camera.  The one-camera rig must equal the single-camera path to the bit."""
+import math
+import re
+
+import numpy as np
+import pytest
+
+from aruco_slam_amd import capi, synth
+from oracle import pyoracle as orc
+from oracle.ekf_literal import LiteralSlam, norm_angle
+import parity_common as pc
+
+E_INVALID, E_CAPACITY, E_STATE = -1, -4, -5
+
+
+def rotate_observation(z0, mount):
+    """(x0, y0, theta0) of the reference's forward camera -> base_link through a planar mount (mx, my, psi)"""
+    mx, my, psi = mount
+    c, s = math.cos(psi), math.sin(psi)
+    x0, y0, th0 = z0
+    return np.array([(c * x0 - s * y0) + mx, (s * x0 + c * y0) + my, norm_angle(th0 + psi)])
+
+
+class RigSlam(LiteralSlam):
+    """LiteralSlam with one observation model per camera and one queue per rig step (push order: camera 0's detections in
+    detection order, then camera 1's, ...)"""
+
+    def __init__(self, cams, **kw):
+        super().__init__(r2c=(0.0, 0.0), **kw)
+        self.cams = cams                      # [(K, D, (mx, my, psi)), ...]
+        self._flat = []
+
+    def make_observation(self, k, corners, rvec, tvec):
+        cam, marker_id = self._flat[k]
+        K, D, mount = self.cams[cam]
+        self.K, self.D = np.asarray(K, float), np.asarray(D, float)
+        ob = super().make_observation(marker_id, corners, rvec, tvec)
+        if ob is None:
+            return None
+        ob["z"] = rotate_observation(ob["z"], mount)
+        ob["cam"] = cam
+        return ob
+
+    def add_rig_poses(self, per_cam):
+        """per_cam[c] = (ids, corners, rvecs, tvecs) of camera c's image"""
+        self._flat = [(c, int(i)) for c, d in enumerate(per_cam) for i in d[0]]
+        cat = [np.concatenate([np.asarray(d[j], float).reshape(len(d[0]), width) for d in per_cam]) for j, width in ((1, 8), (2, 3), (3, 3))]
+        self.add_poses(list(range(len(self._flat))), *cat)
+
+    def last_pops(self):
+        ids = np.array([o["id"] for o in self.last_observed], np.int32)
+        idx = np.array([e[1] for e in self.log], np.int32)
+        act = np.array([e[2] for e in self.log], np.int32)
+        cam = np.array([o["cam"] for o in self.last_observed], np.int32)
+        z = np.array([o["z"] for o in self.last_observed]).reshape(-1, 3)
+        return ids, idx, act, cam, z
+
+    def state(self):
+        return self.mu.copy(), self.sigma.copy()
+
+
+def small_ring(lap=120):
+    return synth.SceneConfig(kind="ring", rows=240, cols=320, f=260.0, grid=(2, 2), n_panels=8, ring_radius=1.8,
+                             ring_robot_radius=0.2, ring_lap_frames=lap)
+
+
+def oracle_detect(img, K, D, marker_length=0.27):
+    ids, corners = orc.detect(img)
+    rv = np.zeros((len(ids), 3)); tv = np.zeros((len(ids), 3))
+    for j in range(len(ids)):
+        rv[j], tv[j], _ = orc.solve_pnp(corners[j], marker_length, K, D)
+    return ids, corners, rv, tv
+
+
+def check_state(ref, ctx, where):
+    mu_o, S_o = ref.state()
+    mu_g, S_g = ctx.get_state()
+    assert mu_o.shape == mu_g.shape, f"{where}: state size differs"
+    assert np.allclose(mu_o, mu_g, rtol=pc.POSE_RTOL, atol=1e-8), f"{where}: mu differs by {np.abs(mu_o - mu_g).max()}"
+    e_S = np.abs(S_o - S_g).max() / max(np.abs(S_o).max(), 1e-300)
+    assert e_S < pc.POSE_RTOL, f"{where}: sigma differs by {e_S} (relative to max |sigma|)"
+
+
+def check_pops(ref, ctx, where):
+    oi, ox, oa, oc, oz = ref.last_pops()
+    gi, gx, ga, gc, gz, _ = ctx.get_rig_observations()
+    assert np.array_equal(oi, gi), f"{where}: pop order (ids) differs"
+    assert np.array_equal(ox, gx), f"{where}: landmark indices differ"
+    assert np.array_equal(oa, ga), f"{where}: update / augment / stationary decisions differ"
+    assert np.array_equal(oc, gc), f"{where}: cameras of the popped observations differ"
+    assert np.allclose(oz, gz, rtol=pc.POSE_RTOL, atol=1e-9), f"{where}: observations differ"
+
+
+def drive_rig(world, cams, n_steps, mode, batch_steps=1, ctx_kwargs=None, noise_amp=2):
+    """Drive a rig over n_steps rig steps of world.rig_frame, through add_images (mode "images") or run_staged_rig in batches of
+    batch_steps steps (mode "staged"), against RigSlam on the same images.  Returns (context, reference, per-step marker counts)."""
+    cfg = world.cfg
+    C = len(cams)
+    mounts = [m for _, _, m in cams]
+    kw = dict(max_rows=cfg.rows, max_cols=cfg.cols, max_batch=C * batch_steps, max_landmarks=world.L + 8)
+    kw.update(ctx_kwargs or {})
+    ctx = capi.Context(**kw)
+    ctx.set_camera_rig(cams)
+    ref = RigSlam(cams)
+    t_now = 0.0
+    counts = []
+    for s0 in range(0, n_steps, batch_steps):
+        nb = min(batch_steps, n_steps - s0)
+        steps = [world.rig_frame(s0 + s, mounts) for s in range(nb)]
+        imgs = [[ctx.synth_render(s * C + c, cfg.rows, cfg.cols, cams[c][0], fr.ids, fr.poses, noise_amp=noise_amp, seed=(s0 + s) * C + c)
+                 for c, fr in enumerate(frs)] for s, frs in enumerate(steps)]
+        if mode == "staged":
+            n = nb * C
+            ctx.stage_encoders([steps[i // C][0].wl for i in range(n)], [steps[i // C][0].wr for i in range(n)],
+                               [steps[i // C][0].dt for i in range(n)])
+            ctx.run_staged_rig(0, nb, with_ekf=True)
+            ctx.sync()
+        expect_stats = []
+        for s in range(nb):
+            fr0 = steps[s][0]
+            t_now += fr0.dt
+            if mode == "images":
+                ctx.add_encoder(fr0.wl, fr0.wr, t_now)
+                ctx.add_images(imgs[s])
+            ref.add_encoder(fr0.wl, fr0.wr, t_now)
+            per_cam = []
+            for c in range(C):
+                K, D, _ = cams[c]
+                o = oracle_detect(imgs[s][c], K, D)
+                slot = c if mode == "images" else s * C + c
+                g_ids, g_c, g_rv, g_tv = ctx.get_slot_detections(slot)
+                assert np.array_equal(o[0], g_ids), f"step {s0 + s} camera {c}: marker ids differ"
+                assert np.array_equal(o[1], g_c), f"step {s0 + s} camera {c}: marker corners differ"
+                pc.check_poses(g_ids, g_c, g_rv, g_tv, K, D)
+                per_cam.append(o)
+            ref.add_rig_poses(per_cam)
+            acts = np.array([e[2] for e in ref.log], np.int32)
+            expect_stats.append([sum(len(p[0]) for p in per_cam), int((acts == 0).sum()), int((acts == 1).sum()), int((acts == 2).sum())])
+            counts.append(expect_stats[-1][0])
+            if mode == "images":
+                check_pops(ref, ctx, f"step {s0 + s}")
+                check_state(ref, ctx, f"step {s0 + s}")
+        got = ctx.get_rig_step_ekf_stats(0, nb) if mode == "staged" else np.array([ctx.get_rig_step_ekf_stats(0, 1)[0]])
+        if mode == "images":
+            expect_stats = expect_stats[-1:]
+        assert np.array_equal(got, np.array(expect_stats)), f"steps {s0}..: per-step detections / augments / updates / stationary differ"
+        if mode == "staged":
+            check_pops(ref, ctx, f"batch at step {s0}")
+            check_state(ref, ctx, f"batch at step {s0}")
+    got_ids = ctx.get_landmark_ids()
+    assert np.array_equal(np.array(sorted(ref.id_map, key=ref.id_map.get), np.int32), got_ids), "landmark id table differs"
+    return ctx, ref, counts
+
+
+def one_camera_equivalence(cfg, n_steps, mode, batch=8, ctx_kwargs=None):
+    """the one-camera rig {K, D, (r2c.x, r2c.y, 0)} against the single-camera path on the same images: == everywhere"""
+    w = synth.RingWorld(cfg)
+    D = np.array([0.02, -0.01, 0.0005, -0.0003, 0.0])
+    r2c = (0.11, -0.04)
+    kw = dict(max_rows=cfg.rows, max_cols=cfg.cols, max_batch=batch, max_landmarks=w.L + 8)
+    kw.update(ctx_kwargs or {})
+    a = capi.Context(r2c_t=(r2c[0], r2c[1], 0.0), **kw)
+    a.set_camera(w.K, D)
+    b = capi.Context(**kw)                                   # r2c_t stays 0: the mount must come from the rig
+    b.set_camera_rig([(w.K, D, (r2c[0], r2c[1], 0.0))])
+    t_now = 0.0
+    for f0 in range(0, n_steps, batch if mode == "staged" else 1):
+        nb = min(batch, n_steps - f0) if mode == "staged" else 1
+        frs = [w.rig_frame(f0 + i, [(r2c[0], r2c[1], 0.0)])[0] for i in range(nb)]
+        imgs = [a.synth_render(i, cfg.rows, cfg.cols, w.K, fr.ids, fr.poses, noise_amp=2, seed=f0 + i) for i, fr in enumerate(frs)]
+        if mode == "staged":
+            b.stage_frames(np.stack(imgs))
+            for ctx in (a, b):
+                ctx.stage_encoders([fr.wl for fr in frs], [fr.wr for fr in frs], [fr.dt for fr in frs])
+            a.run_staged(0, nb, with_ekf=True)
+            b.run_staged_rig(0, nb, with_ekf=True)
+            a.sync(); b.sync()
+        else:
+            t_now += frs[0].dt
+            a.add_encoder(frs[0].wl, frs[0].wr, t_now); a.add_image(imgs[0])
+            b.add_encoder(frs[0].wl, frs[0].wr, t_now); b.add_images(imgs)
+        for i in range(nb):
+            for x, y in zip(a.get_slot_detections(i), b.get_slot_detections(i)):
+                assert np.array_equal(x, y), f"step {f0 + i}: detections differ"
+            for x, y in zip(a.get_slot_raw_observations(i), b.get_slot_raw_observations(i)):
+                assert np.array_equal(x, y), f"step {f0 + i}: observations differ"
+        assert np.array_equal(a.get_slot_ekf_stats(0, nb), b.get_rig_step_ekf_stats(0, nb)), f"steps {f0}..: EKF step counts differ"
+        oa, ob = a.get_observations(), b.get_rig_observations()
+        for x, y in zip(oa, ob[:3] + ob[4:]):
+            assert np.array_equal(x, y), f"step {f0 + nb - 1}: popped observations differ"
+        assert np.all(ob[3] == 0)
+        for x, y in zip(a.get_state(), b.get_state()):
+            assert np.array_equal(x, y), f"step {f0 + nb - 1}: filter state differs"
+    assert a.plan_stats() == b.plan_stats()
+    assert np.array_equal(a.get_landmark_ids(), b.get_landmark_ids())
+    return a, b
+
+
+# ---- without a GPU: CPU emulation of the kernels at 240 x 320 -------------------------------------------------------------------
+
+def test_one_camera_rig_add_images_equals_add_image():
+    one_camera_equivalence(small_ring(), 22, "images", ctx_kwargs=dict(persistent_waves=4))
+
+
+def test_one_camera_rig_staged_equals_run_staged():
+    one_camera_equivalence(small_ring(), 24, "staged", ctx_kwargs=dict(persistent_waves=4))
+
+
+def two_camera_rig_small():
+    w = synth.RingWorld(small_ring())
+    K2 = synth.camera_matrix(240, 320, 240.0)
+    cams = [(w.K, np.zeros(5), (0.12, 0.02, 0.0)),
+            (K2, np.array([0.01, -0.004, 0.0, 0.0, 0.0]), (-0.15, -0.03, math.pi))]
+    return w, cams
+
+
+@pytest.mark.parametrize("mode", ["images", "staged"])
+def test_two_camera_rig_against_reference(mode):
+    w, cams = two_camera_rig_small()
+    ctx, ref, counts = drive_rig(w, cams, 24, mode, batch_steps=4, ctx_kwargs=dict(persistent_waves=4))
+    assert min(counts) >= 6, counts                           # both cameras see their markers
+    cams_seen = {int(o["cam"]) for o in ref.last_observed}
+    assert cams_seen == {0, 1}
+    assert len(ctx.get_landmark_ids()) >= 12
+
+
+def test_merged_step_list_overflow_reports_capacity():
+    ctx = capi.Context(max_rows=64, max_cols=96, max_batch=2, max_landmarks=300, persistent_waves=4)
+    K = synth.camera_matrix(64, 96, 100.0)
+    ctx.set_camera_rig([(K, None, (0.0, 0.0, 0.0)), (K, None, (0.0, 0.0, math.pi))])
+    ctx.stage_encoders([0.0, 0.0], [0.0, 0.0], [0.1, 0.1])
+
+    def inject(n0, n1, base):                                # new landmarks only: nothing but the list length can overflow
+        for slot, (lo, n) in enumerate(((base, n0), (base + 100, n1))):
+            ids = np.arange(lo, lo + n)
+            xyth = np.stack([1.0 + 0.01 * ids, 0.001 * ids, 0.0 * ids], 1)
+            ctx.inject_observations(slot, ids, np.ones(n), xyth, np.full((n, 3), 0.02))
+
+    inject(64, 64, 0)                                        # exactly kMarkerMax: fine
+    ctx.run_staged_rig(0, 1, with_ekf=2)
+    ctx.sync()
+    assert ctx.get_rig_step_ekf_stats(0, 1)[0].tolist() == [128, 128, 0, 0]
+    inject(70, 60, 300)
+    ctx.run_staged_rig(0, 1, with_ekf=2)
+    with pytest.raises(capi.AslamError) as e:
+        ctx.sync()
+    assert e.value.code == E_CAPACITY
+    assert int(re.search(r"mask 0x([0-9a-f]+)", str(e.value)).group(1), 16) == 16      # the markers bit alone
+    assert ctx.get_rig_step_ekf_stats(0, 1)[0].tolist() == [128, 128, 0, 0]          # the first 128 of the step were processed
+
+
+def test_rig_refusals():
+    K = synth.camera_matrix(64, 96, 100.0)
+    ctx = capi.Context(max_rows=64, max_cols=96, max_batch=4, persistent_waves=4)
+    cam = (K, None, (0.0, 0.0, 0.0))
+    with pytest.raises(capi.AslamError) as e:
+        ctx.add_images([np.zeros((64, 96), np.uint8)])        # no rig yet
+    assert e.value.code == E_STATE
+    for bad in ([], [cam] * 9, [cam] * 5):                    # C = 0, C = 9, C > max_batch
+        with pytest.raises(capi.AslamError) as e:
+            ctx.set_camera_rig(bad)
+        assert e.value.code == E_INVALID
+    for yaw in (-math.pi, 3.2, -4.0, float("nan")):
+        with pytest.raises(capi.AslamError) as e:
+            ctx.set_camera_rig([cam, (K, None, (0.0, 0.0, yaw))])
+        assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.set_camera_rig([(K, np.zeros(6), (0.0, 0.0, 0.0))])
+    assert e.value.code == E_INVALID
+    ctx.set_camera_rig([cam, (K, None, (0.0, 0.0, math.pi))])  # pi itself is inside (-pi, pi]
+    ctx.add_encoder(0.0, 0.0, 0.0)
+    with pytest.raises(ValueError):
+        ctx.add_images([np.zeros((64, 96), np.uint8), np.zeros((60, 96), np.uint8)])
+    with pytest.raises(capi.AslamError) as e:
+        ctx.add_images([np.zeros((64, 96), np.uint8)])        # one image for a 2-camera rig
+    assert e.value.code == E_INVALID
+    ctx.add_images([np.zeros((64, 96), np.uint8)] * 2)
+    with pytest.raises(capi.AslamError) as e:
+        ctx.detected_markers()                                # describes one camera only
+    assert e.value.code == E_STATE
+    ctx.stage_frames(np.zeros((64, 96), np.uint8), slot0=0)
+    ctx.stage_frames(np.zeros((32, 48), np.uint8), slot0=1)  # a step whose frames differ in size
+    with pytest.raises(capi.AslamError) as e:
+        ctx.run_staged_rig(0, 1, with_ekf=False)
+    assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.run_staged_rig(0, 3, with_ekf=False)              # 3 steps x 2 cameras > max_batch
+    assert e.value.code == E_INVALID
+
+
+def test_rotated_observation_formula():
+    """hand-built marker poses, observed through mounts of heading +-pi/2, pi and +-small: the library's observations are the
+    formula applied (with the host's libm cos / sin) to what the same camera observes at heading 0 from the origin, to the bit;
+    the gates and the covariance do not depend on the mount.  Facing markers are observed at theta0 = pi - yaw, near +-pi."""
+    rows, cols, f = 240, 320, 260.0
+    K = synth.camera_matrix(rows, cols, f)
+    D = np.array([0.01, 0.0, 0.0, 0.0, 0.0])
+    ids = synth.unambiguous_ids(4, start=5)
+    poses = np.zeros((4, 12))
+    for k, (t, yaw) in enumerate((((-0.45, -0.2, 1.3), 0.02), ((0.4, -0.15, 1.5), -0.03), ((-0.1, 0.25, 1.2), 0.4), ((0.35, 0.3, 1.6), -0.5))):
+        R, tt = synth.marker_pose(t, yaw)
+        poses[k, :9] = R.reshape(-1)
+        poses[k, 9:] = tt
+    ctx = capi.Context(max_rows=rows, max_cols=cols, max_batch=1, persistent_waves=4)
+    ctx.synth_render(0, rows, cols, K, ids, poses, noise_amp=2, seed=3)
+    ctx.set_camera_rig([(K, D, (0.0, 0.0, 0.0))])
+    ctx.run_staged_rig(0, 1, with_ekf=False)
+    base_ids, base_valid, base_z, base_R = ctx.get_slot_raw_observations(0)
+    assert sorted(base_ids.tolist()) == sorted(ids) and base_valid.all()
+    th0 = base_z[:, 2]
+    assert (th0 > 3.0).any() and (th0 < -3.0).any()           # both sides of the wrap
+    for yaw in (math.pi / 2, -math.pi / 2, math.pi, 1e-3, -1e-3, 2.5):
+        mount = (0.13, -0.07, yaw)
+        ctx.set_camera_rig([(K, D, mount)])
+        ctx.run_staged_rig(0, 1, with_ekf=False)
+        g_ids, g_valid, g_z, g_R = ctx.get_slot_raw_observations(0)
+        assert np.array_equal(g_ids, base_ids) and np.array_equal(g_valid, base_valid) and np.array_equal(g_R, base_R)
+        want = np.array([rotate_observation(z, mount) for z in base_z])
+        assert np.array_equal(g_z, want), f"heading {yaw}: {np.abs(g_z - want).max()}"
+        assert np.all(np.abs(g_z[:, 2]) <= math.pi)
+
+
+# ---- on the MI355X at 1280 x 720 ------------------------------------------------------------------------------------------------
+
+def ring_1280(lap):
+    cfg = synth.CONFIGS["cfg2_sliding"]
+    return synth.SceneConfig(**{**cfg.__dict__, "ring_lap_frames": lap})
+
+
+@pytest.mark.gpu
+def test_gpu_four_camera_rig_lap_staged():
+    """front, left, rear, right: about 80 corrections per step, all on the per-frame general chain"""
+    cfg = ring_1280(100)
+    w = synth.RingWorld(cfg)
+    K = w.K
+    cams = [(K, np.zeros(5), (0.20, 0.00, 0.0)), (K, np.zeros(5), (0.00, 0.15, math.pi / 2)),
+            (K, np.zeros(5), (-0.22, 0.01, math.pi)), (K, np.zeros(5), (0.01, -0.16, -math.pi / 2))]
+    kw = dict(max_updates_per_frame=128)
+    ctx, ref, counts = drive_rig(w, cams, w.lap_length(), "staged", batch_steps=16, ctx_kwargs=kw)
+    assert np.mean(counts) > 60, np.mean(counts)
+    assert len(ctx.get_landmark_ids()) > 0.9 * w.L
+    ps = ctx.plan_stats()
+    print("4-camera lap:", ps, "markers per step", np.mean(counts))
+
+
+@pytest.mark.gpu
+def test_gpu_two_camera_rig_windows():
+    """front and rear, about 40 markers per step: once every landmark is known the steps are fused inside windows"""
+    cfg = ring_1280(80)
+    w = synth.RingWorld(cfg)
+    cams = [(w.K, np.zeros(5), (0.2, 0.0, 0.0)), (w.K, np.zeros(5), (-0.2, 0.0, math.pi))]
+    ctx, ref, counts = drive_rig(w, cams, w.lap_length() + 40, "staged", batch_steps=20, ctx_kwargs=dict(max_updates_per_frame=64))
+    ps = ctx.plan_stats()
+    print("2-camera run:", ps, "markers per step", np.mean(counts))
+    assert np.mean(counts) > 30
+    assert ps["windows"] > 0 and ps["frames_in_windows"] > 0
+
+
+@pytest.mark.gpu
+def test_gpu_two_camera_rig_add_images():
+    cfg = ring_1280(100)
+    w = synth.RingWorld(cfg)
+    K2 = synth.camera_matrix(cfg.rows, cfg.cols, 800.0)
+    cams = [(w.K, np.zeros(5), (0.2, 0.03, 0.0)), (K2, np.array([0.01, -0.005, 0.0, 0.0, 0.0]), (-0.2, 0.0, math.pi))]
+    drive_rig(w, cams, 40, "images", ctx_kwargs=dict(max_updates_per_frame=64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["images", "staged"])
+def test_gpu_one_camera_rig_equivalence(mode):
+    one_camera_equivalence(ring_1280(100), 40, mode, batch=16)
