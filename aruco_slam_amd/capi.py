@@ -118,6 +118,10 @@ _SIGS = {
     "aslam_export_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_draw_detected_markers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]),
     "aslam_load_map_txt": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _ip, C.c_void_p]),
+    "aslam_localize_begin": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp]),
+    "aslam_localize_end": (C.c_int, [C.c_void_p]),
+    "aslam_is_localizing": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_landmarks_from_markers": (C.c_int, [C.c_int, C.c_void_p, _ip, _dp]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -228,6 +232,52 @@ def default_init(**over):
     return init
 
 
+def _marker_msgs(markers):
+    """marker dicts (Context.load_map_txt / map_markers) -> MarkerMsg array"""
+    arr = (MarkerMsg * max(len(markers), 1))()
+    for a, m in zip(arr, markers):
+        a.id = int(m["id"])
+        for k in range(3):
+            a.scale[k] = float(m["scale"][k]) if "scale" in m else 0.0
+            a.position[k] = float(m["position"][k])
+        for k in range(4):
+            a.orientation[k] = float(m["orientation"][k])
+    return arr
+
+
+def landmarks_from_markers(markers):
+    """MapLoader markers (dicts with id, position, orientation (x, y, z, w)) -> (ids, xyth n x 3): heading of each marker's +z axis"""
+    n = len(markers)
+    arr = _marker_msgs(markers)
+    ids = np.zeros(max(n, 1), np.int32)
+    xyth = np.zeros((max(n, 1), 3))
+    lib = load()
+    rc = lib.aslam_landmarks_from_markers(n, arr, _ptr(ids, _ip), _ptr(xyth, _dp))
+    if rc != ASLAM_OK:
+        raise AslamError(rc, lib.aslam_last_error(None).decode())
+    return ids[:n].copy(), xyth[:n].copy()
+
+
+def load_map_txt(path):
+    """aslam_load_map_txt without a context: the marker dicts of a MapLoader map file"""
+    lib = load()
+    n = C.c_int(0)
+    rc = lib.aslam_load_map_txt(None, str(path).encode(), 0, C.byref(n), None)
+    if rc != ASLAM_OK:
+        raise AslamError(rc, f"cannot read {path}")
+    arr = (MarkerMsg * max(n.value, 1))()
+    rc = lib.aslam_load_map_txt(None, str(path).encode(), n.value, C.byref(n), arr)
+    if rc != ASLAM_OK:
+        raise AslamError(rc, f"cannot read {path}")
+    return [dict(id=a.id, scale=tuple(a.scale), color=tuple(a.color), position=np.array(a.position), orientation=np.array(a.orientation),
+                 lifetime=a.lifetime_sec) for a in arr[:n.value]]
+
+
+def known_map_from_txt(path):
+    """a MapLoader map file -> (ids, xyth n x 3), the arguments of Context.localize_begin"""
+    return landmarks_from_markers(load_map_txt(path))
+
+
 class Context:
     """One filter fed by one camera stream (set_camera) or by a camera rig (set_camera_rig): thin RAII wrapper over aslam_ctx
     (mirrors the `ArucoSlam` class surface)."""
@@ -303,6 +353,22 @@ class Context:
         return [dict(id=a.id, scale=tuple(a.scale), color=tuple(a.color), position=np.array(a.position), orientation=np.array(a.orientation),
                      lifetime=a.lifetime_sec) for a in arr[:n.value]]
 
+    # -- localization against a fixed, known marker map (include/aruco_slam_hip.h) ----------
+    def localize_begin(self, ids, xyth, pose, pose_sigma):
+        """freeze the map (ids, xyth: n x 3) and track the pose from `pose` with covariance `pose_sigma` (3 x 3)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        xyth = np.ascontiguousarray(xyth, dtype=np.float64).reshape(-1, 3)
+        if xyth.shape[0] != ids.size:
+            raise ValueError("one (x, y, theta) row per landmark id")
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3)
+        ps = np.ascontiguousarray(pose_sigma, dtype=np.float64).reshape(9)
+        self._ck(self.lib.aslam_localize_begin(self.h, int(ids.size), _ptr(ids, _ip), _ptr(xyth, _dp), _ptr(pose, _dp), _ptr(ps, _dp)))
+    def localize_end(self):
+        self._ck(self.lib.aslam_localize_end(self.h))
+    def is_localizing(self):
+        on = C.c_int(0)
+        self._ck(self.lib.aslam_is_localizing(self.h, C.byref(on)))
+        return bool(on.value)
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))
 

@@ -31,10 +31,10 @@ constexpr int kWinWidenFrames = 16;     // a window of at least this many frames
 constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (its log is replayed meanwhile); <= kWinPieceMax
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
-              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_COUNT };
+              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
-                                   "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next"};
+                                   "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -115,6 +115,7 @@ struct aslam_ctx {
     EkfState ekf{};
     double last_time = 0;
     bool is_init = false;
+    bool localizing = false;              // aslam_localize_begin: the map is frozen, every EKF step is a k_loc_steps step
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -466,6 +467,18 @@ int run_ekf_frame(aslam_ctx* c, int slot, double wl, double wr, double dt, bool 
     return ASLAM_OK;
 }
 
+// localization steps of EKF slots [first, first + count) on the EKF stream, behind the detection that produced their lists: one
+// launch for all of them, no host round trip and no window planning
+int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    prof_begin(c, P_LOC_STEPS, st);
+    launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return ASLAM_OK;
+}
+
 int sync_streams(aslam_ctx* c) {
     { int r = finalize_pending(c); if (r) return r; }
     if (c->stream_copy) HIP_TRY(c, hipStreamSynchronize(c->stream_copy));
@@ -684,7 +697,10 @@ void aslam_destroy(aslam_ctx* c) {
     delete c;
 }
 
-const char* aslam_last_error(const aslam_ctx* c) { return c ? c->err.c_str() : "null context"; }
+namespace {
+thread_local std::string host_err;      // the last refusal of a host-only call made without a context (aslam_landmarks_from_markers)
+}
+const char* aslam_last_error(const aslam_ctx* c) { return c ? c->err.c_str() : (host_err.empty() ? "null context" : host_err.c_str()); }
 
 int aslam_set_camera(aslam_ctx* c, const double K[9], const double* D, int nD) {
     if (!c || !K || nD < 0 || (nD > 0 && !D)) return fail(c, ASLAM_E_INVALID, "bad camera arguments");
@@ -1065,6 +1081,17 @@ int run_staged(aslam_ctx* c, int first, int count, int with_ekf, hipEvent_t wait
 // the EKF steps of EKF slots [first, first + count) (frames, or rig steps' merged lists), behind the detection that produced them
 int schedule_ekf(aslam_ctx* c, int first, int count) {
     int r = ASLAM_OK;
+    if (c->localizing) {                       // frozen map: one k_loc_steps launch, not counted by aslam_get_plan_stats
+        r = finalize_pending(c);
+        if (r) return r;
+        const bool predict = c->is_init;       // addEncoder semantics (aruco_slam.cpp:24-29): the very first sample only arms the filter
+        c->is_init = true;
+        r = run_loc_steps(c, first, count, predict);
+        if (r) return r;
+        HIP_TRY(c, hipEventRecord(c->ev_ekf, c->stream_ekf));
+        note_ekf_range(c, first, count);
+        return ASLAM_OK;
+    }
     if (!c->win_enabled) {                     // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
@@ -1170,8 +1197,12 @@ int aslam_add_images(aslam_ctx* c, int n_cams, const uint8_t* const* px, int row
     r = merge_rig_steps(c, 0, 1);
     if (r) return r;
     const auto t2 = clk::now();
-    HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
-    r = run_ekf_frame(c, rig_step_slot(c, 0, 0), 0, 0, 0, false);     // the prediction came with aslam_add_encoder
+    if (c->localizing) {
+        r = run_loc_steps(c, rig_step_slot(c, 0, 0), 1, false);       // the prediction came with aslam_add_encoder
+    } else {
+        HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+        r = run_ekf_frame(c, rig_step_slot(c, 0, 0), 0, 0, 0, false);     // the prediction came with aslam_add_encoder
+    }
     if (r) return r;
     const auto t3 = clk::now();
     r = sync_streams(c);
@@ -1460,8 +1491,12 @@ int aslam_add_image(aslam_ctx* c, const uint8_t* px, int rows, int cols, int cha
     if (r) return r;
     const auto t2 = clk::now();
     c->rig_last = false;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
-    r = run_ekf_frame(c, 0, 0, 0, 0, false);
+    if (c->localizing) {
+        r = run_loc_steps(c, 0, 1, false);     // the prediction came with aslam_add_encoder
+    } else {
+        HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+        r = run_ekf_frame(c, 0, 0, 0, 0, false);
+    }
     if (r) return r;
     const auto t3 = clk::now();
     r = sync_streams(c);
@@ -1502,6 +1537,7 @@ int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, 
     const int L = (N - 3) / 3;
     if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
+    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
     { int rs = sync_streams(c); if (rs) return rs; }
     std::vector<double> tmp((size_t)c->ekf.ld * c->ekf.ld, 0.0);
     for (int col = 0; col < N; col++) std::memcpy(&tmp[(size_t)col * c->ekf.ld], sigma + (size_t)col * N, sizeof(double) * N);
@@ -1730,6 +1766,84 @@ int aslam_load_map_txt(aslam_ctx* c, const char* path, int max, int* n, aslam_ma
     return ASLAM_OK;
 }
 
+// ---- localization against a frozen map (include/aruco_slam_hip.h) -------------------------------------------
+int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth, const double pose[3], const double pose_sigma[9]) {
+    if (!c || !ids || !xyth || !pose || !pose_sigma) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (n < 1 || n > c->ekf.max_landmarks) return fail(c, ASLAM_E_INVALID, "a map of 1..max_landmarks landmarks");
+    std::vector<int> id2idx(kIdTableSize, -1), idx2id(c->ekf.max_landmarks, -1);
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= kIdTableSize) return fail(c, ASLAM_E_INVALID, "landmark id " + std::to_string(ids[i]) + " outside [0, 1024)");
+        if (id2idx[ids[i]] >= 0) return fail(c, ASLAM_E_INVALID, "landmark id " + std::to_string(ids[i]) + " given twice");
+        id2idx[ids[i]] = i;
+        idx2id[i] = ids[i];
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(xyth[3 * i + k])) return fail(c, ASLAM_E_INVALID, "landmark " + std::to_string(ids[i]) + ": non-finite value");
+    }
+    for (int k = 0; k < 3; k++) if (!std::isfinite(pose[k])) return fail(c, ASLAM_E_INVALID, "non-finite pose");
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            if (!std::isfinite(pose_sigma[i * 3 + j])) return fail(c, ASLAM_E_INVALID, "non-finite pose covariance");
+            if (pose_sigma[i * 3 + j] != pose_sigma[j * 3 + i]) return fail(c, ASLAM_E_INVALID, "pose covariance not symmetric");
+        }
+    { int rs = sync_streams(c); if (rs) return rs; }
+    // state := [pose, map], Sigma := blockdiag(pose_sigma, 0) in the SLAM layout (column-major, ld = N_max)
+    const size_t ld = (size_t)c->ekf.ld;
+    HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
+    for (int col = 0; col < 3; col++) {
+        const double v[3] = {pose_sigma[col], pose_sigma[3 + col], pose_sigma[6 + col]};
+        HIP_TRY(c, hipMemcpy(c->ekf.d_sigma + (size_t)col * ld, v, sizeof(v), hipMemcpyHostToDevice));
+    }
+    std::vector<double> mu(3 + 3 * (size_t)n);
+    for (int k = 0; k < 3; k++) mu[k] = pose[k];
+    std::memcpy(mu.data() + 3, xyth, sizeof(double) * 3 * n);
+    HIP_TRY(c, hipMemcpy(c->ekf.d_mu, mu.data(), sizeof(double) * mu.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->ekf.d_id2idx, id2idx.data(), sizeof(int) * kIdTableSize, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->ekf.d_idx2id, idx2id.data(), sizeof(int) * c->ekf.max_landmarks, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->ekf.d_L, &n, sizeof(int), hipMemcpyHostToDevice));
+    int zero = 0;
+    HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
+    c->mirror_dirty = true;
+    c->localizing = true;
+    return ASLAM_OK;
+}
+
+int aslam_localize_end(aslam_ctx* c) {
+    if (!c) return ASLAM_E_INVALID;
+    { int rs = sync_streams(c); if (rs) return rs; }
+    c->mirror_dirty = true;
+    c->localizing = false;
+    return ASLAM_OK;
+}
+
+int aslam_is_localizing(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->localizing ? 1 : 0;
+    return ASLAM_OK;
+}
+
+// MapLoader markers -> planar landmarks: heading of the marker's +z axis (third column of Matrix3x3(orientation)), which is what an
+// observation's atan2(-R02, R22) measures (aruco_slam.cpp:361)
+int aslam_landmarks_from_markers(int n, const aslam_marker_msg* in, int* ids, double* xyth) {
+    if (n < 0 || (n > 0 && (!in || !ids || !xyth))) { host_err = "null argument"; return ASLAM_E_INVALID; }
+    const double PI = 3.14159265358979323846;
+    for (int i = 0; i < n; i++) {
+        const double ez[3] = {0.0, 0.0, 1.0};
+        double r[3];
+        quat_rotate(in[i].orientation, ez, r);
+        if (!(std::hypot(r[0], r[1]) >= 1e-6)) {
+            host_err = "marker " + std::to_string(in[i].id) + ": its +z axis has no horizontal component (the marker lies flat), no heading";
+            return ASLAM_E_INVALID;
+        }
+        double th = std::atan2(r[1], r[0]);
+        if (th >= PI) th -= 2.0 * PI;                                   // normAngle (aruco_slam.cpp:412-421)
+        if (th < -PI) th += 2.0 * PI;
+        ids[i] = in[i].id;
+        xyth[3 * i] = in[i].position[0]; xyth[3 * i + 1] = in[i].position[1]; xyth[3 * i + 2] = th;
+    }
+    return ASLAM_OK;
+}
+
 // ---- persistence (no counterpart in the reference: warm starts of large maps) ----------------------------
 int aslam_save_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
@@ -1758,6 +1872,7 @@ int aslam_save_state(aslam_ctx* c, const char* path) {
 
 int aslam_load_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, ASLAM_E_INVALID, std::string("cannot read ") + path);
     char magic[8];

@@ -99,6 +99,10 @@ void launch_ekf_gather(hipStream_t st, const EkfState& E);
 void launch_ekf_small(hipStream_t st, const EkfState& E);
 void launch_ekf_T(hipStream_t st, const EkfState& E);
 void launch_ekf_export_map(hipStream_t st, const EkfState& E);
+// localization steps of EKF slots [first, first + count) in one launch (ekf_localize.h): the map stays frozen, only the pose block
+// is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder)
+void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
+                      const double* enc, int first, int count, int predict_first);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays

@@ -1404,3 +1404,5 @@ void launch_ekf_export_map(hipStream_t st, const EkfState& E) {
 }
 
 } // namespace aslam
+
+#include "ekf_localize.h"     // localization against a frozen map: k_loc_steps and its launcher

@@ -1,0 +1,265 @@
+// Localization against a frozen map: the reference's addImage update (src/aruco_slam.cpp:88-207) on a state whose
+// landmark blocks are fixed, mu_l frozen, Sigma_ll = 0, Sigma_xl = 0.  With those zero blocks K = Sigma Gx^T (Gx Sigma Gx^T + R)^-1
+// has zero landmark rows, so every correction reduces to the 3 x 3 pose block:
+//     S = H P H^T + R,   K = P H^T S^-1,   mu_x += K ze,   P <- (I - K H) P          (H = pose part of Gxm, P = Sigma_xx)
+// and the landmark rows of mu / Sigma are never written.  Included by ekf.hip (both the gfx950 build and the CPU emulation see it).
+//
+// k_loc_steps runs the EKF steps of slots [first, first + count) in ONE launch of one workgroup (128 lanes = one per observation):
+// per slot the lanes load the observations, look up the landmark index (unknown ids and gated observations are dropped before the
+// queue), rank the pop order, test "stationary" against the previous step's list and prepare every correction's H, ze and R; lane 0
+// keeps mu_x and P in registers across all slots and runs the predict and the dependent chain of 3 x 3 corrections.
+#pragma once
+#include "common.h"
+#include "ekf.h"
+#include "ekf_dev.h"
+
+namespace aslam {
+
+struct LocCorr {                     // one prepared correction: H (row-major 3 x 3), innovation, diag R
+    double H[9];
+    double ze[3];
+    double r[3];
+};
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                         const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                         int first, int count, int predict_first) {
+    __shared__ LastObs sLast[kMarkerMax];       // last_observed_marker_ of the previous step
+    __shared__ int sIndex[kMarkerMax];          // landmark index per observation slot (-2: dropped)
+    __shared__ int sOrder[kMarkerMax];          // pop order
+    __shared__ int sHeap[kMarkerMax];
+    __shared__ LocCorr sCorr[kMarkerMax];       // the step's corrections in pop order
+    __shared__ double sPose[3];                 // frame-start pose (after the predict)
+    __shared__ int sDup, sNl, sCnt[2], sUpdCnt[2], sStatCnt[2];
+    const int tid = threadIdx.x;
+    const int ld = E.ld;
+
+    double mx = 0, my = 0, mt = 0, P[9];        // lane 0: the pose and Sigma_xx, in registers for the whole launch
+    if (tid == 0) {
+        mx = E.d_mu[0]; my = E.d_mu[1]; mt = E.d_mu[2];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) P[i * 3 + j] = E.d_sigma[(size_t)j * ld + i];
+        sNl = min(*E.d_nlast, kMarkerMax);
+    }
+    sLast[tid] = E.d_last[tid];                 // entries beyond the list length are never read
+    __syncthreads();
+
+    for (int k = 0; k < count; k++) {
+        const int slot = first + k;
+        const int nM = (int)min(n_markers[slot], (unsigned)kMarkerMax);
+        // checkLandmark (aruco_slam.cpp:423-435): an id outside the map is dropped like a gated observation (never augmented)
+        ObsRaw o{};
+        int myIndex = -2;
+        if (tid < nM) {
+            o = obs[(size_t)slot * kMarkerMax + tid];
+            if (o.valid && o.id >= 0 && o.id < kIdTableSize) {
+                const int ix = E.d_id2idx[o.id];
+                if (ix >= 0) myIndex = ix;
+            }
+        }
+        sIndex[tid] = myIndex;
+        if (tid == 0) {
+            sDup = 0;
+            if (k > 0 || predict_first) {
+                // addEncoder (aruco_slam.cpp:35-73) on the pose block, the arithmetic of predict_block (ekf.hip) in the same order:
+                // with Sigma_xl = 0 the landmark rows and columns stay zero
+                const double* e = enc + (size_t)3 * slot;
+                const double wl = e[0], wr = e[1], dt = e[2];
+                double delta_enl = dt * wl, delta_enr = dt * wr;
+                double delta_sl = sp.kl * delta_enl, delta_sr = sp.kr * delta_enr;
+                double l_ = 2 * sp.b;
+                double delta_theta = (delta_sr - delta_sl) / l_;
+                double delta_s = 0.5 * (delta_sr + delta_sl);
+                double tmp_th = mt + 0.5 * delta_theta;
+                double c, s;
+                sincos(tmp_th, &s, &c);
+                double th = mt + delta_theta;
+                wrap1(th);
+                const double Hp[9] = {1.0, 0.0, -delta_s * s, 0.0, 1.0, delta_s * c, 0.0, 0.0, 1.0};
+                mx = mx + delta_s * c; my = my + delta_s * s; mt = th;
+                const double f = 0.5 * sp.kl * dt;                       // kl for BOTH wheels (quirk Q7)
+                double wkh[6] = {f * c, f * c, f * s, f * s, f * (1 / sp.b), f * (-1 / sp.b)};
+                double su0 = sp.Q_k * fabs(wl), su1 = sp.Q_k * fabs(wr);
+                double Q[9], T[9];
+                for (int i = 0; i < 3; i++)
+                    for (int j = 0; j < 3; j++) Q[i * 3 + j] = wkh[i * 2] * su0 * wkh[j * 2] + wkh[i * 2 + 1] * su1 * wkh[j * 2 + 1];
+                for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T[i * 3 + j] = Hp[i * 3] * P[j] + Hp[i * 3 + 1] * P[3 + j] + Hp[i * 3 + 2] * P[6 + j];
+                for (int i = 0; i < 3; i++)
+                    for (int j = 0; j < 3; j++)
+                        P[i * 3 + j] = (T[i * 3] * Hp[j * 3] + T[i * 3 + 1] * Hp[j * 3 + 1] + T[i * 3 + 2] * Hp[j * 3 + 2]) + Q[i * 3 + j];
+            }
+            sPose[0] = mx; sPose[1] = my; sPose[2] = mt;
+        }
+        {
+            const unsigned long long b = __ballot(myIndex >= 0);
+            if ((tid & 63) == 0) sCnt[tid >> 6] = __popcll(b);
+        }
+        __syncthreads();
+        // pop order: every key is a landmark index >= 0, so unless one id was detected twice it is ascending index -> rank in parallel
+        if (myIndex >= 0) {
+            int rank = 0;
+            for (int j = 0; j < nM; j++) {
+                const int kj = sIndex[j];
+                rank += (kj >= 0 && kj < myIndex);
+                if (j != tid && kj == myIndex) sDup = 1;
+            }
+            sOrder[rank] = tid;
+        }
+        __syncthreads();
+        if (tid == 0 && sDup) {
+            // one id twice: libstdc++ push_heap / pop_heap on the same keys (k_ekf_plan, oracle/ekf_literal.py::_Heap)
+            int len = 0;
+            for (int i = 0; i < nM; i++) {
+                if (sIndex[i] < 0) continue;
+                int hole = len++, value = i;
+                int parent = (hole - 1) / 2;
+                while (hole > 0 && sIndex[sHeap[parent]] > sIndex[value]) {
+                    sHeap[hole] = sHeap[parent];
+                    hole = parent;
+                    parent = (hole - 1) / 2;
+                }
+                sHeap[hole] = value;
+            }
+            int np = 0;
+            while (len > 0) {
+                sOrder[np++] = sHeap[0];
+                if (len > 1) {
+                    int value = sHeap[len - 1];
+                    sHeap[len - 1] = sHeap[0];
+                    int n = len - 1, hole = 0, second = 0;
+                    while (second < (n - 1) / 2) {
+                        second = 2 * (second + 1);
+                        if (sIndex[sHeap[second]] > sIndex[sHeap[second - 1]]) second--;
+                        sHeap[hole] = sHeap[second];
+                        hole = second;
+                    }
+                    if ((n & 1) == 0 && second == (n - 2) / 2) {
+                        second = 2 * (second + 1);
+                        sHeap[hole] = sHeap[second - 1];
+                        hole = second - 1;
+                    }
+                    int parent = (hole - 1) / 2;
+                    while (hole > 0 && sIndex[sHeap[parent]] > sIndex[value]) {
+                        sHeap[hole] = sHeap[parent];
+                        hole = parent;
+                        parent = (hole - 1) / 2;
+                    }
+                    sHeap[hole] = value;
+                }
+                len--;
+            }
+        }
+        __syncthreads();
+        const int np = sCnt[0] + sCnt[1];
+        const int nl = sNl;
+        // popped observation q = tid: "stationary" test against the previous step's list (aruco_slam.cpp:192-198), then the
+        // correction's operands from the frame-start pose (aruco_slam.cpp:116-143)
+        ObsRaw po{};
+        int pidx = -1, act = 0;
+        double pl[3] = {0, 0, 0};
+        if (tid < np) {
+            const int det = sOrder[tid];
+            pidx = sIndex[det];
+            po = obs[(size_t)slot * kMarkerMax + det];
+            bool stationary = false;
+            for (int j = 0; j < nl; j++)
+                if (sLast[j].id == po.id) {                              // std::find: first with the same id
+                    double d0 = sLast[j].z[0] - po.x, d1 = sLast[j].z[1] - po.y, d2 = sLast[j].z[2] - po.th;
+                    stationary = sqrt(d0 * d0 + d1 * d1 + d2 * d2) < 0.01;   // NaN compares false (Q2/Q3)
+                    break;
+                }
+            act = stationary ? 2 : 1;
+            const double* lm = E.d_mu + 3 + 3 * pidx;
+            pl[0] = lm[0]; pl[1] = lm[1]; pl[2] = lm[2];
+            PopRec pr;
+            pr.id = po.id; pr.index = pidx; pr.action = act; pr.det = det;
+            pr.z[0] = po.x; pr.z[1] = po.y; pr.z[2] = po.th;
+            pr.r[0] = po.r[0]; pr.r[1] = po.r[1]; pr.r[2] = po.r[2];
+            if (k == count - 1) E.d_pop[tid] = pr;
+        }
+        const unsigned long long bU = __ballot(act == 1), bS = __ballot(act == 2);
+        if ((tid & 63) == 0) { sUpdCnt[tid >> 6] = __popcll(bU); sStatCnt[tid >> 6] = __popcll(bS); }
+        __syncthreads();                                                 // every lane finished reading sLast / sOrder
+        const int m = sUpdCnt[0] + sUpdCnt[1];
+        if (act == 1) {
+            const int up = (tid >= 64 ? sUpdCnt[0] : 0) + __popcll(bU & ((1ull << (tid & 63)) - 1ull));
+            const double x = sPose[0], y = sPose[1], theta = sPose[2];
+            double sintheta, costheta;
+            sincos(theta, &sintheta, &costheta);
+            double gdx = pl[0] - x, gdy = pl[1] - y, gdth = pl[2] - theta;
+            wrap1(gdth);
+            const double zh0 = gdx * costheta + gdy * sintheta, zh1 = -gdx * sintheta + gdy * costheta;
+            LocCorr cr;
+            cr.ze[0] = po.x - zh0; cr.ze[1] = po.y - zh1; cr.ze[2] = po.th - gdth;
+            wrap1(cr.ze[2]);
+            cr.H[0] = -costheta; cr.H[1] = -sintheta; cr.H[2] = -gdx * sintheta + gdy * costheta;
+            cr.H[3] = sintheta;  cr.H[4] = -costheta; cr.H[5] = -gdx * costheta - gdy * sintheta;
+            cr.H[6] = 0.0;       cr.H[7] = 0.0;       cr.H[8] = -1.0;
+            cr.r[0] = po.r[0]; cr.r[1] = po.r[1]; cr.r[2] = po.r[2];
+            sCorr[up] = cr;
+        }
+        // last_observed_marker_ = observed_marker (aruco_slam.cpp:263); last_observation_ is set in the update branch only
+        if (tid < np) {
+            LastObs lo;
+            lo.id = po.id; lo.pad = 0;
+            if (act == 1) { lo.z[0] = po.x; lo.z[1] = po.y; lo.z[2] = po.th; }
+            else { lo.z[0] = lo.z[1] = lo.z[2] = nan(""); }
+            sLast[tid] = lo;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            // the dependent chain: m sequential corrections of the pose block (aruco_slam.cpp:145-205 with zero landmark blocks)
+            for (int q = 0; q < m; q++) {
+                const LocCorr& cr = sCorr[q];
+                double H[9], HP[9], PHt[9], S[9], Si[9], K[9], A[9], Pn[9];
+#pragma unroll
+                for (int i = 0; i < 9; i++) H[i] = cr.H[i];
+                mul3(H, P, HP);                                          // H P
+#pragma unroll
+                for (int i = 0; i < 3; i++)
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        PHt[i * 3 + j] = P[i * 3] * H[j * 3] + P[i * 3 + 1] * H[j * 3 + 1] + P[i * 3 + 2] * H[j * 3 + 2];   // P H^T
+                        S[i * 3 + j] = HP[i * 3] * H[j * 3] + HP[i * 3 + 1] * H[j * 3 + 1] + HP[i * 3 + 2] * H[j * 3 + 2]       // H P H^T
+                                       + (i == j ? cr.r[i] : 0.0);
+                    }
+                inv3_reg(S, Si);
+                mul3(PHt, Si, K);                                        // K_x = P H^T S^-1
+                mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
+                my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
+                mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
+                mul3(K, H, A);                                           // I - K H
+#pragma unroll
+                for (int i = 0; i < 9; i++) A[i] = ((i % 4) == 0 ? 1.0 : 0.0) - A[i];
+                mul3(A, P, Pn);
+#pragma unroll
+                for (int i = 0; i < 9; i++) P[i] = Pn[i];
+            }
+            sNl = np;
+            if (slot < E.max_slots) {                                    // detections, appended (never), corrections, no-ops
+                int* st = E.d_slot_stat + 4 * slot;
+                st[0] = nM; st[1] = 0; st[2] = m; st[3] = sStatCnt[0] + sStatCnt[1];
+            }
+            if (k == count - 1) { *E.d_npop = np; *E.d_m = m; }
+        }
+        __syncthreads();
+    }
+    if (tid < sNl) E.d_last[tid] = sLast[tid];
+    if (tid == 0) {
+        *E.d_nlast = sNl;
+        E.d_mu[0] = mx; E.d_mu[1] = my; E.d_mu[2] = mt;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) E.d_sigma[(size_t)j * ld + i] = P[i * 3 + j];
+    }
+}
+
+void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
+                      const double* enc, int first, int count, int predict_first) {
+    hipLaunchKernelGGL(k_loc_steps, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
+}
+
+} // namespace aslam

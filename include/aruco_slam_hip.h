@@ -202,6 +202,33 @@ int aslam_draw_detected_markers(aslam_ctx* ctx, uint8_t* bgr, int rows, int cols
  * the crossed roll / yaw fallbacks) into marker messages (frame "world", rgba (1,1,1,.5)).  Host only; ctx may be NULL. */
 int aslam_load_map_txt(aslam_ctx* ctx, const char* path, int max, int* n, aslam_marker_msg* out);
 
+/* ---- localization: track the pose against a fixed, known marker map (no reference counterpart) ----------------
+ * The reference's addImage update (aruco_slam.cpp:88-207) applied to a state whose landmark blocks are frozen: mu_l fixed,
+ * Sigma_ll = 0, Sigma_xl = 0.  With those zero blocks the reference's K has zero landmark rows, so every correction is
+ *     S = H Sigma_xx H^T + R,  K_x = Sigma_xx H^T S^-1,  mu_x += K_x ze,  Sigma_xx <- (I - K_x H) Sigma_xx     (H = pose part of Gxm)
+ * and the landmark rows and blocks stay bit for bit unchanged.  Everything else is the reference's: the predict, the observation
+ * assembly and its gates, z_hat from the frame-start pose, the single normAngle wrap, the "stationary" no-op against the previous
+ * step's list.  An observation whose id is not in the map is dropped before the queue like a gated one: nothing is ever appended.
+ * The state keeps the SLAM layout (mu = [pose, map], Sigma = blockdiag(Sigma_xx, 0)), so the state, pose, map, export and gather
+ * getters and aslam_save_state work unchanged.  While localizing, every image entry point (aslam_add_image, aslam_run_staged,
+ * aslam_add_images, aslam_run_staged_rig, the host-fed stream) runs localization steps: one kernel launch per call, behind the
+ * detection, never counted by aslam_get_plan_stats; the EKF stats report 0 landmarks appended; aslam_get_observations lists the
+ * popped (known-id) observations with action 1 or 2 and their map index.  aslam_set_state / aslam_load_state refuse with
+ * ASLAM_E_STATE.  Every marker has the one init.marker_length (per-marker lengths of a map file are not used), and only a
+ * landmark's (x, y, heading) enters: the map's z, roll and pitch do not. */
+/* enter localization: state := [pose, map], Sigma := blockdiag(pose_sigma, 0), id tables := map, last-observed list cleared;
+   arming (is_init / last_time) untouched.  1 <= n <= max_landmarks, ids unique in [0, 1024), finite values, pose_sigma symmetric. */
+int aslam_localize_begin(aslam_ctx* ctx, int n, const int* ids, const double* xyth /* n x 3 */,
+                         const double pose[3], const double pose_sigma[9] /* row-major */);
+/* leave it: the state stays as it is and later steps are SLAM steps (new ids augment again) */
+int aslam_localize_end(aslam_ctx* ctx);
+int aslam_is_localizing(aslam_ctx* ctx, int* on);
+/* host only, ctx may be NULL: MapLoader markers (aslam_load_map_txt) -> planar landmarks: id, (x, y) = position,
+   theta = normAngle(atan2(r_y, r_x)) with r = third column of Matrix3x3(orientation) (the marker's +z axis, which is what
+   the observation's atan2(-R02, R22) measures); refuses (ASLAM_E_INVALID, names the id in aslam_last_error(NULL)) a marker
+   whose +z axis has no horizontal component (|(r_x, r_y)| < 1e-6) */
+int aslam_landmarks_from_markers(int n, const aslam_marker_msg* in, int* ids, double* xyth);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
