@@ -24,10 +24,11 @@
 //   k_ekf_win_step    one launch per piece, three roles by workgroup:
 //     chain   (workgroup 0) walks the steps of piece i.  P lives in the f64 matrix-core accumulators of the worker waves for the
 //             whole piece (wave w: RW tile rows of T 16 x 16 tiles); a step is one v_mfma_f64_16x16x4_f64 per tile (depth 3 or 4).
-//             A separate "prepare" wave (lane = column) runs one step AHEAD: the workers publish the six rows (pose + landmark) of
-//             step j + 2 as they stand after step j, the prepare wave applies step j + 1's correction to them itself from the
-//             operands of the previous step, forms c, S, S^-1, Kt and hands the operands to the workers: one barrier per step.  It
-//             also logs -Kt, S^-1, ze and the Jacobian scalars;
+//             A separate "prepare" wave (lane = column) runs one step AHEAD: the workers publish the three landmark rows of step
+//             j + 2 as they stand after step j, the prepare wave applies step j + 1's correction to them and to the pose rows it
+//             carries in its own registers, forms c, S, S^-1, Kt and hands the operands to the workers: one barrier per step.  The
+//             workers log -Kt (the A operand they read) and worker wave 0 the header the prepare wave leaves in LDS (S^-1, ze, the
+//             Jacobian scalars);
 //     replay  (SP / 8 workgroups) replays the log of piece i - 1, each on its own 8 columns of Lambda (all rows; in LDS) and its
 //             part of psi, and logs t and u;
 //     Psi     (T workgroups) adds the t^T u of piece i - 2 to Psi on the matrix cores.
@@ -127,7 +128,11 @@ template <int T> struct WinChainLds {
     static constexpr int SP = 16 * T, SPP = SP + 16, NSMAX = kWinPieceMax * 64;
     double sA[2][4][SPP];                  // a step's A operand rows  Aop[k][row]   (P += Aop^T Bop)
     double sB[2][4][SPP];                  // ... and B operand rows   Bop[k][column]
-    double sPub[2][6][SPP];                // rows 0..2 (pose) and the landmark rows of the step after next
+    double sPub[2][3][SPP];                // the landmark rows of the step after next
+    double sHdr[2][kWinHdr];               // a step's log header, from the prepare wave to worker wave 0 (which stores it)
+#ifdef ASLAM_WIN_POSE_CHECK
+    double sDbg[2][3][SPP];                // the accumulators' pose rows, to compare with the prepare wave's own
+#endif
     double sMu[SPP];                       // prepare wave's scratch: mu_S by position
     int sS[SP];
     int sOff[kWinPieceMax + 1];
@@ -151,7 +156,8 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     const int li = lane & 15, lk = lane >> 4;
     for (int e = tid; e < SP; e += NT) sS[e] = e < s ? win_state_index(wd, e) : 0;
     for (int e = tid; e < 2 * 4 * SPP; e += NT) { (&sA[0][0][0])[e] = 0.0; (&sB[0][0][0])[e] = 0.0; }
-    for (int e = tid; e < 2 * 6 * SPP; e += NT) (&sPub[0][0][0])[e] = 0.0;
+    for (int e = tid; e < 2 * 3 * SPP; e += NT) (&sPub[0][0][0])[e] = 0.0;
+    for (int e = tid; e < 2 * kWinHdr; e += NT) (&L.sHdr[0][0])[e] = 0.0;
     // steps per frame (1 predict + m corrections), every frame's count loaded by its own thread (one thread walking the plan would
     // pay one dependent global load per frame), then the running sum
     if (tid < wd.K) sOff[tid + 1] = 1 + frames[wd.first_slot + tid].m;
@@ -172,11 +178,12 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     }
     __syncthreads();
 
+    const double* Pimg = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
+    const bool from_img = wd.piece != 0 || wd.from_image != 0;
+    double* const logbase = E.d_win_log + (size_t)wd.log0 * win_log_stride(T);
     if (wave < NWK) {
         // =================================== worker waves: P in the accumulators ===================================
         v4d acc[RW][T];
-        const double* Pimg = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
-        const bool from_img = wd.piece != 0 || wd.from_image != 0;
 #pragma unroll
         for (int rr = 0; rr < RW; rr++)
 #pragma unroll
@@ -191,16 +198,14 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     }
                     acc[rr][t][reg] = v;
                 }
-        // rows of step 0 (pose rows only: a predict) and of step 1, as they stand before any step
-        if (wave == 0) {
+        // landmark rows of step 1 as they stand before any step (step 0 is a predict; the prepare wave carries the pose rows itself)
+#ifdef ASLAM_WIN_POSE_CHECK
+        if (wave == 0 && lk < 3) {
 #pragma unroll
-            for (int q = 0; q < 3; q++)
-                if (lk == q) {
-#pragma unroll
-                    for (int t = 0; t < T; t++) { sPub[0][q][16 * t + li] = acc[0][t][0]; sPub[1][q][16 * t + li] = acc[0][t][0]; }
-                }
+            for (int t = 0; t < T; t++) { L.sDbg[0][lk][16 * t + li] = acc[0][t][0]; L.sDbg[1][lk][16 * t + li] = acc[0][t][0]; }
         }
-        if (NS > 1 && sPos[1] != 255) win_publish<T, RW>(acc, 3 + 3 * sPos[1], wave, lk, li, &sPub[1][3][0], SPP);
+#endif
+        if (NS > 1 && sPos[1] != 255) win_publish<T, RW>(acc, 3 + 3 * sPos[1], wave, lk, li, &sPub[1][0][0], SPP);
         ASLAM_LDS_BARRIER();
 #ifdef ASLAM_WIN_STAMPS
         long long stamp_acc[4] = {0, 0, 0, 0}, stamp_last = clock64();
@@ -209,6 +214,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
             WSTAMP(0);
             if (j >= 0) {
                 const int cb = j & 1;
+                double* const log = logbase + (size_t)j * win_log_stride(T);
                 double b[T];
 #pragma unroll
                 for (int t = 0; t < T; t++) b[t] = sB[cb][lk][16 * t + li];
@@ -218,18 +224,18 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     const double a = sA[cb][lk][16 * (wave * RW + rr) + li];
 #pragma unroll
                     for (int t = 0; t < T; t++) acc[rr][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[t], acc[rr][t], 0, 0, 0);
+                    if (lk < 3) log[lk * SP + 16 * (wave * RW + rr) + li] = a;     // the step's log rows: -Kt (predict: its rows 0..2)
                 }
-                if (j + 2 < NS) {                                   // rows of step j + 2 as they stand after step j
-                    if (wave == 0) {
+                if (wave == 0 && lane < kWinHdr) log[3 * SP + lane] = L.sHdr[cb][lane];
+                if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
+#ifdef ASLAM_WIN_POSE_CHECK
+                    if (wave == 0 && lk < 3) {
 #pragma unroll
-                        for (int q = 0; q < 3; q++)
-                            if (lk == q) {
-#pragma unroll
-                                for (int t = 0; t < T; t++) sPub[cb][q][16 * t + li] = acc[0][t][0];
-                            }
+                        for (int t = 0; t < T; t++) L.sDbg[cb][lk][16 * t + li] = acc[0][t][0];
                     }
+#endif
                     const int pn = sPos[j + 2];
-                    if (pn != 255) win_publish<T, RW>(acc, 3 + 3 * pn, wave, lk, li, &sPub[cb][3][0], SPP);
+                    if (pn != 255) win_publish<T, RW>(acc, 3 + 3 * pn, wave, lk, li, &sPub[cb][0][0], SPP);
                 }
             }
             WSTAMP(1);
@@ -258,17 +264,22 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     __builtin_amdgcn_s_setprio(3);                                  // the critical path of the kernel: wins the issue slot over the worker wave it shares a SIMD with
 #endif
     const double kl = sp.kl, kr = sp.kr, inv2b = 1.0 / (2 * sp.b), invb = 1 / sp.b, Qk = sp.Q_k;
-    double* const logbase = E.d_win_log + (size_t)wd.log0 * win_log_stride(T);
     double* const muimg = E.d_win_small + wsm_MU(E.win_sp_max, wd.wpar);
     double mu[NC], pB[4][NC];
+    double rp[3][NC];                                              // the pose rows of P, carried here (the workers publish landmark rows only)
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         const int col = lane + 64 * c;
         // mu_S travels between the pieces of a window in its image; only the window's last piece puts it back into the state
-        mu[c] = col >= s ? 0.0 : (wd.piece != 0 || wd.from_image != 0) ? muimg[col] : E.d_mu[sS[col]];
+        mu[c] = col >= s ? 0.0 : from_img ? muimg[col] : E.d_mu[sS[col]];
 #pragma unroll
         for (int k = 0; k < 4; k++) pB[k][c] = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; q++) rp[q][c] = from_img ? Pimg[(size_t)q * SP + col] : col < s ? E.d_sigma[(size_t)sS[col] * ld + sS[q]] : 0.0;   // (as the workers load them)
     }
+#ifdef ASLAM_WIN_POSE_CHECK
+    double dmax = 0.0, dend = 0.0;
+#endif
     // per-frame records, lane a = correction a of the frame (aruco_slam.cpp:119-143 at the frozen mean)
     double rze0 = 0, rze1 = 0, rze2 = 0, rR0 = 0, rR1 = 0, rR2 = 0, rg02 = 0, rg12 = 0;
     double cth = 1.0, sth = 0.0;
@@ -294,26 +305,46 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
             const int lrow = is_predict ? 0 : 3 + 3 * pos;         // first landmark row (a predict has none: copies of the pose rows)
             double r[6][NC];
 #pragma unroll
-            for (int i = 0; i < 6; i++)
+            for (int c = 0; c < NC; c++) {
+                r[0][c] = rp[0][c]; r[1][c] = rp[1][c]; r[2][c] = rp[2][c];
+                r[3][c] = sPub[nb][0][lane + 64 * c]; r[4][c] = sPub[nb][1][lane + 64 * c]; r[5][c] = sPub[nb][2][lane + 64 * c];
+            }
+#ifdef ASLAM_WIN_POSE_CHECK
+            dend = 0.0;
 #pragma unroll
-                for (int c = 0; c < NC; c++) r[i][c] = sPub[nb][i][lane + 64 * c];
+            for (int q = 0; q < 3; q++)
+#pragma unroll
+                for (int c = 0; c < NC; c++) dend = fmax(dend, fabs(r[q][c] - L.sDbg[nb][q][lane + 64 * c]));
+            dmax = fmax(dmax, dend);
+#endif
             if (j >= 0) {
                 // step j's correction of these rows: P[R][col] += sum_k Aop_j[k][R] Bop_j[k][col]
+                const int kd = prev_predict ? 4 : 3;                // a correction has depth 3
+                double f[4][6];
 #pragma unroll
                 for (int kk = 0; kk < 4; kk++) {
-                    if (kk == 3 && !prev_predict) break;            // a correction has depth 3
-                    const double f0 = sA[pb][kk][0], f1 = sA[pb][kk][1], f2 = sA[pb][kk][2];      // (LDS broadcast reads: measured faster than v_readlane)
-                    const double f3 = sA[pb][kk][lrow], f4 = sA[pb][kk][lrow + 1], f5 = sA[pb][kk][lrow + 2];
+                    if (kk >= kd) break;
+                    f[kk][0] = sA[pb][kk][0]; f[kk][1] = sA[pb][kk][1]; f[kk][2] = sA[pb][kk][2];      // (LDS broadcast reads: measured faster than v_readlane)
+                    f[kk][3] = sA[pb][kk][lrow]; f[kk][4] = sA[pb][kk][lrow + 1]; f[kk][5] = sA[pb][kk][lrow + 2];
+                }
+#ifdef ASLAM_WIN_STAMPS
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (stamps only: the reads' wait apart from the FMAs)
+                WSTAMP(7);
+#endif
+#pragma unroll
+                for (int kk = 0; kk < 4; kk++) {
+                    if (kk >= kd) break;
 #pragma unroll
                     for (int c = 0; c < NC; c++) {
-                        r[0][c] = fma(f0, pB[kk][c], r[0][c]); r[1][c] = fma(f1, pB[kk][c], r[1][c]); r[2][c] = fma(f2, pB[kk][c], r[2][c]);
-                        r[3][c] = fma(f3, pB[kk][c], r[3][c]); r[4][c] = fma(f4, pB[kk][c], r[4][c]); r[5][c] = fma(f5, pB[kk][c], r[5][c]);
+                        r[0][c] = fma(f[kk][0], pB[kk][c], r[0][c]); r[1][c] = fma(f[kk][1], pB[kk][c], r[1][c]); r[2][c] = fma(f[kk][2], pB[kk][c], r[2][c]);
+                        r[3][c] = fma(f[kk][3], pB[kk][c], r[3][c]); r[4][c] = fma(f[kk][4], pB[kk][c], r[4][c]); r[5][c] = fma(f[kk][5], pB[kk][c], r[5][c]);
                     }
                 }
             }
+#pragma unroll
+            for (int c = 0; c < NC; c++) { rp[0][c] = r[0][c]; rp[1][c] = r[1][c]; rp[2][c] = r[2][c]; }
             WSTAMP(1);
-            double* log = logbase + (size_t)n * win_log_stride(T);
-            double* hdr = log + 3 * SP;
+            double* const hdr = L.sHdr[nb];
             double A[4][NC], B[4][NC];
             if (is_predict) {
 #ifdef ASLAM_WIN_STAMPS
@@ -451,22 +482,21 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     for (int c = 0; c < NC; c++) { sA[nb][3][lane + 64 * c] = 0.0; sB[nb][3][lane + 64 * c] = 0.0; }
                     if (nb) dirty1 = false; else dirty0 = false;
                 }
-                // header of the logged step, stored by the lanes that hold the values
+                // header of the logged step (to LDS: worker wave 0 stores it to the log)
                 if (lane == 0) {
                     hdr[WH_TYPE] = 1.0; hdr[WH_POS] = (double)pos;
 #pragma unroll
                     for (int q = 0; q < 9; q++) hdr[WH_SI + q] = Si[q];
+                    hdr[WH_ZE] = ze0; hdr[WH_ZE + 1] = ze1; hdr[WH_ZE + 2] = ze2; hdr[WH_G02] = g02; hdr[WH_G12] = g12;
                 }
-                if (lane == a) { hdr[WH_ZE] = rze0; hdr[WH_ZE + 1] = rze1; hdr[WH_ZE + 2] = rze2; hdr[WH_G02] = rg02; hdr[WH_G12] = rg12; }
                 WSTAMP(5);
             }
-            // operands to the workers, the log, and this wave's own copy
+            // operands to the workers (who also log them), and this wave's own copy
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 const int col = lane + 64 * c;
                 sA[nb][0][col] = A[0][c]; sA[nb][1][col] = A[1][c]; sA[nb][2][col] = A[2][c];
                 if (is_predict) { sB[nb][0][col] = B[0][c]; sB[nb][1][col] = B[1][c]; sB[nb][2][col] = B[2][c]; }
-                log[col] = A[0][c]; log[SP + col] = A[1][c]; log[2 * SP + col] = A[2][c];
 #pragma unroll
                 for (int kk = 0; kk < 4; kk++) pB[kk][c] = B[kk][c];
             }
@@ -478,10 +508,14 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
     if (lane == 0 && wd.piece == 1) {
         const int nc = NS - n_pred;
-        printf("prepare T %d steps %d (%d predict): barrier %lld | rows+correct %lld | predict path %lld per predict | c %lld S+inv %lld Kt+hdr %lld per correction | operands+log %lld per step\n",
-               T, NS, n_pred, stamp_acc[0] / (NS + 1), stamp_acc[1] / NS, stamp_acc[2] / (n_pred ? n_pred : 1), stamp_acc[3] / (nc ? nc : 1), stamp_acc[4] / (nc ? nc : 1),
+        printf("prepare T %d steps %d (%d predict): barrier %lld | rows wait %lld correct %lld | predict path %lld per predict | c %lld S+inv %lld Kt+hdr %lld per correction | operands+log %lld per step\n",
+               T, NS, n_pred, stamp_acc[0] / (NS + 1), stamp_acc[7] / NS, stamp_acc[1] / NS, stamp_acc[2] / (n_pred ? n_pred : 1), stamp_acc[3] / (nc ? nc : 1), stamp_acc[4] / (nc ? nc : 1),
                stamp_acc[5] / (nc ? nc : 1), stamp_acc[6] / NS);
     }
+#endif
+#ifdef ASLAM_WIN_POSE_CHECK
+    // the last comparison is of the rows as they stand after step NS - 2: the step before the piece's last
+    if (lane == 0) printf("pose-check T %d piece %d steps %d: max |prepare - accumulator| pose rows %.3e over the piece, %.3e at its end\n", T, wd.piece, NS, dmax, dend);
 #endif
     // ---- mu_S for the next piece; back into the state at the window's end ----
 #pragma unroll
