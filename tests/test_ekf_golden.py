@@ -1,4 +1,5 @@
-"""The device EKF (plan / gather / small / T / update kernels) replayed on the committed golden vectors of the numpy
+"""The device EKF's per-frame chains (fast: cap <= 24, medium: cap <= 64, general: above; every replay checks which one ran)
+replayed on the committed golden vectors of the numpy
 literal transcription (oracle/ekf_literal.py): observations are formed in Python exactly as the reference does
 (aruco_slam.cpp:325-374), injected into the slots, and only the EKF steps run.  Covers what the rendered scenes cannot:
 duplicate ids in one frame (Q10), the "stationary" branch (Q2), range/covariance gates, many new landmarks per frame
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 from aruco_slam_amd import capi
+from ekf_reference import CHAIN_KERNELS, chain_of, ekf_kernels_run
 from oracle.ekf_literal import LiteralSlam
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ekf_literal_*.npz")))
@@ -37,6 +39,8 @@ def replay(path, batch, max_updates=24):
         xyth = [np.zeros(3) if o is None else o["z"] for o in obs]
         Rd = [np.ones(3) if o is None else np.diag(o["R"]) for o in obs]
         ctx.inject_observations(f, ids, valid, np.array(xyth).reshape(-1, 3), np.array(Rd).reshape(-1, 3))
+    ctx.profile_enable(True)
+    ctx.profile_reset()
     seen = np.zeros(3, int)
     for f0 in range(0, nfr, batch):
         nb = min(batch, nfr - f0)
@@ -50,6 +54,9 @@ def replay(path, batch, max_updates=24):
         assert np.allclose(mu, g[f"out{f}_mu"], rtol=1e-9, atol=1e-11)
         assert np.abs(S - g[f"out{f}_sigma"]).max() <= 1e-9 * np.abs(S).max()
         seen += np.bincount(act, minlength=3)[:3]
+    # the per-frame chain the cap selects (capi.hip: run_ekf_frame) and no other; windows may run beside it
+    ran = {k for k in ekf_kernels_run(ctx.profile_get()) if not k.startswith("k_ekf_win")}
+    assert ran == CHAIN_KERNELS[chain_of(max_updates)], f"max_updates_per_frame {max_updates}: ran {sorted(ran)}"
     return seen
 
 
@@ -65,16 +72,19 @@ def test_device_ekf_replays_golden_batched(path):
 
 
 def test_device_ekf_general_chain():
-    """max_updates_per_frame > 24 selects the general 5-kernel chain (used by 50-marker frames)"""
-    replay(GOLDEN[2], batch=1, max_updates=64)
+    """max_updates_per_frame > 64 selects the general chain (gather, small, T, update); 65 is its smallest cap"""
+    replay(GOLDEN[2], batch=1, max_updates=65)
 
 
 def test_device_ekf_medium_chain():
-    """25 .. 64 updates per frame: register-block Gauss-Jordan with 2 x 2 blocks per thread + the f64 MFMA covariance update"""
+    """max_updates_per_frame 25 .. 64 selects the medium chain: register-block Gauss-Jordan with 2 x 2 blocks per thread
+    (k_ekf_mid64), then T and the f64 MFMA covariance update; 64 is its largest cap"""
     replay(GOLDEN[2], batch=1, max_updates=48)
+    replay(GOLDEN[2], batch=1, max_updates=64)
 
 
 def test_device_ekf_general_chain_above_64():
+    """the general chain at cap 100"""
     replay(GOLDEN[1], batch=1, max_updates=100)
 
 

@@ -1,57 +1,20 @@
 """The medium EKF chain (k_ekf_mid64 -> k_ekf_T -> k_ekf_update_mfma) at a state size where the update really is a dense
 contraction (N = 1503 / 3003 is what cfg3 runs at): one predict + 50 fused corrections against a numpy restatement of the
 reference's sequential recursion (aruco_slam.cpp:35-73, 108-207) written in its rank-3 form
-(sigma <- sigma - K (Gx sigma), the same products the reference forms with dense N x N matrices)."""
+(tests/ekf_reference.py: sigma <- sigma - K (Gx sigma), the same products the reference forms with dense N x N matrices)."""
 import math
 
 import numpy as np
 import pytest
 
 from aruco_slam_amd import capi
+from ekf_reference import reference_step, wrap_once
 
 pytestmark = pytest.mark.gpu
 
 
 def wrap(a):
-    if a >= math.pi:
-        a -= 2 * math.pi
-    if a < -math.pi:
-        a += 2 * math.pi
-    return a
-
-
-def reference_step(mu, S, wl, wr, dt, obs, kl=0.05, kr=0.05, b=0.09, Qk=0.01):
-    """addEncoder + addImage for already-mapped landmarks; obs = [(index, z(3), Rdiag(3))] in pop order (ascending index)"""
-    mu = mu.copy(); S = S.copy()
-    dsl, dsr = kl * dt * wl, kr * dt * wr
-    dth = (dsr - dsl) / (2 * b); ds = 0.5 * (dsr + dsl)
-    th = mu[2] + 0.5 * dth
-    c, s = math.cos(th), math.sin(th)
-    mu[0] += ds * c; mu[1] += ds * s; mu[2] = wrap(mu[2] + dth)
-    H = np.array([[1, 0, -ds * s], [0, 1, ds * c], [0, 0, 1.0]])
-    f = 0.5 * kl * dt
-    wkh = np.array([[f * c, f * c], [f * s, f * s], [f / b, -f / b]])
-    Q = wkh @ np.diag([Qk * abs(wl), Qk * abs(wr)]) @ wkh.T
-    S[:3, :] = H @ S[:3, :]
-    S[:, :3] = S[:, :3] @ H.T
-    S[:3, :3] += Q
-    mu0 = mu.copy()                                           # every correction is linearised at the pre-frame mean (Q1)
-    for idx, z, Rd in obs:
-        li = 3 + 3 * idx
-        st, ct = math.sin(mu0[2]), math.cos(mu0[2])
-        dx, dy = mu0[li] - mu0[0], mu0[li + 1] - mu0[1]
-        dth = wrap(mu0[li + 2] - mu0[2])
-        zh = np.array([dx * ct + dy * st, -dx * st + dy * ct, dth])
-        ze = z - zh
-        ze[2] = wrap(ze[2])
-        G = np.array([[-ct, -st, -dx * st + dy * ct, ct, st, 0], [st, -ct, -dx * ct - dy * st, -st, ct, 0], [0, 0, -1, 0, 0, 1.0]])
-        cols = [0, 1, 2, li, li + 1, li + 2]
-        GS = G @ S[cols, :]                                    # Gx * sigma_   (3 x N)
-        Sk = GS[:, cols] @ G.T + np.diag(Rd)
-        K = S[:, cols] @ G.T @ np.linalg.inv(Sk)               # sigma_ * Gx^T * S^-1
-        mu += K @ ze
-        S -= K @ GS
-    return mu, S
+    return float(wrap_once(a))
 
 
 @pytest.mark.parametrize("L,M", [(500, 50), (1000, 40)])
@@ -82,7 +45,7 @@ def test_medium_chain_at_dense_update_size(L, M):
     ctx.run_staged(0, 2, with_ekf=2)
     ctx.sync()
     mu_g, S_g = ctx.get_state()
-    mu_r, S_r = reference_step(mu, S, 2.0, 2.3, 1 / 30.0, obs)
+    mu_r, S_r = reference_step(mu, S, 2.0, 2.3, 1 / 30.0, obs, dtype=np.float64)
     gi, gx, ga, _, _ = ctx.get_observations()
     assert np.array_equal(gx, seen) and (ga == 1).all()
     assert np.allclose(mu_g, mu_r, rtol=1e-9, atol=1e-11)
