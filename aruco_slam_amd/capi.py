@@ -66,6 +66,7 @@ class DetectorParams(C.Structure):
 
 
 MAX_CAMERAS = 8
+MAX_ROBOTS = 256
 
 
 class Camera(C.Structure):
@@ -122,6 +123,13 @@ _SIGS = {
     "aslam_localize_end": (C.c_int, [C.c_void_p]),
     "aslam_is_localizing": (C.c_int, [C.c_void_p, _ip]),
     "aslam_landmarks_from_markers": (C.c_int, [C.c_int, C.c_void_p, _ip, _dp]),
+    "aslam_fleet_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _ip, _dp, _dp, _dp]),
+    "aslam_fleet_add_images": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _P(C.c_void_p), C.c_int, C.c_int, C.c_int, _P(C.c_size_t)]),
+    "aslam_fleet_run_staged": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int]),
+    "aslam_fleet_get_poses": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
+    "aslam_fleet_set_pose": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "aslam_fleet_end": (C.c_int, [C.c_void_p]),
+    "aslam_is_fleet": (C.c_int, [C.c_void_p, _ip]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -369,6 +377,60 @@ class Context:
         on = C.c_int(0)
         self._ck(self.lib.aslam_is_localizing(self.h, C.byref(on)))
         return bool(on.value)
+    # -- fleet localization: many robots, one camera each, on one frozen map ----------------------------
+    def fleet_begin(self, cams, ids, xyth, poses, pose_sigmas):
+        """cams: one Camera (or (K, D, mount) tuple) per robot; poses R x 3, pose_sigmas R x 3 x 3; map as localize_begin"""
+        cams = [c if isinstance(c, Camera) else Camera.make(*c) for c in cams]
+        arr = (Camera * max(len(cams), 1))(*cams)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        xyth = np.ascontiguousarray(xyth, dtype=np.float64).reshape(-1, 3)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        sig = np.ascontiguousarray(pose_sigmas, dtype=np.float64).reshape(-1, 9)
+        self._ck(self.lib.aslam_fleet_begin(self.h, len(cams), arr, int(ids.size), _ptr(ids, _ip), _ptr(xyth, _dp), _ptr(poses, _dp),
+                                            _ptr(sig, _dp)))
+
+    def fleet_add_images(self, robots, imgs, wl, wr, dt):
+        """one synchronous call: imgs[i] (all of one size) is robot robots[i]'s frame, after its encoder sample (wl[i], wr[i], dt[i])"""
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise ValueError("the images of a fleet call must all have the same size and channels")
+        rows, cols = imgs[0].shape[:2]
+        ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
+        robots = np.ascontiguousarray(robots, dtype=np.int32)
+        wl, wr, dt = (np.ascontiguousarray(v, dtype=np.float64) for v in (wl, wr, dt))
+        ptrs = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        steps = (C.c_size_t * len(imgs))(*[im.strides[0] for im in imgs])
+        self._ck(self.lib.aslam_fleet_add_images(self.h, len(imgs), _ptr(robots, _ip), _ptr(wl, _dp), _ptr(wr, _dp), _ptr(dt, _dp), ptrs,
+                                                 rows, cols, ch, steps))
+
+    def fleet_run_staged(self, first, robot_of_slot, with_ekf=True):
+        """staged slots first .. first + len(robot_of_slot) - 1; slot first + i is robot robot_of_slot[i]'s frame"""
+        rs = np.ascontiguousarray(robot_of_slot, dtype=np.int32)
+        self._ck(self.lib.aslam_fleet_run_staged(self.h, int(first), int(rs.size), _ptr(rs, _ip), int(with_ekf)))
+
+    def fleet_get_poses(self):
+        """(R x 3 poses, R x 3 x 3 Sigma_xx)"""
+        n = C.c_int()
+        self._ck(self.lib.aslam_fleet_get_poses(self.h, 0, C.byref(n), None, None))
+        R = n.value
+        poses = np.zeros((R, 3)); sig = np.zeros((R, 3, 3))
+        self._ck(self.lib.aslam_fleet_get_poses(self.h, R, C.byref(n), _ptr(poses, _dp), _ptr(sig, _dp)))
+        return poses, sig
+
+    def fleet_set_pose(self, robot, pose, sigma):
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3)
+        sig = np.ascontiguousarray(sigma, dtype=np.float64).reshape(9)
+        self._ck(self.lib.aslam_fleet_set_pose(self.h, int(robot), _ptr(pose, _dp), _ptr(sig, _dp)))
+
+    def fleet_end(self):
+        self._ck(self.lib.aslam_fleet_end(self.h))
+
+    def is_fleet(self):
+        """robots of the active fleet, 0 outside fleet mode"""
+        n = C.c_int()
+        self._ck(self.lib.aslam_is_fleet(self.h, C.byref(n)))
+        return n.value
+
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))
 

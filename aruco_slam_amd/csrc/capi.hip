@@ -31,10 +31,11 @@ constexpr int kWinWidenFrames = 16;     // a window of at least this many frames
 constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (its log is replayed meanwhile); <= kWinPieceMax
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
-              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_COUNT };
+              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
-                                   "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps"};
+                                   "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
+                                   "k_fleet_steps"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -116,6 +117,22 @@ struct aslam_ctx {
     double last_time = 0;
     bool is_init = false;
     bool localizing = false;              // aslam_localize_begin: the map is frozen, every EKF step is a k_loc_steps step
+
+    // fleet localization (aslam_fleet_begin): R robots, each with its own camera and pose filter, on the frozen map in
+    // the id table and the landmark rows of mu.  Device buffers are allocated by the first aslam_fleet_begin for min(max_batch, 256)
+    // robots.  The per-call tables go up from two pinned halves each, alternating; a half is rewritten only after its copy ran.
+    int fleet_n = 0;                      // robots of the active fleet; 0 = no fleet
+    int fleet_cap = 0;                    // robots the device buffers hold
+    std::vector<char> fleet_armed;        // per robot: its first frame has armed the filter (the next one predicts)
+    FleetState fleet{};                   // poses / Sigma_xx, last_observed_marker_ lists and their lengths
+    RigCam* d_fleet_cams = nullptr;       // per robot
+    int* d_fleet_camidx = nullptr;        // per frame slot: the robot whose camera k_pose uses
+    int* d_fleet_work = nullptr;          // the work list of a k_fleet_steps launch (ekf_fleet.h)
+    int* h_fleet_cam[2] = {nullptr, nullptr};
+    int* h_fleet_work[2] = {nullptr, nullptr};
+    hipEvent_t ev_fleet_cam[2] = {nullptr, nullptr}, ev_fleet_work[2] = {nullptr, nullptr};
+    bool ev_fleet_cam_set[2] = {false, false}, ev_fleet_work_set[2] = {false, false};
+    int fleet_cam_half = 0, fleet_work_half = 0;
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -340,11 +357,12 @@ PoseCams single_camera(const aslam_ctx* c) {
 }
 
 // detection + pose for `count` staged frames starting at slot `first` (asynchronous on the stream).  rig: frame first + i is camera
-// i % rig->n of the rig (nullptr: the single camera); latency: the configuration of a one-frame call (one rig step)
+// i % rig->n of the rig (nullptr: the single camera); latency: the configuration of a one-frame call (one rig step); robots (host,
+// count entries, fleet mode): frame first + i is robot robots[i]'s frame and uses that robot's camera
 int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipEvent_t wait_before = nullptr, const PoseCams* rig = nullptr,
-               bool latency = false) {
+               bool latency = false, const int* robots = nullptr) {
     if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
-    if (!rig && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    if (!rig && !robots && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
     PoseCams cams = rig ? *rig : single_camera(c);
     // the CU-masked stream only pays off while an EKF chain is actually in flight beside this detection; the first batch after
     // a synchronisation gets the whole GPU
@@ -363,6 +381,15 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
     if (c->ekf_count > 0 && first < c->ekf_hi && c->ekf_lo < first + count) {
         HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));   // EKF work in flight still reads observations of these slots
         c->ekf_count = 0;
+    }
+    if (robots) {                                           // the frames' camera indices, on the stream ahead of k_pose
+        const int h = c->fleet_cam_half;
+        c->fleet_cam_half ^= 1;
+        if (c->ev_fleet_cam_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_cam[h]));
+        std::memcpy(c->h_fleet_cam[h], robots, sizeof(int) * count);
+        HIP_TRY(c, hipMemcpyAsync(c->d_fleet_camidx + first, c->h_fleet_cam[h], sizeof(int) * count, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipEventRecord(c->ev_fleet_cam[h], st));
+        c->ev_fleet_cam_set[h] = true;
     }
     // frames per launch of the detection kernels: everything of the call at once (the work queues balance it) unless
     // ASLAM_DETECT_CHUNK asks for smaller sub-batches (an experiment knob: mask planes of fewer frames stay cache-resident
@@ -413,11 +440,15 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
         prof_end(c);
         prof_begin(c, P_POSE, st);
         cams.cam0 = (f0 - first) % cams.n;
-        launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
-                    c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr,
-                    RefineCfg{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
-                              g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
-                              c->d_refine_mask, gray});
+        const RefineCfg rf{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
+                           g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
+                           c->d_refine_mask, gray};
+        if (robots)
+            launch_pose_table(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
+                              c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, c->d_ctr, rf);
+        else
+            launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
+                        c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr, rf);
         prof_end(c);
     }
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
@@ -477,6 +508,10 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
+}
+
+int fleet_refuses(aslam_ctx* c) {
+    return fail(c, ASLAM_E_STATE, "a fleet is active: this call reads or writes the single filter or camera (aslam_fleet_end first)");
 }
 
 int sync_streams(aslam_ctx* c) {
@@ -678,6 +713,14 @@ void aslam_destroy(aslam_ctx* c) {
     hipFree(c->d_nfinal); hipFree(c->d_work); hipFree(c->d_dict); hipFree(c->d_markers); hipFree(c->d_nmarkers);
     hipFree(c->d_obs); hipFree(c->d_enc); hipFree(c->d_synth);
     ekf_free(c->ekf);
+    hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
+    hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
+    for (int h = 0; h < 2; h++) {
+        if (c->h_fleet_cam[h]) hipHostFree(c->h_fleet_cam[h]);
+        if (c->h_fleet_work[h]) hipHostFree(c->h_fleet_work[h]);
+        if (c->ev_fleet_cam[h]) hipEventDestroy(c->ev_fleet_cam[h]);
+        if (c->ev_fleet_work[h]) hipEventDestroy(c->ev_fleet_work[h]);
+    }
     if (c->ev_detect) hipEventDestroy(c->ev_detect);
     if (c->ev_ekf) hipEventDestroy(c->ev_ekf);
     if (c->stream_copy) { hipStreamSynchronize(c->stream_copy); hipStreamDestroy(c->stream_copy); }
@@ -704,6 +747,7 @@ const char* aslam_last_error(const aslam_ctx* c) { return c ? c->err.c_str() : (
 
 int aslam_set_camera(aslam_ctx* c, const double K[9], const double* D, int nD) {
     if (!c || !K || nD < 0 || (nD > 0 && !D)) return fail(c, ASLAM_E_INVALID, "bad camera arguments");
+    if (c->fleet_n) return fleet_refuses(c);
     c->cam.fx = K[0]; c->cam.fy = K[4]; c->cam.cx = K[2]; c->cam.cy = K[5];
     c->cam.nD = std::min(nD, 5);
     for (int i = 0; i < 5; i++) c->cam.k[i] = i < c->cam.nD ? D[i] : 0.0;
@@ -1124,28 +1168,37 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
 
 int aslam_run_staged(aslam_ctx* c, int first, int count, int with_ekf) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n && with_ekf) return fleet_refuses(c);
     return run_staged(c, first, count, with_ekf, nullptr);
 }
 
 // ---- camera rig (include/aruco_slam_hip.h): C frames per step, one batched detection pass, one EKF step per rig step ---------
+namespace {
+// one aslam_camera checked (nD <= 5, finite mount, heading in (-pi, pi]) and converted for k_pose
+int rig_camera(aslam_ctx* c, const aslam_camera& a, RigCam& e) {
+    const double PI = 3.14159265358979323846;
+    if (a.nD < 0 || a.nD > 5) return fail(c, ASLAM_E_INVALID, "camera distortion: 0..5 plumb-bob coefficients");
+    if (!(a.mount_yaw > -PI && a.mount_yaw <= PI) || !std::isfinite(a.mount_x) || !std::isfinite(a.mount_y))
+        return fail(c, ASLAM_E_INVALID, "camera mount: finite (x, y) and a heading in (-pi, pi]");
+    e.cam.fx = a.K[0]; e.cam.fy = a.K[4]; e.cam.cx = a.K[2]; e.cam.cy = a.K[5];
+    e.cam.nD = a.nD;
+    for (int i = 0; i < 5; i++) e.cam.k[i] = i < a.nD ? a.D[i] : 0.0;
+    e.mx = a.mount_x; e.my = a.mount_y;
+    e.psi = a.mount_yaw; e.cpsi = std::cos(a.mount_yaw); e.spsi = std::sin(a.mount_yaw);
+    return ASLAM_OK;
+}
+}  // namespace
+
 int aslam_set_camera_rig(aslam_ctx* c, int n_cams, const aslam_camera* cams) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     if (n_cams < 1 || n_cams > ASLAM_MAX_CAMERAS || !cams) return fail(c, ASLAM_E_INVALID, "a rig has 1..ASLAM_MAX_CAMERAS cameras");
     if (n_cams > c->max_batch) return fail(c, ASLAM_E_INVALID, "a rig step (one frame per camera) must fit into max_batch slots");
-    const double PI = 3.14159265358979323846;
     PoseCams pc{};
     pc.n = n_cams;
     for (int k = 0; k < n_cams; k++) {
-        const aslam_camera& a = cams[k];
-        if (a.nD < 0 || a.nD > 5) return fail(c, ASLAM_E_INVALID, "camera distortion: 0..5 plumb-bob coefficients");
-        if (!(a.mount_yaw > -PI && a.mount_yaw <= PI) || !std::isfinite(a.mount_x) || !std::isfinite(a.mount_y))
-            return fail(c, ASLAM_E_INVALID, "camera mount: finite (x, y) and a heading in (-pi, pi]");
-        RigCam& e = pc.e[k];
-        e.cam.fx = a.K[0]; e.cam.fy = a.K[4]; e.cam.cx = a.K[2]; e.cam.cy = a.K[5];
-        e.cam.nD = a.nD;
-        for (int i = 0; i < 5; i++) e.cam.k[i] = i < a.nD ? a.D[i] : 0.0;
-        e.mx = a.mount_x; e.my = a.mount_y;
-        e.psi = a.mount_yaw; e.cpsi = std::cos(a.mount_yaw); e.spsi = std::sin(a.mount_yaw);
+        int r = rig_camera(c, cams[k], pc.e[k]);
+        if (r) return r;
     }
     c->rig = pc;                               // taken by value at every launch: batches already submitted keep their cameras
     c->rig_n = n_cams;
@@ -1177,6 +1230,7 @@ int merge_rig_steps(aslam_ctx* c, int first, int n_steps) {
 
 int aslam_add_images(aslam_ctx* c, int n_cams, const uint8_t* const* px, int rows, int cols, int channels, const size_t* step) {
     if (!c || !px || !step) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     if (c->rig_n == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
     if (n_cams != c->rig_n) return fail(c, ASLAM_E_INVALID, "one image per camera of the rig");
     for (int k = 0; k < n_cams; k++) if (!px[k]) return fail(c, ASLAM_E_INVALID, "null image");
@@ -1217,6 +1271,7 @@ int aslam_add_images(aslam_ctx* c, int n_cams, const uint8_t* const* px, int row
 
 int aslam_run_staged_rig(aslam_ctx* c, int first, int n_steps, int with_ekf) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n && with_ekf) return fleet_refuses(c);
     const int C = c->rig_n;
     if (C == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
     if (n_steps <= 0) return fail(c, ASLAM_E_INVALID, "at least one rig step");
@@ -1253,6 +1308,7 @@ int aslam_run_staged_rig(aslam_ctx* c, int first, int n_steps, int with_ekf) {
 
 int aslam_get_rig_observations(aslam_ctx* c, int* n_out, int* ids, int* idx, int* action, int* cam, double* xyth, double* Rdiag) {
     if (!c || !n_out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was not a camera-rig call");
     int r = aslam_get_observations(c, n_out, ids, idx, action, xyth, Rdiag);
     if (r || !cam) return r;
@@ -1307,6 +1363,7 @@ int ring_submit(aslam_ctx* c) {
 
 int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames_per_submit) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     if (frames_per_submit < 1 || 2 * frames_per_submit > c->max_batch) return fail(c, ASLAM_E_INVALID, "frames_per_submit must be in [1, max_batch / 2]");
     int r = sync_streams(c);
     if (r) return r;
@@ -1330,6 +1387,7 @@ int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames
 
 int aslam_stream_acquire(aslam_ctx* c, uint8_t** px, size_t* step) {
     if (!c || !px) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
     if (!c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
     *px = c->h_ring + ((size_t)c->ring_half * c->ring_H + c->ring_fill) * c->in_frame_bytes;
@@ -1340,6 +1398,7 @@ int aslam_stream_acquire(aslam_ctx* c, uint8_t** px, size_t* step) {
 
 int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->ring_acquired) return fail(c, ASLAM_E_STATE, "aslam_stream_acquire first");
     c->ring_acquired = false;
     double* e = &c->ring_enc[(size_t)3 * c->ring_fill];
@@ -1350,6 +1409,7 @@ int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
 
 int aslam_stream_push(aslam_ctx* c, const uint8_t* px, size_t step, double wl, double wr, double dt) {
     if (!c || !px) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     uint8_t* dst = nullptr;
     size_t dstep = 0;
     int r = aslam_stream_acquire(c, &dst, &dstep);
@@ -1362,6 +1422,7 @@ int aslam_stream_push(aslam_ctx* c, const uint8_t* px, size_t step, double wl, d
 
 int aslam_stream_flush(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
     int r = ring_submit(c);
     if (r) return r;
@@ -1463,6 +1524,7 @@ int aslam_set_dictionary_bytes(aslam_ctx* c, int marker_size, int n_markers, int
 
 int aslam_add_encoder(aslam_ctx* c, double wl, double wr, double t_now) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     { int rp = finalize_pending(c); if (rp) return rp; }     // a pending batch arms the filter itself (is_init is set there)
     if (!c->is_init) {                       // aruco_slam.cpp:24-29
         c->last_time = t_now;
@@ -1478,6 +1540,7 @@ int aslam_add_encoder(aslam_ctx* c, double wl, double wr, double t_now) {
 
 int aslam_add_image(aslam_ctx* c, const uint8_t* px, int rows, int cols, int channels, size_t step) {
     if (!c || !px) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     int r = finalize_pending(c);
     if (r) return r;
     if (!c->is_init) return ASLAM_OK;        // aruco_slam.cpp:84-85: nothing happens before the first encoder message
@@ -1517,6 +1580,7 @@ int aslam_get_last_timing(aslam_ctx* c, double out[6]) {
 
 int aslam_get_state(aslam_ctx* c, int* N, double* mu, double* sigma) {
     if (!c || !N) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
     int L = 0;
     HIP_TRY(c, hipMemcpy(&L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
@@ -1534,6 +1598,7 @@ int aslam_get_state(aslam_ctx* c, int* N, double* mu, double* sigma) {
 
 int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, const int* landmark_ids) {
     if (!c || !mu || !sigma || N < 3 || (N - 3) % 3 != 0) return fail(c, ASLAM_E_INVALID, "bad state");
+    if (c->fleet_n) return fleet_refuses(c);
     const int L = (N - 3) / 3;
     if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
@@ -1625,6 +1690,7 @@ void fill_marker(aslam_marker_msg& m, int id, double length, double x, double y,
 
 int aslam_get_pose_msg(aslam_ctx* c, aslam_pose_msg* out) {                   // ArucoSlam::toRosPose, aruco_slam.cpp:378-410
     if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
     double mu[3], S[9];
     HIP_TRY(c, hipMemcpy(mu, c->ekf.d_mu, sizeof(mu), hipMemcpyDeviceToHost));
@@ -1641,6 +1707,7 @@ int aslam_get_pose_msg(aslam_ctx* c, aslam_pose_msg* out) {                   //
 
 int aslam_get_map_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) {   // detected_map_, aruco_slam.cpp:265-281
     if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
     int L = 0;
     HIP_TRY(c, hipMemcpy(&L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
@@ -1658,6 +1725,7 @@ int aslam_get_map_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) 
 
 int aslam_get_detected_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) {   // detected_markers_, aruco_slam.cpp:325-347
     if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: detected-marker messages describe one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
@@ -1709,6 +1777,7 @@ void draw_line(uint8_t* img, int rows, int cols, size_t step, int x0, int y0, in
 
 int aslam_draw_detected_markers(aslam_ctx* c, uint8_t* bgr, int rows, int cols, size_t step) {
     if (!c || !bgr || rows <= 0 || cols <= 0 || step < (size_t)cols * 3) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    if (c->fleet_n) return fleet_refuses(c);
     if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: the overlay describes one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
@@ -1767,8 +1836,10 @@ int aslam_load_map_txt(aslam_ctx* c, const char* path, int max, int* n, aslam_ma
 }
 
 // ---- localization against a frozen map (include/aruco_slam_hip.h) -------------------------------------------
-int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth, const double pose[3], const double pose_sigma[9]) {
-    if (!c || !ids || !xyth || !pose || !pose_sigma) return fail(c, ASLAM_E_INVALID, "null argument");
+namespace {
+// the frozen map of localization and of a fleet: checked (write = false), or written (write = true) into the id tables and the
+// landmark rows of mu, with the pose rows of mu and all of Sigma zero
+int install_frozen_map(aslam_ctx* c, int n, const int* ids, const double* xyth, bool write) {
     if (n < 1 || n > c->ekf.max_landmarks) return fail(c, ASLAM_E_INVALID, "a map of 1..max_landmarks landmarks");
     std::vector<int> id2idx(kIdTableSize, -1), idx2id(c->ekf.max_landmarks, -1);
     for (int i = 0; i < n; i++) {
@@ -1779,27 +1850,47 @@ int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth
         for (int k = 0; k < 3; k++)
             if (!std::isfinite(xyth[3 * i + k])) return fail(c, ASLAM_E_INVALID, "landmark " + std::to_string(ids[i]) + ": non-finite value");
     }
-    for (int k = 0; k < 3; k++) if (!std::isfinite(pose[k])) return fail(c, ASLAM_E_INVALID, "non-finite pose");
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            if (!std::isfinite(pose_sigma[i * 3 + j])) return fail(c, ASLAM_E_INVALID, "non-finite pose covariance");
-            if (pose_sigma[i * 3 + j] != pose_sigma[j * 3 + i]) return fail(c, ASLAM_E_INVALID, "pose covariance not symmetric");
-        }
-    { int rs = sync_streams(c); if (rs) return rs; }
-    // state := [pose, map], Sigma := blockdiag(pose_sigma, 0) in the SLAM layout (column-major, ld = N_max)
+    if (!write) return ASLAM_OK;
     const size_t ld = (size_t)c->ekf.ld;
     HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
-    for (int col = 0; col < 3; col++) {
-        const double v[3] = {pose_sigma[col], pose_sigma[3 + col], pose_sigma[6 + col]};
-        HIP_TRY(c, hipMemcpy(c->ekf.d_sigma + (size_t)col * ld, v, sizeof(v), hipMemcpyHostToDevice));
-    }
-    std::vector<double> mu(3 + 3 * (size_t)n);
-    for (int k = 0; k < 3; k++) mu[k] = pose[k];
+    std::vector<double> mu(3 + 3 * (size_t)n, 0.0);
     std::memcpy(mu.data() + 3, xyth, sizeof(double) * 3 * n);
+    HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
     HIP_TRY(c, hipMemcpy(c->ekf.d_mu, mu.data(), sizeof(double) * mu.size(), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->ekf.d_id2idx, id2idx.data(), sizeof(int) * kIdTableSize, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->ekf.d_idx2id, idx2id.data(), sizeof(int) * c->ekf.max_landmarks, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->ekf.d_L, &n, sizeof(int), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int check_pose(aslam_ctx* c, const double* pose, const double* sigma) {
+    for (int k = 0; k < 3; k++) if (!std::isfinite(pose[k])) return fail(c, ASLAM_E_INVALID, "non-finite pose");
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            if (!std::isfinite(sigma[i * 3 + j])) return fail(c, ASLAM_E_INVALID, "non-finite pose covariance");
+            if (sigma[i * 3 + j] != sigma[j * 3 + i]) return fail(c, ASLAM_E_INVALID, "pose covariance not symmetric");
+        }
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth, const double pose[3], const double pose_sigma[9]) {
+    if (!c || !ids || !xyth || !pose || !pose_sigma) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
+    int r = install_frozen_map(c, n, ids, xyth, false);
+    if (r) return r;
+    r = check_pose(c, pose, pose_sigma);
+    if (r) return r;
+    { int rs = sync_streams(c); if (rs) return rs; }
+    // state := [pose, map], Sigma := blockdiag(pose_sigma, 0) in the SLAM layout (column-major, ld = N_max)
+    r = install_frozen_map(c, n, ids, xyth, true);
+    if (r) return r;
+    const size_t ld = (size_t)c->ekf.ld;
+    for (int col = 0; col < 3; col++) {
+        const double v[3] = {pose_sigma[col], pose_sigma[3 + col], pose_sigma[6 + col]};
+        HIP_TRY(c, hipMemcpy(c->ekf.d_sigma + (size_t)col * ld, v, sizeof(v), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(c, hipMemcpy(c->ekf.d_mu, pose, 3 * sizeof(double), hipMemcpyHostToDevice));
     int zero = 0;
     HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
@@ -1810,6 +1901,7 @@ int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth
 
 int aslam_localize_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
+    if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
     c->mirror_dirty = true;
     c->localizing = false;
@@ -1819,6 +1911,231 @@ int aslam_localize_end(aslam_ctx* c) {
 int aslam_is_localizing(aslam_ctx* c, int* on) {
     if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
     *on = c->localizing ? 1 : 0;
+    return ASLAM_OK;
+}
+
+// ---- fleet localization: many robots on one frozen map (include/aruco_slam_hip.h) -------------------------------
+namespace {
+int fleet_alloc(aslam_ctx* c) {
+    if (c->fleet_cap) return ASLAM_OK;
+    const int R = std::min(c->max_batch, ASLAM_MAX_ROBOTS), B = c->max_batch;
+    HIP_TRY(c, dalloc(&c->fleet.pose, (size_t)kFleetState * R));
+    HIP_TRY(c, dalloc(&c->fleet.last, (size_t)kMarkerMax * R));
+    HIP_TRY(c, dalloc(&c->fleet.nlast, R));
+    HIP_TRY(c, dalloc(&c->d_fleet_cams, R));
+    HIP_TRY(c, dalloc(&c->d_fleet_camidx, B));
+    HIP_TRY(c, dalloc(&c->d_fleet_work, 4 * R + B));
+    for (int h = 0; h < 2; h++) {
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_cam[h]), sizeof(int) * B, hipHostMallocDefault));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_work[h]), sizeof(int) * (4 * R + B), hipHostMallocDefault));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_cam[h], hipEventDisableTiming));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_work[h], hipEventDisableTiming));
+    }
+    c->fleet_cap = R;
+    return ASLAM_OK;
+}
+
+// one robot's filter := (pose, sigma), its last-observed list emptied, disarmed
+int fleet_seat(aslam_ctx* c, int robot, const double* pose, const double* sigma) {
+    double st[kFleetState];
+    for (int k = 0; k < 3; k++) st[k] = pose[k];
+    for (int k = 0; k < 9; k++) st[3 + k] = sigma[k];
+    HIP_TRY(c, hipMemcpy(c->fleet.pose + (size_t)kFleetState * robot, st, sizeof(st), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(c->fleet.nlast + robot, 0, sizeof(int)));
+    c->fleet_armed[robot] = 0;
+    return ASLAM_OK;
+}
+
+// fleet steps of frame slots [first, first + count), slot first + i belonging to robot robots[i]: one k_fleet_steps workgroup per
+// robot present (in order of first appearance), its slots ascending, behind the detection that produced their lists.  The host
+// keeps the armed flags: a robot's first frame after aslam_fleet_begin / aslam_fleet_set_pose only arms its filter.
+int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
+    std::vector<int> group(c->fleet_n, -1), robot_of_group;
+    std::vector<std::vector<int>> slots_of;
+    for (int i = 0; i < count; i++) {
+        int& g = group[robots[i]];
+        if (g < 0) { g = (int)slots_of.size(); slots_of.emplace_back(); robot_of_group.push_back(robots[i]); }
+        slots_of[g].push_back(first + i);
+    }
+    const int ng = (int)slots_of.size();
+    const int h = c->fleet_work_half;
+    c->fleet_work_half ^= 1;
+    if (c->ev_fleet_work_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_work[h]));   // the copy that last read this half ran
+    int* hdr = c->h_fleet_work[h];
+    int* slots = hdr + 4 * ng;
+    int ns = 0;
+    for (int g = 0; g < ng; g++) {
+        const int r = robot_of_group[g];
+        hdr[4 * g] = r; hdr[4 * g + 1] = c->fleet_armed[r] ? 1 : 0; hdr[4 * g + 2] = ns; hdr[4 * g + 3] = (int)slots_of[g].size();
+        for (int sl : slots_of[g]) slots[ns++] = sl;
+        c->fleet_armed[r] = 1;
+    }
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, hipMemcpyAsync(c->d_fleet_work, hdr, sizeof(int) * (4 * ng + ns), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev_fleet_work[h], st));
+    c->ev_fleet_work_set[h] = true;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    prof_begin(c, P_FLEET_STEPS, st);
+    launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_ekf, st));
+    note_ekf_range(c, first, count);
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth, const double* poses,
+                      const double* pose_sigmas) {
+    if (!c || !cams || !ids || !xyth || !poses || !pose_sigmas) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: one filter is active (aslam_localize_end first)");
+    if (n_robots < 1 || n_robots > std::min(c->max_batch, ASLAM_MAX_ROBOTS))
+        return fail(c, ASLAM_E_INVALID, "a fleet has 1..min(max_batch, ASLAM_MAX_ROBOTS) robots");
+    std::vector<RigCam> rc(n_robots);
+    for (int k = 0; k < n_robots; k++) {
+        int r = rig_camera(c, cams[k], rc[k]);
+        if (r) return r;
+    }
+    int r = install_frozen_map(c, n, ids, xyth, false);
+    if (r) return r;
+    for (int k = 0; k < n_robots; k++) {
+        r = check_pose(c, poses + 3 * k, pose_sigmas + 9 * k);
+        if (r) return r;
+    }
+    r = sync_streams(c);
+    if (r) return r;
+    r = fleet_alloc(c);
+    if (r) return r;
+    r = install_frozen_map(c, n, ids, xyth, true);
+    if (r) return r;
+    int zero = 0;
+    HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_fleet_cams, rc.data(), sizeof(RigCam) * n_robots, hipMemcpyHostToDevice));
+    c->fleet_armed.assign(n_robots, 0);
+    c->fleet_n = n_robots;
+    for (int k = 0; k < n_robots; k++) {
+        r = fleet_seat(c, k, poses + 3 * k, pose_sigmas + 9 * k);
+        if (r) { c->fleet_n = 0; return r; }
+    }
+    c->mirror_dirty = true;
+    return ASLAM_OK;
+}
+
+int aslam_fleet_add_images(aslam_ctx* c, int n, const int* robots, const double* wl, const double* wr, const double* dt,
+                           const uint8_t* const* px, int rows, int cols, int channels, const size_t* step_bytes) {
+    if (!c || !robots || !wl || !wr || !dt || !px || !step_bytes) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (n < 1 || n > c->max_batch) return fail(c, ASLAM_E_INVALID, "1..max_batch frames per call");
+    std::vector<char> seen(c->fleet_n, 0);
+    for (int i = 0; i < n; i++) {
+        if (robots[i] < 0 || robots[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+        if (seen[robots[i]]) return fail(c, ASLAM_E_INVALID, "a robot named twice in one aslam_fleet_add_images");
+        seen[robots[i]] = 1;
+        if (!px[i]) return fail(c, ASLAM_E_INVALID, "null image");
+    }
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    for (int i = 0; i < n; i++) {
+        int r = aslam_stage_frames(c, i, px[i], 1, rows, cols, channels, step_bytes[i], 0);
+        if (r) return r;
+    }
+    int r = aslam_stage_encoders(c, 0, n, wl, wr, dt);
+    if (r) return r;
+    const auto t1 = clk::now();
+    r = run_detect(c, 0, n, false, nullptr, nullptr, true, robots);     // one batched pass, the cut lattice of aslam_add_images
+    if (r) return r;
+    c->rig_last = false;
+    const auto t2 = clk::now();
+    r = run_fleet_steps(c, 0, n, robots);
+    if (r) return r;
+    const auto t3 = clk::now();
+    r = sync_streams(c);
+    const auto t4 = clk::now();
+    if (!r) r = sync_and_check(c);
+    const auto t5 = clk::now();
+    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
+    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
+    return r;
+}
+
+int aslam_fleet_run_staged(aslam_ctx* c, int first, int count, const int* robot_of_slot, int with_ekf) {
+    if (!c || !robot_of_slot) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    int r = check_slot_range(c, first, count);
+    if (r) return r;
+    if (with_ekf < 0 || with_ekf > 2) return fail(c, ASLAM_E_INVALID, "with_ekf: 0, 1 or 2");
+    for (int i = 0; i < count; i++)
+        if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    if (with_ekf && c->enc_host.size() < (size_t)3 * (first + count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
+    if (with_ekf != 2) {
+        for (int i = first; i < first + count; i++)
+            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+                return fail(c, ASLAM_E_INVALID, "the frames of a fleet call must all be staged with the same rows, cols and channels");
+        r = run_detect(c, first, count, false, nullptr, nullptr, count == 1, robot_of_slot);
+        if (r) return r;
+    } else {
+        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
+        c->last_detect = c->stream;
+        HIP_TRY(c, hipEventRecord(c->ev_detect, c->stream));
+    }
+    c->rig_last = false;
+    if (!with_ekf) return ASLAM_OK;
+    return run_fleet_steps(c, first, count, robot_of_slot);
+}
+
+int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, double* sigmas) {
+    if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    const int R = c->fleet_n;
+    *n_robots = R;
+    std::vector<double> h((size_t)kFleetState * R);
+    HIP_TRY(c, hipMemcpy(h.data(), c->fleet.pose, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < std::min(max, R); k++) {
+        if (poses) std::memcpy(poses + 3 * k, &h[(size_t)kFleetState * k], 3 * sizeof(double));
+        if (sigmas) std::memcpy(sigmas + 9 * k, &h[(size_t)kFleetState * k + 3], 9 * sizeof(double));
+    }
+    return ASLAM_OK;
+}
+
+int aslam_fleet_set_pose(aslam_ctx* c, int robot, const double pose[3], const double sigma[9]) {
+    if (!c || !pose || !sigma) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    int r = check_pose(c, pose, sigma);
+    if (r) return r;
+    r = sync_streams(c);
+    if (r) return r;
+    return fleet_seat(c, robot, pose, sigma);
+}
+
+int aslam_fleet_end(aslam_ctx* c) {
+    if (!c) return ASLAM_E_INVALID;
+    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    // the single filter as aslam_create leaves it (ekf_alloc)
+    const size_t ld = (size_t)c->ekf.ld;
+    HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
+    HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
+    HIP_TRY(c, hipMemset(c->ekf.d_L, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_id2idx, 0xFF, kIdTableSize * sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_idx2id, 0xFF, (size_t)c->ekf.max_landmarks * sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_nlast, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_npop, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_m, 0, sizeof(int)));
+    c->is_init = false;
+    c->last_time = 0;
+    c->mirror_dirty = true;
+    c->fleet_n = 0;
+    c->fleet_armed.clear();
+    return ASLAM_OK;
+}
+
+int aslam_is_fleet(aslam_ctx* c, int* n_robots) {
+    if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
+    *n_robots = c->fleet_n;
     return ASLAM_OK;
 }
 
@@ -1847,6 +2164,7 @@ int aslam_landmarks_from_markers(int n, const aslam_marker_msg* in, int* ids, do
 // ---- persistence (no counterpart in the reference: warm starts of large maps) ----------------------------
 int aslam_save_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     int N = 0;
     int r = aslam_get_state(c, &N, nullptr, nullptr);
     if (r) return r;
@@ -1872,6 +2190,7 @@ int aslam_save_state(aslam_ctx* c, const char* path) {
 
 int aslam_load_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, ASLAM_E_INVALID, std::string("cannot read ") + path);
@@ -1943,6 +2262,7 @@ int aslam_get_slot_raw_observations(aslam_ctx* c, int slot, int* n_out, int* ids
 
 int aslam_get_observations(aslam_ctx* c, int* n_out, int* ids, int* idx, int* action, double* xyth, double* Rdiag) {
     if (!c || !n_out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
     int n = 0;
     HIP_TRY(c, hipMemcpy(&n, c->ekf.d_npop, sizeof(int), hipMemcpyDeviceToHost));
@@ -2009,6 +2329,7 @@ int aslam_detect_batch(aslam_ctx* c, const uint8_t* frames, int nframes, int row
 
 int aslam_export_map(aslam_ctx* c, void* dst, int dst_is_device) {
     if (!c || !dst) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     { int rp = finalize_pending(c); if (rp) return rp; }
     launch_ekf_export_map(c->stream_ekf, c->ekf);
     HIP_TRY(c, hipGetLastError());
@@ -2020,6 +2341,7 @@ int aslam_export_map(aslam_ctx* c, void* dst, int dst_is_device) {
 
 int aslam_export_map_async(aslam_ctx* c, void* d_dst, int buffer) {
     if (!c || !d_dst || buffer < 0 || buffer > 1) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->ev_export[buffer]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_export[buffer], hipEventDisableTiming));
     { int rp = finalize_pending(c); if (rp) return rp; }
     launch_ekf_export_map(c->stream_ekf, c->ekf);              // ordered after the EKF steps enqueued so far
@@ -2095,6 +2417,7 @@ int aslam_comm_create(aslam_ctx* c, const void* id, int world, int rank) {
 
 int aslam_comm_gather_maps(aslam_ctx* c, void* dst, int dst_is_device) {
     if (!c || !dst) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->fleet_n) return fleet_refuses(c);
     if (!c->comm) return fail(c, ASLAM_E_STATE, "aslam_comm_create first");
     Rccl* r = rccl();
     const size_t nb = (size_t)ASLAM_MAP_RECORD_BYTES * c->ekf.max_landmarks;

@@ -103,6 +103,15 @@ void launch_ekf_export_map(hipStream_t st, const EkfState& E);
 // is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder)
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
                       const double* enc, int first, int count, int predict_first);
+// fleet localization (ekf_fleet.h): one workgroup per robot of the work list (n_groups robots), each on its own filter in F
+constexpr int kFleetState = 12;        // doubles per robot: mu_x (3), then Sigma_xx row-major (9)
+struct FleetState {
+    double* pose;                      // R x kFleetState
+    LastObs* last;                     // R x kMarkerMax: each robot's last_observed_marker_
+    int* nlast;                        // R: their lengths
+};
+void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays

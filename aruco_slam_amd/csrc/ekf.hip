@@ -1406,3 +1406,4 @@ void launch_ekf_export_map(hipStream_t st, const EkfState& E) {
 } // namespace aslam
 
 #include "ekf_localize.h"     // localization against a frozen map: k_loc_steps and its launcher
+#include "ekf_fleet.h"        // fleet localization: k_fleet_steps, one workgroup per robot, and its launcher

@@ -8,6 +8,9 @@
 // per slot the lanes load the observations, look up the landmark index (unknown ids and gated observations are dropped before the
 // queue), rank the pop order, test "stationary" against the previous step's list and prepare every correction's H, ze and R; lane 0
 // keeps mu_x and P in registers across all slots and runs the predict and the dependent chain of 3 x 3 corrections.
+//
+// The body is loc_steps<Src>: Src says which slots the workgroup steps through and where the filter it corrects lives.  LocSingle
+// is the context's one filter (k_loc_steps); a fleet's workgroup uses LocFleet, its robot's own filter (ekf_fleet.h).
 #pragma once
 #include "common.h"
 #include "ekf.h"
@@ -21,9 +24,36 @@ struct LocCorr {                     // one prepared correction: H (row-major 3 
     double r[3];
 };
 
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                         const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                         int first, int count, int predict_first) {
+// the context's filter: slots first .. first + count - 1, pose in mu / Sigma, last_observed_marker_ in d_last; it also leaves the last
+// slot's popped observations for aslam_get_observations
+struct LocSingle {
+    const EkfState& E;
+    int first, count, predict_first;
+    static constexpr bool kPopList = true;
+    __device__ __forceinline__ int n() const { return count; }
+    __device__ __forceinline__ int slot(int k) const { return first + k; }
+    __device__ __forceinline__ bool predict(int k) const { return k > 0 || predict_first; }
+    __device__ __forceinline__ void load(double& mx, double& my, double& mt, double* P) const {
+        mx = E.d_mu[0]; my = E.d_mu[1]; mt = E.d_mu[2];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) P[i * 3 + j] = E.d_sigma[(size_t)j * E.ld + i];
+    }
+    __device__ __forceinline__ void store(double mx, double my, double mt, const double* P) const {
+        E.d_mu[0] = mx; E.d_mu[1] = my; E.d_mu[2] = mt;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) E.d_sigma[(size_t)j * E.ld + i] = P[i * 3 + j];
+    }
+    __device__ __forceinline__ LastObs* last() const { return E.d_last; }
+    __device__ __forceinline__ int* nlast() const { return E.d_nlast; }
+};
+
+template <class Src>
+__device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
+                                          const double* enc) {
     __shared__ LastObs sLast[kMarkerMax];       // last_observed_marker_ of the previous step
     __shared__ int sIndex[kMarkerMax];          // landmark index per observation slot (-2: dropped)
     __shared__ int sOrder[kMarkerMax];          // pop order
@@ -32,22 +62,18 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams
     __shared__ double sPose[3];                 // frame-start pose (after the predict)
     __shared__ int sDup, sNl, sCnt[2], sUpdCnt[2], sStatCnt[2];
     const int tid = threadIdx.x;
-    const int ld = E.ld;
+    const int count = src.n();
 
     double mx = 0, my = 0, mt = 0, P[9];        // lane 0: the pose and Sigma_xx, in registers for the whole launch
     if (tid == 0) {
-        mx = E.d_mu[0]; my = E.d_mu[1]; mt = E.d_mu[2];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) P[i * 3 + j] = E.d_sigma[(size_t)j * ld + i];
-        sNl = min(*E.d_nlast, kMarkerMax);
+        src.load(mx, my, mt, P);
+        sNl = min(*src.nlast(), kMarkerMax);
     }
-    sLast[tid] = E.d_last[tid];                 // entries beyond the list length are never read
+    sLast[tid] = src.last()[tid];               // entries beyond the list length are never read
     __syncthreads();
 
     for (int k = 0; k < count; k++) {
-        const int slot = first + k;
+        const int slot = src.slot(k);
         const int nM = (int)min(n_markers[slot], (unsigned)kMarkerMax);
         // checkLandmark (aruco_slam.cpp:423-435): an id outside the map is dropped like a gated observation (never augmented)
         ObsRaw o{};
@@ -62,7 +88,7 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams
         sIndex[tid] = myIndex;
         if (tid == 0) {
             sDup = 0;
-            if (k > 0 || predict_first) {
+            if (src.predict(k)) {
                 // addEncoder (aruco_slam.cpp:35-73) on the pose block, the arithmetic of predict_block (ekf.hip) in the same order:
                 // with Sigma_xl = 0 the landmark rows and columns stay zero
                 const double* e = enc + (size_t)3 * slot;
@@ -177,7 +203,7 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams
             pr.id = po.id; pr.index = pidx; pr.action = act; pr.det = det;
             pr.z[0] = po.x; pr.z[1] = po.y; pr.z[2] = po.th;
             pr.r[0] = po.r[0]; pr.r[1] = po.r[1]; pr.r[2] = po.r[2];
-            if (k == count - 1) E.d_pop[tid] = pr;
+            if (Src::kPopList && k == count - 1) E.d_pop[tid] = pr;
         }
         const unsigned long long bU = __ballot(act == 1), bS = __ballot(act == 2);
         if ((tid & 63) == 0) { sUpdCnt[tid >> 6] = __popcll(bU); sStatCnt[tid >> 6] = __popcll(bS); }
@@ -242,19 +268,21 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams
                 int* st = E.d_slot_stat + 4 * slot;
                 st[0] = nM; st[1] = 0; st[2] = m; st[3] = sStatCnt[0] + sStatCnt[1];
             }
-            if (k == count - 1) { *E.d_npop = np; *E.d_m = m; }
+            if (Src::kPopList && k == count - 1) { *E.d_npop = np; *E.d_m = m; }
         }
         __syncthreads();
     }
-    if (tid < sNl) E.d_last[tid] = sLast[tid];
+    if (tid < sNl) src.last()[tid] = sLast[tid];
     if (tid == 0) {
-        *E.d_nlast = sNl;
-        E.d_mu[0] = mx; E.d_mu[1] = my; E.d_mu[2] = mt;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) E.d_sigma[(size_t)j * ld + i] = P[i * 3 + j];
+        *src.nlast() = sNl;
+        src.store(mx, my, mt, P);
     }
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                         const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                         int first, int count, int predict_first) {
+    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc);
 }
 
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,

@@ -14,6 +14,9 @@ struct RefineCfg {
 
 void launch_pose(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers,
                  unsigned* n_markers, ObsRaw* obs, const PoseCams& cams, const SlamParams& sp, Counters* ctr, const RefineCfg& rf);
+// launch_pose with frame f's camera read from a device table: tab[cam_of_frame[f]] (a fleet, one camera per robot)
+void launch_pose_table(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers, unsigned* n_markers,
+                       ObsRaw* obs, const RigCam* tab, const int* cam_of_frame, const SlamParams& sp, Counters* ctr, const RefineCfg& rf);
 // concatenates the observation lists of n_steps rig steps (C = n_cams frames each, from slot frame0) into step lists at slots step0..
 void launch_rig_merge(hipStream_t st, int n_steps, ObsRaw* obs, unsigned* n_markers, double* enc, int frame0, int n_cams, int step0, Counters* ctr);
 

@@ -350,8 +350,8 @@ __device__ __forceinline__ float subpix_at(const SubPix& P, int i, int j) {     
     return P.gray[(size_t)y0 * P.cols + x0] * P.a11 + P.gray[(size_t)y0 * P.cols + x1] * P.a12 + P.gray[(size_t)y1 * P.cols + x0] * P.a21 +
            P.gray[(size_t)y1 * P.cols + x1] * P.a22;
 }
-__device__ void corner_sub_pix_one(const uint8_t* gray, int rows, int cols, const float* __restrict__ mask, int win, int max_iters,
-                                   double eps2, float& x, float& y) {
+__device__ __forceinline__ void corner_sub_pix_one(const uint8_t* gray, int rows, int cols, const float* __restrict__ mask, int win, int max_iters,
+                                                   double eps2, float& x, float& y) {
     const int win_w = 2 * win + 1, pw = win_w + 2;
     const float cTx = x, cTy = y;
     float cIx = x, cIy = y;
@@ -400,9 +400,21 @@ __device__ void corner_sub_pix_one(const uint8_t* gray, int rows, int cols, cons
     x = cIx; y = cIy;
 }
 
+// Where frame f's camera comes from.  A rig passes its table by value (PoseCams, at most kMaxCameras entries: frame f is camera
+// (cam0 + f) % n).  A fleet has one camera per robot, up to 256: the table lives in device memory and a per-frame
+// index picks the entry.  f is the workgroup, so the index is a scalar load; the entry itself is read with vector loads (the compiler
+// cannot prove the table read-only), a few dozen loads per workgroup.
+struct CamTable {
+    const RigCam* tab;
+    const int* cam_of_frame;
+};
+__device__ __forceinline__ const RigCam& frame_cam(const PoseCams& c, int f) { return c.e[(c.cam0 + f) % c.n]; }
+__device__ __forceinline__ const RigCam& frame_cam(const CamTable& c, int f) { return c.tab[c.cam_of_frame[f]]; }
+
+template <class Cams>
 __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ finals, const unsigned* __restrict__ n_final,
                                               Marker* __restrict__ markers, unsigned* __restrict__ n_markers,
-                                              ObsRaw* __restrict__ obs, PoseCams cams, SlamParams sp, Counters* ctr, RefineCfg rf) {
+                                              ObsRaw* __restrict__ obs, Cams cams, SlamParams sp, Counters* ctr, RefineCfg rf) {
     __shared__ float sC[kMarkerMax][8];
     __shared__ int sId[kMarkerMax];
     __shared__ unsigned char sRem[kMarkerMax];
@@ -410,7 +422,7 @@ __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ fina
     __shared__ int sN, sM;
     const int tid = threadIdx.x;
     const int f = blockIdx.x;
-    const RigCam& rc = cams.e[(cams.cam0 + f) % cams.n];          // this frame's camera: intrinsics and mount
+    const RigCam& rc = frame_cam(cams, f);                        // this frame's camera: intrinsics and mount
     const CamParams& cam = rc.cam;
     const FinalCand* fin = finals + (size_t)f * kCandMax;
     const int nF = (int)min(n_final[f], (unsigned)kCandMax);
@@ -533,7 +545,13 @@ __global__ __launch_bounds__(128) void k_pose(const FinalCand* __restrict__ fina
 
 void launch_pose(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers,
                  unsigned* n_markers, ObsRaw* obs, const PoseCams& cams, const SlamParams& sp, Counters* ctr, const RefineCfg& rf) {
-    hipLaunchKernelGGL(k_pose, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, cams, sp, ctr, rf);
+    hipLaunchKernelGGL(k_pose<PoseCams>, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, cams, sp, ctr, rf);
+}
+
+void launch_pose_table(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers, unsigned* n_markers,
+                       ObsRaw* obs, const RigCam* tab, const int* cam_of_frame, const SlamParams& sp, Counters* ctr, const RefineCfg& rf) {
+    hipLaunchKernelGGL(k_pose<CamTable>, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, CamTable{tab, cam_of_frame},
+                       sp, ctr, rf);
 }
 
 // One rig step = the observation lists of its C frames (slots frame0 + s C + c) concatenated in camera order into one list at

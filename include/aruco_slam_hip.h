@@ -229,6 +229,43 @@ int aslam_is_localizing(aslam_ctx* ctx, int* on);
    whose +z axis has no horizontal component (|(r_x, r_y)| < 1e-6) */
 int aslam_landmarks_from_markers(int n, const aslam_marker_msg* in, int* ids, double* xyth);
 
+/* ---- fleet localization: many robots tracked against one shared frozen map (no reference counterpart) ------
+ * A fleet is R robots, 1 <= R <= min(max_batch, ASLAM_MAX_ROBOTS).  Each robot has one camera (aslam_camera: K, D and planar mount,
+ * as in a rig), its own pose filter (mu_x, Sigma_xx), its own last-observed list and its own armed flag; all share one frozen map
+ * given as to aslam_localize_begin.  For every robot, the frames it is given produce bit for bit what a single localizing context
+ * produces on them (aslam_set_camera_rig with that one camera, aslam_localize_begin with the same map, pose and Sigma, driven by
+ * aslam_run_staged_rig): its first frame after aslam_fleet_begin or aslam_fleet_set_pose only arms it (that frame's encoder
+ * sample is not applied), and every rule of localization holds per robot, the "stationary" test against its own previous list.
+ * A call may carry any subset of the robots; a robot named in several slots of one staged call takes them in ascending order.
+ * Robots never interact.  Per call: one batched detection pass, then one EKF kernel launch with one workgroup per robot present.
+ * aslam_get_slot_detections, aslam_get_slot_raw_observations and aslam_get_slot_ekf_stats (appended = 0) work on fleet slots.
+ * While a fleet is active every entry point that reads or writes the single filter refuses with ASLAM_E_STATE (aslam_add_encoder,
+ * aslam_add_image, aslam_add_images, aslam_run_staged / aslam_run_staged_rig with EKF, the host-fed stream, aslam_localize_begin /
+ * _end, the state get / set / save / load, the pose / map / detected-marker messages and the overlay, aslam_get_observations,
+ * aslam_get_rig_observations, the map export and gather), and so do aslam_set_camera and aslam_set_camera_rig.  Detection-only
+ * calls and detector / dictionary changes stay allowed.  Outside fleet mode the fleet calls refuse with ASLAM_E_STATE. */
+#define ASLAM_MAX_ROBOTS 256
+/* enter fleet mode: cams, poses (R x 3) and pose_sigmas (R x 9, row-major) one per robot, map (ids, xyth) as aslam_localize_begin;
+   the camera checks of aslam_set_camera_rig, the map and pose checks of aslam_localize_begin; every robot disarmed.  Refuses with
+   ASLAM_E_STATE while localizing.  Called again while a fleet is active, it starts a new fleet. */
+int aslam_fleet_begin(aslam_ctx* ctx, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth /* n x 3 */,
+                      const double* poses /* R x 3 */, const double* pose_sigmas /* R x 9 */);
+/* one batched call, synchronous: n frames (px[i] borrowed, step_bytes[i]; all of one size) of n distinct robots robots[i], each with
+   its own encoder sample (wl[i], wr[i], dt[i]) taken before the frame; uses frame slots 0 .. n-1 */
+int aslam_fleet_add_images(aslam_ctx* ctx, int n, const int* robots, const double* wl, const double* wr, const double* dt,
+                           const uint8_t* const* px, int rows, int cols, int channels, const size_t* step_bytes);
+/* staged frames / encoder samples (aslam_stage_frames / aslam_stage_encoders): slot first + i belongs to robot robot_of_slot[i];
+   with_ekf as aslam_run_staged (0 detection only, 1 detection + EKF, 2 EKF on injected observations), asynchronous as it */
+int aslam_fleet_run_staged(aslam_ctx* ctx, int first, int count, const int* robot_of_slot, int with_ekf);
+/* *n_robots = R; the first min(max, R) robots' poses (x, y, theta) and Sigma_xx (row-major) */
+int aslam_fleet_get_poses(aslam_ctx* ctx, int max, int* n_robots, double* poses /* R x 3 */, double* sigmas /* R x 9 */);
+/* re-seat one robot: pose and Sigma_xx replaced, its last-observed list emptied, disarmed (pose / sigma checked as at begin) */
+int aslam_fleet_set_pose(aslam_ctx* ctx, int robot, const double pose[3], const double sigma[9]);
+/* leave fleet mode: the single filter is as aslam_create leaves it (empty map, disarmed); cameras and detector settings stay */
+int aslam_fleet_end(aslam_ctx* ctx);
+/* *n_robots = R of the active fleet, 0 outside fleet mode */
+int aslam_is_fleet(aslam_ctx* ctx, int* n_robots);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
