@@ -130,6 +130,11 @@ _SIGS = {
     "aslam_fleet_set_pose": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "aslam_fleet_end": (C.c_int, [C.c_void_p]),
     "aslam_is_fleet": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_fleet_slam_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "aslam_is_fleet_slam": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_fleet_get_state": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
+    "aslam_fleet_set_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "aslam_fleet_get_landmark_ids": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -430,6 +435,41 @@ class Context:
         n = C.c_int()
         self._ck(self.lib.aslam_is_fleet(self.h, C.byref(n)))
         return n.value
+
+    # -- fleet SLAM: many robots, one camera and one SLAM filter each -------------------------------------------
+    def fleet_slam_begin(self, cams):
+        """cams: one Camera (or (K, D, mount) tuple) per robot; every robot starts with an empty map, disarmed"""
+        cams = [c if isinstance(c, Camera) else Camera.make(*c) for c in cams]
+        arr = (Camera * max(len(cams), 1))(*cams)
+        self._ck(self.lib.aslam_fleet_slam_begin(self.h, len(cams), arr))
+
+    def is_fleet_slam(self):
+        on = C.c_int()
+        self._ck(self.lib.aslam_is_fleet_slam(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def fleet_get_state(self, robot):
+        """robot's (mu, Sigma), as get_state"""
+        n = C.c_int()
+        self._ck(self.lib.aslam_fleet_get_state(self.h, int(robot), C.byref(n), None, None))
+        N = n.value
+        mu = np.zeros(N)
+        sigma = np.zeros((N, N), order="F")
+        self._ck(self.lib.aslam_fleet_get_state(self.h, int(robot), C.byref(n), _ptr(mu, _dp), _ptr(sigma, _dp)))
+        return mu, np.array(sigma)
+
+    def fleet_set_state(self, robot, mu, sigma, landmark_ids):
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        sig = np.asfortranarray(sigma, dtype=np.float64)
+        ids = np.ascontiguousarray(landmark_ids, dtype=np.int32)
+        self._ck(self.lib.aslam_fleet_set_state(self.h, int(robot), int(mu.size), _ptr(mu, _dp), _ptr(sig, _dp),
+                                                _ptr(ids, _ip) if ids.size else None))
+
+    def fleet_get_landmark_ids(self, robot):
+        n = C.c_int()
+        ids = np.zeros(max(int(self.init.max_landmarks), 1), np.int32)
+        self._ck(self.lib.aslam_fleet_get_landmark_ids(self.h, int(robot), C.byref(n), _ptr(ids, _ip)))
+        return ids[: n.value].copy()
 
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))

@@ -133,6 +133,10 @@ struct aslam_ctx {
     hipEvent_t ev_fleet_cam[2] = {nullptr, nullptr}, ev_fleet_work[2] = {nullptr, nullptr};
     bool ev_fleet_cam_set[2] = {false, false}, ev_fleet_work_set[2] = {false, false};
     int fleet_cam_half = 0, fleet_work_half = 0;
+    // fleet SLAM (aslam_fleet_slam_begin): every robot a complete SLAM filter (ekf_fleet_slam.h), allocated for the R
+    // requested; the cameras, armed flags and work-list buffers above serve it as they serve fleet localization
+    bool fleet_slam = false;
+    FleetSlam fslam{};
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -456,46 +460,53 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
     return ASLAM_OK;
 }
 
-int run_ekf_frame(aslam_ctx* c, int slot, double wl, double wr, double dt, bool do_predict) {
+// the per-frame chain behind k_ekf_plan, sized by max_updates_per_frame: on the single filter (s = c->ekf) or on one round of a fleet
+// SLAM call (s = FleetRound)
+template <class S> int run_chain(aslam_ctx* c, const S& s) {
     hipStream_t st = c->stream_ekf;
     const bool fast = c->init.max_updates_per_frame <= ekf_fast_max_updates();
-    prof_begin(c, P_EKF_PLAN, st);
-    launch_ekf_plan(st, c->ekf, c->sp, wl, wr, dt, do_predict ? 1 : 0, c->d_obs + (size_t)slot * kMarkerMax, c->d_nmarkers + slot, c->d_ctr,
-                    c->init.max_updates_per_frame, slot);
-    prof_end(c);
     if (fast) {
         prof_begin(c, P_EKF_MID, st);
-        launch_ekf_mid(st, c->ekf);
+        launch_ekf_mid(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_APPLY, st);
-        launch_ekf_apply(st, c->ekf);
+        launch_ekf_apply(st, s);
         prof_end(c);
     } else if (c->init.max_updates_per_frame <= ekf_mid_max_updates()) {
         prof_begin(c, P_EKF_MID64, st);
-        launch_ekf_mid64(st, c->ekf);
+        launch_ekf_mid64(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_T, st);
-        launch_ekf_T(st, c->ekf);
+        launch_ekf_T(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_UPDATE, st);
-        launch_ekf_update_mfma(st, c->ekf);
+        launch_ekf_update_mfma(st, s);
         prof_end(c);
     } else {
         prof_begin(c, P_EKF_GATHER, st);
-        launch_ekf_gather(st, c->ekf);
+        launch_ekf_gather(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_SMALL, st);
-        launch_ekf_small(st, c->ekf);
+        launch_ekf_small(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_T, st);
-        launch_ekf_T(st, c->ekf);
+        launch_ekf_T(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_UPDATE, st);
-        launch_ekf_update_mfma(st, c->ekf);
+        launch_ekf_update_mfma(st, s);
         prof_end(c);
     }
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
+}
+
+int run_ekf_frame(aslam_ctx* c, int slot, double wl, double wr, double dt, bool do_predict) {
+    hipStream_t st = c->stream_ekf;
+    prof_begin(c, P_EKF_PLAN, st);
+    launch_ekf_plan(st, c->ekf, c->sp, wl, wr, dt, do_predict ? 1 : 0, c->d_obs + (size_t)slot * kMarkerMax, c->d_nmarkers + slot, c->d_ctr,
+                    c->init.max_updates_per_frame, slot);
+    prof_end(c);
+    return run_chain(c, c->ekf);
 }
 
 // localization steps of EKF slots [first, first + count) on the EKF stream, behind the detection that produced their lists: one
@@ -713,6 +724,7 @@ void aslam_destroy(aslam_ctx* c) {
     hipFree(c->d_nfinal); hipFree(c->d_work); hipFree(c->d_dict); hipFree(c->d_markers); hipFree(c->d_nmarkers);
     hipFree(c->d_obs); hipFree(c->d_enc); hipFree(c->d_synth);
     ekf_free(c->ekf);
+    ekf_fleet_free(c->fslam);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
     hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
     for (int h = 0; h < 2; h++) {
@@ -1578,22 +1590,58 @@ int aslam_get_last_timing(aslam_ctx* c, double out[6]) {
     return ASLAM_OK;
 }
 
+namespace {
+// state of filter E (the single one or a fleet robot's), streams synchronised by the caller
+int read_state(aslam_ctx* c, const EkfState& E, int* N, double* mu, double* sigma) {
+    int L = 0;
+    HIP_TRY(c, hipMemcpy(&L, E.d_L, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = 3 + 3 * L;
+    *N = n;
+    if (mu) HIP_TRY(c, hipMemcpy(mu, E.d_mu, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (sigma) {
+        // device layout: column-major with leading dimension ld = N_max; pack to ld = N
+        std::vector<double> tmp((size_t)E.ld * n);
+        HIP_TRY(c, hipMemcpy(tmp.data(), E.d_sigma, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int col = 0; col < n; col++) std::memcpy(sigma + (size_t)col * n, &tmp[(size_t)col * E.ld], sizeof(double) * n);
+    }
+    return ASLAM_OK;
+}
+
+// filter E := (mu, sigma, ids), its last-observed list emptied (N, L and the ids' presence checked by the caller, streams synchronised)
+int write_state(aslam_ctx* c, const EkfState& E, int N, const double* mu, const double* sigma, const int* landmark_ids) {
+    const int L = (N - 3) / 3;
+    std::vector<double> tmp((size_t)E.ld * E.ld, 0.0);
+    for (int col = 0; col < N; col++) std::memcpy(&tmp[(size_t)col * E.ld], sigma + (size_t)col * N, sizeof(double) * N);
+    HIP_TRY(c, hipMemcpy(E.d_sigma, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(E.d_mu, mu, sizeof(double) * N, hipMemcpyHostToDevice));
+    std::vector<int> id2idx(kIdTableSize, -1), idx2id(E.max_landmarks, -1);
+    for (int i = 0; i < L; i++) {
+        if (landmark_ids[i] < 0 || landmark_ids[i] >= kIdTableSize) return fail(c, ASLAM_E_INVALID, "landmark id out of range");
+        if (id2idx[landmark_ids[i]] < 0) id2idx[landmark_ids[i]] = i;
+        idx2id[i] = landmark_ids[i];
+    }
+    HIP_TRY(c, hipMemcpy(E.d_id2idx, id2idx.data(), sizeof(int) * kIdTableSize, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(E.d_idx2id, idx2id.data(), sizeof(int) * E.max_landmarks, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(E.d_L, &L, sizeof(int), hipMemcpyHostToDevice));
+    int zero = 0;
+    HIP_TRY(c, hipMemcpy(E.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int read_landmark_ids(aslam_ctx* c, const EkfState& E, int* L, int* ids) {
+    int n = 0;
+    HIP_TRY(c, hipMemcpy(&n, E.d_L, sizeof(int), hipMemcpyDeviceToHost));
+    *L = n;
+    if (ids && n) HIP_TRY(c, hipMemcpy(ids, E.d_idx2id, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return ASLAM_OK;
+}
+}  // namespace
+
 int aslam_get_state(aslam_ctx* c, int* N, double* mu, double* sigma) {
     if (!c || !N) return fail(c, ASLAM_E_INVALID, "null argument");
     if (c->fleet_n) return fleet_refuses(c);
     { int rs = sync_streams(c); if (rs) return rs; }
-    int L = 0;
-    HIP_TRY(c, hipMemcpy(&L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = 3 + 3 * L;
-    *N = n;
-    if (mu) HIP_TRY(c, hipMemcpy(mu, c->ekf.d_mu, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (sigma) {
-        // device layout: column-major with leading dimension ld = N_max; pack to ld = N
-        std::vector<double> tmp((size_t)c->ekf.ld * n);
-        HIP_TRY(c, hipMemcpy(tmp.data(), c->ekf.d_sigma, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int col = 0; col < n; col++) std::memcpy(sigma + (size_t)col * n, &tmp[(size_t)col * c->ekf.ld], sizeof(double) * n);
-    }
-    return ASLAM_OK;
+    return read_state(c, c->ekf, N, mu, sigma);
 }
 
 int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, const int* landmark_ids) {
@@ -1604,21 +1652,8 @@ int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, 
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
     if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
     { int rs = sync_streams(c); if (rs) return rs; }
-    std::vector<double> tmp((size_t)c->ekf.ld * c->ekf.ld, 0.0);
-    for (int col = 0; col < N; col++) std::memcpy(&tmp[(size_t)col * c->ekf.ld], sigma + (size_t)col * N, sizeof(double) * N);
-    HIP_TRY(c, hipMemcpy(c->ekf.d_sigma, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->ekf.d_mu, mu, sizeof(double) * N, hipMemcpyHostToDevice));
-    std::vector<int> id2idx(kIdTableSize, -1), idx2id(c->ekf.max_landmarks, -1);
-    for (int i = 0; i < L; i++) {
-        if (landmark_ids[i] < 0 || landmark_ids[i] >= kIdTableSize) return fail(c, ASLAM_E_INVALID, "landmark id out of range");
-        if (id2idx[landmark_ids[i]] < 0) id2idx[landmark_ids[i]] = i;
-        idx2id[i] = landmark_ids[i];
-    }
-    HIP_TRY(c, hipMemcpy(c->ekf.d_id2idx, id2idx.data(), sizeof(int) * kIdTableSize, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->ekf.d_idx2id, idx2id.data(), sizeof(int) * c->ekf.max_landmarks, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->ekf.d_L, &L, sizeof(int), hipMemcpyHostToDevice));
-    int zero = 0;
-    HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
+    int r = write_state(c, c->ekf, N, mu, sigma, landmark_ids);
+    if (r) return r;
     c->mirror_dirty = true;
     return ASLAM_OK;
 }
@@ -1924,10 +1959,10 @@ int fleet_alloc(aslam_ctx* c) {
     HIP_TRY(c, dalloc(&c->fleet.nlast, R));
     HIP_TRY(c, dalloc(&c->d_fleet_cams, R));
     HIP_TRY(c, dalloc(&c->d_fleet_camidx, B));
-    HIP_TRY(c, dalloc(&c->d_fleet_work, 4 * R + B));
+    HIP_TRY(c, dalloc(&c->d_fleet_work, 4 * R + 4 * B));       // a localization call's CSR list, or a SLAM call's 4 ints per slot
     for (int h = 0; h < 2; h++) {
         HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_cam[h]), sizeof(int) * B, hipHostMallocDefault));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_work[h]), sizeof(int) * (4 * R + B), hipHostMallocDefault));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_work[h]), sizeof(int) * (4 * R + 4 * B), hipHostMallocDefault));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_cam[h], hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_work[h], hipEventDisableTiming));
     }
@@ -1983,6 +2018,79 @@ int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
     note_ekf_range(c, first, count);
     return ASLAM_OK;
 }
+
+// fleet SLAM steps of frame slots [first, first + count), slot first + i belonging to robot robots[i], in rounds: round k holds the k-th
+// slot of every robot that has one, and is one launch of each kernel of the per-frame chain with one z-slice per robot.  The work list
+// (4 ints per slot: robot, slot, predict, 0, round after round) goes up once per call; the host keeps the armed flags.
+int run_fleet_slam(aslam_ctx* c, int first, int count, const int* robots) {
+    std::vector<int> taken(c->fleet_n, 0);
+    std::vector<std::vector<int>> rounds;
+    for (int i = 0; i < count; i++) {
+        const int k = taken[robots[i]]++;
+        if (k == (int)rounds.size()) rounds.emplace_back();
+        rounds[k].push_back(i);
+    }
+    const int h = c->fleet_work_half;
+    c->fleet_work_half ^= 1;
+    if (c->ev_fleet_work_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_work[h]));   // the copy that last read this half ran
+    int* w = c->h_fleet_work[h];
+    int n = 0;
+    for (const std::vector<int>& rd : rounds)
+        for (int i : rd) {
+            const int r = robots[i];
+            w[4 * n] = r; w[4 * n + 1] = first + i; w[4 * n + 2] = c->fleet_armed[r] ? 1 : 0; w[4 * n + 3] = 0;
+            c->fleet_armed[r] = 1;
+            n++;
+        }
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, hipMemcpyAsync(c->d_fleet_work, w, sizeof(int) * 4 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev_fleet_work[h], st));
+    c->ev_fleet_work_set[h] = true;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    int row = 0;
+    for (const std::vector<int>& rd : rounds) {
+        const FleetRound R{c->fslam, c->d_fleet_work + 4 * row, c->d_enc, (int)rd.size()};
+        prof_begin(c, P_EKF_PLAN, st);
+        launch_ekf_plan(st, R, c->sp, c->d_obs, c->d_nmarkers, c->d_ctr, c->init.max_updates_per_frame);
+        prof_end(c);
+        int r = run_chain(c, R);
+        if (r) return r;
+        row += (int)rd.size();
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_ekf, st));
+    note_ekf_range(c, first, count);
+    return ASLAM_OK;
+}
+
+// the EKF part of a fleet call, whichever kind the fleet is
+int run_fleet_ekf(aslam_ctx* c, int first, int count, const int* robots) {
+    return c->fleet_slam ? run_fleet_slam(c, first, count, robots) : run_fleet_steps(c, first, count, robots);
+}
+
+int fleet_slam_refuses(aslam_ctx* c) {
+    return fail(c, ASLAM_E_STATE, "no fleet SLAM (aslam_fleet_slam_begin first)");
+}
+
+// leave the active fleet, if any: the single filter as aslam_create leaves it (ekf_alloc), the robots' filters freed (streams synchronised)
+int fleet_leave(aslam_ctx* c) {
+    const size_t ld = (size_t)c->ekf.ld;
+    HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
+    HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
+    HIP_TRY(c, hipMemset(c->ekf.d_L, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_id2idx, 0xFF, kIdTableSize * sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_idx2id, 0xFF, (size_t)c->ekf.max_landmarks * sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_nlast, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_npop, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(c->ekf.d_m, 0, sizeof(int)));
+    c->is_init = false;
+    c->last_time = 0;
+    c->mirror_dirty = true;
+    c->fleet_n = 0;
+    c->fleet_armed.clear();
+    c->fleet_slam = false;
+    ekf_fleet_free(c->fslam);
+    return ASLAM_OK;
+}
 }  // namespace
 
 int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth, const double* poses,
@@ -2006,6 +2114,8 @@ int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int 
     if (r) return r;
     r = fleet_alloc(c);
     if (r) return r;
+    c->fleet_slam = false;                   // a SLAM fleet ends here
+    ekf_fleet_free(c->fslam);
     r = install_frozen_map(c, n, ids, xyth, true);
     if (r) return r;
     int zero = 0;
@@ -2047,7 +2157,7 @@ int aslam_fleet_add_images(aslam_ctx* c, int n, const int* robots, const double*
     if (r) return r;
     c->rig_last = false;
     const auto t2 = clk::now();
-    r = run_fleet_steps(c, 0, n, robots);
+    r = run_fleet_ekf(c, 0, n, robots);
     if (r) return r;
     const auto t3 = clk::now();
     r = sync_streams(c);
@@ -2082,7 +2192,7 @@ int aslam_fleet_run_staged(aslam_ctx* c, int first, int count, const int* robot_
     }
     c->rig_last = false;
     if (!with_ekf) return ASLAM_OK;
-    return run_fleet_steps(c, first, count, robot_of_slot);
+    return run_fleet_ekf(c, first, count, robot_of_slot);
 }
 
 int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, double* sigmas) {
@@ -2092,7 +2202,20 @@ int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, d
     const int R = c->fleet_n;
     *n_robots = R;
     std::vector<double> h((size_t)kFleetState * R);
-    HIP_TRY(c, hipMemcpy(h.data(), c->fleet.pose, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    if (c->fleet_slam) {
+        // every robot's mu[0..2] and the first three entries of Sigma's columns 0..2, gathered as rows of kFleetState doubles
+        const FleetSlam& F = c->fslam;
+        HIP_TRY(c, hipMemcpy2D(h.data(), sizeof(double) * kFleetState, F.base.d_mu, F.stride, 3 * sizeof(double), R, hipMemcpyDeviceToHost));
+        for (int j = 0; j < 3; j++)
+            HIP_TRY(c, hipMemcpy2D(h.data() + 3 + 3 * j, sizeof(double) * kFleetState, F.base.d_sigma + (size_t)j * F.base.ld, F.stride,
+                                   3 * sizeof(double), R, hipMemcpyDeviceToHost));
+        for (int k = 0; k < R; k++) {        // column-major -> row-major Sigma_xx
+            double* S = &h[(size_t)kFleetState * k + 3];
+            std::swap(S[1], S[3]); std::swap(S[2], S[6]); std::swap(S[5], S[7]);
+        }
+    } else {
+        HIP_TRY(c, hipMemcpy(h.data(), c->fleet.pose, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    }
     for (int k = 0; k < std::min(max, R); k++) {
         if (poses) std::memcpy(poses + 3 * k, &h[(size_t)kFleetState * k], 3 * sizeof(double));
         if (sigmas) std::memcpy(sigmas + 9 * k, &h[(size_t)kFleetState * k + 3], 9 * sizeof(double));
@@ -2103,6 +2226,7 @@ int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, d
 int aslam_fleet_set_pose(aslam_ctx* c, int robot, const double pose[3], const double sigma[9]) {
     if (!c || !pose || !sigma) return fail(c, ASLAM_E_INVALID, "null argument");
     if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (c->fleet_slam) return fail(c, ASLAM_E_STATE, "fleet SLAM: a robot's pose is correlated with its map (aslam_fleet_set_state)");
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     int r = check_pose(c, pose, sigma);
     if (r) return r;
@@ -2115,28 +2239,74 @@ int aslam_fleet_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
     if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
     { int rs = sync_streams(c); if (rs) return rs; }
-    // the single filter as aslam_create leaves it (ekf_alloc)
-    const size_t ld = (size_t)c->ekf.ld;
-    HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
-    HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
-    HIP_TRY(c, hipMemset(c->ekf.d_L, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_id2idx, 0xFF, kIdTableSize * sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_idx2id, 0xFF, (size_t)c->ekf.max_landmarks * sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_nlast, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_npop, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_m, 0, sizeof(int)));
-    c->is_init = false;
-    c->last_time = 0;
-    c->mirror_dirty = true;
-    c->fleet_n = 0;
-    c->fleet_armed.clear();
-    return ASLAM_OK;
+    return fleet_leave(c);
 }
 
 int aslam_is_fleet(aslam_ctx* c, int* n_robots) {
     if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
     *n_robots = c->fleet_n;
     return ASLAM_OK;
+}
+
+// ---- fleet SLAM: many robots, each building its own map (include/aruco_slam_hip.h) ------------------------------
+int aslam_fleet_slam_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams) {
+    if (!c || !cams) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: one filter is active (aslam_localize_end first)");
+    if (n_robots < 1 || n_robots > std::min(c->max_batch, ASLAM_MAX_ROBOTS))
+        return fail(c, ASLAM_E_INVALID, "a fleet has 1..min(max_batch, ASLAM_MAX_ROBOTS) robots");
+    std::vector<RigCam> rc(n_robots);
+    for (int k = 0; k < n_robots; k++) {
+        int r = rig_camera(c, cams[k], rc[k]);
+        if (r) return r;
+    }
+    int r = sync_streams(c);
+    if (r) return r;
+    r = fleet_alloc(c);
+    if (r) return r;
+    r = fleet_leave(c);                      // the fleet active so far, if any, ends; the single filter as aslam_create leaves it
+    if (r) return r;
+    const hipError_t e = ekf_fleet_alloc(c->fslam, n_robots, c->ekf);
+    if (e != hipSuccess)
+        return fail(c, ASLAM_E_CAPACITY, std::to_string(n_robots) + " filters of max_landmarks " + std::to_string(c->ekf.max_landmarks) +
+                                             " do not fit: " + hipGetErrorString(e));
+    HIP_TRY(c, hipMemcpy(c->d_fleet_cams, rc.data(), sizeof(RigCam) * n_robots, hipMemcpyHostToDevice));
+    c->fleet_armed.assign(n_robots, 0);
+    c->fleet_n = n_robots;
+    c->fleet_slam = true;
+    return ASLAM_OK;
+}
+
+int aslam_is_fleet_slam(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->fleet_slam ? 1 : 0;
+    return ASLAM_OK;
+}
+
+int aslam_fleet_get_state(aslam_ctx* c, int robot, int* N, double* mu, double* sigma) {
+    if (!c || !N) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    return read_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma);
+}
+
+int aslam_fleet_set_state(aslam_ctx* c, int robot, int N, const double* mu, const double* sigma, const int* landmark_ids) {
+    if (!c || !mu || !sigma || N < 3 || (N - 3) % 3 != 0) return fail(c, ASLAM_E_INVALID, "bad state");
+    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    const int L = (N - 3) / 3;
+    if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
+    if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    return write_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma, landmark_ids);
+}
+
+int aslam_fleet_get_landmark_ids(aslam_ctx* c, int robot, int* L, int* ids) {
+    if (!c || !L) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    return read_landmark_ids(c, ekf_fleet_robot(c->fslam, robot), L, ids);
 }
 
 // MapLoader markers -> planar landmarks: heading of the marker's +z axis (third column of Matrix3x3(orientation)), which is what an
@@ -2289,11 +2459,7 @@ int aslam_get_slot_ekf_stats(aslam_ctx* c, int first, int count, int* stats) {
 int aslam_get_landmark_ids(aslam_ctx* c, int* L, int* ids) {
     if (!c || !L) return fail(c, ASLAM_E_INVALID, "null argument");
     { int rs = sync_streams(c); if (rs) return rs; }
-    int n = 0;
-    HIP_TRY(c, hipMemcpy(&n, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
-    *L = n;
-    if (ids && n) HIP_TRY(c, hipMemcpy(ids, c->ekf.d_idx2id, sizeof(int) * n, hipMemcpyDeviceToHost));
-    return ASLAM_OK;
+    return read_landmark_ids(c, c->ekf, L, ids);
 }
 
 int aslam_detect_batch(aslam_ctx* c, const uint8_t* frames, int nframes, int rows, int cols, int channels, size_t step,

@@ -112,6 +112,34 @@ struct FleetState {
 };
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
                         const unsigned* n_markers, const double* enc, const int* work, int n_groups);
+// fleet SLAM (ekf_fleet_slam.h): R complete filters with the single filter's chain layouts in one allocation; robot r's buffers lie
+// r * stride bytes past robot 0's.  No window buffers; d_slot_stat and max_slots are the context's.
+struct FleetSlam {
+    EkfState base;                     // robot 0's filter
+    size_t stride;                     // bytes from one robot's buffers to the next one's
+    void* mem;                         // the allocation (nullptr: none)
+    int n;                             // robots
+};
+hipError_t ekf_fleet_alloc(FleetSlam& F, int n_robots, const EkfState& single);
+void ekf_fleet_free(FleetSlam& F);
+EkfState ekf_fleet_robot(const FleetSlam& F, int robot);   // robot's filter (device pointers)
+// one round of a fleet SLAM call: n robots, one frame each, robot k = workgroups with blockIdx.z = k.  work: n device rows
+// {robot, slot, predict, 0}; enc: the context's per-slot encoder samples.  The launchers below run the per-frame chain's kernels in
+// their fleet instantiation with the single filter's grids in x / y.
+struct FleetRound {
+    FleetSlam F;
+    const int* work;
+    const double* enc;
+    int n;
+};
+void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m);
+void launch_ekf_mid(hipStream_t st, const FleetRound& R);
+void launch_ekf_apply(hipStream_t st, const FleetRound& R);
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R);
+void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R);
+void launch_ekf_gather(hipStream_t st, const FleetRound& R);
+void launch_ekf_small(hipStream_t st, const FleetRound& R);
+void launch_ekf_T(hipStream_t st, const FleetRound& R);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays

@@ -14,8 +14,10 @@
 #include "common.h"
 #include "ekf.h"
 #include "ekf_dev.h"
+#include "ekf_fleet_slam.h"
 #include <cmath>
 #include <algorithm>
+#include <type_traits>
 
 namespace aslam {
 
@@ -142,9 +144,15 @@ __global__ __launch_bounds__(256) void k_ekf_predict(EkfState E, SlamParams sp, 
 }
 
 // ---- plan: predict + queue order + augment + update plan (one workgroup) -----------------------------------
-__global__ __launch_bounds__(256) void k_ekf_plan(EkfState E, SlamParams sp, double wl, double wr, double dt, int do_predict,
+// The chain kernels below are templates on where their filter comes from (EkfSingle / EkfFleet, ekf_fleet_slam.h).  They are static:
+// the __shared__ arrays of an instantiation then keep internal linkage, which lets the optimiser split and drop them as it did before
+// they were templates (with linkonce_odr arrays k_ekf_plan<EkfSingle> kept sQ and laid its LDS out differently).
+template <class Src>
+static __global__ __launch_bounds__(256) void k_ekf_plan(Src S, SlamParams sp, double wl, double wr, double dt, int do_predict,
                                                   const ObsRaw* __restrict__ obs, const unsigned* __restrict__ n_markers,
                                                   Counters* ctr, int max_m, int slot) {
+    const EkfState E = S.state();
+    S.frame(wl, wr, dt, do_predict, obs, n_markers, slot);
     __shared__ double sH[9], sQ[9], sMu[5];
     __shared__ ObsRaw sObs[kMarkerMax];
     __shared__ LastObs sLast[kMarkerMax];
@@ -429,7 +437,9 @@ __device__ __forceinline__ void gather_vw(const EkfState& E, int t, int N, int m
 }
 
 // grid (columns / 256, update slices)
-__global__ __launch_bounds__(256) void k_ekf_gather(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(256) void k_ekf_gather(Src S) {
+    const EkfState E = S.state();
     gather_vw(E, blockIdx.x * 256 + threadIdx.x, 3 + 3 * (*E.d_L), *E.d_m, blockIdx.y, gridDim.y);
 }
 
@@ -440,7 +450,10 @@ __global__ __launch_bounds__(256) void k_ekf_gather(EkfState E) {
 //   alpha_i. = e_i - sum_{j<i} D_ij alpha_j.             beta_.i = e_i - sum_{j<i} gamma_.j C_ji
 //   gamma_.i = beta_.i S_i^-1                            G = sum_i gamma_.i alpha_i.      g = sum_i gamma_.i ze_i
 // where Sv_li = V_l H_i^T and Sw_il = H_i W_l are the 3x3 blocks of H Sigma0 H^T taken from rows / columns.
-__device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 2*9*kMarkerMax + 9*kMarkerMax + 9 doubles of LDS */) {
+// a template on k_ekf_small's state source only so that each instantiation has a callee of its own: shared by two kernels, the inliner
+// treated it differently and k_ekf_small<EkfSingle> no longer compiled to the instructions of the former k_ekf_small
+template <class Src>
+static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 2*9*kMarkerMax + 9*kMarkerMax + 9 doubles of LDS */) {
     double* sC = scratch;
     double* sD = scratch + kMarkerMax * 9;
     double* sBeta = scratch + 2 * kMarkerMax * 9;
@@ -556,7 +569,9 @@ __device__ __forceinline__ void inv3_cof(const double* P, int n3, double* o) {  
     o[6] = C * id; o[7] = (b * g - a * h) * id; o[8] = (a * e - b * d) * id;
 }
 
-__global__ __launch_bounds__(768) void k_ekf_small(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(768) void k_ekf_small(Src S) {
+    const EkfState E = S.state();
     __shared__ double sA0[kSmallMax * kSmallMax];     // ping
     __shared__ double sA1[kSmallMax * kSmallMax];     // pong
     __shared__ double sZe[kSmallMax], sNu[kSmallMax];
@@ -566,7 +581,7 @@ __global__ __launch_bounds__(768) void k_ekf_small(EkfState E) {
     const int ld = E.ld;
     const int tc = tid % kSmallMax, tr = tid / kSmallMax;     // column, row group (0..7); rows r = tr + 8*i
     if (n3 > kSmallMax) {                              // uniform branch
-        ekf_small_general(E, sA0);
+        ekf_small_general<Src>(E, sA0);
     } else if (m > 0) {
         // A[(3i+a)][(3j+b)] = (V_i H_j^T)[a][b] + delta_ij R_i[a][b]   (aruco_slam.cpp:146: (Gx*sigma_)*Gx^T + Rk)
         if (tc < n3) {
@@ -651,7 +666,9 @@ __global__ __launch_bounds__(768) void k_ekf_small(EkfState E) {
 // workgroups cover the GPU where 47 scalar ones did not.  Workgroups with y = 0 also add W g to their 32 entries of mu.
 constexpr int TC = 32, TR = 64;
 
-__global__ __launch_bounds__(256) void k_ekf_T(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(256) void k_ekf_T(Src S) {
+    const EkfState E = S.state();
     __shared__ double sMu[8][TC];
     const int m = *E.d_m;
     const int n3 = 3 * m;
@@ -717,7 +734,9 @@ constexpr int kFastN3 = 3 * kFastM;      // 72
 constexpr int MIDT = 576;                // kFastM x kFastM: one thread per 3x3 block of the innovation matrix
 
 // <= 128 VGPRs (4 waves per SIMD) so that the workgroup always finds room beside the persistent detection waves of the other stream
-__global__ __launch_bounds__(576, 4) void k_ekf_mid(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
+    const EkfState E = S.state();
     __shared__ __align__(16) double sCol[2][kFastM][10];   // pivot column blocks (bi, ib); rows padded to 80 B for 128-bit LDS reads
     __shared__ __align__(16) double sRow[2][kFastM][10];   // pivot row blocks (ib, bj), unscaled
     __shared__ __align__(16) double sPinv[2][10];          // S_ib^-1 (from the owner of the pivot block, one step ahead)
@@ -886,7 +905,9 @@ constexpr int APK = kFastN3;             // padded depth of the LDS images (72)
 // A[i][k] in lane k*16+i, B[k][j] in lane k*16+j, D rows (lane>>4)+4*reg, column lane&15.  The Sigma tile is formed
 // transposed, D'[c][r] = sum_p T[p][c] W^T[p][r], so each accumulator register covers 16 consecutive rows r of one
 // column c and the read-modify-write of the column-major Sigma is coalesced.
-__global__ __launch_bounds__(256) void k_ekf_apply(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(256) void k_ekf_apply(Src S) {
+    const EkfState E = S.state();
     __shared__ double sGt[APK * APK + 16];    // G transposed: sGt[p][q], row stride APK, zero padded (+16: the 5th q-tile reads 8 past)
     __shared__ double sVW[APK][64];           // V tile, later the W^T tile
     __shared__ double sT[APK + 8][64];        // T tile = G V tile (rows 72..79 belong to the padded 5th q-tile)
@@ -1017,7 +1038,9 @@ constexpr int M64T = 512;                // threads of k_ekf_mid64: 8 wavefronts
 constexpr int M64B = (kMidM * kMidM + M64T - 1) / M64T;   // 3x3 blocks per thread (8)
 
 // The fast chain's Gauss-Jordan with up to M64B blocks per thread, dense block index e = tid + M64T k -> (e / m, e % m).
-__global__ __launch_bounds__(M64T) void k_ekf_mid64(EkfState E) {
+template <class Src>
+static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
+    const EkfState E = S.state();
     __shared__ __align__(16) double sCol[2][kMidM][10];
     __shared__ __align__(16) double sY[kMidM][10];
     __shared__ double sPinv[9];
@@ -1188,8 +1211,9 @@ constexpr int MUR = 64;                  // rows of Sigma per workgroup
 // N = 3003, 128-wide tiles make 1128 workgroups = a second, nearly empty round, 160-wide ones 893 <= 1024.  The Sigma tile is
 // loaded straight into the accumulators before the depth loop (its latency hides behind the first chunks) and the product
 // is subtracted by negating one operand: the epilogue is a pure store.
-template <int WCT>
-__global__ __launch_bounds__(128) void k_ekf_update_mfma(EkfState E, int depth) {
+template <class Src, int WCT>
+static __global__ __launch_bounds__(128) void k_ekf_update_mfma(Src S, int depth) {
+    const EkfState E = S.state();
     constexpr int MUC = 2 * 16 * WCT;                              // columns per workgroup
     __shared__ double sT[2][MUK][MUC];
     __shared__ double sW[2][MUK][MUR];
@@ -1366,41 +1390,135 @@ void launch_ekf_predict_only(hipStream_t st, const EkfState& E, const SlamParams
 }
 void launch_ekf_plan(hipStream_t st, const EkfState& E, const SlamParams& sp, double wl, double wr, double dt, int do_predict,
                      const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m, int slot) {
-    hipLaunchKernelGGL(k_ekf_plan, dim3(1), dim3(256), 0, st, E, sp, wl, wr, dt, do_predict, obs, n_markers, ctr, max_m, slot);
+    hipLaunchKernelGGL(k_ekf_plan<EkfSingle>, dim3(1), dim3(256), 0, st, EkfSingle{E}, sp, wl, wr, dt, do_predict, obs, n_markers, ctr, max_m, slot);
 }
 void launch_ekf_gather(hipStream_t st, const EkfState& E) {
-    hipLaunchKernelGGL(k_ekf_gather, dim3((E.ld + 255) / 256, 32), dim3(256), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_gather<EkfSingle>, dim3((E.ld + 255) / 256, 32), dim3(256), 0, st, EkfSingle{E});
 }
 void launch_ekf_small(hipStream_t st, const EkfState& E) {
-    hipLaunchKernelGGL(k_ekf_small, dim3(1), dim3(SMT), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_small<EkfSingle>, dim3(1), dim3(SMT), 0, st, EkfSingle{E});
 }
 void launch_ekf_T(hipStream_t st, const EkfState& E) {
-    hipLaunchKernelGGL(k_ekf_T, dim3((E.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR), dim3(256), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_T<EkfSingle>, dim3((E.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR), dim3(256), 0, st, EkfSingle{E});
 }
 void launch_ekf_mid(hipStream_t st, const EkfState& E) {
     const int ncg = (E.ld + MIDT - 1) / MIDT;
-    hipLaunchKernelGGL(k_ekf_mid, dim3(1 + ncg * 12), dim3(MIDT), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_mid<EkfSingle>, dim3(1 + ncg * 12), dim3(MIDT), 0, st, EkfSingle{E});
 }
 void launch_ekf_apply(hipStream_t st, const EkfState& E) {
     const int t = (E.ld + 63) / 64;
-    hipLaunchKernelGGL(k_ekf_apply, dim3(t, t), dim3(256), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_apply<EkfSingle>, dim3(t, t), dim3(256), 0, st, EkfSingle{E});
 }
 int ekf_fast_max_updates() { return kFastM; }
 int ekf_mid_max_updates() { return kMidM; }
 void launch_ekf_mid64(hipStream_t st, const EkfState& E) {
     const int ncg = (E.ld + M64T - 1) / M64T;
-    hipLaunchKernelGGL(k_ekf_mid64, dim3(1 + ncg * 16), dim3(M64T), 0, st, E);
+    hipLaunchKernelGGL(k_ekf_mid64<EkfSingle>, dim3(1 + ncg * 16), dim3(M64T), 0, st, EkfSingle{E});
+}
+// the narrowest tile whose workgroups all fit on the device at once (256 CUs x 4); N_max stands in for the current N
+static bool update_tile4(const EkfState& E) {
+    const int rt = (E.ld + MUR - 1) / MUR;
+    return rt * ((E.ld + 127) / 128) <= 1024 || rt * ((E.ld + 159) / 160) > 1024;
 }
 void launch_ekf_update_mfma(hipStream_t st, const EkfState& E, int depth) {
-    // the narrowest tile whose workgroups all fit on the device at once (256 CUs x 4); N_max stands in for the current N
     const int rt = (E.ld + MUR - 1) / MUR;
-    if (rt * ((E.ld + 127) / 128) <= 1024 || rt * ((E.ld + 159) / 160) > 1024)
-        hipLaunchKernelGGL(k_ekf_update_mfma<4>, dim3(rt, (E.ld + 127) / 128), dim3(128), 0, st, E, depth);
+    if (update_tile4(E))
+        hipLaunchKernelGGL((k_ekf_update_mfma<EkfSingle, 4>), dim3(rt, (E.ld + 127) / 128), dim3(128), 0, st, EkfSingle{E}, depth);
     else
-        hipLaunchKernelGGL(k_ekf_update_mfma<5>, dim3(rt, (E.ld + 159) / 160), dim3(128), 0, st, E, depth);
+        hipLaunchKernelGGL((k_ekf_update_mfma<EkfSingle, 5>), dim3(rt, (E.ld + 159) / 160), dim3(128), 0, st, EkfSingle{E}, depth);
 }
 void launch_ekf_export_map(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_export_map, dim3((E.max_landmarks + 255) / 256), dim3(256), 0, st, E);
+}
+
+// ---- fleet SLAM (ekf_fleet_slam.h): R filters in one allocation, the chain kernels' fleet instantiations -------------------------
+hipError_t ekf_fleet_alloc(FleetSlam& F, int n_robots, const EkfState& single) {
+    F = FleetSlam{};
+    EkfState& b = F.base;
+    b.max_landmarks = single.max_landmarks;
+    b.ld = single.ld;
+    b.d_slot_stat = single.d_slot_stat;
+    b.max_slots = single.max_slots;
+    // robot 0's buffers as byte offsets first (the chain layouts of ekf_alloc, no window buffers), then moved into the allocation
+    const size_t ld = (size_t)b.ld, n3 = 3 * (size_t)kMarkerMax;
+    size_t off = 0;
+    auto take = [&off](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(off);
+        off += (count * sizeof(*p) + 255) / 256 * 256;
+    };
+    take(b.d_mu, ld);
+    take(b.d_sigma, ld * ld);
+    take(b.d_L, 1);
+    take(b.d_id2idx, kIdTableSize);                   // the two id tables back to back: one memset initialises both
+    take(b.d_idx2id, (size_t)b.max_landmarks);
+    const size_t tables = reinterpret_cast<size_t>(b.d_id2idx), tables_end = off;
+    take(b.d_last, kMarkerMax);
+    take(b.d_nlast, 1);
+    take(b.d_pop, kMarkerMax);
+    take(b.d_npop, 1);
+    take(b.d_upd, kMarkerMax);
+    take(b.d_m, 1);
+    take(b.d_V, n3 * ld);
+    take(b.d_Wt, n3 * ld);
+    take(b.d_T, n3 * ld);
+    take(b.d_Sv, n3 * n3);
+    take(b.d_Sw, n3 * n3);
+    take(b.d_alpha, n3 * n3);
+    take(b.d_gamma, n3 * n3);
+    take(b.d_G, n3 * n3);
+    take(b.d_g, n3);
+    F.stride = (off + 4095) / 4096 * 4096;
+    hipError_t e = hipMalloc(&F.mem, F.stride * n_robots);
+    if (e != hipSuccess) { (void)hipGetLastError(); F = FleetSlam{}; return e; }
+    b = ekf_robot_state(b, reinterpret_cast<size_t>(F.mem), 1);   // offsets -> pointers into the allocation
+    F.n = n_robots;
+    // ArucoSlam::ArucoSlam (aruco_slam.cpp:13-18) per robot: mu = 0, sigma = 0, empty map and lists; id tables -1
+    if ((e = hipMemset(F.mem, 0, F.stride * n_robots)) != hipSuccess) { ekf_fleet_free(F); return e; }
+    for (int r = 0; r < n_robots; r++)
+        if ((e = hipMemset(static_cast<char*>(F.mem) + F.stride * r + tables, 0xFF, tables_end - tables)) != hipSuccess) { ekf_fleet_free(F); return e; }
+    return hipSuccess;
+}
+
+void ekf_fleet_free(FleetSlam& F) {
+    if (F.mem) hipFree(F.mem);
+    F = FleetSlam{};
+}
+
+EkfState ekf_fleet_robot(const FleetSlam& F, int robot) { return ekf_robot_state(F.base, F.stride, robot); }
+
+static EkfFleet fleet_source(const FleetRound& R) { return EkfFleet{R.F.base, R.F.stride, R.work, R.enc}; }
+
+void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m) {
+    hipLaunchKernelGGL(k_ekf_plan<EkfFleet>, dim3(1, 1, R.n), dim3(256), 0, st, fleet_source(R), sp, 0.0, 0.0, 0.0, 0, obs, n_markers, ctr, max_m, 0);
+}
+void launch_ekf_gather(hipStream_t st, const FleetRound& R) {
+    hipLaunchKernelGGL(k_ekf_gather<EkfFleet>, dim3((R.F.base.ld + 255) / 256, 32, R.n), dim3(256), 0, st, fleet_source(R));
+}
+void launch_ekf_small(hipStream_t st, const FleetRound& R) {
+    hipLaunchKernelGGL(k_ekf_small<EkfFleet>, dim3(1, 1, R.n), dim3(SMT), 0, st, fleet_source(R));
+}
+void launch_ekf_T(hipStream_t st, const FleetRound& R) {
+    hipLaunchKernelGGL(k_ekf_T<EkfFleet>, dim3((R.F.base.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR, R.n), dim3(256), 0, st, fleet_source(R));
+}
+void launch_ekf_mid(hipStream_t st, const FleetRound& R) {
+    const int ncg = (R.F.base.ld + MIDT - 1) / MIDT;
+    hipLaunchKernelGGL(k_ekf_mid<EkfFleet>, dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, fleet_source(R));
+}
+void launch_ekf_apply(hipStream_t st, const FleetRound& R) {
+    const int t = (R.F.base.ld + 63) / 64;
+    hipLaunchKernelGGL(k_ekf_apply<EkfFleet>, dim3(t, t, R.n), dim3(256), 0, st, fleet_source(R));
+}
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R) {
+    const int ncg = (R.F.base.ld + M64T - 1) / M64T;
+    hipLaunchKernelGGL(k_ekf_mid64<EkfFleet>, dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, fleet_source(R));
+}
+void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
+    const EkfState& E = R.F.base;                  // the single filter's tile choice: the same grid per robot
+    const int rt = (E.ld + MUR - 1) / MUR;
+    if (update_tile4(E))
+        hipLaunchKernelGGL((k_ekf_update_mfma<EkfFleet, 4>), dim3(rt, (E.ld + 127) / 128, R.n), dim3(128), 0, st, fleet_source(R), -1);
+    else
+        hipLaunchKernelGGL((k_ekf_update_mfma<EkfFleet, 5>), dim3(rt, (E.ld + 159) / 160, R.n), dim3(128), 0, st, fleet_source(R), -1);
 }
 
 } // namespace aslam

@@ -263,8 +263,36 @@ int aslam_fleet_get_poses(aslam_ctx* ctx, int max, int* n_robots, double* poses 
 int aslam_fleet_set_pose(aslam_ctx* ctx, int robot, const double pose[3], const double sigma[9]);
 /* leave fleet mode: the single filter is as aslam_create leaves it (empty map, disarmed); cameras and detector settings stay */
 int aslam_fleet_end(aslam_ctx* ctx);
-/* *n_robots = R of the active fleet, 0 outside fleet mode */
+/* *n_robots = R of the active fleet (either kind), 0 outside fleet mode */
 int aslam_is_fleet(aslam_ctx* ctx, int* n_robots);
+
+/* ---- fleet SLAM: many robots, each building its own map, in one context (no reference counterpart) -----------
+ * A SLAM fleet is R robots, 1 <= R <= min(max_batch, ASLAM_MAX_ROBOTS), each with one camera (aslam_camera) and a complete EKF-SLAM
+ * filter of its own: mu and Sigma of capacity init.max_landmarks, id <-> index tables, last-observed list, pop list and armed flag.
+ * A robot starts as aslam_create leaves the single filter (mu = 0, Sigma = 0, empty map, disarmed; its first frame only arms it).
+ * For every robot, the frames it is given produce bit for bit what one SLAM context produces on them: aslam_set_camera_rig with that
+ * one camera, the same aslam_init, every frame on the per-frame chain (windows off, as with ASLAM_NO_WINDOWS), driven by
+ * aslam_run_staged_rig: mu, Sigma, landmark ids and order, the per-slot statistics of aslam_get_slot_ekf_stats and the detections.
+ * A call may carry any subset of the robots; a robot named in several slots of one staged call takes them in ascending slot order;
+ * robots never interact, and one that overflows its map or its corrections per frame is reported as the single filter reports it
+ * (ASLAM_E_CAPACITY at the next sync) without touching the others.  aslam_fleet_add_images and aslam_fleet_run_staged (with_ekf 0, 1
+ * or 2) serve both fleet kinds; a SLAM call is one batched detection pass, then rounds: round k holds the k-th slot of every robot
+ * that has one and is one launch of each kernel of the configured chain for all its robots.  aslam_fleet_get_poses returns every
+ * robot's pose and Sigma_xx; aslam_fleet_set_pose refuses with ASLAM_E_STATE (a robot's pose is correlated with its map: re-seat it
+ * with aslam_fleet_set_state).  The mode rules of fleet localization hold: the single-filter entry points refuse while either kind is
+ * active, aslam_fleet_begin / aslam_fleet_slam_begin start a new fleet of the requested kind, aslam_fleet_end leaves the single
+ * filter as aslam_create does and frees the robots' filters.  Outside fleet SLAM the per-robot calls below refuse with
+ * ASLAM_E_STATE; a robot index outside the fleet is ASLAM_E_INVALID. */
+/* enter fleet SLAM: one camera per robot, checked as by aslam_set_camera_rig; ASLAM_E_STATE while localizing; ASLAM_E_CAPACITY when
+   the R filters (about 18 MB each at max_landmarks 256) cannot be allocated, leaving no fleet active */
+int aslam_fleet_slam_begin(aslam_ctx* ctx, int n_robots, const aslam_camera* cams);
+/* *on = 1 while a SLAM fleet is active */
+int aslam_is_fleet_slam(aslam_ctx* ctx, int* on);
+/* one robot's filter, with the checks and layouts of aslam_get_state / aslam_set_state / aslam_get_landmark_ids; set_state empties
+   the robot's last-observed list and leaves its armed flag */
+int aslam_fleet_get_state(aslam_ctx* ctx, int robot, int* N, double* mu, double* sigma);
+int aslam_fleet_set_state(aslam_ctx* ctx, int robot, int N, const double* mu, const double* sigma, const int* landmark_ids);
+int aslam_fleet_get_landmark_ids(aslam_ctx* ctx, int robot, int* L, int* ids);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
