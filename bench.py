@@ -8,7 +8,9 @@ the stream, frames already resident in HBM: detection + pose run batched over th
 stream order.  N > 1 (`--gpus N`): one independent stream per rank (weak scaling) plus one RCCL all-gather of the landmark
 map per step; when started without torchrun's environment the script launches the N ranks itself.
 
-Prints ONE JSON line (task contract) with
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes `--dump-outputs`, checks the
+timed frames and prints ONE JSON line (task contract: metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+`--full` runs everything else as well and adds to the line
   roofline      SURVEY §8(d): ALG_BYTES(frame) x frames per launch / average launch time of the dominant kernel (HIP events on
                 the library's streams) / 8 TB/s; `traffic` = that kernel's HBM bytes per launch from the committed PMC passes
                 (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, FETCH_SIZE doubled as MI355X_MICROARCH.md §HBM prescribes);
@@ -20,7 +22,8 @@ Prints ONE JSON line (task contract) with
                 the reference runs it, aruco_slam.cpp:313 - nothing forced, fused counts reported), `cfg2_sliding` (a ring
                 world whose visible set changes every 2.5 frames) and `cfg2_sliding_reference_defaults`; each with the
                 share of frames the EKF fused inside windows.
-Every timed frame is checked afterwards: M markers detected and M corrections fused (no observation lost to the gates).
+Every timed frame is checked afterwards, in either mode: M markers detected and M corrections fused (no observation lost to
+the gates).
 """
 import argparse
 import json
@@ -227,7 +230,7 @@ def dump_outputs(np, out_dir, ctx, slots, with_ekf):
 
 
 def run_config(mods, args, cfg_name, steps, warmup, batch, with_ekf, rank, local_rank, world_size, cpu_frames, want_gather,
-               detector="scene", qualify=True, dump_dir=None):
+               detector="scene", qualify=True, dump_dir=None, profile=True):
     np, torch, dist, capi, synth, MapGather = mods
     cfg, world, lap, ctx, frames, host = scene_setup(np, capi, synth, cfg_name, rank, local_rank, args, with_ekf,
                                                      cpu_frames if rank == 0 else 0, detector=detector, qualify=qualify)
@@ -306,31 +309,35 @@ def run_config(mods, args, cfg_name, steps, warmup, batch, with_ekf, rank, local
         for i in range(0, lap, max(1, lap // 16)):
             assert len(ctx.get_slot_detections(i)[0]) == world.M, f"frame {i}: marker lost"
 
-    # ---- roofline: a second, identical pass with HIP events around every kernel family on the library's streams
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    for _ in range(steps):
-        step()
-    ctx.sync()
-    prof = ctx.profile_get()
-    ctx.profile_enable(False)
-    dominant = max(prof, key=lambda k: prof[k][1])
-    calls, total_ms = prof[dominant]
+    # ---- roofline (--full): a second, identical pass with HIP events around every kernel family on the library's streams
+    prof = None
+    if profile:
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        for _ in range(steps):
+            step()
+        ctx.sync()
+        prof = ctx.profile_get()
+        ctx.profile_enable(False)
     N = int(ctx.get_state()[0].size) if with_ekf else 0
-    alg_frame = cfg.rows * cfg.cols + ((16 * N * N + 16 * N) if with_ekf else 0) + 84 * world.M      # SURVEY §8(d) ALG_BYTES
-    launches = max(calls, 1)
-    fpl = steps * B / launches                                       # frames one launch of the dominant kernel processes
-    avg_s = total_ms / 1e3 / launches
-    achieved = alg_frame * fpl / avg_s if avg_s > 0 else 0.0
-    pmc_file, traffic_all = load_pmc(cfg_name, with_ekf)
-    traffic = traffic_all.get(dominant)
     fps = world_size * steps * B / elapsed
-    roofline = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK, 6), "traffic": traffic,
-                "avg_launch_us": round(avg_s * 1e6, 2), "frames_per_launch": round(fpl, 2), "alg_bytes_per_frame": int(alg_frame),
-                "path_achieved": round(alg_frame * (fps / world_size) / 1e9, 3), "path_frac": round(alg_frame * (fps / world_size) / HBM_PEAK, 6),
-                "traffic_per_launch_by_kernel": traffic_all or None, "traffic_source": pmc_file if traffic_all else None,
-                "kernel_ms_per_step": {k: round(v[1] / max(steps, 1), 4) for k, v in prof.items() if v[0] > 0}}
+    roofline = None
+    if prof is not None:
+        dominant = max(prof, key=lambda k: prof[k][1])
+        calls, total_ms = prof[dominant]
+        alg_frame = cfg.rows * cfg.cols + ((16 * N * N + 16 * N) if with_ekf else 0) + 84 * world.M      # SURVEY §8(d) ALG_BYTES
+        launches = max(calls, 1)
+        fpl = steps * B / launches                                       # frames one launch of the dominant kernel processes
+        avg_s = total_ms / 1e3 / launches
+        achieved = alg_frame * fpl / avg_s if avg_s > 0 else 0.0
+        pmc_file, traffic_all = load_pmc(cfg_name, with_ekf)
+        traffic = traffic_all.get(dominant)
+        roofline = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK, 6), "traffic": traffic,
+                    "avg_launch_us": round(avg_s * 1e6, 2), "frames_per_launch": round(fpl, 2), "alg_bytes_per_frame": int(alg_frame),
+                    "path_achieved": round(alg_frame * (fps / world_size) / 1e9, 3), "path_frac": round(alg_frame * (fps / world_size) / HBM_PEAK, 6),
+                    "traffic_per_launch_by_kernel": traffic_all or None, "traffic_source": pmc_file if traffic_all else None,
+                    "kernel_ms_per_step": {k: round(v[1] / max(steps, 1), 4) for k, v in prof.items() if v[0] > 0}}
     det_used = cfg.detector if detector == "scene" else {}
     res = {"value": round(fps, 2), "ms_per_step": round(elapsed / steps * 1e3, 4), "frames_per_step": B, "N": N,
            "workload": f"{cfg_name}: {cfg.cols}x{cfg.rows} gray stream per GPU, {world.M} markers/frame in view"
@@ -338,8 +345,9 @@ def run_config(mods, args, cfg_name, steps, warmup, batch, with_ekf, rank, local
                        + (f"{world.L}-landmark EKF (N={N})" if with_ekf else "detect + pose only") + ", frames resident in HBM"
                        + (f", detector {det_used}" if det_used else ", detector = cv::aruco::DetectorParameters defaults (aruco_slam.cpp:313)"),
            "asserted": (f"every frame: {world.M} markers detected" + (f", {world.M} corrections fused" if with_ekf else "")) if qualify
-                       else "nothing forced: whatever the default detector finds and the gates (aruco_slam.cpp:327-333, 367-368) let through is fused",
-           "roofline": roofline}
+                       else "nothing forced: whatever the default detector finds and the gates (aruco_slam.cpp:327-333, 367-368) let through is fused"}
+    if roofline is not None:
+        res["roofline"] = roofline
     if per_frame is not None:
         res["per_frame"] = per_frame
     if plan is not None:
@@ -462,7 +470,7 @@ def host_fed_rate(np, run, H=100):
     return out
 
 
-def cfg5_run(np, capi, synth, args, steps, dump_dir=None):
+def cfg5_run(np, capi, synth, args, steps, dump_dir=None, profile=True):
     """BASELINE configs[4]: 64 x 640x480 frames per step, 4 markers each, detect + PnP only"""
     rows, cols, f, n = 480, 640, 450.0, 64
     K = synth.camera_matrix(rows, cols, f)
@@ -486,27 +494,28 @@ def cfg5_run(np, capi, synth, args, steps, dump_dir=None):
         dump_outputs(np, dump_dir, ctx, [((steps - 1) & 1) * n + i for i in range(n)], False)
     found = sum(len(ctx.get_slot_detections(i)[0]) for i in range(2 * n))
     assert found == 2 * n * 4, f"cfg5: {found} of {2 * n * 4} markers found"
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    for s in range(steps):
-        ctx.run_staged((s & 1) * n, n, with_ekf=False)
-    ctx.sync()
-    prof = ctx.profile_get()
-    ctx.profile_enable(False)
-    dominant = max(prof, key=lambda k: prof[k][1])
-    avg_s = prof[dominant][1] / 1e3 / max(prof[dominant][0], 1)
-    alg_frame = rows * cols + 84 * 4
-    achieved = alg_frame * n / avg_s
-    pmc_file, traffic_all = load_pmc("cfg5", False)
     res = {"value": round(steps * n / el, 1), "unit": "frames/s", "ms_per_step": round(el / steps * 1e3, 4), "frames_per_step": n,
            "workload": "cfg5: 64 x 640x480 gray frames per step, 4 markers each, detect + PnP only (one context)",
-           "asserted": "every frame: 4 markers detected",
-           "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK, 6), "traffic": traffic_all.get(dominant), "avg_launch_us": round(avg_s * 1e6, 2),
-                        "frames_per_launch": n, "alg_bytes_per_frame": alg_frame,
-                        "traffic_per_launch_by_kernel": traffic_all or None, "traffic_source": pmc_file if traffic_all else None,
-                        "path_frac": round(alg_frame * steps * n / el / HBM_PEAK, 6),
-                        "kernel_ms_per_step": {k: round(v[1] / steps, 4) for k, v in prof.items() if v[0] > 0}}}
+           "asserted": "every frame: 4 markers detected"}
+    if profile:                                          # --full: a second pass with HIP events, as run_config's roofline
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        for s in range(steps):
+            ctx.run_staged((s & 1) * n, n, with_ekf=False)
+        ctx.sync()
+        prof = ctx.profile_get()
+        ctx.profile_enable(False)
+        dominant = max(prof, key=lambda k: prof[k][1])
+        avg_s = prof[dominant][1] / 1e3 / max(prof[dominant][0], 1)
+        alg_frame = rows * cols + 84 * 4
+        achieved = alg_frame * n / avg_s
+        pmc_file, traffic_all = load_pmc("cfg5", False)
+        res["roofline"] = {"bound": "hbm", "kernel": dominant, "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK, 6), "traffic": traffic_all.get(dominant), "avg_launch_us": round(avg_s * 1e6, 2),
+                           "frames_per_launch": n, "alg_bytes_per_frame": alg_frame,
+                           "traffic_per_launch_by_kernel": traffic_all or None, "traffic_source": pmc_file if traffic_all else None,
+                           "path_frac": round(alg_frame * steps * n / el / HBM_PEAK, 6),
+                           "kernel_ms_per_step": {k: round(v[1] / steps, 4) for k, v in prof.items() if v[0] > 0}}
     ctx.close()
     return res, np.stack(host), K
 
@@ -554,10 +563,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=320, help="frames per step (one lap of the headline scene; the lap is staged twice, so consecutive steps use disjoint slots)")
     ap.add_argument("--config", default="cfg2")
-    ap.add_argument("--cpu-sample", type=int, default=240, help="frames handed to the CPU oracle (0 = skip the CPU baseline)")
-    ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work per baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline pass, the CPU baselines and the extras (other configs, latency, host-fed stream)")
+    ap.add_argument("--cpu-sample", type=int, default=240, help="--full: frames handed to the CPU oracle (0 = skip the CPU baseline)")
+    ap.add_argument("--cpu-budget", type=float, default=10.0, help="--full: seconds of CPU work per baseline leg")
     ap.add_argument("--no-ekf", action="store_true", help="detect + pose only")
-    ap.add_argument("--no-extra", action="store_true", help="skip the cfg3 / cfg5 / latency / host-fed extras")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the cfg3 / cfg5 / latency / host-fed extras")
     ap.add_argument("--waves", type=int, default=0, help="wavefronts of the work-queue kernels (0 = library default)")
     ap.add_argument("--force-gather", action="store_true", help="run the (pipelined) map gather even with one rank (development check)")
     ap.add_argument("--reserve", type=int, default=0, help="CUs per XCD kept free of detection beside the EKF chain (0 = library default 16, <0 = off)")
@@ -593,21 +604,24 @@ def main():
     if world > 1 or (args.force_gather and "RANK" in os.environ):
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
     if args.config == "cfg5":                      # BASELINE configs[4] on its own (profiling runs): detect + PnP only
-        r5, _, _ = cfg5_run(np, capi, synth, args, steps=args.steps, dump_dir=args.dump_outputs)
-        print(json.dumps({"metric": "frames/s (detect+pose) cfg5", "value": r5["value"], "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
-                          "warmup": 3, "ms_per_step": r5["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                          "dtype": "u8/f64", "data": "synthetic", "config": {"workload": r5["workload"], "asserted": r5["asserted"]},
-                          "roofline": r5["roofline"], "cpu_baseline": None}), flush=True)
+        r5, _, _ = cfg5_run(np, capi, synth, args, steps=args.steps, dump_dir=args.dump_outputs, profile=args.full)
+        out = {"metric": "frames/s (detect+pose) cfg5", "value": r5["value"], "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
+               "warmup": 3, "ms_per_step": r5["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": "u8/f64", "data": "synthetic", "config": {"workload": r5["workload"], "asserted": r5["asserted"]}}
+        if args.full:
+            out.update(roofline=r5["roofline"], cpu_baseline=None)
+        print(json.dumps(out), flush=True)
         return
     with_ekf = not args.no_ekf
-    extras_on = rank == 0 and world == 1 and not args.no_extra and args.config == "cfg2" and with_ekf
+    cpu_on = args.full and rank == 0 and args.cpu_sample > 0
+    extras_on = args.full and rank == 0 and world == 1 and not args.no_extra and args.config == "cfg2" and with_ekf
 
     head, run = run_config(mods, args, args.config, args.steps, args.warmup, args.batch, with_ekf, rank, local_rank, world,
-                           (max(args.cpu_sample, 400 if extras_on else 0) if args.cpu_sample > 0 else 0),
-                           want_gather=(world > 1 or args.force_gather), dump_dir=args.dump_outputs)
+                           (max(args.cpu_sample, 400 if extras_on else 0) if cpu_on else 0),
+                           want_gather=(world > 1 or args.force_gather), dump_dir=args.dump_outputs, profile=args.full)
     cpu = None
     extra = None
-    if rank == 0 and args.cpu_sample > 0:
+    if cpu_on:
         sample_run = dict(run, host=run["host"][:args.cpu_sample])
         cpu = cpu_baseline(np, synth, sample_run, args.config, with_ekf, ("all", "literal"), args.cpu_budget)
     if extras_on:
@@ -671,8 +685,9 @@ def main():
             "config": {"workload": head["workload"], "frames_per_step": head["frames_per_step"], "streams": world, "ekf": with_ekf,
                        "asserted": head["asserted"],
                        "map_gather": "rccl all_gather per step, pipelined one step behind" if world > 1 else "none"},
-            "roofline": head["roofline"], "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update(roofline=head["roofline"], cpu_baseline=cpu)
         if extra is not None:
             out["extra"] = extra
         print(json.dumps(out), flush=True)

@@ -1,10 +1,12 @@
 #!/bin/bash
-# one gpurun call: rocprofv3 kernel-trace stats + the two PMC passes for each named config (scripts/profile_round.sh), then the default bench
+# rocprofv3 kernel-trace stats + the two PMC passes for each named config (scripts/profile_round.sh), then the full bench line
+# usage: OUT_DIR=<dir> scripts/gpu_profiles.sh <tag> <config>...
 tag=${1:-r03}; shift
-mkdir -p gpurun_out
+out=${OUT_DIR:?set OUT_DIR to the directory for the logs and the bench line}
+mkdir -p "$out"
 for cfg in "$@"; do
-  timeout -k 10 ${PROF_TIMEOUT:-330} bash scripts/profile_round.sh $tag $cfg > gpurun_out/${tag}_prof_${cfg}.log 2>&1 || { echo "profile $cfg failed"; tail -5 gpurun_out/${tag}_prof_${cfg}.log; exit 1; }
+  timeout -k 10 ${PROF_TIMEOUT:-330} bash scripts/profile_round.sh $tag $cfg > "$out/${tag}_prof_${cfg}.log" 2>&1 || { echo "profile $cfg failed"; tail -5 "$out/${tag}_prof_${cfg}.log"; exit 1; }
   echo "profile $cfg done"
 done
-timeout -k 10 400 python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err
-tail -c 500 gpurun_out/${tag}_bench_default.json
+timeout -k 10 400 python bench.py --full > "$out/${tag}_bench_default.json" 2> "$out/${tag}_bench_default.err"
+tail -c 500 "$out/${tag}_bench_default.json"

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU" "SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD" "SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY" "SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU SQ_WAIT_INST_ANY SQ_INSTS_VMEM_WR"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --output-format csv -d $out/g$i -o run -- python3 $root/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extra > $out/b$i.json 2> $out/e$i.err || { tail -5 $out/e$i.err; echo "group $i failed"; }
+  rocprofv3 --pmc $grp --output-format csv -d $out/g$i -o run -- python3 $root/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extra > $out/b$i.json 2> $out/e$i.err || { tail -5 $out/e$i.err; echo "group $i failed"; }
 done
 cd $root
 python3 - <<'PY'
