@@ -39,6 +39,18 @@ const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_wr
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
+// Which filter the context runs.  The single filter serves Slam and Localize (aslam_localize_begin: the map is frozen, every EKF step
+// is a k_loc_steps step); the two fleet modes run R robots instead.
+enum class Mode { Slam, Localize, FleetLocalize, FleetSlam };
+
+// a per-call table that goes up from page-locked memory in two alternating halves: a half is rewritten only after its copy ran
+struct PinnedPair {
+    int* h[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_set[2] = {false, false};
+    int half = 0;
+};
+
 } // namespace
 
 struct aslam_ctx {
@@ -116,26 +128,21 @@ struct aslam_ctx {
     EkfState ekf{};
     double last_time = 0;
     bool is_init = false;
-    bool localizing = false;              // aslam_localize_begin: the map is frozen, every EKF step is a k_loc_steps step
+    Mode mode = Mode::Slam;               // changed by enter_mode only
 
     // fleet localization (aslam_fleet_begin): R robots, each with its own camera and pose filter, on the frozen map in
     // the id table and the landmark rows of mu.  Device buffers are allocated by the first aslam_fleet_begin for min(max_batch, 256)
-    // robots.  The per-call tables go up from two pinned halves each, alternating; a half is rewritten only after its copy ran.
-    int fleet_n = 0;                      // robots of the active fleet; 0 = no fleet
+    // robots.
+    int fleet_n = 0;                      // robots of the active fleet: nonzero exactly in the two fleet modes
     int fleet_cap = 0;                    // robots the device buffers hold
     std::vector<char> fleet_armed;        // per robot: its first frame has armed the filter (the next one predicts)
     FleetState fleet{};                   // poses / Sigma_xx, last_observed_marker_ lists and their lengths
     RigCam* d_fleet_cams = nullptr;       // per robot
     int* d_fleet_camidx = nullptr;        // per frame slot: the robot whose camera k_pose uses
     int* d_fleet_work = nullptr;          // the work list of a k_fleet_steps launch (ekf_fleet.h)
-    int* h_fleet_cam[2] = {nullptr, nullptr};
-    int* h_fleet_work[2] = {nullptr, nullptr};
-    hipEvent_t ev_fleet_cam[2] = {nullptr, nullptr}, ev_fleet_work[2] = {nullptr, nullptr};
-    bool ev_fleet_cam_set[2] = {false, false}, ev_fleet_work_set[2] = {false, false};
-    int fleet_cam_half = 0, fleet_work_half = 0;
+    PinnedPair fleet_camidx_up, fleet_work_up;   // the uploads of d_fleet_camidx / d_fleet_work
     // fleet SLAM (aslam_fleet_slam_begin): every robot a complete SLAM filter (ekf_fleet_slam.h), allocated for the R
     // requested; the cameras, armed flags and work-list buffers above serve it as they serve fleet localization
-    bool fleet_slam = false;
     FleetSlam fslam{};
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
@@ -192,6 +199,53 @@ int fail(aslam_ctx* c, int code, const std::string& msg) {
     } while (0)
 
 template <class T> hipError_t dalloc(T** p, size_t count) { return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)); }
+
+// the modes an entry point runs in, as a set: every mode-dependent entry point states its rule as `if (int r = allow(c, ...)) return r;`
+constexpr unsigned in(Mode m) { return 1u << (int)m; }
+constexpr unsigned kSlam = in(Mode::Slam), kLocalize = in(Mode::Localize), kFleetLocalize = in(Mode::FleetLocalize),
+                   kFleetSlam = in(Mode::FleetSlam);
+constexpr unsigned kSingle = kSlam | kLocalize, kFleet = kFleetLocalize | kFleetSlam, kAnyMode = kSingle | kFleet;
+
+// ASLAM_OK if the context's mode is in `allowed`, else ASLAM_E_STATE and why
+int allow(aslam_ctx* c, unsigned allowed) {
+    const unsigned now = in(c->mode);
+    if (allowed & now) return ASLAM_OK;
+    const char* why;
+    if ((now & kFleet) && !(allowed & kFleet)) why = "a fleet is active: this call reads or writes the single filter or camera (aslam_fleet_end first)";
+    else if (c->mode == Mode::FleetSlam) why = "fleet SLAM: a robot's pose is correlated with its map (aslam_fleet_set_state)";
+    else if (allowed == kFleetSlam) why = "no fleet SLAM (aslam_fleet_slam_begin first)";
+    else if (!(allowed & kSingle)) why = "no fleet (aslam_fleet_begin first)";
+    else if (allowed & kFleet) why = "localizing: one filter is active (aslam_localize_end first)";     // a call that starts a fleet
+    else why = "localizing: the map is frozen (aslam_localize_end first)";
+    return fail(c, ASLAM_E_STATE, why);
+}
+
+int pinned_alloc(aslam_ctx* c, PinnedPair& p, size_t n) {
+    for (int h = 0; h < 2; h++) {
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&p.h[h]), sizeof(int) * n, hipHostMallocDefault));
+        HIP_TRY(c, hipEventCreateWithFlags(&p.ev[h], hipEventDisableTiming));
+    }
+    return ASLAM_OK;
+}
+
+void pinned_free(PinnedPair& p) {
+    for (int h = 0; h < 2; h++) {
+        if (p.h[h]) hipHostFree(p.h[h]);
+        if (p.ev[h]) hipEventDestroy(p.ev[h]);
+    }
+}
+
+// n ints from src to d_dst on stream st, through the next half
+int pinned_upload(aslam_ctx* c, PinnedPair& p, int* d_dst, const int* src, size_t n, hipStream_t st) {
+    const int h = p.half;
+    p.half ^= 1;
+    if (p.ev_set[h]) HIP_TRY(c, hipEventSynchronize(p.ev[h]));     // the copy that last read this half ran
+    std::memcpy(p.h[h], src, sizeof(int) * n);
+    HIP_TRY(c, hipMemcpyAsync(d_dst, p.h[h], sizeof(int) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(p.ev[h], st));
+    p.ev_set[h] = true;
+    return ASLAM_OK;
+}
 
 // DICT_ARUCO_ORIGINAL from first principles: 5 rows x 2 id bits (MSB first) through the words
 // 10000 / 10111 / 01001 / 01110 (original ArUco library).  parameters.yaml:16 selects enum 16.
@@ -360,14 +414,26 @@ PoseCams single_camera(const aslam_ctx* c) {
     return pc;
 }
 
-// detection + pose for `count` staged frames starting at slot `first` (asynchronous on the stream).  rig: frame first + i is camera
-// i % rig->n of the rig (nullptr: the single camera); latency: the configuration of a one-frame call (one rig step); robots (host,
-// count entries, fleet mode): frame first + i is robot robots[i]'s frame and uses that robot's camera
-int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipEvent_t wait_before = nullptr, const PoseCams* rig = nullptr,
-               bool latency = false, const int* robots = nullptr) {
+// What a staged or one-shot call runs: detection + pose over frame slots [first, first + count), then `steps` filter steps on EKF slots
+// [ekf_first, ekf_first + steps).  The camera source and the filter go together: the single camera and filter; a rig (frame first + i is
+// camera i % rig->n, step s is EKF slot max_batch + first + s: its frames' merged lists); or a fleet (frame first + i is robot robots[i]'s,
+// host array of count entries).
+struct Call {
+    int first, count;
+    const PoseCams* rig;
+    const int* robots;
+    int ekf_first, steps;
+};
+Call single_call(int first, int count) { return {first, count, nullptr, nullptr, first, count}; }
+Call rig_call(const aslam_ctx* c, int first, int n_steps) { return {first, n_steps * c->rig_n, &c->rig, nullptr, c->max_batch + first, n_steps}; }
+Call fleet_call(int first, int count, const int* robots) { return {first, count, nullptr, robots, first, count}; }
+
+// detection + pose of the call's frames (asynchronous on the stream).  latency: the configuration of a one-frame call (one rig step)
+int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = false, hipEvent_t wait_before = nullptr) {
+    const int first = k.first, count = k.count;
     if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
-    if (!rig && !robots && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
-    PoseCams cams = rig ? *rig : single_camera(c);
+    if (!k.rig && !k.robots && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    PoseCams cams = k.rig ? *k.rig : single_camera(c);
     // the CU-masked stream only pays off while an EKF chain is actually in flight beside this detection; the first batch after
     // a synchronisation gets the whole GPU
     hipStream_t st = (beside_ekf && c->stream_part && (c->ekf_count > 0 || c->pend.active)) ? c->stream_part : c->stream;
@@ -386,14 +452,9 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
         HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));   // EKF work in flight still reads observations of these slots
         c->ekf_count = 0;
     }
-    if (robots) {                                           // the frames' camera indices, on the stream ahead of k_pose
-        const int h = c->fleet_cam_half;
-        c->fleet_cam_half ^= 1;
-        if (c->ev_fleet_cam_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_cam[h]));
-        std::memcpy(c->h_fleet_cam[h], robots, sizeof(int) * count);
-        HIP_TRY(c, hipMemcpyAsync(c->d_fleet_camidx + first, c->h_fleet_cam[h], sizeof(int) * count, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipEventRecord(c->ev_fleet_cam[h], st));
-        c->ev_fleet_cam_set[h] = true;
+    if (k.robots) {                                         // the frames' camera indices, on the stream ahead of k_pose
+        int r = pinned_upload(c, c->fleet_camidx_up, c->d_fleet_camidx + first, k.robots, count, st);
+        if (r) return r;
     }
     // frames per launch of the detection kernels: everything of the call at once (the work queues balance it) unless
     // ASLAM_DETECT_CHUNK asks for smaller sub-batches (an experiment knob: mask planes of fewer frames stay cache-resident
@@ -447,7 +508,7 @@ int run_detect(aslam_ctx* c, int first, int count, bool beside_ekf = false, hipE
         const RefineCfg rf{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
                            g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
                            c->d_refine_mask, gray};
-        if (robots)
+        if (k.robots)
             launch_pose_table(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
                               c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, c->d_ctr, rf);
         else
@@ -519,10 +580,6 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
-}
-
-int fleet_refuses(aslam_ctx* c) {
-    return fail(c, ASLAM_E_STATE, "a fleet is active: this call reads or writes the single filter or camera (aslam_fleet_end first)");
 }
 
 int sync_streams(aslam_ctx* c) {
@@ -727,12 +784,8 @@ void aslam_destroy(aslam_ctx* c) {
     ekf_fleet_free(c->fslam);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
     hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
-    for (int h = 0; h < 2; h++) {
-        if (c->h_fleet_cam[h]) hipHostFree(c->h_fleet_cam[h]);
-        if (c->h_fleet_work[h]) hipHostFree(c->h_fleet_work[h]);
-        if (c->ev_fleet_cam[h]) hipEventDestroy(c->ev_fleet_cam[h]);
-        if (c->ev_fleet_work[h]) hipEventDestroy(c->ev_fleet_work[h]);
-    }
+    pinned_free(c->fleet_camidx_up);
+    pinned_free(c->fleet_work_up);
     if (c->ev_detect) hipEventDestroy(c->ev_detect);
     if (c->ev_ekf) hipEventDestroy(c->ev_ekf);
     if (c->stream_copy) { hipStreamSynchronize(c->stream_copy); hipStreamDestroy(c->stream_copy); }
@@ -759,7 +812,7 @@ const char* aslam_last_error(const aslam_ctx* c) { return c ? c->err.c_str() : (
 
 int aslam_set_camera(aslam_ctx* c, const double K[9], const double* D, int nD) {
     if (!c || !K || nD < 0 || (nD > 0 && !D)) return fail(c, ASLAM_E_INVALID, "bad camera arguments");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     c->cam.fx = K[0]; c->cam.fy = K[4]; c->cam.cx = K[2]; c->cam.cy = K[5];
     c->cam.nD = std::min(nD, 5);
     for (int i = 0; i < 5; i++) c->cam.k[i] = i < c->cam.nD ? D[i] : 0.0;
@@ -1111,33 +1164,10 @@ int finalize_pending(aslam_ctx* c) {
     return ASLAM_OK;
 }
 
-int schedule_ekf(aslam_ctx* c, int first, int count);
-
-int run_staged(aslam_ctx* c, int first, int count, int with_ekf, hipEvent_t wait_before) {
-    int r = check_slot_range(c, first, count);
-    if (r) return r;
-    if (with_ekf && c->enc_host.size() < (size_t)3 * (first + count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
-    if (c->pend.active && first < c->pend.first + c->pend.count && c->pend.first < first + count) {
-        r = finalize_pending(c);               // the pending batch still needs the observations in these slots
-        if (r) return r;
-    }
-    if (with_ekf != 2) {                       // 2 = EKF only, on observations already present in the slots (tests)
-        r = run_detect(c, first, count, with_ekf == 1, wait_before);
-        if (r) return r;
-    } else {
-        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
-        c->last_detect = c->stream;
-        HIP_TRY(c, hipEventRecord(c->ev_detect, c->stream));
-    }
-    c->rig_last = false;
-    if (!with_ekf) return ASLAM_OK;
-    return schedule_ekf(c, first, count);
-}
-
 // the EKF steps of EKF slots [first, first + count) (frames, or rig steps' merged lists), behind the detection that produced them
 int schedule_ekf(aslam_ctx* c, int first, int count) {
     int r = ASLAM_OK;
-    if (c->localizing) {                       // frozen map: one k_loc_steps launch, not counted by aslam_get_plan_stats
+    if (c->mode == Mode::Localize) {           // frozen map: one k_loc_steps launch, not counted by aslam_get_plan_stats
         r = finalize_pending(c);
         if (r) return r;
         const bool predict = c->is_init;       // addEncoder semantics (aruco_slam.cpp:24-29): the very first sample only arms the filter
@@ -1178,10 +1208,108 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
     return ASLAM_OK;
 }
 
+namespace {
+int merge_rig_steps(aslam_ctx* c, int first, int n_steps);
+int run_fleet_ekf(aslam_ctx* c, int first, int count, const int* robots);
+
+// which kind of call ran last: aslam_get_rig_observations and the single-camera message getters depend on it
+void note_last_call(aslam_ctx* c, const Call& k) {
+    c->rig_last = k.rig != nullptr;
+    if (k.rig) { c->rig_last_slot0 = k.first + (k.steps - 1) * k.rig->n; c->rig_last_n = k.rig->n; }
+}
+
+// a staged call (aslam_run_staged, aslam_run_staged_rig, aslam_fleet_run_staged, a submit of the host-fed stream).  with_ekf: 0 detection
+// only, 1 detection + EKF, 2 EKF only on the observations already in the slots; wait_before: frames still in flight on the copy stream
+int run_staged(aslam_ctx* c, const Call& k, int with_ekf, hipEvent_t wait_before = nullptr) {
+    int r = check_slot_range(c, k.first, k.count);
+    if (r) return r;
+    if (with_ekf < 0 || with_ekf > 2) return fail(c, ASLAM_E_INVALID, "with_ekf: 0, 1 or 2");
+    if (k.robots)
+        for (int i = 0; i < k.count; i++)
+            if (k.robots[i] < 0 || k.robots[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    if (with_ekf && c->enc_host.size() < (size_t)3 * (k.first + k.count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
+    if (with_ekf != 2 && (k.rig || k.robots)) {  // (the host-fed stream's ring records no slot shapes)
+        for (int i = k.first; i < k.first + k.count; i++)
+            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+                return fail(c, ASLAM_E_INVALID, "the frames of a rig or fleet call must all be staged with the same rows, cols and channels");
+    }
+    const aslam_ctx::Pending& p = c->pend;
+    if (p.active && ((k.first < p.first + p.count && p.first < k.first + k.count) ||
+                     (k.ekf_first < p.first + p.count && p.first < k.ekf_first + k.steps))) {
+        r = finalize_pending(c);               // the pending batch still needs the observations in these slots
+        if (r) return r;
+    }
+    if (with_ekf != 2) {
+        r = run_detect(c, k, k.steps == 1, with_ekf == 1 && !k.robots, wait_before);   // (a fleet's steps do not take the CU-masked stream)
+        if (r) return r;
+    } else {                                   // EKF only: the slots' lists as if c->stream had just produced them
+        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
+        c->last_detect = c->stream;
+        HIP_TRY(c, hipEventRecord(c->ev_detect, c->stream));
+    }
+    note_last_call(c, k);
+    if (!with_ekf) return ASLAM_OK;
+    if (k.robots) return run_fleet_ekf(c, k.first, k.count, k.robots);
+    if (k.rig) {
+        r = merge_rig_steps(c, k.first, k.steps);
+        if (r) return r;
+    }
+    return schedule_ekf(c, k.ekf_first, k.steps);
+}
+
+// a one-shot call (aslam_add_image, aslam_add_images, aslam_fleet_add_images): frame i of px (rows of step[i] bytes) into slot first + i,
+// with its encoder sample (wl, wr, dt) = enc[0..2][i] if enc is given; detection in the latency configuration; the EKF step(s); synchronised
+// and checked, host times in last_timing.  The single filter's prediction came with aslam_add_encoder.
+int add_frames(aslam_ctx* c, const Call& k, const uint8_t* const* px, int rows, int cols, int channels, const size_t* step,
+               const double* const* enc = nullptr) {
+    int r = finalize_pending(c);
+    if (r) return r;
+    if (!k.robots && !c->is_init) return ASLAM_OK;   // aruco_slam.cpp:84-85: nothing happens before the first encoder message (a robot arms on its own)
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    c->mirror_dirty = true;                  // planned on the device: the host's copy of the tables is stale afterwards
+    for (int i = 0; i < k.count; i++) {
+        r = aslam_stage_frames(c, k.first + i, px[i], 1, rows, cols, channels, step[i], 0);
+        if (r) return r;
+    }
+    if (enc) {
+        r = aslam_stage_encoders(c, k.first, k.count, enc[0], enc[1], enc[2]);
+        if (r) return r;
+    }
+    const auto t1 = clk::now();
+    r = run_detect(c, k, true);              // one batched pass over the call's frames
+    if (r) return r;
+    note_last_call(c, k);
+    if (k.rig) {
+        r = merge_rig_steps(c, k.first, k.steps);
+        if (r) return r;
+    }
+    const auto t2 = clk::now();
+    if (k.robots) {
+        r = run_fleet_ekf(c, k.first, k.count, k.robots);
+    } else if (c->mode == Mode::Localize) {
+        r = run_loc_steps(c, k.ekf_first, 1, false);
+    } else {
+        HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+        r = run_ekf_frame(c, k.ekf_first, 0, 0, 0, false);
+    }
+    if (r) return r;
+    const auto t3 = clk::now();
+    r = sync_streams(c);
+    const auto t4 = clk::now();
+    if (!r) r = sync_and_check(c);
+    const auto t5 = clk::now();
+    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
+    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
+    return r;
+}
+}  // namespace
+
 int aslam_run_staged(aslam_ctx* c, int first, int count, int with_ekf) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n && with_ekf) return fleet_refuses(c);
-    return run_staged(c, first, count, with_ekf, nullptr);
+    if (int r = allow(c, with_ekf ? kSingle : kAnyMode)) return r;
+    return run_staged(c, single_call(first, count), with_ekf);
 }
 
 // ---- camera rig (include/aruco_slam_hip.h): C frames per step, one batched detection pass, one EKF step per rig step ---------
@@ -1203,7 +1331,7 @@ int rig_camera(aslam_ctx* c, const aslam_camera& a, RigCam& e) {
 
 int aslam_set_camera_rig(aslam_ctx* c, int n_cams, const aslam_camera* cams) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (n_cams < 1 || n_cams > ASLAM_MAX_CAMERAS || !cams) return fail(c, ASLAM_E_INVALID, "a rig has 1..ASLAM_MAX_CAMERAS cameras");
     if (n_cams > c->max_batch) return fail(c, ASLAM_E_INVALID, "a rig step (one frame per camera) must fit into max_batch slots");
     PoseCams pc{};
@@ -1234,93 +1362,30 @@ int merge_rig_steps(aslam_ctx* c, int first, int n_steps) {
     c->enc_host.resize((size_t)3 * 2 * c->max_batch);
     for (int s = 0; s < n_steps; s++)
         std::memcpy(&c->enc_host[(size_t)3 * (e0 + s)], &c->enc_host[(size_t)3 * (first + s * C)], 3 * sizeof(double));
-    c->rig_last_slot0 = first + (n_steps - 1) * C;
-    c->rig_last_n = C;
     return ASLAM_OK;
 }
 }  // namespace
 
 int aslam_add_images(aslam_ctx* c, int n_cams, const uint8_t* const* px, int rows, int cols, int channels, const size_t* step) {
     if (!c || !px || !step) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (c->rig_n == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
     if (n_cams != c->rig_n) return fail(c, ASLAM_E_INVALID, "one image per camera of the rig");
     for (int k = 0; k < n_cams; k++) if (!px[k]) return fail(c, ASLAM_E_INVALID, "null image");
-    int r = finalize_pending(c);
-    if (r) return r;
-    if (!c->is_init) return ASLAM_OK;        // aruco_slam.cpp:84-85: nothing happens before the first encoder message
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    c->mirror_dirty = true;                  // planned on the device: the host's copy of the tables is stale afterwards
-    for (int k = 0; k < n_cams; k++) {
-        r = aslam_stage_frames(c, k, px[k], 1, rows, cols, channels, step[k], 0);
-        if (r) return r;
-    }
-    const auto t1 = clk::now();
-    r = run_detect(c, 0, n_cams, false, nullptr, &c->rig, true);      // one batched pass over the step's frames, latency configuration
-    if (r) return r;
-    c->rig_last = true;
-    r = merge_rig_steps(c, 0, 1);
-    if (r) return r;
-    const auto t2 = clk::now();
-    if (c->localizing) {
-        r = run_loc_steps(c, rig_step_slot(c, 0, 0), 1, false);       // the prediction came with aslam_add_encoder
-    } else {
-        HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
-        r = run_ekf_frame(c, rig_step_slot(c, 0, 0), 0, 0, 0, false);     // the prediction came with aslam_add_encoder
-    }
-    if (r) return r;
-    const auto t3 = clk::now();
-    r = sync_streams(c);
-    const auto t4 = clk::now();
-    if (!r) r = sync_and_check(c);
-    const auto t5 = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
-    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
-    return r;
+    return add_frames(c, rig_call(c, 0, 1), px, rows, cols, channels, step);
 }
 
 int aslam_run_staged_rig(aslam_ctx* c, int first, int n_steps, int with_ekf) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n && with_ekf) return fleet_refuses(c);
-    const int C = c->rig_n;
-    if (C == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
+    if (int r = allow(c, with_ekf ? kSingle : kAnyMode)) return r;
+    if (c->rig_n == 0) return fail(c, ASLAM_E_STATE, "camera rig not set (aslam_set_camera_rig)");
     if (n_steps <= 0) return fail(c, ASLAM_E_INVALID, "at least one rig step");
-    const int count = n_steps * C;
-    int r = check_slot_range(c, first, count);
-    if (r) return r;
-    if (with_ekf && c->enc_host.size() < (size_t)3 * (first + count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
-    if (with_ekf != 2) {
-        for (int i = first; i < first + count; i++)
-            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
-                return fail(c, ASLAM_E_INVALID, "the frames of a rig call must all be staged with the same rows, cols and channels");
-    }
-    const int e0 = rig_step_slot(c, first, 0);
-    if (c->pend.active && ((first < c->pend.first + c->pend.count && c->pend.first < first + count) ||
-                           (e0 < c->pend.first + c->pend.count && c->pend.first < e0 + n_steps))) {
-        r = finalize_pending(c);               // the pending batch still needs the observations in these slots
-        if (r) return r;
-    }
-    if (with_ekf != 2) {
-        r = run_detect(c, first, count, with_ekf == 1, nullptr, &c->rig, n_steps == 1);
-        if (r) return r;
-    } else {
-        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
-        c->last_detect = c->stream;
-    }
-    c->rig_last = true;
-    c->rig_last_slot0 = first + (n_steps - 1) * C;
-    c->rig_last_n = C;
-    if (!with_ekf) return ASLAM_OK;
-    r = merge_rig_steps(c, first, n_steps);
-    if (r) return r;
-    return schedule_ekf(c, e0, n_steps);
+    return run_staged(c, rig_call(c, first, n_steps), with_ekf);
 }
 
 int aslam_get_rig_observations(aslam_ctx* c, int* n_out, int* ids, int* idx, int* action, int* cam, double* xyth, double* Rdiag) {
     if (!c || !n_out) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was not a camera-rig call");
     int r = aslam_get_observations(c, n_out, ids, idx, action, xyth, Rdiag);
     if (r || !cam) return r;
@@ -1362,7 +1427,7 @@ int ring_submit(aslam_ctx* c) {
     c->ev_up_set[h] = true;
     c->enc_host.resize((size_t)3 * 2 * c->max_batch);
     std::memcpy(&c->enc_host[(size_t)3 * slot0], c->ring_enc.data(), (size_t)3 * n * sizeof(double));
-    int r = run_staged(c, slot0, n, 1, c->ev_up[h]);
+    int r = run_staged(c, single_call(slot0, n), 1, c->ev_up[h]);
     if (r) return r;
     HIP_TRY(c, hipEventRecord(c->ev_det[h], c->last_detect));
     c->ev_det_set[h] = true;
@@ -1375,7 +1440,7 @@ int ring_submit(aslam_ctx* c) {
 
 int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames_per_submit) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (frames_per_submit < 1 || 2 * frames_per_submit > c->max_batch) return fail(c, ASLAM_E_INVALID, "frames_per_submit must be in [1, max_batch / 2]");
     int r = sync_streams(c);
     if (r) return r;
@@ -1399,7 +1464,7 @@ int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames
 
 int aslam_stream_acquire(aslam_ctx* c, uint8_t** px, size_t* step) {
     if (!c || !px) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
     if (!c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
     *px = c->h_ring + ((size_t)c->ring_half * c->ring_H + c->ring_fill) * c->in_frame_bytes;
@@ -1410,7 +1475,7 @@ int aslam_stream_acquire(aslam_ctx* c, uint8_t** px, size_t* step) {
 
 int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->ring_acquired) return fail(c, ASLAM_E_STATE, "aslam_stream_acquire first");
     c->ring_acquired = false;
     double* e = &c->ring_enc[(size_t)3 * c->ring_fill];
@@ -1421,7 +1486,7 @@ int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
 
 int aslam_stream_push(aslam_ctx* c, const uint8_t* px, size_t step, double wl, double wr, double dt) {
     if (!c || !px) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     uint8_t* dst = nullptr;
     size_t dstep = 0;
     int r = aslam_stream_acquire(c, &dst, &dstep);
@@ -1434,7 +1499,7 @@ int aslam_stream_push(aslam_ctx* c, const uint8_t* px, size_t step, double wl, d
 
 int aslam_stream_flush(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
     int r = ring_submit(c);
     if (r) return r;
@@ -1536,7 +1601,7 @@ int aslam_set_dictionary_bytes(aslam_ctx* c, int marker_size, int n_markers, int
 
 int aslam_add_encoder(aslam_ctx* c, double wl, double wr, double t_now) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rp = finalize_pending(c); if (rp) return rp; }     // a pending batch arms the filter itself (is_init is set there)
     if (!c->is_init) {                       // aruco_slam.cpp:24-29
         c->last_time = t_now;
@@ -1552,36 +1617,8 @@ int aslam_add_encoder(aslam_ctx* c, double wl, double wr, double t_now) {
 
 int aslam_add_image(aslam_ctx* c, const uint8_t* px, int rows, int cols, int channels, size_t step) {
     if (!c || !px) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
-    int r = finalize_pending(c);
-    if (r) return r;
-    if (!c->is_init) return ASLAM_OK;        // aruco_slam.cpp:84-85: nothing happens before the first encoder message
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    c->mirror_dirty = true;                  // planned on the device: the host's copy of the tables is stale afterwards
-    r = aslam_stage_frames(c, 0, px, 1, rows, cols, channels, step, 0);
-    if (r) return r;
-    const auto t1 = clk::now();
-    r = run_detect(c, 0, 1);
-    if (r) return r;
-    const auto t2 = clk::now();
-    c->rig_last = false;
-    if (c->localizing) {
-        r = run_loc_steps(c, 0, 1, false);     // the prediction came with aslam_add_encoder
-    } else {
-        HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
-        r = run_ekf_frame(c, 0, 0, 0, 0, false);
-    }
-    if (r) return r;
-    const auto t3 = clk::now();
-    r = sync_streams(c);
-    const auto t4 = clk::now();
-    if (!r) r = sync_and_check(c);
-    const auto t5 = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
-    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
-    return r;
+    if (int r = allow(c, kSingle)) return r;
+    return add_frames(c, single_call(0, 1), &px, rows, cols, channels, &step);
 }
 
 int aslam_get_last_timing(aslam_ctx* c, double out[6]) {
@@ -1639,18 +1676,17 @@ int read_landmark_ids(aslam_ctx* c, const EkfState& E, int* L, int* ids) {
 
 int aslam_get_state(aslam_ctx* c, int* N, double* mu, double* sigma) {
     if (!c || !N) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     return read_state(c, c->ekf, N, mu, sigma);
 }
 
 int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, const int* landmark_ids) {
     if (!c || !mu || !sigma || N < 3 || (N - 3) % 3 != 0) return fail(c, ASLAM_E_INVALID, "bad state");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSlam)) return r;
     const int L = (N - 3) / 3;
     if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
-    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
     { int rs = sync_streams(c); if (rs) return rs; }
     int r = write_state(c, c->ekf, N, mu, sigma, landmark_ids);
     if (r) return r;
@@ -1725,7 +1761,7 @@ void fill_marker(aslam_marker_msg& m, int id, double length, double x, double y,
 
 int aslam_get_pose_msg(aslam_ctx* c, aslam_pose_msg* out) {                   // ArucoSlam::toRosPose, aruco_slam.cpp:378-410
     if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     double mu[3], S[9];
     HIP_TRY(c, hipMemcpy(mu, c->ekf.d_mu, sizeof(mu), hipMemcpyDeviceToHost));
@@ -1742,7 +1778,7 @@ int aslam_get_pose_msg(aslam_ctx* c, aslam_pose_msg* out) {                   //
 
 int aslam_get_map_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) {   // detected_map_, aruco_slam.cpp:265-281
     if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     int L = 0;
     HIP_TRY(c, hipMemcpy(&L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
@@ -1760,7 +1796,7 @@ int aslam_get_map_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) 
 
 int aslam_get_detected_markers(aslam_ctx* c, int max, int* n, aslam_marker_msg* out) {   // detected_markers_, aruco_slam.cpp:325-347
     if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: detected-marker messages describe one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
@@ -1812,7 +1848,7 @@ void draw_line(uint8_t* img, int rows, int cols, size_t step, int x0, int y0, in
 
 int aslam_draw_detected_markers(aslam_ctx* c, uint8_t* bgr, int rows, int cols, size_t step) {
     if (!c || !bgr || rows <= 0 || cols <= 0 || step < (size_t)cols * 3) return fail(c, ASLAM_E_INVALID, "bad arguments");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (c->rig_last) return fail(c, ASLAM_E_STATE, "the last call was a camera-rig call: the overlay describes one camera");
     int M = 0;
     int r = aslam_get_detections(c, &M, nullptr, nullptr, nullptr, nullptr);
@@ -1909,9 +1945,72 @@ int check_pose(aslam_ctx* c, const double* pose, const double* sigma) {
 }
 }  // namespace
 
+namespace {
+int fleet_alloc(aslam_ctx* c) {
+    if (c->fleet_cap) return ASLAM_OK;
+    const int R = std::min(c->max_batch, ASLAM_MAX_ROBOTS), B = c->max_batch;
+    HIP_TRY(c, dalloc(&c->fleet.pose, (size_t)kFleetState * R));
+    HIP_TRY(c, dalloc(&c->fleet.last, (size_t)kMarkerMax * R));
+    HIP_TRY(c, dalloc(&c->fleet.nlast, R));
+    HIP_TRY(c, dalloc(&c->d_fleet_cams, R));
+    HIP_TRY(c, dalloc(&c->d_fleet_camidx, B));
+    HIP_TRY(c, dalloc(&c->d_fleet_work, 4 * R + 4 * B));       // a localization call's CSR list, or a SLAM call's 4 ints per slot
+    int r = pinned_alloc(c, c->fleet_camidx_up, B);
+    if (!r) r = pinned_alloc(c, c->fleet_work_up, 4 * R + 4 * B);
+    if (r) return r;
+    c->fleet_cap = R;
+    return ASLAM_OK;
+}
+
+// The one place the mode changes (streams synchronised by the caller; for Localize and FleetLocalize the frozen map is already written).
+// Fleet SLAM, and SLAM after a fleet, start from the single filter as aslam_create leaves it (ekf_alloc); the frozen modes start with
+// empty last-observed and pop lists.  Leaving a fleet frees its SLAM filters; a fleet of cams.size() robots gets its device tables on
+// first use and those cameras, every robot disarmed.
+int enter_mode(aslam_ctx* c, Mode m, const std::vector<RigCam>& cams = {}) {
+    const bool fleet = m == Mode::FleetLocalize || m == Mode::FleetSlam, was_fleet = c->fleet_n > 0;
+    if (fleet) {
+        int r = fleet_alloc(c);
+        if (r) return r;
+    }
+    ekf_fleet_free(c->fslam);
+    c->mode = Mode::Slam;
+    c->fleet_n = 0;
+    c->fleet_armed.clear();
+    c->mirror_dirty = true;
+    if (m == Mode::FleetSlam || (m == Mode::Slam && was_fleet)) {
+        const size_t ld = (size_t)c->ekf.ld;
+        HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
+        HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
+        HIP_TRY(c, hipMemset(c->ekf.d_L, 0, sizeof(int)));
+        HIP_TRY(c, hipMemset(c->ekf.d_id2idx, 0xFF, kIdTableSize * sizeof(int)));
+        HIP_TRY(c, hipMemset(c->ekf.d_idx2id, 0xFF, (size_t)c->ekf.max_landmarks * sizeof(int)));
+        HIP_TRY(c, hipMemset(c->ekf.d_m, 0, sizeof(int)));
+        c->is_init = false;
+        c->last_time = 0;
+    }
+    if (m != Mode::Slam || was_fleet) {
+        const int zero = 0;
+        HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
+    }
+    const int R = (int)cams.size();
+    if (m == Mode::FleetSlam) {
+        const hipError_t e = ekf_fleet_alloc(c->fslam, R, c->ekf);
+        if (e != hipSuccess)
+            return fail(c, ASLAM_E_CAPACITY, std::to_string(R) + " filters of max_landmarks " + std::to_string(c->ekf.max_landmarks) +
+                                                 " do not fit: " + hipGetErrorString(e));
+    }
+    if (fleet) HIP_TRY(c, hipMemcpy(c->d_fleet_cams, cams.data(), sizeof(RigCam) * R, hipMemcpyHostToDevice));
+    c->mode = m;
+    c->fleet_n = fleet ? R : 0;
+    c->fleet_armed.assign(c->fleet_n, 0);
+    return ASLAM_OK;
+}
+}  // namespace
+
 int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth, const double pose[3], const double pose_sigma[9]) {
     if (!c || !ids || !xyth || !pose || !pose_sigma) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     int r = install_frozen_map(c, n, ids, xyth, false);
     if (r) return r;
     r = check_pose(c, pose, pose_sigma);
@@ -1926,50 +2025,24 @@ int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth
         HIP_TRY(c, hipMemcpy(c->ekf.d_sigma + (size_t)col * ld, v, sizeof(v), hipMemcpyHostToDevice));
     }
     HIP_TRY(c, hipMemcpy(c->ekf.d_mu, pose, 3 * sizeof(double), hipMemcpyHostToDevice));
-    int zero = 0;
-    HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
-    c->mirror_dirty = true;
-    c->localizing = true;
-    return ASLAM_OK;
+    return enter_mode(c, Mode::Localize);
 }
 
 int aslam_localize_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
-    c->mirror_dirty = true;
-    c->localizing = false;
-    return ASLAM_OK;
+    return enter_mode(c, Mode::Slam);
 }
 
 int aslam_is_localizing(aslam_ctx* c, int* on) {
     if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
-    *on = c->localizing ? 1 : 0;
+    *on = c->mode == Mode::Localize ? 1 : 0;
     return ASLAM_OK;
 }
 
 // ---- fleet localization: many robots on one frozen map (include/aruco_slam_hip.h) -------------------------------
 namespace {
-int fleet_alloc(aslam_ctx* c) {
-    if (c->fleet_cap) return ASLAM_OK;
-    const int R = std::min(c->max_batch, ASLAM_MAX_ROBOTS), B = c->max_batch;
-    HIP_TRY(c, dalloc(&c->fleet.pose, (size_t)kFleetState * R));
-    HIP_TRY(c, dalloc(&c->fleet.last, (size_t)kMarkerMax * R));
-    HIP_TRY(c, dalloc(&c->fleet.nlast, R));
-    HIP_TRY(c, dalloc(&c->d_fleet_cams, R));
-    HIP_TRY(c, dalloc(&c->d_fleet_camidx, B));
-    HIP_TRY(c, dalloc(&c->d_fleet_work, 4 * R + 4 * B));       // a localization call's CSR list, or a SLAM call's 4 ints per slot
-    for (int h = 0; h < 2; h++) {
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_cam[h]), sizeof(int) * B, hipHostMallocDefault));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet_work[h]), sizeof(int) * (4 * R + 4 * B), hipHostMallocDefault));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_cam[h], hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fleet_work[h], hipEventDisableTiming));
-    }
-    c->fleet_cap = R;
-    return ASLAM_OK;
-}
-
 // one robot's filter := (pose, sigma), its last-observed list emptied, disarmed
 int fleet_seat(aslam_ctx* c, int robot, const double* pose, const double* sigma) {
     double st[kFleetState];
@@ -1993,22 +2066,16 @@ int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
         slots_of[g].push_back(first + i);
     }
     const int ng = (int)slots_of.size();
-    const int h = c->fleet_work_half;
-    c->fleet_work_half ^= 1;
-    if (c->ev_fleet_work_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_work[h]));   // the copy that last read this half ran
-    int* hdr = c->h_fleet_work[h];
-    int* slots = hdr + 4 * ng;
-    int ns = 0;
+    std::vector<int> w(4 * ng);             // per group: robot, predicts, its first entry in the slot list, its slots; then the slot list
     for (int g = 0; g < ng; g++) {
         const int r = robot_of_group[g];
-        hdr[4 * g] = r; hdr[4 * g + 1] = c->fleet_armed[r] ? 1 : 0; hdr[4 * g + 2] = ns; hdr[4 * g + 3] = (int)slots_of[g].size();
-        for (int sl : slots_of[g]) slots[ns++] = sl;
+        w[4 * g] = r; w[4 * g + 1] = c->fleet_armed[r] ? 1 : 0; w[4 * g + 2] = (int)w.size() - 4 * ng; w[4 * g + 3] = (int)slots_of[g].size();
+        w.insert(w.end(), slots_of[g].begin(), slots_of[g].end());
         c->fleet_armed[r] = 1;
     }
     hipStream_t st = c->stream_ekf;
-    HIP_TRY(c, hipMemcpyAsync(c->d_fleet_work, hdr, sizeof(int) * (4 * ng + ns), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->ev_fleet_work[h], st));
-    c->ev_fleet_work_set[h] = true;
+    int rc = pinned_upload(c, c->fleet_work_up, c->d_fleet_work, w.data(), w.size(), st);
+    if (rc) return rc;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_FLEET_STEPS, st);
     launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng);
@@ -2030,22 +2097,16 @@ int run_fleet_slam(aslam_ctx* c, int first, int count, const int* robots) {
         if (k == (int)rounds.size()) rounds.emplace_back();
         rounds[k].push_back(i);
     }
-    const int h = c->fleet_work_half;
-    c->fleet_work_half ^= 1;
-    if (c->ev_fleet_work_set[h]) HIP_TRY(c, hipEventSynchronize(c->ev_fleet_work[h]));   // the copy that last read this half ran
-    int* w = c->h_fleet_work[h];
-    int n = 0;
+    std::vector<int> w;
     for (const std::vector<int>& rd : rounds)
         for (int i : rd) {
             const int r = robots[i];
-            w[4 * n] = r; w[4 * n + 1] = first + i; w[4 * n + 2] = c->fleet_armed[r] ? 1 : 0; w[4 * n + 3] = 0;
+            w.insert(w.end(), {r, first + i, c->fleet_armed[r] ? 1 : 0, 0});
             c->fleet_armed[r] = 1;
-            n++;
         }
     hipStream_t st = c->stream_ekf;
-    HIP_TRY(c, hipMemcpyAsync(c->d_fleet_work, w, sizeof(int) * 4 * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->ev_fleet_work[h], st));
-    c->ev_fleet_work_set[h] = true;
+    int rc = pinned_upload(c, c->fleet_work_up, c->d_fleet_work, w.data(), w.size(), st);
+    if (rc) return rc;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     int row = 0;
     for (const std::vector<int>& rd : rounds) {
@@ -2064,31 +2125,18 @@ int run_fleet_slam(aslam_ctx* c, int first, int count, const int* robots) {
 
 // the EKF part of a fleet call, whichever kind the fleet is
 int run_fleet_ekf(aslam_ctx* c, int first, int count, const int* robots) {
-    return c->fleet_slam ? run_fleet_slam(c, first, count, robots) : run_fleet_steps(c, first, count, robots);
+    return c->mode == Mode::FleetSlam ? run_fleet_slam(c, first, count, robots) : run_fleet_steps(c, first, count, robots);
 }
 
-int fleet_slam_refuses(aslam_ctx* c) {
-    return fail(c, ASLAM_E_STATE, "no fleet SLAM (aslam_fleet_slam_begin first)");
-}
-
-// leave the active fleet, if any: the single filter as aslam_create leaves it (ekf_alloc), the robots' filters freed (streams synchronised)
-int fleet_leave(aslam_ctx* c) {
-    const size_t ld = (size_t)c->ekf.ld;
-    HIP_TRY(c, hipMemset(c->ekf.d_mu, 0, ld * sizeof(double)));
-    HIP_TRY(c, hipMemset(c->ekf.d_sigma, 0, ld * ld * sizeof(double)));
-    HIP_TRY(c, hipMemset(c->ekf.d_L, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_id2idx, 0xFF, kIdTableSize * sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_idx2id, 0xFF, (size_t)c->ekf.max_landmarks * sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_nlast, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_npop, 0, sizeof(int)));
-    HIP_TRY(c, hipMemset(c->ekf.d_m, 0, sizeof(int)));
-    c->is_init = false;
-    c->last_time = 0;
-    c->mirror_dirty = true;
-    c->fleet_n = 0;
-    c->fleet_armed.clear();
-    c->fleet_slam = false;
-    ekf_fleet_free(c->fslam);
+// the cameras of a new fleet of n_robots, checked and converted for k_pose
+int fleet_cameras(aslam_ctx* c, int n_robots, const aslam_camera* cams, std::vector<RigCam>& rc) {
+    if (n_robots < 1 || n_robots > std::min(c->max_batch, ASLAM_MAX_ROBOTS))
+        return fail(c, ASLAM_E_INVALID, "a fleet has 1..min(max_batch, ASLAM_MAX_ROBOTS) robots");
+    rc.resize(n_robots);
+    for (int k = 0; k < n_robots; k++) {
+        int r = rig_camera(c, cams[k], rc[k]);
+        if (r) return r;
+    }
     return ASLAM_OK;
 }
 }  // namespace
@@ -2096,15 +2144,11 @@ int fleet_leave(aslam_ctx* c) {
 int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth, const double* poses,
                       const double* pose_sigmas) {
     if (!c || !cams || !ids || !xyth || !poses || !pose_sigmas) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: one filter is active (aslam_localize_end first)");
-    if (n_robots < 1 || n_robots > std::min(c->max_batch, ASLAM_MAX_ROBOTS))
-        return fail(c, ASLAM_E_INVALID, "a fleet has 1..min(max_batch, ASLAM_MAX_ROBOTS) robots");
-    std::vector<RigCam> rc(n_robots);
-    for (int k = 0; k < n_robots; k++) {
-        int r = rig_camera(c, cams[k], rc[k]);
-        if (r) return r;
-    }
-    int r = install_frozen_map(c, n, ids, xyth, false);
+    if (int r = allow(c, kSlam | kFleet)) return r;
+    std::vector<RigCam> rc;
+    int r = fleet_cameras(c, n_robots, cams, rc);
+    if (r) return r;
+    r = install_frozen_map(c, n, ids, xyth, false);
     if (r) return r;
     for (int k = 0; k < n_robots; k++) {
         r = check_pose(c, poses + 3 * k, pose_sigmas + 9 * k);
@@ -2112,30 +2156,21 @@ int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int 
     }
     r = sync_streams(c);
     if (r) return r;
-    r = fleet_alloc(c);
-    if (r) return r;
-    c->fleet_slam = false;                   // a SLAM fleet ends here
-    ekf_fleet_free(c->fslam);
     r = install_frozen_map(c, n, ids, xyth, true);
     if (r) return r;
-    int zero = 0;
-    HIP_TRY(c, hipMemcpy(c->ekf.d_nlast, &zero, sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->ekf.d_npop, &zero, sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_fleet_cams, rc.data(), sizeof(RigCam) * n_robots, hipMemcpyHostToDevice));
-    c->fleet_armed.assign(n_robots, 0);
-    c->fleet_n = n_robots;
+    r = enter_mode(c, Mode::FleetLocalize, rc);
+    if (r) return r;
     for (int k = 0; k < n_robots; k++) {
         r = fleet_seat(c, k, poses + 3 * k, pose_sigmas + 9 * k);
-        if (r) { c->fleet_n = 0; return r; }
+        if (r) return r;
     }
-    c->mirror_dirty = true;
     return ASLAM_OK;
 }
 
 int aslam_fleet_add_images(aslam_ctx* c, int n, const int* robots, const double* wl, const double* wr, const double* dt,
                            const uint8_t* const* px, int rows, int cols, int channels, const size_t* step_bytes) {
     if (!c || !robots || !wl || !wr || !dt || !px || !step_bytes) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (int r = allow(c, kFleet)) return r;
     if (n < 1 || n > c->max_batch) return fail(c, ASLAM_E_INVALID, "1..max_batch frames per call");
     std::vector<char> seen(c->fleet_n, 0);
     for (int i = 0; i < n; i++) {
@@ -2144,65 +2179,24 @@ int aslam_fleet_add_images(aslam_ctx* c, int n, const int* robots, const double*
         seen[robots[i]] = 1;
         if (!px[i]) return fail(c, ASLAM_E_INVALID, "null image");
     }
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    for (int i = 0; i < n; i++) {
-        int r = aslam_stage_frames(c, i, px[i], 1, rows, cols, channels, step_bytes[i], 0);
-        if (r) return r;
-    }
-    int r = aslam_stage_encoders(c, 0, n, wl, wr, dt);
-    if (r) return r;
-    const auto t1 = clk::now();
-    r = run_detect(c, 0, n, false, nullptr, nullptr, true, robots);     // one batched pass, the cut lattice of aslam_add_images
-    if (r) return r;
-    c->rig_last = false;
-    const auto t2 = clk::now();
-    r = run_fleet_ekf(c, 0, n, robots);
-    if (r) return r;
-    const auto t3 = clk::now();
-    r = sync_streams(c);
-    const auto t4 = clk::now();
-    if (!r) r = sync_and_check(c);
-    const auto t5 = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    c->last_timing[0] = us(t0, t1); c->last_timing[1] = us(t1, t2); c->last_timing[2] = us(t2, t3); c->last_timing[3] = us(t3, t4);
-    c->last_timing[4] = us(t4, t5); c->last_timing[5] = us(t0, t5);
-    return r;
+    const double* enc[3] = {wl, wr, dt};
+    return add_frames(c, fleet_call(0, n, robots), px, rows, cols, channels, step_bytes, enc);
 }
 
 int aslam_fleet_run_staged(aslam_ctx* c, int first, int count, const int* robot_of_slot, int with_ekf) {
     if (!c || !robot_of_slot) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
-    int r = check_slot_range(c, first, count);
-    if (r) return r;
-    if (with_ekf < 0 || with_ekf > 2) return fail(c, ASLAM_E_INVALID, "with_ekf: 0, 1 or 2");
-    for (int i = 0; i < count; i++)
-        if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
-    if (with_ekf && c->enc_host.size() < (size_t)3 * (first + count)) return fail(c, ASLAM_E_STATE, "encoders not staged");
-    if (with_ekf != 2) {
-        for (int i = first; i < first + count; i++)
-            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
-                return fail(c, ASLAM_E_INVALID, "the frames of a fleet call must all be staged with the same rows, cols and channels");
-        r = run_detect(c, first, count, false, nullptr, nullptr, count == 1, robot_of_slot);
-        if (r) return r;
-    } else {
-        if (c->last_detect && c->last_detect != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_detect, 0));
-        c->last_detect = c->stream;
-        HIP_TRY(c, hipEventRecord(c->ev_detect, c->stream));
-    }
-    c->rig_last = false;
-    if (!with_ekf) return ASLAM_OK;
-    return run_fleet_ekf(c, first, count, robot_of_slot);
+    if (int r = allow(c, kFleet)) return r;
+    return run_staged(c, fleet_call(first, count, robot_of_slot), with_ekf);
 }
 
 int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, double* sigmas) {
     if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (int r = allow(c, kFleet)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     const int R = c->fleet_n;
     *n_robots = R;
     std::vector<double> h((size_t)kFleetState * R);
-    if (c->fleet_slam) {
+    if (c->mode == Mode::FleetSlam) {
         // every robot's mu[0..2] and the first three entries of Sigma's columns 0..2, gathered as rows of kFleetState doubles
         const FleetSlam& F = c->fslam;
         HIP_TRY(c, hipMemcpy2D(h.data(), sizeof(double) * kFleetState, F.base.d_mu, F.stride, 3 * sizeof(double), R, hipMemcpyDeviceToHost));
@@ -2225,8 +2219,7 @@ int aslam_fleet_get_poses(aslam_ctx* c, int max, int* n_robots, double* poses, d
 
 int aslam_fleet_set_pose(aslam_ctx* c, int robot, const double pose[3], const double sigma[9]) {
     if (!c || !pose || !sigma) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
-    if (c->fleet_slam) return fail(c, ASLAM_E_STATE, "fleet SLAM: a robot's pose is correlated with its map (aslam_fleet_set_state)");
+    if (int r = allow(c, kFleetLocalize)) return r;
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     int r = check_pose(c, pose, sigma);
     if (r) return r;
@@ -2237,9 +2230,9 @@ int aslam_fleet_set_pose(aslam_ctx* c, int robot, const double pose[3], const do
 
 int aslam_fleet_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
-    if (!c->fleet_n) return fail(c, ASLAM_E_STATE, "no fleet (aslam_fleet_begin first)");
+    if (int r = allow(c, kFleet)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
-    return fleet_leave(c);
+    return enter_mode(c, Mode::Slam);
 }
 
 int aslam_is_fleet(aslam_ctx* c, int* n_robots) {
@@ -2251,40 +2244,24 @@ int aslam_is_fleet(aslam_ctx* c, int* n_robots) {
 // ---- fleet SLAM: many robots, each building its own map (include/aruco_slam_hip.h) ------------------------------
 int aslam_fleet_slam_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams) {
     if (!c || !cams) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: one filter is active (aslam_localize_end first)");
-    if (n_robots < 1 || n_robots > std::min(c->max_batch, ASLAM_MAX_ROBOTS))
-        return fail(c, ASLAM_E_INVALID, "a fleet has 1..min(max_batch, ASLAM_MAX_ROBOTS) robots");
-    std::vector<RigCam> rc(n_robots);
-    for (int k = 0; k < n_robots; k++) {
-        int r = rig_camera(c, cams[k], rc[k]);
-        if (r) return r;
-    }
-    int r = sync_streams(c);
+    if (int r = allow(c, kSlam | kFleet)) return r;
+    std::vector<RigCam> rc;
+    int r = fleet_cameras(c, n_robots, cams, rc);
     if (r) return r;
-    r = fleet_alloc(c);
+    r = sync_streams(c);
     if (r) return r;
-    r = fleet_leave(c);                      // the fleet active so far, if any, ends; the single filter as aslam_create leaves it
-    if (r) return r;
-    const hipError_t e = ekf_fleet_alloc(c->fslam, n_robots, c->ekf);
-    if (e != hipSuccess)
-        return fail(c, ASLAM_E_CAPACITY, std::to_string(n_robots) + " filters of max_landmarks " + std::to_string(c->ekf.max_landmarks) +
-                                             " do not fit: " + hipGetErrorString(e));
-    HIP_TRY(c, hipMemcpy(c->d_fleet_cams, rc.data(), sizeof(RigCam) * n_robots, hipMemcpyHostToDevice));
-    c->fleet_armed.assign(n_robots, 0);
-    c->fleet_n = n_robots;
-    c->fleet_slam = true;
-    return ASLAM_OK;
+    return enter_mode(c, Mode::FleetSlam, rc);          // the fleet active so far, if any, ends
 }
 
 int aslam_is_fleet_slam(aslam_ctx* c, int* on) {
     if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
-    *on = c->fleet_slam ? 1 : 0;
+    *on = c->mode == Mode::FleetSlam ? 1 : 0;
     return ASLAM_OK;
 }
 
 int aslam_fleet_get_state(aslam_ctx* c, int robot, int* N, double* mu, double* sigma) {
     if (!c || !N) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (int r = allow(c, kFleetSlam)) return r;
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     { int rs = sync_streams(c); if (rs) return rs; }
     return read_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma);
@@ -2292,7 +2269,7 @@ int aslam_fleet_get_state(aslam_ctx* c, int robot, int* N, double* mu, double* s
 
 int aslam_fleet_set_state(aslam_ctx* c, int robot, int N, const double* mu, const double* sigma, const int* landmark_ids) {
     if (!c || !mu || !sigma || N < 3 || (N - 3) % 3 != 0) return fail(c, ASLAM_E_INVALID, "bad state");
-    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (int r = allow(c, kFleetSlam)) return r;
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     const int L = (N - 3) / 3;
     if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
@@ -2303,7 +2280,7 @@ int aslam_fleet_set_state(aslam_ctx* c, int robot, int N, const double* mu, cons
 
 int aslam_fleet_get_landmark_ids(aslam_ctx* c, int robot, int* L, int* ids) {
     if (!c || !L) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (!c->fleet_slam) return fleet_slam_refuses(c);
+    if (int r = allow(c, kFleetSlam)) return r;
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     { int rs = sync_streams(c); if (rs) return rs; }
     return read_landmark_ids(c, ekf_fleet_robot(c->fslam, robot), L, ids);
@@ -2334,7 +2311,7 @@ int aslam_landmarks_from_markers(int n, const aslam_marker_msg* in, int* ids, do
 // ---- persistence (no counterpart in the reference: warm starts of large maps) ----------------------------
 int aslam_save_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     int N = 0;
     int r = aslam_get_state(c, &N, nullptr, nullptr);
     if (r) return r;
@@ -2360,8 +2337,7 @@ int aslam_save_state(aslam_ctx* c, const char* path) {
 
 int aslam_load_state(aslam_ctx* c, const char* path) {
     if (!c || !path) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
-    if (c->localizing) return fail(c, ASLAM_E_STATE, "localizing: the map is frozen (aslam_localize_end first)");
+    if (int r = allow(c, kSlam)) return r;
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, ASLAM_E_INVALID, std::string("cannot read ") + path);
     char magic[8];
@@ -2432,7 +2408,7 @@ int aslam_get_slot_raw_observations(aslam_ctx* c, int slot, int* n_out, int* ids
 
 int aslam_get_observations(aslam_ctx* c, int* n_out, int* ids, int* idx, int* action, double* xyth, double* Rdiag) {
     if (!c || !n_out) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     int n = 0;
     HIP_TRY(c, hipMemcpy(&n, c->ekf.d_npop, sizeof(int), hipMemcpyDeviceToHost));
@@ -2469,7 +2445,7 @@ int aslam_detect_batch(aslam_ctx* c, const uint8_t* frames, int nframes, int row
         int nb = std::min(c->max_batch, nframes - f0);
         int r = aslam_stage_frames(c, 0, frames + (size_t)f0 * frame_stride, nb, rows, cols, channels, step, frame_stride);
         if (r) return r;
-        r = run_detect(c, 0, nb);
+        r = run_detect(c, single_call(0, nb), false);
         if (r) return r;
         c->rig_last = false;
         r = sync_and_check(c);
@@ -2495,7 +2471,7 @@ int aslam_detect_batch(aslam_ctx* c, const uint8_t* frames, int nframes, int row
 
 int aslam_export_map(aslam_ctx* c, void* dst, int dst_is_device) {
     if (!c || !dst) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     { int rp = finalize_pending(c); if (rp) return rp; }
     launch_ekf_export_map(c->stream_ekf, c->ekf);
     HIP_TRY(c, hipGetLastError());
@@ -2507,7 +2483,7 @@ int aslam_export_map(aslam_ctx* c, void* dst, int dst_is_device) {
 
 int aslam_export_map_async(aslam_ctx* c, void* d_dst, int buffer) {
     if (!c || !d_dst || buffer < 0 || buffer > 1) return fail(c, ASLAM_E_INVALID, "bad arguments");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->ev_export[buffer]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_export[buffer], hipEventDisableTiming));
     { int rp = finalize_pending(c); if (rp) return rp; }
     launch_ekf_export_map(c->stream_ekf, c->ekf);              // ordered after the EKF steps enqueued so far
@@ -2583,7 +2559,7 @@ int aslam_comm_create(aslam_ctx* c, const void* id, int world, int rank) {
 
 int aslam_comm_gather_maps(aslam_ctx* c, void* dst, int dst_is_device) {
     if (!c || !dst) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (c->fleet_n) return fleet_refuses(c);
+    if (int r = allow(c, kSingle)) return r;
     if (!c->comm) return fail(c, ASLAM_E_STATE, "aslam_comm_create first");
     Rccl* r = rccl();
     const size_t nb = (size_t)ASLAM_MAP_RECORD_BYTES * c->ekf.max_landmarks;

@@ -136,7 +136,8 @@ int aslam_get_landmark_ids(aslam_ctx* ctx, int* L, int* ids);
  * aslam_stage_encoders stores, per slot, the encoder sample (wl, wr, dt) that precedes that frame;
  * aslam_run_staged(first, count, with_ekf) then runs (with_ekf: 0 detection+pose only, 1 full path, 2 EKF steps only), entirely on the device and asynchronously on the context's
  * stream: detection + pose for all `count` frames batched, followed (with_ekf != 0) by `count` sequential
- * addEncoder(dt) + addImage EKF steps.  aslam_sync waits and reports device-side overflow.
+ * addEncoder(dt) + addImage EKF steps.  Any other with_ekf is refused with ASLAM_E_INVALID, here and in the rig and
+ * fleet staged calls.  aslam_sync waits and reports device-side overflow.
  * Re-staging rule: aslam_run_staged returns before the batch has run (its EKF work is even enqueued one call
  * later, once its observations have reached the host).  aslam_stage_frames / aslam_stage_encoders on slots a
  * submitted batch still reads first finish that batch's use of them (they enqueue the deferred EKF work and

@@ -281,6 +281,10 @@ def test_rig_refusals():
     with pytest.raises(capi.AslamError) as e:
         ctx.detected_markers()                                # describes one camera only
     assert e.value.code == E_STATE
+    for fn in (ctx.run_staged, ctx.run_staged_rig):           # with_ekf outside {0, 1, 2}
+        with pytest.raises(capi.AslamError) as e:
+            fn(0, 1, 3)
+        assert e.value.code == E_INVALID
     ctx.stage_frames(np.zeros((64, 96), np.uint8), slot0=0)
     ctx.stage_frames(np.zeros((32, 48), np.uint8), slot0=1)  # a step whose frames differ in size
     with pytest.raises(capi.AslamError) as e:

@@ -261,11 +261,22 @@ def test_mode_and_argument_rules(tmp_path):
         refused(E_INVALID, fn, *a)
     refused(E_CAPACITY, ctx.fleet_set_state, 0, np.zeros(18), np.eye(18), [1, 2, 3, 4, 5])   # 5 landmarks > max_landmarks 4
     img = np.full((64, 64), 128, np.uint8)
-    for fn, a in [(ctx.add_encoder, (1.0, 1.0, 0.1)), (ctx.add_image, (img,)), (ctx.run_staged, (0, 1, 2)),
-                  (ctx.run_staged_rig, (0, 1, True)), (ctx.get_state, ()), (ctx.set_state, (fresh_mu, fresh_S, [])),
-                  (ctx.save_state, (str(tmp_path / "s.bin"),)), (ctx.get_observations, ()), (ctx.export_map, ()),
-                  (ctx.localize_begin, (ids, xyth, pose0, sig0)), (ctx.set_camera, (cam[0], np.zeros(5))), (ctx.pose_msg, ())]:
+    dev_buf = np.zeros(64, np.uint8)
+
+    def comm_gather():
+        ctx._ck(ctx.lib.aslam_comm_gather_maps(ctx.h, dev_buf.ctypes.data, 0))
+    for fn, a in [(ctx.add_encoder, (1.0, 1.0, 0.1)), (ctx.add_image, (img,)), (ctx.add_images, ([img],)),
+                  (ctx.run_staged, (0, 1, True)), (ctx.run_staged, (0, 1, 2)), (ctx.run_staged_rig, (0, 1, True)),
+                  (ctx.stream_open, (64, 64, 1, 1)), (ctx.stream_slot, (64, 64)), (ctx.stream_commit, (1.0, 1.0, 0.05)),
+                  (ctx.stream_push, (img, 1.0, 1.0, 0.05)), (ctx.stream_flush, ()), (ctx.export_map_async, (dev_buf.ctypes.data, 0)),
+                  (comm_gather, ()), (ctx.localize_begin, (ids, xyth, pose0, sig0)), (ctx.localize_end, ()),
+                  (ctx.get_state, ()), (ctx.set_state, (fresh_mu, fresh_S, [])), (ctx.save_state, (str(tmp_path / "s.bin"),)),
+                  (ctx.load_state, (str(tmp_path / "s.bin"),)), (ctx.pose_msg, ()), (ctx.map_markers, ()), (ctx.detected_markers, ()),
+                  (ctx.draw_detected_markers, (np.zeros((64, 64, 3), np.uint8),)), (ctx.get_observations, ()),
+                  (ctx.get_rig_observations, ()), (ctx.export_map, ()), (ctx.set_camera, (cam[0], np.zeros(5))),
+                  (ctx.set_camera_rig, ([cam],))]:
         refused(E_STATE, fn, *a)
+    assert not (tmp_path / "s.bin").exists()
 
     # set_state: that robot only, its last-observed list emptied, its armed flag kept
     mu1 = np.array([0.5, 0.1, 0.2, 1.0, 2.0, 0.3])
