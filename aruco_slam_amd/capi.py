@@ -177,6 +177,8 @@ _SIGS = {
     "aslam_debug_get_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, _ip, _ip, _ip, _ip, _llp]),
     "aslam_debug_get_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, _fp, _ip, _ip]),
     "aslam_debug_inject_observations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp, _dp]),
+    "aslam_debug_inject_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _fp]),
+    "aslam_debug_run_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
     "aslam_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_profile_reset": (C.c_int, [C.c_void_p]),
     "aslam_get_plan_stats": (C.c_int, [C.c_void_p, _llp]),
@@ -648,6 +650,21 @@ class Context:
         ids = np.ascontiguousarray(ids, dtype=np.int32); valid = np.ascontiguousarray(valid, dtype=np.int32)
         xyth = np.ascontiguousarray(xyth, dtype=np.float64).reshape(-1, 3); Rdiag = np.ascontiguousarray(Rdiag, dtype=np.float64).reshape(-1, 3)
         self._ck(self.lib.aslam_debug_inject_observations(self.h, int(slot), int(ids.size), _ptr(ids, _ip), _ptr(valid, _ip), _ptr(xyth, _dp), _ptr(Rdiag, _dp)))
+
+    def inject_candidates(self, slot, ids, rots, corners):
+        """overwrite slot's final candidate list: ids (-1 = rejected), corner rotations 0..3, corners n x 4 x 2 (float32)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1); rots = np.ascontiguousarray(rots, dtype=np.int32).reshape(-1)
+        corners = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 8)
+        if not ids.size == rots.size == corners.shape[0]:
+            raise ValueError("one id, one rotation and 4 corners per candidate")
+        self._ck(self.lib.aslam_debug_inject_candidates(self.h, int(slot), int(ids.size), _ptr(ids, _ip), _ptr(rots, _ip), _ptr(corners, _fp)))
+
+    def run_pose(self, first, count, robot_of_slot=None):
+        """the pose stage alone on the slots' injected candidates (robot_of_slot: a fleet's robot of each slot)"""
+        rs = None if robot_of_slot is None else np.ascontiguousarray(robot_of_slot, dtype=np.int32).reshape(-1)
+        if rs is not None and rs.size != count:
+            raise ValueError("one robot per slot")
+        self._ck(self.lib.aslam_debug_run_pose(self.h, int(first), int(count), _ptr(rs, _ip)))
 
     def sync(self):
         self._ck(self.lib.aslam_sync(self.h))

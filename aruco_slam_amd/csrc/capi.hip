@@ -428,12 +428,34 @@ Call single_call(int first, int count) { return {first, count, nullptr, nullptr,
 Call rig_call(const aslam_ctx* c, int first, int n_steps) { return {first, n_steps * c->rig_n, &c->rig, nullptr, c->max_batch + first, n_steps}; }
 Call fleet_call(int first, int count, const int* robots) { return {first, count, nullptr, robots, first, count}; }
 
+// frames per launch of the detection kernels: everything of the call at once (the work queues balance it) unless
+// ASLAM_DETECT_CHUNK asks for smaller sub-batches (an experiment knob: mask planes of fewer frames stay cache-resident
+// between k_threshold and k_trace, at the price of one longest-walk tail per sub-batch)
+int detect_chunk() {
+    static const int chunk_env = [] { const char* e = std::getenv("ASLAM_DETECT_CHUNK"); return e ? std::max(1, std::atoi(e)) : 0; }();
+    return chunk_env > 0 ? std::min(chunk_env, max_frames_per_call()) : max_frames_per_call();
+}
+
+// k_pose over frames [f0, f0 + nf) of call k, on stream st (a fleet's camera indices are already on the stream)
+void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int nf, const RefineCfg& rf) {
+    prof_begin(c, P_POSE, st);
+    if (k.robots) {
+        launch_pose_table(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
+                          c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, c->d_ctr, rf);
+    } else {
+        PoseCams cams = k.rig ? *k.rig : single_camera(c);
+        cams.cam0 = (f0 - k.first) % cams.n;
+        launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
+                    c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr, rf);
+    }
+    prof_end(c);
+}
+
 // detection + pose of the call's frames (asynchronous on the stream).  latency: the configuration of a one-frame call (one rig step)
 int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = false, hipEvent_t wait_before = nullptr) {
     const int first = k.first, count = k.count;
     if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
     if (!k.rig && !k.robots && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
-    PoseCams cams = k.rig ? *k.rig : single_camera(c);
     // the CU-masked stream only pays off while an EKF chain is actually in flight beside this detection; the first batch after
     // a synchronisation gets the whole GPU
     hipStream_t st = (beside_ekf && c->stream_part && (c->ekf_count > 0 || c->pend.active)) ? c->stream_part : c->stream;
@@ -456,11 +478,7 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
         int r = pinned_upload(c, c->fleet_camidx_up, c->d_fleet_camidx + first, k.robots, count, st);
         if (r) return r;
     }
-    // frames per launch of the detection kernels: everything of the call at once (the work queues balance it) unless
-    // ASLAM_DETECT_CHUNK asks for smaller sub-batches (an experiment knob: mask planes of fewer frames stay cache-resident
-    // between k_threshold and k_trace, at the price of one longest-walk tail per sub-batch)
-    static const int chunk_env = [] { const char* e = std::getenv("ASLAM_DETECT_CHUNK"); return e ? std::max(1, std::atoi(e)) : 0; }();
-    const int chunk = chunk_env > 0 ? std::min(chunk_env, max_frames_per_call()) : max_frames_per_call();
+    const int chunk = detect_chunk();
     for (int f0 = first; f0 < first + count; f0 += chunk) {
         const int nf = std::min(chunk, first + count - f0);
         // queue heads, work count and the per-frame list sizes of these frames, in one launch (the overflow mask is sticky)
@@ -503,18 +521,10 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
         prof_begin(c, P_IDENTIFY, st);
         launch_identify(st, c->nwaves, g, c->d_ctr, gray, c->d_finals + (size_t)f0 * kCandMax, c->d_work, c->d_dict);
         prof_end(c);
-        prof_begin(c, P_POSE, st);
-        cams.cam0 = (f0 - first) % cams.n;
         const RefineCfg rf{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
                            g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
                            c->d_refine_mask, gray};
-        if (k.robots)
-            launch_pose_table(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
-                              c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, c->d_ctr, rf);
-        else
-            launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
-                        c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr, rf);
-        prof_end(c);
+        launch_pose_stage(c, k, st, f0, nf, rf);
     }
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
     HIP_TRY(c, hipGetLastError());
@@ -813,6 +823,10 @@ const char* aslam_last_error(const aslam_ctx* c) { return c ? c->err.c_str() : (
 int aslam_set_camera(aslam_ctx* c, const double K[9], const double* D, int nD) {
     if (!c || !K || nD < 0 || (nD > 0 && !D)) return fail(c, ASLAM_E_INVALID, "bad camera arguments");
     if (int r = allow(c, kSingle)) return r;
+    // k_pose has the 5-coefficient plumb-bob model (k1, k2, p1, p2, k3).  A longer vector is taken only zero-padded: the reference's
+    // estimatePoseSingleMarkers would use k4..k6 of the 8-coefficient rational model, which k_pose does not have.
+    for (int i = 5; i < nD; i++)
+        if (D[i] != 0.0) return fail(c, ASLAM_E_INVALID, "camera distortion: a coefficient after the fifth is nonzero (the rational model k4..k6 is not supported; plumb-bob k1, k2, p1, p2, k3 only)");
     c->cam.fx = K[0]; c->cam.fy = K[4]; c->cam.cx = K[2]; c->cam.cy = K[5];
     c->cam.nD = std::min(nD, 5);
     for (int i = 0; i < 5; i++) c->cam.k[i] = i < c->cam.nD ? D[i] : 0.0;
@@ -2687,6 +2701,63 @@ int aslam_debug_inject_observations(aslam_ctx* c, int slot, int n, const int* id
     unsigned un = (unsigned)n;
     if (n) HIP_TRY(c, hipMemcpy(c->d_obs + (size_t)slot * kMarkerMax, h.data(), n * sizeof(ObsRaw), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_nmarkers + slot, &un, sizeof(unsigned), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int aslam_debug_inject_candidates(aslam_ctx* c, int slot, int n, const int* ids, const int* rots, const float* corners) {
+    if (!c || n < 0 || n > kCandMax || (n && (!ids || !rots || !corners))) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slot_range(c, slot, 1);
+    if (r) return r;
+    std::vector<FinalCand> h(n);
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < -1 || rots[i] < 0 || rots[i] > 3) return fail(c, ASLAM_E_INVALID, "candidate: id >= -1 and rotation 0..3");
+        for (int k = 0; k < 8; k++) {
+            if (!std::isfinite(corners[8 * i + k])) return fail(c, ASLAM_E_INVALID, "candidate: non-finite corner");
+            h[i].c[k] = corners[8 * i + k];
+        }
+        h[i].n = 0;
+        h[i].id = ids[i];
+        h[i].pad[0] = rots[i];
+        h[i].pad[1] = 0;
+    }
+    r = sync_streams(c);
+    if (r) return r;
+    unsigned un = (unsigned)n;
+    if (n) HIP_TRY(c, hipMemcpy(c->d_finals + (size_t)slot * kCandMax, h.data(), n * sizeof(FinalCand), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_nfinal + slot, &un, sizeof(unsigned), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of_slot) {
+    if (!c) return ASLAM_E_INVALID;
+    int r = check_slot_range(c, first, count);
+    if (r) return r;
+    if ((c->fleet_n > 0) != (robot_of_slot != nullptr))
+        return fail(c, ASLAM_E_INVALID, "robot_of_slot: given exactly when a fleet is active");
+    if (robot_of_slot)
+        for (int i = 0; i < count; i++)
+            if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    if (!robot_of_slot && c->rig_n == 0 && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    r = sync_streams(c);
+    if (r) return r;
+    // what run_detect launches at P_POSE for the call's frames, chunk by chunk (slot first + i: camera i % n of a rig), without
+    // corner refinement (there is no grey frame)
+    const Call k{first, count, c->rig_n > 0 ? &c->rig : nullptr, robot_of_slot, first, count};
+    hipStream_t st = c->stream;
+    if (c->last_detect && c->last_detect != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    c->last_detect = st;
+    c->last_first = first;
+    c->last_count = count;
+    if (robot_of_slot) {
+        r = pinned_upload(c, c->fleet_camidx_up, c->d_fleet_camidx + first, robot_of_slot, count, st);
+        if (r) return r;
+    }
+    RefineCfg rf{};
+    rf.on = 0;
+    const int chunk = detect_chunk();
+    for (int f0 = first; f0 < first + count; f0 += chunk) launch_pose_stage(c, k, st, f0, std::min(chunk, first + count - f0), rf);
+    HIP_TRY(c, hipEventRecord(c->ev_detect, st));
+    HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
 }
 

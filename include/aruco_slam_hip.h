@@ -66,7 +66,9 @@ int  aslam_create(const aslam_init* init, aslam_ctx** out);
 void aslam_destroy(aslam_ctx* ctx);
 const char* aslam_last_error(const aslam_ctx* ctx);
 
-/* ArucoSlam::setCameraParameters(pair<cv::Mat K, cv::Mat D>) — aruco_slam.h:129-133; K row-major 3x3, D n x 1 */
+/* ArucoSlam::setCameraParameters(pair<cv::Mat K, cv::Mat D>) — aruco_slam.h:129-133; K row-major 3x3, D n x 1: the plumb-bob
+ * k1, k2, p1, p2, k3.  More than 5 coefficients only if every one after the fifth is zero (ASLAM_E_INVALID otherwise: the rational
+ * model's k4..k6 are not supported). */
 int aslam_set_camera(aslam_ctx* ctx, const double K[9], const double* D, int nD);
 
 /* cv::aruco::DetectorParameters (OpenCV 3.2.0 field names and defaults).  The reference passes none (aruco_slam.cpp:313 uses
@@ -356,6 +358,16 @@ int aslam_debug_get_candidates(aslam_ctx* ctx, int slot, int stage /*0 quads (un
  * device EKF without the detector (tests/test_ekf_golden.py). */
 int aslam_debug_inject_observations(aslam_ctx* ctx, int slot, int n, const int* ids, const int* valid, const double* xyth,
                                     const double* Rdiag);
+/* the pose stage on given quads, without the detector (tests/test_pose_kernel.py).  aslam_debug_inject_candidates overwrites a slot's
+ * final candidate list with n <= 2048 quads: ids[i] (-1 = rejected), rots[i] in 0..3 (the corner rotation identification found) and
+ * corners[8 i .. 8 i + 7] (x0 y0 .. x3 y3 before the rotation).  aslam_debug_run_pose then launches on slots [first, first + count)
+ * what a detection call launches after identification: the ordered list of identified candidates (at most 128), the same-id
+ * inside-quad filter, solvePnP, the observation and its gates, without corner refinement.  Slot first + i is camera i % n of the rig
+ * when one is set (the single camera otherwise); robot_of_slot[i] names its robot while a fleet is active (NULL otherwise).  The
+ * results read back through aslam_get_slot_detections / aslam_get_slot_raw_observations, and aslam_run_staged(..., with_ekf = 2)
+ * fuses them. */
+int aslam_debug_inject_candidates(aslam_ctx* ctx, int slot, int n, const int* ids, const int* rots, const float* corners /* n x 8 */);
+int aslam_debug_run_pose(aslam_ctx* ctx, int first, int count, const int* robot_of_slot /* count entries, or NULL */);
 /* HIP-event timing of each kernel family on the context's stream, accumulated since the last reset:
  * names[i] (static strings), calls[i], total_ms[i]; returns the number of entries. */
 int aslam_profile_enable(aslam_ctx* ctx, int on);

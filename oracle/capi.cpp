@@ -162,6 +162,25 @@ void orc_solve_pnp(const float corners[8], float L, const double K[9], const dou
     solve_pnp_marker(cc, L, c, rvec, tvec, iters);
 }
 
+// _filterDetectedMarkers on n (id, 4 corners) detections: keep_out[i] = 1 if detection i survives
+void orc_filter_detected_markers(int n, const int* ids, const float* corners, int* keep_out) {
+    std::vector<Detection> d(n);
+    for (int i = 0; i < n; i++) {
+        d[i].id = ids[i];
+        for (int k = 0; k < 4; k++) d[i].c[k] = Pt2f{corners[8 * i + 2 * k], corners[8 * i + 2 * k + 1]};
+    }
+    // the filter keeps the survivors in input order: match them to the input in order (of identical detections, the first)
+    std::vector<Detection> kept = d;
+    filter_detected_markers(kept);
+    size_t j = 0;
+    for (int i = 0; i < n; i++) {
+        bool same = j < kept.size() && kept[j].id == d[i].id;
+        for (int k = 0; k < 4 && same; k++) same = kept[j].c[k].x == d[i].c[k].x && kept[j].c[k].y == d[i].c[k].y;
+        keep_out[i] = same ? 1 : 0;
+        if (same) j++;
+    }
+}
+
 // pop order of std::priority_queue<ArucoMarker> for the given push sequence of aruco_index_ values
 void orc_heap_order(int n, const int* indices, int* pop_order) {
     std::priority_queue<Observation> q;

@@ -65,6 +65,7 @@ def load():
         L.orc_project_points.argtypes = [_dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp]
         L.orc_solve_pnp.argtypes = [_fp, C.c_float, _dp, _dp, C.c_int, _dp, _dp, _ip]
         L.orc_heap_order.argtypes = [C.c_int, _ip, _ip]
+        L.orc_filter_detected_markers.argtypes = [C.c_int, _ip, _fp, _ip]
         L.orc_perspective_transform.argtypes = [_fp, _fp, _dp]
         _lib = L
     return _lib
@@ -231,6 +232,15 @@ def solve_pnp(corners, L, K, D):
     rv = np.zeros(3); tv = np.zeros(3); it = C.c_int()
     load().orc_solve_pnp(_p(c, _fp), C.c_float(L), _p(K, _dp), _p(D, _dp), int(D.size), _p(rv, _dp), _p(tv, _dp), C.byref(it))
     return rv, tv, it.value
+
+
+def filter_detected_markers(ids, corners):
+    """_filterDetectedMarkers: a keep flag per detection (same id, one quad inside the other: the inner one goes)"""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    c = np.ascontiguousarray(corners, np.float32).reshape(-1, 8)
+    keep = np.zeros(ids.size, np.int32)
+    load().orc_filter_detected_markers(int(ids.size), _p(ids, _ip), _p(c, _fp), _p(keep, _ip))
+    return keep.astype(bool)
 
 
 def heap_order(indices):

@@ -27,8 +27,9 @@ def build(src, out):
     assert r.returncode == 0, r.stderr[-4000:]
 
 
-def make_scenario(d, n_frames=5):
-    """bgr8 frames + interleaved encoder samples + parameter server + TF + a ground-truth map file"""
+def make_scenario(d, n_frames=5, n_dist=5):
+    """bgr8 frames + interleaved encoder samples + parameter server + TF + a ground-truth map file; the camera_info carries
+    n_dist zero distortion coefficients"""
     cfg = synth.SceneConfig(rows=ROWS, cols=COLS, f=F, grid=(2, 2), n_panels=3, col_spacing=0.9, row_spacing=0.7, step=0.05,
                             tz_far=2.4, tz_near=1.9, r2c=(R2C[0], R2C[1]))
     w = synth.PanelWorld(cfg)
@@ -46,7 +47,7 @@ def make_scenario(d, n_frames=5):
             f.write(f"/aruco_slam_node/{k} {v}\n")
         f.write("tf base_link camera_optical " + " ".join(str(x) for x in R2C) + "\n")
     events, expect = [], []
-    events.append("caminfo %r %r %r %r 5 0 0 0 0 0" % (float(w.K[0, 0]), float(w.K[1, 1]), float(w.K[0, 2]), float(w.K[1, 2])))
+    events.append("caminfo %r %r %r %r %d" % (float(w.K[0, 0]), float(w.K[1, 1]), float(w.K[0, 2]), float(w.K[1, 2]), n_dist) + " 0" * n_dist)
     expect.append(("real_map", ctx.load_map_txt(os.path.join(d, "map.txt"))))
     t = 100.0
     # an image BEFORE the first encoder message must be ignored (aruco_slam.cpp:84-85)
@@ -119,9 +120,9 @@ def run_node(exe, d):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
 
 
-def _dropin(tmp_path, src, label):
+def _dropin(tmp_path, src, label, n_dist=5):
     d = str(tmp_path)
-    expect = make_scenario(d)
+    expect = make_scenario(d, n_dist=n_dist)
     exe = os.path.join(d, "node")
     build(src, exe)
     run_node(exe, d)
@@ -130,6 +131,12 @@ def _dropin(tmp_path, src, label):
 
 def test_harness_node_publishes_what_the_ctypes_path_computes(tmp_path):
     _dropin(tmp_path, os.path.join(ROOT, "tests", "cpp", "node_harness.cpp"), "harness")
+
+
+def test_harness_node_takes_a_zero_padded_distortion_vector(tmp_path):
+    """camera_info with 8 coefficients, k4..k6 zero (the rational model's length): setCameraParameters passes all 8 and the
+    library takes them as the 5-coefficient plumb-bob (a nonzero k4..k6 is refused: tests/test_pose_kernel.py)"""
+    _dropin(tmp_path, os.path.join(ROOT, "tests", "cpp", "node_harness.cpp"), "harness/D8", n_dist=8)
 
 
 @pytest.mark.gpu

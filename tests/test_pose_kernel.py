@@ -1,0 +1,589 @@
+"""k_pose (pose.hip) on injected quads, against the oracle and against the long-double restatement in tests/pose_reference.py.
+
+aslam_debug_inject_candidates writes a slot's final candidate list (id, corner rotation, 4 corners) and aslam_debug_run_pose launches
+what a detection call launches after identification.  Every case checks:
+  - the marker list: ids, order and corners bit-exact against the oracle's _filterDetectedMarkers on the rotated identified candidates
+    (at most 128, in candidate order);
+  - the pose against the oracle's solvePnP on the same float corners (rotation matrices and t, not rvec components: near |r| = pi,
+    r and -r (2 pi - |r|) / |r| are one rotation);
+  - the pose against the reference: its reprojection cost at most that of the true pose and that of the oracle's pose (plus a
+    slack), and on noise-free, well-conditioned cases a stationary point (the Gauss-Newton step from it below solvePnP's
+    own stopping rule);
+  - the observation (x, y, theta, diag R, valid) against the oracle's getObservations body fed the kernel's own pose (the tail
+    alone, independent of the LM), and against the reference formulas.
+
+Measured worst cases, emulation build / MI355X (the bounds in EMU_TOL / GPU_TOL are at most 10x these):
+  pose vs oracle (rotation distance, t relative):    1.3e-14 / 4.0e-14
+  observation vs oracle (relative):                   0       / 8.9e-16
+  observation vs reference (relative):                9.8e-16 / 7.9e-16
+  cost above min(true pose, oracle pose) (relative):  2.2e-11 / 7.6e-10
+  Gauss-Newton step from the pose (relative):         2.1e-8  / 2.1e-8   (solvePnP stops below FLT_EPSILON = 1.2e-7)
+Runs on whichever library the session loads: the emulation here, the gfx950 build on the MI355X."""
+import math
+
+import numpy as np
+import pytest
+
+import pose_reference as pr
+from aruco_slam_amd import capi
+from oracle import pyoracle as orc
+from oracle.ekf_literal import LiteralSlam
+
+E_INVALID, E_CAPACITY = -1, -4
+ROWS, COLS = 720, 1280
+L = 0.27
+K900 = np.array([[900.0, 0, 640], [0, 900, 360], [0, 0, 1]])
+D_DEFAULT = np.array([0.0416, -0.0477, -0.00326, -0.00399, 0.0111])      # plumb_bob of the reference's default.yaml:16-20
+D_STRONG = np.array([-0.3, 0.12, 1e-3, -5e-4, -0.02])
+CAMERAS = {"none": np.zeros(0), "default": D_DEFAULT, "strong": D_STRONG, "nd4": D_STRONG[:4]}
+
+# bounds per library, each at most 10x the worst case measured on it (the module docstring)
+EMU_TOL = dict(pose=1e-13, obs=0.0, obs_ref=5e-15, cost=1e-10, step=1e-7)
+GPU_TOL = dict(pose=2e-13, obs=5e-15, obs_ref=5e-15, cost=5e-9, step=1e-7)
+
+
+@pytest.fixture(scope="module")
+def tol(on_emulation):
+    return EMU_TOL if on_emulation else GPU_TOL
+
+
+WORST = {}
+
+
+def note(key, v):
+    WORST[key] = max(WORST.get(key, 0.0), float(v))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report():
+    yield
+    print("\nworst cases: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(WORST.items())))
+
+
+def context(batch, landmarks=16, **over):
+    return capi.Context(max_rows=64, max_cols=64, max_batch=batch, persistent_waves=4, max_landmarks=landmarks, **over)
+
+
+def corners_of(R, t, K, D, marker_length=L):
+    """the float corners of a marker at (R, t) (exact projection rounded to float)"""
+    return np.asarray(pr.project(R, t, K, D, marker_length), np.float64).astype(np.float32)
+
+
+def injected(corners, rot):
+    """the candidate corners that identification with rotation rot turns into `corners` (k_pose: new[j] = old[(j + 4 - rot) % 4])"""
+    return np.roll(corners, -rot, axis=0)
+
+
+class Slot:
+    """one slot's candidate list: ids (-1 = rejected), rotations, candidate corners (n x 4 x 2) and, per candidate, the true pose
+    (R, t) or None; cam = (K, D, mount)"""
+
+    def __init__(self, cam):
+        self.cam = cam
+        self.ids, self.rots, self.corners, self.truth, self.clean = [], [], [], [], []
+
+    def add(self, mid, corners, rot=0, truth=None, clean=False):
+        self.ids.append(int(mid))
+        self.rots.append(int(rot))
+        self.corners.append(injected(np.asarray(corners, np.float32).reshape(4, 2), rot))
+        self.truth.append(truth)
+        self.clean.append(clean)
+
+    def expected(self):
+        """candidate indices of the marker list: identified in candidate order, the first 128, then the oracle's filter"""
+        idx = [i for i, m in enumerate(self.ids) if m >= 0][:128]
+        if not idx:
+            return []
+        rotated = np.array([np.roll(self.corners[i], self.rots[i], axis=0) for i in idx])
+        keep = orc.filter_detected_markers([self.ids[i] for i in idx], rotated)
+        return [i for i, k in zip(idx, keep) if k]
+
+
+def observe_oracle(K, D, rv, tv, corners, mount, threshold=3.0):
+    """getObservations' body in the oracle (camera frame), one marker, then the mount: (valid, xyth, diag R)"""
+    o = orc.Slam(useful_distance_threshold=threshold)
+    o.set_camera(K, D)
+    o.add_encoder(0, 0, 0)
+    o.add_poses([0], corners[None], rv[None], tv[None])
+    _, _, _, xyth, R = o.log_observations()
+    if len(xyth) == 0:
+        return False, None, None
+    x0, y0, th0 = xyth[0]
+    mx, my, psi = mount
+    c, s = math.cos(psi), math.sin(psi)
+    return True, np.array([(c * x0 - s * y0) + mx, (s * x0 + c * y0) + my, orc.norm_angle(th0 + psi)]), np.diag(R[0])
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1.0)))
+
+
+def angle_diff(a, b):
+    """|a - b|, taken modulo 2 pi only where both lie within 1e-9 of the wrap at +-pi (elsewhere an unwrapped angle is an error)"""
+    a, b = np.asarray(a, np.longdouble), np.asarray(b, np.longdouble)
+    d = np.abs(a - b)
+    at_wrap = (pr.PI - np.abs(a) < 1e-9) & (pr.PI - np.abs(b) < 1e-9)
+    return np.where(at_wrap, np.abs((a - b + pr.PI) % (2 * pr.PI) - pr.PI), d)
+
+
+def run_slots(ctx, slots, tol, first=0, robots=None, threshold=3.0, check_cost=True):
+    for s, sl in enumerate(slots):
+        ctx.inject_candidates(first + s, sl.ids, sl.rots, np.array(sl.corners, np.float32).reshape(-1, 8) if sl.ids else np.zeros((0, 8)))
+    ctx.run_pose(first, len(slots), robots)
+    out = []
+    for s, sl in enumerate(slots):
+        out.append(check_slot(ctx, first + s, sl, tol, threshold, check_cost))
+    return out
+
+
+def check_slot(ctx, slot, sl, tol, threshold, check_cost):
+    K, D, mount = sl.cam
+    exp = sl.expected()
+    ids, corners, rv, tv = ctx.get_slot_detections(slot)
+    assert ids.tolist() == [sl.ids[i] for i in exp], f"slot {slot}: marker ids / order differ"
+    want = np.array([np.roll(sl.corners[i], sl.rots[i], axis=0) for i in exp], np.float32).reshape(-1, 4, 2)
+    assert np.array_equal(corners, want), f"slot {slot}: marker corners differ"
+    oids, valid, xyth, Rd = ctx.get_slot_raw_observations(slot)
+    assert np.array_equal(oids, ids)
+    if not exp:
+        return ids
+    # pose against the oracle's solvePnP on the same float corners
+    po = [orc.solve_pnp(c, L, K, D) for c in corners]
+    rvo, tvo = np.array([p[0] for p in po]), np.array([p[1] for p in po])
+    e_rot = pr.rotation_distance(rv, rvo)
+    e_t = np.max(np.abs(tv - tvo), axis=1) / np.linalg.norm(tvo, axis=1)
+    note("pose vs oracle", max(e_rot.max(), e_t.max()))
+    assert e_rot.max() <= tol["pose"] and e_t.max() <= tol["pose"], f"slot {slot}: pose differs from the oracle by {e_rot.max():.3g} / {e_t.max():.3g}"
+    # pose against the reference
+    c_k = pr.cost(rv, tv, corners, K, D, L)
+    c_o = pr.cost(rvo, tvo, corners, K, D, L)
+    bound = c_o
+    tr = [sl.truth[i] for i in exp]
+    have = np.array([t is not None for t in tr])
+    if have.any():
+        Rt = np.array([t[0] for t in tr if t is not None]); tt = np.array([t[1] for t in tr if t is not None])
+        c_t = pr.cost_at(Rt, tt, corners[have], K, D, L)
+        bound = bound.copy()
+        bound[have] = np.minimum(bound[have], c_t)
+    excess = float(np.max(c_k / bound - 1))
+    note("cost excess", excess)
+    if check_cost:
+        assert excess <= tol["cost"], f"slot {slot}: reprojection cost up to {excess:.3g} (relative) above that of the true / oracle pose"
+    clean = np.array([sl.clean[i] for i in exp])
+    if clean.any():
+        g = pr.newton_step(rv[clean], tv[clean], corners[clean], K, D, L)
+        note("Gauss-Newton step", g.max())
+        assert g.max() <= tol["step"], f"slot {slot}: not a stationary point of the cost (Gauss-Newton step {g.max():.3g} relative)"
+    # observation against the oracle's tail fed the kernel's own pose, and against the reference formulas
+    for j in range(len(ids)):
+        ok, z, r = observe_oracle(K, D, rv[j], tv[j], corners[j], mount, threshold)
+        assert bool(valid[j]) == ok, f"slot {slot} marker {j}: valid {valid[j]}, oracle {ok}"
+        if ok:
+            e = max(rel(xyth[j, :2], z[:2]), float(angle_diff(xyth[j, 2], z[2])), rel(Rd[j], r))
+            note("observation vs oracle", e)
+            assert e <= tol["obs"], f"slot {slot} marker {j}: observation differs from the oracle by {e:.3g}"
+    assert ((xyth[:, 2] >= -math.pi) & (xyth[:, 2] < math.pi)).all(), f"slot {slot}: theta outside [-pi, pi)"
+    z_ref = pr.observation(rv, tv, mount)
+    e = max(rel(xyth[:, :2], z_ref[:, :2]), float(angle_diff(xyth[:, 2], z_ref[:, 2]).max()))
+    note("observation vs reference", e)
+    assert e <= tol["obs_ref"], f"slot {slot}: observation differs from the reference by {e:.3g}"
+    R_ref, slack = pr.covariance(rv, tv, corners, K, D, L)
+    dR = np.abs(Rd - np.asarray(R_ref, np.float64))
+    assert (dR <= tol["obs_ref"] * np.asarray(R_ref, np.float64) + np.asarray(slack, np.float64)).all(), f"slot {slot}: diag R differs from the reference"
+    pass_d, m_d = pr.range_gate(tv, threshold)
+    pass_c, m_c = pr.covariance_gate(R_ref)
+    m_c = m_c - np.sqrt(np.sum(np.asarray(slack, np.float64) ** 2, axis=1))
+    sure = (m_d > 1e-9) & ((m_c > 1e-9) | ~pass_d)
+    ref_valid = pass_d & pass_c
+    assert np.array_equal(valid.astype(bool)[sure], ref_valid[sure]), f"slot {slot}: valid differs from the reference's gates"
+    return ids
+
+
+# ---- poses -------------------------------------------------------------------------------------------------------------------
+
+def spread_poses(rng, n, K, D, margin=2.0):
+    """n poses whose quads lie inside the 1280 x 720 frame, centres spread over it (a quarter of them in the corner regions)"""
+    out = []
+    while len(out) < n:
+        corner = len(out) % 4 == 0
+        z = rng.uniform(0.6, 2.8)
+        if corner:
+            u = rng.choice([rng.uniform(0, 0.12), rng.uniform(0.88, 1.0)]) * COLS
+            v = rng.choice([rng.uniform(0, 0.15), rng.uniform(0.85, 1.0)]) * ROWS
+        else:
+            u, v = rng.uniform(0, COLS), rng.uniform(0, ROWS)
+        x, y = (u - K[0, 2]) / K[0, 0] * z, (v - K[1, 2]) / K[1, 1] * z
+        R = pr.rot_x(rng.uniform(-0.6, 0.6)) @ pr.rot_y(rng.uniform(-0.6, 0.6)) @ pr.rot_z(rng.uniform(-math.pi, math.pi)) @ pr.facing()
+        t = np.array([x, y, z], np.longdouble)
+        c = corners_of(R, t, K, D)
+        if (c[:, 0] >= margin).all() and (c[:, 0] <= COLS - margin).all() and (c[:, 1] >= margin).all() and (c[:, 1] <= ROWS - margin).all():
+            out.append((R, t, c))
+    return out
+
+
+@pytest.mark.parametrize("cam", list(CAMERAS))
+def test_spread_over_the_frame(cam, tol):
+    """216 poses over the whole field of view (54 in the corner regions), up to 128 markers per slot over 3 slots"""
+    D = CAMERAS[cam]
+    rng = np.random.RandomState(11)
+    poses = spread_poses(rng, 216, K900, D)
+    ctx = context(3)
+    ctx.set_camera(K900, D)
+    slots = []
+    for s, chunk in enumerate((poses[:128], poses[128:200], poses[200:])):
+        sl = Slot((K900, D, (0.0, 0.0, 0.0)))
+        for k, (R, t, c) in enumerate(chunk):
+            sl.add(k, c, rot=k % 4, truth=(R, t), clean=True)
+        slots.append(sl)
+    got = run_slots(ctx, slots, tol)
+    assert [len(g) for g in got] == [128, 72, 16]
+    ctx.sync()
+
+
+def near_pi_cases():
+    cases = []
+    for z in (0.8, 2.0):
+        for d in (0.0, 1e-7, 1e-6, 1e-5, 3e-5, 1e-4):
+            cases.append((pr.rot_z(d) @ pr.facing(), z))            # in-plane: the rotation angle stays pi, its axis turns
+            cases.append((pr.rot_x(d) @ pr.facing(), z))            # out of plane: angle pi - d
+            cases.append((pr.rot_y(-d) @ pr.facing(), z))
+        for a in (0.5, 1.0, 2.0, -1.0, 3.0):                        # rolled in the image plane, no tilt: angle pi
+            cases.append((pr.rot_z(a) @ pr.facing(), z))
+    return cases
+
+
+@pytest.mark.parametrize("cam", ["none", "default"])
+def test_rotation_near_pi(cam, tol):
+    """fronto-parallel markers on the optical axis at theta = pi exactly and 1e-7 .. 1e-4 rad off it, in and out of the image
+    plane: both sides of rodrigues_inv's s < 1e-5 switch"""
+    D = CAMERAS[cam]
+    ctx = context(1)
+    ctx.set_camera(K900, D)
+    sl = Slot((K900, D, (0.0, 0.0, 0.0)))
+    for k, (R, z) in enumerate(near_pi_cases()):
+        t = np.array([0, 0, z], np.longdouble)
+        sl.add(k, corners_of(R, t, K900, D), truth=(R, t), clean=True)
+    run_slots(ctx, [sl], tol)
+
+
+def hard_geometry():
+    out = []
+    for a in (60, 75, 80, 85):                                       # grazing: turned about the image's vertical axis
+        for sgn in (1, -1):
+            out.append(("grazing", pr.rot_y(sgn * math.radians(a)) @ pr.facing(), np.array([0.1 * sgn, -0.05, 1.2], np.longdouble)))
+            out.append(("grazing", pr.rot_x(sgn * math.radians(a)) @ pr.facing(), np.array([-0.2, 0.1 * sgn, 1.6], np.longdouble)))
+    for z in (16.0, 20.0, 24.0):                                     # tiny: 10 .. 15 px per side
+        out.append(("tiny", pr.rot_y(0.2) @ pr.facing(), np.array([0.5, -0.3, z], np.longdouble)))
+    for z in (5.0, 8.0, 12.0):
+        out.append(("far", pr.rot_x(-0.3) @ pr.facing(), np.array([-0.8, 0.4, z], np.longdouble)))
+    out.append(("large", pr.rot_y(0.1) @ pr.facing(), np.array([0.0, 0.0, 0.34], np.longdouble)))   # 700 px across
+    return out
+
+
+@pytest.mark.parametrize("cam", ["none", "default", "strong"])
+def test_hard_geometry(cam, tol):
+    """grazing markers at 60 .. 85 degrees, tiny (10 - 15 px), far (5 - 12 m) and one filling most of the frame"""
+    D = CAMERAS[cam]
+    ctx = context(1)
+    ctx.set_camera(K900, D)
+    sl = Slot((K900, D, (0.0, 0.0, 0.0)))
+    for k, (kind, R, t) in enumerate(hard_geometry()):
+        c = corners_of(R, t, K900, D)
+        if kind == "tiny":
+            side = np.linalg.norm(c[0] - c[1])
+            assert 9 <= side <= 16, side
+        sl.add(k, c, truth=(R, t))
+    run_slots(ctx, [sl], tol)
+
+
+# ---- gates -------------------------------------------------------------------------------------------------------------------
+
+def test_range_gate_near_three_metres(tol):
+    """|t| at 2.9 and 3.1 m and within a few float ulps of 3.0 (the gate compares float(|t|) with the float threshold)"""
+    ctx = context(1)
+    ctx.set_camera(K900, D_DEFAULT)
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    u = np.spacing(np.float32(3.0))
+    norms = [2.9, 3.1] + [3.0 + k * float(u) for k in (-3, -1, 0, 1, 3)]
+    rng = np.random.RandomState(3)
+    for k, n in enumerate(norms):
+        d = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.2, 0.2), 1.0])
+        t = np.array(d / np.linalg.norm(d) * n, np.longdouble)
+        R = pr.rot_y(0.3) @ pr.facing()
+        sl.add(k, corners_of(R, t, K900, D_DEFAULT), truth=(R, t))
+    run_slots(ctx, [sl], tol)
+    _, valid, _, _ = ctx.get_slot_raw_observations(0)
+    assert valid[0] == 1 and valid[1] == 0
+
+
+def gate_value(corners, K, D):
+    rv, tv, _ = orc.solve_pnp(corners, L, K, D)
+    R, _ = pr.covariance(rv, tv, corners, K, D, L)
+    return float(np.sqrt(np.sum(np.asarray(R, np.float64) ** 2)))
+
+
+def test_covariance_gate_near_one(tol):
+    """corner noise sized so that |diag R| lands at 0.5x, 0.99x, 1.01x and 2x the gate"""
+    ctx = context(1)
+    ctx.set_camera(K900, D_DEFAULT)
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    rng = np.random.RandomState(4)
+    R = pr.rot_x(0.25) @ pr.facing()
+    t = np.array([0.1, 0.05, 1.5], np.longdouble)
+    c0 = corners_of(R, t, K900, D_DEFAULT)
+    pattern = rng.normal(size=(4, 2))
+    for k, target in enumerate((0.5, 0.99, 1.01, 2.0)):
+        lo, hi = 0.0, 200.0
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if gate_value((c0 + mid * pattern).astype(np.float32), K900, D_DEFAULT) < target else (lo, mid)
+        c = (c0 + hi * pattern).astype(np.float32)
+        assert abs(gate_value(c, K900, D_DEFAULT) / target - 1) < 1e-3
+        sl.add(k, c, truth=(R, t))
+    run_slots(ctx, [sl], tol)
+    _, valid, _, _ = ctx.get_slot_raw_observations(0)
+    assert valid.tolist() == [1, 1, 0, 0]
+
+
+# ---- mounts: rig and fleet cameras -------------------------------------------------------------------------------------------
+
+def rig_cameras(n):
+    Ks = [np.array([[f, 0, cx], [0, f * a, cy], [0, 0, 1]]) for f, a, cx, cy in
+          ((900, 1.0, 640, 360), (620, 1.01, 630, 350), (1100, 0.99, 655, 372), (750, 1.0, 640, 360))]
+    Ds = [D_DEFAULT, np.zeros(5), D_STRONG, D_STRONG[:4], np.zeros(0)]
+    mounts = [(0.1, 0.0, 0.0), (-0.2, 0.05, math.pi), (0.0, 0.15, -math.pi / 2), (0.05, -0.15, math.pi / 2), (0.3, 0.1, 2.5),
+              (-0.1, -0.1, -2.9), (0.0, 0.0, 1e-3), (0.2, 0.2, -1.0)]
+    return [(Ks[i % len(Ks)], Ds[i % len(Ds)], mounts[i]) for i in range(n)]
+
+
+def mount_slot(cam, rng, n=12):
+    """markers whose heading in the camera frame, atan2(-R02, R22), lies near +-pi (facing) or spread over (-pi, pi)"""
+    K, D, _ = cam
+    sl = Slot(cam)
+    k = 0
+    while k < n:
+        yaw = rng.choice([rng.uniform(-1e-3, 1e-3), rng.uniform(-1.2, 1.2)])
+        R = pr.rot_y(yaw) @ pr.facing()
+        t = np.array([rng.uniform(-0.5, 0.5), rng.uniform(-0.3, 0.3), rng.uniform(0.8, 2.5)], np.longdouble)
+        c = corners_of(R, t, K, D)
+        if (c[:, 0] > 0).all() and (c[:, 0] < COLS).all() and (c[:, 1] > 0).all() and (c[:, 1] < ROWS).all():
+            sl.add(k, c, rot=k % 4, truth=(R, t), clean=True)
+            k += 1
+    return sl
+
+
+@pytest.mark.parametrize("n", [2, 3, 8])
+def test_rig_cameras_and_mounts(n, tol):
+    """slot i is camera i % n of the rig (its own K, D and mount; headings pi and -pi/2 among them), two rounds of the rig"""
+    cams = rig_cameras(n)
+    ctx = context(2 * n)
+    ctx.set_camera_rig(cams)
+    rng = np.random.RandomState(20 + n)
+    slots = [mount_slot(cams[i % n], rng) for i in range(2 * n)]
+    run_slots(ctx, slots, tol)
+
+
+def test_rig_cameras_past_the_first_launch(tol):
+    """a call longer than one launch (1024 frames): the second launch starts at camera 1024 % 3 = 1 of a 3-camera rig"""
+    cams = rig_cameras(3)
+    first, count = 1, 1026
+    ctx = context(first + count)
+    ctx.set_camera_rig(cams)
+    rng = np.random.RandomState(40)
+    slots = [mount_slot(cams[i % 3], rng, n=3) if i in (0, 1, 1022, 1023, 1024, 1025) else Slot(cams[i % 3]) for i in range(count)]
+    run_slots(ctx, slots, tol, first=first)
+
+
+@pytest.mark.parametrize("kind", ["slam", "localize"])
+def test_fleet_cameras(kind, tol):
+    """the same kind of quads through a fleet's camera table (per-robot K, D, mount), robots in a non-identity slot order"""
+    n = 5
+    cams = rig_cameras(n)
+    ctx = context(8)
+    if kind == "slam":
+        ctx.fleet_slam_begin(cams)
+    else:
+        ctx.fleet_begin(cams, [500], [[5.0, 0.0, 0.0]], np.zeros((n, 3)), np.tile(np.eye(3) * 1e-2, (n, 1, 1)))
+    robots = [3, 0, 4, 4, 1, 2, 0, 3]
+    rng = np.random.RandomState(31)
+    slots = [mount_slot(cams[r], rng) for r in robots]
+    run_slots(ctx, slots, tol, robots=robots)
+    with pytest.raises(capi.AslamError):
+        ctx.run_pose(0, 1)                                       # a fleet needs the robot of every slot
+
+
+# ---- the marker list ---------------------------------------------------------------------------------------------------------
+
+def distinct_quads(n, rng):
+    """n small non-overlapping upright marker quads on a grid (noise-free projections at 3 m)"""
+    out = []
+    for k in range(n):
+        x, y = 40 + 80 * (k % 15), 40 + 60 * (k // 15 % 11)
+        t = np.array([(x - 640) / 900 * 2.5, (y - 360) / 900 * 2.5, 2.5 + 0.01 * (k // 165)], np.longdouble)
+        R = pr.rot_y(rng.uniform(-0.3, 0.3)) @ pr.facing()
+        out.append((R, t, corners_of(R, t, K900, D_DEFAULT)))
+    return out
+
+
+def junk(rng):
+    return rng.uniform(0, 1000, (4, 2)).astype(np.float32)
+
+
+def list_case(positions, total, seed, ids=None):
+    rng = np.random.RandomState(seed)
+    quads = distinct_quads(len(positions), rng)
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    at = dict(zip(positions, range(len(positions))))
+    for i in range(total):
+        if i in at:
+            q = at[i]
+            R, t, c = quads[q]
+            sl.add(q if ids is None else ids[q], c, rot=q % 4, truth=(R, t))
+        else:
+            sl.add(-1, junk(rng))
+    return sl
+
+
+def test_rotations_of_one_quad(tol):
+    """rot 0..3 on one quad (distinct ids: the filter keeps all four)"""
+    R, t = pr.rot_y(0.2) @ pr.facing(), np.array([0.1, 0.0, 1.2], np.longdouble)
+    c = corners_of(R, t, K900, D_DEFAULT)
+    ctx = context(1)
+    ctx.set_camera(K900, D_DEFAULT)
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    for rot in range(4):
+        sl.ids.append(7 + rot); sl.rots.append(rot); sl.corners.append(c.copy()); sl.truth.append(None); sl.clean.append(False)
+    run_slots(ctx, [sl], tol)
+    _, got, _, _ = ctx.get_slot_detections(0)
+    for rot in range(4):
+        assert np.array_equal(got[rot], np.roll(c, rot, axis=0))      # new[j] = old[(j + 4 - rot) % 4]
+
+
+def test_compaction_across_waves_and_chunks(tol):
+    """identified candidates at positions 0, 63, 64, 127, 128, 129, 1000 and 2047 of a 2048-candidate list, rejected ones between"""
+    ctx = context(1)
+    ctx.set_camera(K900, D_DEFAULT)
+    positions = [0, 63, 64, 127, 128, 129, 1000, 2047]
+    got = run_slots(ctx, [list_case(positions, 2048, 1)], tol)
+    assert got[0].tolist() == list(range(8))
+    ctx.sync()
+
+
+@pytest.mark.parametrize("n_ident", [128, 129, 300])
+def test_marker_cap(n_ident, tol):
+    """128 identified: all kept; 129 and 300: the first 128 in candidate order, the markers-overflow bit, ASLAM_E_CAPACITY at sync"""
+    rng = np.random.RandomState(n_ident)
+    positions = sorted(rng.choice(2048, n_ident, replace=False).tolist())
+    ctx = context(1, landmarks=8)
+    ctx.set_camera(K900, D_DEFAULT)
+    got = run_slots(ctx, [list_case(positions, 2048, 2)], tol)
+    assert got[0].tolist() == list(range(min(n_ident, 128)))
+    if n_ident <= 128:
+        ctx.sync()
+    else:
+        with pytest.raises(capi.AslamError) as e:
+            ctx.sync()
+        assert e.value.code == E_CAPACITY
+        ctx.sync()                                               # the bit is cleared once reported
+
+
+def square(x0, y0, s):
+    return np.array([[x0, y0], [x0 + s, y0], [x0 + s, y0 + s], [x0, y0 + s]], np.float32)
+
+
+def filter_slot(entries):
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    for mid, c in entries:
+        sl.add(mid, c)
+    return sl
+
+
+def test_filter_detected_markers(tol):
+    """_filterDetectedMarkers: same id disjoint (both kept), same id nested in both orders (inner dropped), different ids nested
+    (both kept), three identical quads (the first kept), a corner exactly on the other quad's edge (on the edge counts as inside)"""
+    outer, inner = square(400, 200, 200), square(450, 250, 80)
+    diamond = np.array([[500, 200], [560, 260], [500, 320], [440, 260]], np.float32)     # top corner on the outer square's top edge
+    cases = [
+        ([(3, square(100, 100, 100)), (3, square(700, 300, 100))], [0, 1]),
+        ([(4, outer), (4, inner)], [0]),
+        ([(4, inner), (4, outer)], [1]),
+        ([(5, outer), (6, inner)], [0, 1]),
+        ([(8, outer), (8, outer), (8, outer)], [0]),
+        ([(9, outer), (9, diamond)], [0]),
+        ([(9, diamond), (9, outer)], [1]),
+        ([(2, inner), (-1, outer), (2, outer), (2, square(900, 400, 60))], [2, 3]),
+    ]
+    ctx = context(len(cases))
+    ctx.set_camera(K900, D_DEFAULT)
+    slots = [filter_slot(e) for e, _ in cases]
+    got = run_slots(ctx, slots, tol)
+    for (entries, keep), g, sl in zip(cases, got, slots):
+        assert g.tolist() == [entries[i][0] for i in keep]
+        _, c, _, _ = ctx.get_slot_detections(slots.index(sl))
+        assert np.array_equal(c, np.array([entries[i][1] for i in keep]))
+
+
+# ---- the hook's refusals and the EKF behind it -------------------------------------------------------------------------------
+
+def test_hook_refuses_bad_input():
+    ctx = context(2)
+    ctx.set_camera(K900, D_DEFAULT)
+    c = square(10, 10, 50)[None]
+    for ids, rots, cc in (([-2], [0], c), ([1], [4], c), ([1], [-1], c), ([1], [0], np.where(np.eye(4, 2, dtype=bool), np.nan, c))):
+        with pytest.raises(capi.AslamError) as e:
+            ctx.inject_candidates(0, ids, rots, cc)
+        assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.inject_candidates(2, [1], [0], c)
+    assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.inject_candidates(0, np.zeros(2049, np.int32), np.zeros(2049, np.int32), np.zeros((2049, 8), np.float32))
+    assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.run_pose(1, 2)
+    assert e.value.code == E_INVALID
+    with pytest.raises(capi.AslamError) as e:
+        ctx.run_pose(0, 1, [0])                                   # no fleet
+    assert e.value.code == E_INVALID
+
+
+def test_hook_lists_feed_the_ekf(tol):
+    """run_pose, then run_staged(with_ekf=2): mu and Sigma equal the literal reference fed the same detections and poses"""
+    WL, WR, DT = 2.0, 2.3, 1 / 30.0
+    rng = np.random.RandomState(8)
+    cam = (K900, D_DEFAULT, (0.0, 0.0, 0.0))
+    sl = mount_slot(cam, rng, n=10)
+    ctx = context(2, landmarks=16)
+    ctx.set_camera(K900, D_DEFAULT)
+    ctx.stage_encoders([0.0, WL], [0.0, WR], [0.0, DT])
+    run_slots(ctx, [Slot(cam), sl], tol)
+    ids, corners, rv, tv = ctx.get_slot_detections(1)
+    assert len(ids) == 10
+    ctx.run_staged(0, 2, with_ekf=2)
+    ctx.sync()
+    lit = LiteralSlam()
+    lit.K, lit.D = K900, D_DEFAULT
+    lit.add_encoder(0.0, 0.0, 0.0)
+    lit.add_encoder(WL, WR, DT)
+    lit.add_poses(ids, corners, rv, tv)
+    mu, S = ctx.get_state()
+    assert mu.shape == lit.mu.shape and mu.size > 3
+    assert np.allclose(mu, lit.mu, rtol=1e-9, atol=1e-11)
+    assert np.abs(S - lit.sigma).max() <= 1e-9 * np.abs(lit.sigma).max()
+
+
+# ---- distortion vectors longer than the plumb-bob model ----------------------------------------------------------------------
+
+def test_set_camera_takes_zero_padded_distortion_only(tol):
+    """8 coefficients: accepted when k4..k6 are zero (and then the same as 5), refused otherwise - k_pose has no rational model"""
+    ctx = context(1)
+    for extra in ([1e-3, 0, 0], [0, 0, -2e-4], [0, 0, 0, 0, 0, 0, 0, 0, 0, 1e-6]):
+        with pytest.raises(capi.AslamError) as e:
+            ctx.set_camera(K900, np.concatenate([D_DEFAULT, extra]))
+        assert e.value.code == E_INVALID and "rational" in str(e.value)
+    ctx.set_camera(K900, np.concatenate([D_DEFAULT, np.zeros(9)]))
+    R, t = pr.rot_y(0.3) @ pr.facing(), np.array([0.9, 0.5, 1.3], np.longdouble)
+    sl = Slot((K900, D_DEFAULT, (0.0, 0.0, 0.0)))
+    sl.add(1, corners_of(R, t, K900, D_DEFAULT), truth=(R, t), clean=True)
+    run_slots(ctx, [sl], tol)
