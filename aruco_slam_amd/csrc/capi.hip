@@ -150,6 +150,8 @@ struct aslam_ctx {
     // behind the NEXT batch's detection, so that the detection stream never waits for the host
     bool win_enabled = true;
     int win_piece = kWinChainFrames;      // frames per chain piece (ASLAM_WIN_PIECE, 1..kWinChainFrames: a test knob)
+    bool win_pieces = false;              // ASLAM_WIN_PIECE set: the piece schedule (several launches per window) instead of one launch per window
+    unsigned win_epoch = 0;               // one-launch windows enqueued so far: the tag of a window's hand-off counters
     bool win_no_early = false;            // ASLAM_WIN_NO_EARLY: every window waits for its own flush (test / comparison knob)
     struct Pending { bool active = false; int first = 0, count = 0, ev = 0; } pend;
     hipEvent_t ev_obs[2] = {nullptr, nullptr}, ev_idx = nullptr;
@@ -626,6 +628,14 @@ int sync_and_check(aslam_ctx* c) {
     prof_collect(c);
     Counters h{};
     HIP_TRY(c, hipMemcpy(&h, c->d_ctr, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.win_err) {
+        unsigned zero = 0;
+        hipMemcpy(&c->d_ctr->win_err, &zero, sizeof(unsigned), hipMemcpyHostToDevice);
+        char buf[160];
+        snprintf(buf, sizeof(buf), "windowed EKF: a %s workgroup of a window launch gave up waiting (code %u); the filter state is not valid",
+                 h.win_err == 1 ? "replay" : "Psi", h.win_err);
+        return fail(c, ASLAM_E_HIP, buf);
+    }
     if (h.overflow) {
         unsigned zero = 0;
         hipMemcpy(&c->d_ctr->overflow, &zero, sizeof(unsigned), hipMemcpyHostToDevice);
@@ -693,7 +703,7 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
 
     c->win_enabled = std::getenv("ASLAM_NO_WINDOWS") == nullptr;
     c->win_no_early = std::getenv("ASLAM_WIN_NO_EARLY") != nullptr;
-    if (const char* e = std::getenv("ASLAM_WIN_PIECE")) c->win_piece = std::min(kWinChainFrames, std::max(1, std::atoi(e)));
+    if (const char* e = std::getenv("ASLAM_WIN_PIECE")) { c->win_piece = std::min(kWinChainFrames, std::max(1, std::atoi(e))); c->win_pieces = true; }
     const int B = c->max_batch;
     const size_t px = (size_t)init->max_rows * init->max_cols;
     const size_t pitch = ((size_t)init->max_cols + 63) / 64 * 64;
@@ -762,6 +772,7 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
     ok = ok && hipMemset(c->d_ncand, 0, sizeof(unsigned) * B) == hipSuccess;
     ok = ok && hipMemset(c->d_enc, 0, sizeof(double) * 3 * 2 * B) == hipSuccess;
     ok = ok && ekf_alloc(c->ekf, init->max_landmarks, 2 * init->max_batch, init->max_updates_per_frame) == hipSuccess;
+    if (ok) c->ekf.d_win_err = &c->d_ctr->win_err;                  // read back with the call's counters (sync_and_check)
     ok = ok && hipEventCreateWithFlags(&c->ev_obs[0], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_obs[1], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_idx, hipEventDisableTiming) == hipSuccess;
@@ -1064,7 +1075,7 @@ int finalize_pending(aslam_ctx* c) {
     // window's LAST piece (which writes mu back) and whatever is not a window wait for the flush.
     hipStream_t sa = c->stream_ekf, sb = c->stream_win;
     auto new_event = [&]() { return c->ev_win[c->ev_win_next++ & 63]; };
-    struct { bool active = false; WinDesc wd{}; } pf;               // the previous window's flush, not yet enqueued
+    struct { bool active = false; WinDesc wd{}; hipEvent_t ev_flush = nullptr; } pf;   // the previous window's flush, not yet enqueued (and its predecessor's flush)
     auto flush_now = [&](const WinDesc& fwd) -> int {                                    // classic order: flush, then the EKF stream goes on
         hipEvent_t evr = new_event();
         HIP_TRY(c, hipEventRecord(evr, sa));                         // the window's replay (Lambda, Psi, psi) is complete
@@ -1095,6 +1106,8 @@ int finalize_pending(aslam_ctx* c) {
         for (int a = 0; a < wd.nS; a++) wd.li[a] = (short)(3 + 3 * o.S[a]);
         hipEvent_t ev_prev_flush = nullptr;
         if (pf.active) {
+            // the previous window's mu outside its S (and P_K, mu images of this parity) are as the flush before it leaves them
+            if (pf.ev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, pf.ev_flush, 0));
             prof_begin(c, P_EKF_WIN_NEXT, sa);                       // (the previous window's Lambda, Psi, psi are complete: same stream)
             launch_ekf_win_next(sa, c->ekf, pf.wd, wd);
             prof_end(c);
@@ -1114,58 +1127,74 @@ int finalize_pending(aslam_ctx* c) {
             HIP_TRY(c, hipStreamWaitEvent(sb, ev, 0));               // Sigma as the EKF stream leaves it
         }
         launch_ekf_win_gather(sb, c->ekf, wd);                       // Y_0 of this window (behind the previous window's flush: same stream)
-        // The pieces of the window, back to back on sa: launch i carries the chain of piece i, the replay of piece i - 1 and the Psi
-        // product of piece i - 2 (ekf_window.hip: k_ekf_win_step), so nothing but the stream orders them; two more launches drain
-        // the replay.  What follows the window waits for that drain: the pieces shrink towards the end (.., 4, 2, 1, 1 frames).
-        struct Piece { WinDesc sub; int nsteps; };
-        std::vector<Piece> pieces;
-        {
-            // piece sizes: the replay of piece i - 1 runs in the launch of piece i and takes about half as long per frame as the
-            // chain, so a piece may be at most twice as long as the one that follows it; from the window's end: 1, 1, 2, 4, 8, 8, ..
-            std::vector<int> sizes;
-            {
-                int left = o.K, nxt = 1, count = 0;
-                while (left > 0) {
-                    int kn = std::min(std::min(nxt, c->win_piece), left);
-                    sizes.push_back(kn);
-                    left -= kn;
-                    if (++count >= 2) nxt = std::min(2 * nxt, c->win_piece);       // 1, 1, 2, 4, ...
-                }
-                std::reverse(sizes.begin(), sizes.end());
-            }
-            int piece = 0, log0 = 0, k0 = 0;
-            for (int kn : sizes) {
-                Piece pc;
-                pc.sub = wd;
-                pc.sub.first_slot = o.frame + k0;
-                pc.sub.K = kn;
-                pc.sub.piece = piece++;
-                pc.sub.log0 = log0;
-                pc.sub.last = k0 + kn == o.K ? 1 : 0;
-                pc.nsteps = 0;
-                for (int k = 0; k < kn; k++) pc.nsteps += 1 + c->h_win_frames[pc.sub.first_slot + k].m;
-                log0 += pc.nsteps;
-                k0 += kn;
-                pieces.push_back(pc);
-            }
-        }
-        const int P = (int)pieces.size();
-        for (int i = 0; i < P + 2; i++) {
+        if (!c->win_pieces) {
+            // The whole window in one launch (ekf_window.hip: k_ekf_win_step, ONE): the chain, the replay of its log and the Psi
+            // product follow each other through in-launch counters.  The chain leaves mu_S in its image only: k_ekf_win_fix puts it
+            // back into the state, behind the previous window's flush, so the launch itself waits for nothing.
             WinDesc cw = wd;
-            cw.K = 0;
-            if (i < P) cw = pieces[i].sub;
-            const Piece* ps = (i >= 1 && i <= P) ? &pieces[i - 1] : nullptr;
-            const Piece* pq = (i >= 2) ? &pieces[i - 2] : nullptr;
-            if (i < P && cw.last && ev_prev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, ev_prev_flush, 0));   // mu_S goes back into the state: after the previous flush's mu_R pass
-            prof_begin(c, i < P ? P_EKF_WIN_CHAIN : P_EKF_WIN_SCAN, sa);
-            launch_ekf_win_step(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, ps ? ps->sub.piece : 0, ps ? ps->sub.log0 : 0, ps ? ps->nsteps : 0,
-                                pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0);
+            cw.first_slot = o.frame; cw.K = o.K; cw.piece = 0; cw.log0 = 0; cw.last = 1; cw.mu_out = 0;
+            if (++c->win_epoch == 0) c->win_epoch = 1;
+            cw.epoch = c->win_epoch;
+            cw.nsteps = 0;
+            for (int k = 0; k < o.K; k++) cw.nsteps += 1 + c->h_win_frames[o.frame + k].m;
+            prof_begin(c, P_EKF_WIN_CHAIN, sa);
+            launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc);
             prof_end(c);
+        } else {
+            // The pieces of the window, back to back on sa: launch i carries the chain of piece i, the replay of piece i - 1 and the Psi
+            // product of piece i - 2 (ekf_window.hip: k_ekf_win_step), so nothing but the stream orders them; two more launches drain
+            // the replay.  What follows the window waits for that drain: the pieces shrink towards the end (.., 4, 2, 1, 1 frames).
+            struct Piece { WinDesc sub; int nsteps; };
+            std::vector<Piece> pieces;
+            {
+                // piece sizes: the replay of piece i - 1 runs in the launch of piece i and takes about half as long per frame as the
+                // chain, so a piece may be at most twice as long as the one that follows it; from the window's end: 1, 1, 2, 4, 8, 8, ..
+                std::vector<int> sizes;
+                {
+                    int left = o.K, nxt = 1, count = 0;
+                    while (left > 0) {
+                        int kn = std::min(std::min(nxt, c->win_piece), left);
+                        sizes.push_back(kn);
+                        left -= kn;
+                        if (++count >= 2) nxt = std::min(2 * nxt, c->win_piece);       // 1, 1, 2, 4, ...
+                    }
+                    std::reverse(sizes.begin(), sizes.end());
+                }
+                int piece = 0, log0 = 0, k0 = 0;
+                for (int kn : sizes) {
+                    Piece pc;
+                    pc.sub = wd;
+                    pc.sub.first_slot = o.frame + k0;
+                    pc.sub.K = kn;
+                    pc.sub.piece = piece++;
+                    pc.sub.log0 = log0;
+                    pc.sub.last = k0 + kn == o.K ? 1 : 0;
+                    pc.sub.mu_out = pc.sub.last;
+                    pc.nsteps = 0;
+                    for (int k = 0; k < kn; k++) pc.nsteps += 1 + c->h_win_frames[pc.sub.first_slot + k].m;
+                    log0 += pc.nsteps;
+                    k0 += kn;
+                    pieces.push_back(pc);
+                }
+            }
+            const int P = (int)pieces.size();
+            for (int i = 0; i < P + 2; i++) {
+                WinDesc cw = wd;
+                cw.K = 0;
+                if (i < P) cw = pieces[i].sub;
+                const Piece* ps = (i >= 1 && i <= P) ? &pieces[i - 1] : nullptr;
+                const Piece* pq = (i >= 2) ? &pieces[i - 2] : nullptr;
+                if (i < P && cw.last && ev_prev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, ev_prev_flush, 0));   // mu_S goes back into the state: after the previous flush's mu_R pass
+                prof_begin(c, i < P ? P_EKF_WIN_CHAIN : P_EKF_WIN_SCAN, sa);
+                launch_ekf_win_step(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, ps ? ps->sub.piece : 0, ps ? ps->sub.log0 : 0, ps ? ps->nsteps : 0,
+                                    pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0);
+                prof_end(c);
+            }
         }
         HIP_TRY(c, hipGetLastError());
         const bool next_is_window = oi + 1 < ops.size() && ops[oi + 1].K > 0 && !c->win_no_early;
         if (next_is_window) {
-            pf.active = true; pf.wd = wd;
+            pf.active = true; pf.wd = wd; pf.ev_flush = ev_prev_flush;
         } else {
             int r = flush_now(wd);
             if (r) return r;

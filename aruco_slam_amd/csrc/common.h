@@ -62,7 +62,9 @@ struct DetectCfg {
 };
 
 struct Counters {                 // per-call scalars (work-queue heads, overflow mask); list sizes live in per-frame arrays
-    unsigned q_trace, q_quads, n_ident, q_ident, q_write, overflow, pad[2];
+    unsigned q_trace, q_quads, n_ident, q_ident, q_write, overflow;
+    unsigned win_err;             // sticky: a workgroup of a one-launch EKF window gave up waiting (ekf_window.hip); 0 = none
+    unsigned pad;
 };
 constexpr int kCounterHeads = 5;  // leading words reset before every detection call (the overflow mask is sticky)
 

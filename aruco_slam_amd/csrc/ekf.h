@@ -34,6 +34,8 @@ constexpr int kWinPieceMax = 16;       // frames per chain piece at most (its st
 constexpr int kWinCorrMax = 63;        // corrections fused per window frame at most (one lane of the prepare wave each)
 constexpr int kWinSMax = 63;           // landmarks in a window's set S at most: 3 + 3 * 63 = 192 = 12 MFMA tiles
 constexpr int kWinHdr = 24;            // doubles of scalar header per logged step (after the 3 operand rows)
+constexpr int kWinSyncLine = 16;       // 64-bit words per hand-off counter of the one-launch window (one 128-B line each)
+constexpr int kWinSyncCounters = 1 + 192 / 8 + 1;   // the chain's step count, one per replay workgroup, the workgroup ticket
 struct WinFrame {                      // host-planned bookkeeping of one window frame (aruco_slam.cpp:92-95, 192-198, 423-435 replayed on the host)
     int m;                             // corrections fused, in pop order = ascending landmark index (aruco_slam.h:85-88)
     int npop;                          // popped observations: the m corrections + the "stationary" no-ops
@@ -51,7 +53,10 @@ struct WinDesc {                       // one chain piece / one window (kernel a
     int piece, log0;                   // index of the piece within its window; steps logged by the earlier pieces
     int last;                          // 1 = the window's last piece: mu_S goes back to the state, the last frame's pop list / last-observation list are left behind
     int wpar;                          // parity of the window within its batch: which of the two P / mu hand-over images it uses
-    int from_image, pad;               // first piece of a window whose P and mu_S were prepared in the image (k_ekf_win_next_*) instead of read from Sigma / mu
+    int from_image;                    // first piece of a window whose P and mu_S were prepared in the image (k_ekf_win_next_*) instead of read from Sigma / mu
+    int mu_out;                        // the chain writes mu_S back into the state (piece schedule: the window's last piece); otherwise k_ekf_win_fix does
+    unsigned epoch;                    // one-launch window: tag of its hand-off counters (unique per window of the context, never 0)
+    int nsteps;                        // one-launch window: steps of the whole window (frames + corrections)
     short li[kWinSMax + 1];            // state offset 3 + 3 index of every landmark of S, ascending
 };
 
@@ -80,6 +85,8 @@ struct EkfState {
     int* d_win_sidx;                   // per state index: position in S or -1
     WinFrame* d_win_frames;            // per staged slot: the host's plan of the frame
     int win_sp_max, win_steps_max;     // capacity: largest SP and most steps (frames + corrections) per window
+    unsigned long long* d_win_sync;    // one-launch window: kWinSyncCounters hand-off counters, kWinSyncLine words apart ({epoch, count})
+    unsigned* d_win_err;               // one-launch window: non-zero = a workgroup gave up waiting (1: replay on the chain, 2: Psi on the replay)
     int* d_slot_stat;                  // per staged slot, written by k_ekf_plan: detections, augments, fused updates, stationary no-ops
     int max_slots;
 };
@@ -142,7 +149,9 @@ void launch_ekf_small(hipStream_t st, const FleetRound& R);
 void launch_ekf_T(hipStream_t st, const FleetRound& R);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
-// (nsteps == 0: none); obs / enc: the context's per-slot arrays
+// (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,
+// epoch set) in one launch, the three roles following each other through in-launch counters
+void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc);
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps);
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd);               // Y_0 = rows S of Sigma, position table

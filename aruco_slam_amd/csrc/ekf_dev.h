@@ -8,7 +8,34 @@
 #define ASLAM_RCP_ESTIMATE(x) __builtin_amdgcn_rcp(x)
 #endif
 
+// In-launch hand-offs between workgroups (ekf_window.hip, one-launch window): an agent-scope acquire, a wait for this wave's older
+// vector-memory operations, and global-address-space 64-bit words for write-through (sc1) stores and counters.  The CPU emulation
+// of the tests has sequentially consistent atomics and no memory counters.
+#if defined(__HIP__)
+#define ASLAM_ACQUIRE_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
+#define ASLAM_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+typedef __attribute__((address_space(1))) unsigned long long aslam_gu64;
+#else
+#define ASLAM_ACQUIRE_AGENT() __threadfence()
+#define ASLAM_VMCNT(n) do { } while (0)
+typedef unsigned long long aslam_gu64;
+#endif
+
 namespace aslam {
+
+// write-through store of one double (global_store_dwordx2 sc1): visible to another XCD once this wave's vmcnt covers it
+__device__ __forceinline__ void st_wt(double* p, double v) {
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, sizeof(b));
+    __hip_atomic_store((aslam_gu64*)p, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void win_signal(unsigned long long* w, unsigned epoch, int count) {          // relaxed agent store, sc1
+    __hip_atomic_store((aslam_gu64*)w, ((unsigned long long)epoch << 32) | (unsigned)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int win_count(const unsigned long long* w, unsigned epoch) {              // relaxed agent load, sc1
+    const unsigned long long v = __hip_atomic_load((const aslam_gu64*)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (unsigned)(v >> 32) == epoch ? (int)(unsigned)v : 0;                                  // an older window's count reads as 0
+}
 
 // value of lane `src` (wave-uniform) in every lane, through two v_readlane - no LDS traffic, unlike __shfl's ds_bpermute
 #ifndef ASLAM_WAVE_BCAST

@@ -47,6 +47,23 @@
 namespace aslam {
 
 constexpr int WBW = 8;                        // columns of Lambda per scan workgroup
+// one-launch window: the chain publishes its step count every kWinPubEvery steps, for the steps kWinPubLag or more behind
+constexpr int kWinPubEvery = 4, kWinPubLag = 4;
+#if defined(__HIP__)
+constexpr unsigned long long kWinSpinTicks = 2000000;   // a wait gives up after 20 ms without progress (wall clock: 100 MHz)
+#else
+constexpr unsigned long long kWinSpinTicks = 6000000000ull;   // (the CPU emulation of the tests runs a step in about a millisecond)
+#endif
+// a wait that gave up: the FIRST code stays (a replay that stalls makes its Psi workgroups give up after it)
+__device__ __forceinline__ void win_fail(const EkfState& E, unsigned code) { atomicCAS(E.d_win_err, 0u, code); }
+// at the end of a publication step: this wave's stores of every step but the last kWinPubLag complete.  A worker wave issues RW
+// log stores per step, worker wave 0 one more (the header) and its count stores: all but the newest RW kWinPubLag (wave 0:
+// (RW + 1) kWinPubLag) store instructions are older than those steps' stores
+template <int RW> __device__ __forceinline__ void win_vmcnt_lag(bool wave0) {
+    static_assert(RW == 2 && kWinPubLag == 4, "the counts below are (RW + 1) kWinPubLag and RW kWinPubLag");
+    if (wave0) ASLAM_VMCNT(12);
+    else ASLAM_VMCNT(8);
+}
 
 // development aid (make FLAGS+=-DASLAM_WIN_STAMPS): cycle stamps of the prepare wave's step phases and of the workers, summed over a piece
 #ifdef ASLAM_WIN_STAMPS
@@ -124,8 +141,8 @@ __device__ __forceinline__ void win_publish(const v4d (&acc)[RW][T], int p, int 
 // T tiles per side, RW tile rows per worker wave: ceil(T / RW) worker waves + 1 prepare wave.  With T = 4 (2 x 2 rows on two
 // workers) the prepare wave - the kernel's critical path - has a SIMD to itself (measured: -11 % per step); at T = 8 the same idea
 // (3 + 3 + 2 rows on three workers) makes the workers the bottleneck (measured: +12 %), so it keeps one worker per SIMD.
-template <int T> struct WinChainLds {
-    static constexpr int SP = 16 * T, SPP = SP + 16, NSMAX = kWinPieceMax * 64;
+template <int T, bool ONE> struct WinChainLds {
+    static constexpr int SP = 16 * T, SPP = SP + 16, KMAX = ONE ? kWinFrames : kWinPieceMax, NSMAX = KMAX * 64;
     double sA[2][4][SPP];                  // a step's A operand rows  Aop[k][row]   (P += Aop^T Bop)
     double sB[2][4][SPP];                  // ... and B operand rows   Bop[k][column]
     double sPub[2][3][SPP];                // the landmark rows of the step after next
@@ -135,15 +152,15 @@ template <int T> struct WinChainLds {
 #endif
     double sMu[SPP];                       // prepare wave's scratch: mu_S by position
     int sS[SP];
-    int sOff[kWinPieceMax + 1];
+    int sOff[KMAX + 1];
     unsigned char sPos[NSMAX], sIdx[NSMAX], sFrm[NSMAX];   // per step: landmark position (255 = predict), correction index, frame
 };
-template <int T, int RW>
+template <int T, int RW, bool ONE>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + 1) * 64;
-    WinChainLds<T>& L = *reinterpret_cast<WinChainLds<T>*>(smem);
+    WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
     auto& sA = L.sA; auto& sB = L.sB; auto& sPub = L.sPub; auto& sMu = L.sMu; auto& sS = L.sS; auto& sOff = L.sOff;
     auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sFrm = L.sFrm;
     if (threadIdx.x >= NT) return;                                  // (the launch's block is sized for its widest role)
@@ -158,25 +175,55 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     for (int e = tid; e < 2 * 4 * SPP; e += NT) { (&sA[0][0][0])[e] = 0.0; (&sB[0][0][0])[e] = 0.0; }
     for (int e = tid; e < 2 * 3 * SPP; e += NT) (&sPub[0][0][0])[e] = 0.0;
     for (int e = tid; e < 2 * kWinHdr; e += NT) (&L.sHdr[0][0])[e] = 0.0;
-    // steps per frame (1 predict + m corrections), every frame's count loaded by its own thread (one thread walking the plan would
-    // pay one dependent global load per frame), then the running sum
-    if (tid < wd.K) sOff[tid + 1] = 1 + frames[wd.first_slot + tid].m;
-    if (tid == 0) sOff[0] = 0;
-    __syncthreads();
-    if (tid == 0)
-        for (int k = 0; k < wd.K; k++) sOff[k + 1] += sOff[k];
-    __syncthreads();
-    const int NS = sOff[wd.K];                                    // steps of the piece: per frame one predict + m corrections
-    for (int k = 0; k < wd.K; k++) {
-        const WinFrame& fr = frames[wd.first_slot + k];
-        for (int a = tid; a <= fr.m; a += NT) {
-            const int st = sOff[k] + a;
-            sPos[st] = a == 0 ? 255 : fr.cpos[a - 1];
-            sIdx[st] = a == 0 ? 0 : (unsigned char)(a - 1);
-            sFrm[st] = (unsigned char)k;
+    if constexpr (ONE) {
+        // the step tables of the whole window (K <= 64 frames): thread k loads frame k's count and its 64 landmark positions at
+        // once, wave 0 forms the running sum with a lane scan, thread k writes its frame's steps
+        int cnt = 0;
+        unsigned cp[16];
+        if (tid < wd.K) {
+            const WinFrame& fr = frames[wd.first_slot + tid];
+            cnt = 1 + fr.m;
+            const unsigned* c4 = reinterpret_cast<const unsigned*>(fr.cpos);
+#pragma unroll
+            for (int q = 0; q < 16; q++) cp[q] = c4[q];
         }
+        if (wave == 0) {
+            int inc = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(inc, d); if (lane >= d) inc += y; }
+            sOff[lane + 1] = inc;
+            if (lane == 0) sOff[0] = 0;
+        }
+        __syncthreads();
+        if (tid < wd.K) {
+            const int o = sOff[tid], m = cnt - 1;
+            sPos[o] = 255; sIdx[o] = 0; sFrm[o] = (unsigned char)tid;
+#pragma unroll
+            for (int a = 0; a < 63; a++)
+                if (a < m) { sPos[o + 1 + a] = (unsigned char)(cp[a >> 2] >> (8 * (a & 3))); sIdx[o + 1 + a] = (unsigned char)a; sFrm[o + 1 + a] = (unsigned char)tid; }
+        }
+        __syncthreads();
+    } else {
+        // steps per frame (1 predict + m corrections), every frame's count loaded by its own thread (one thread walking the plan would
+        // pay one dependent global load per frame), then the running sum
+        if (tid < wd.K) sOff[tid + 1] = 1 + frames[wd.first_slot + tid].m;
+        if (tid == 0) sOff[0] = 0;
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < wd.K; k++) sOff[k + 1] += sOff[k];
+        __syncthreads();
+        for (int k = 0; k < wd.K; k++) {
+            const WinFrame& fr = frames[wd.first_slot + k];
+            for (int a = tid; a <= fr.m; a += NT) {
+                const int st = sOff[k] + a;
+                sPos[st] = a == 0 ? 255 : fr.cpos[a - 1];
+                sIdx[st] = a == 0 ? 0 : (unsigned char)(a - 1);
+                sFrm[st] = (unsigned char)k;
+            }
+        }
+        __syncthreads();
     }
-    __syncthreads();
+    const int NS = sOff[wd.K];                                    // steps of the piece: per frame one predict + m corrections
 
     const double* Pimg = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
     const bool from_img = wd.piece != 0 || wd.from_image != 0;
@@ -212,6 +259,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #endif
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
+            // one-launch window: steps 0 .. j - 1 - kWinPubLag are complete in every worker wave (each waited for them at the end of
+            // step j - 1, before the barrier just passed): one lane publishes their count for the replay workgroups
+            if (ONE && j > kWinPubLag && j % kWinPubEvery == 0 && tid == 0) win_signal(E.d_win_sync, wd.epoch, j - kWinPubLag);
             if (j >= 0) {
                 const int cb = j & 1;
                 double* const log = logbase + (size_t)j * win_log_stride(T);
@@ -224,9 +274,18 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     const double a = sA[cb][lk][16 * (wave * RW + rr) + li];
 #pragma unroll
                     for (int t = 0; t < T; t++) acc[rr][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[t], acc[rr][t], 0, 0, 0);
-                    if (lk < 3) log[lk * SP + 16 * (wave * RW + rr) + li] = a;     // the step's log rows: -Kt (predict: its rows 0..2)
+                    if (lk < 3) {                                                  // the step's log rows: -Kt (predict: its rows 0..2)
+                        if (ONE) st_wt(log + lk * SP + 16 * (wave * RW + rr) + li, a);
+                        else log[lk * SP + 16 * (wave * RW + rr) + li] = a;
+                    }
                 }
-                if (wave == 0 && lane < kWinHdr) log[3 * SP + lane] = L.sHdr[cb][lane];
+                if (wave == 0 && lane < kWinHdr) {
+                    if (ONE) st_wt(log + 3 * SP + lane, L.sHdr[cb][lane]);
+                    else log[3 * SP + lane] = L.sHdr[cb][lane];
+                }
+                // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete.
+                // The wave issues RW log stores per step (wave 0 one more, and its count stores) and no load: a static count
+                if (ONE && (j + 1) % kWinPubEvery == 0) win_vmcnt_lag<RW>(wave == 0);
                 if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
 #ifdef ASLAM_WIN_POSE_CHECK
                     if (wave == 0 && lk < 3) {
@@ -241,8 +300,13 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
             WSTAMP(1);
             ASLAM_LDS_BARRIER();
         }
+        if (ONE) {                                                  // the whole log: after every worker wave's last stores
+            ASLAM_VMCNT(0);
+            ASLAM_LDS_BARRIER();
+            if (tid == 0) win_signal(E.d_win_sync, wd.epoch, NS);
+        }
 #ifdef ASLAM_WIN_STAMPS
-        if (lane == 0 && wd.piece == 1) printf("worker %d T %d steps %d: barrier-wait %lld work %lld cycles per step\n", wave, T, NS, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1));
+        if (lane == 0 && (ONE || wd.piece == 1)) printf("worker %d T %d steps %d: barrier-wait %lld work %lld cycles per step\n", wave, T, NS, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1));
 #endif
         // P_K for the next piece / the flush
         double* Pout = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
@@ -505,8 +569,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         }
         ASLAM_LDS_BARRIER();
     }
+    if (ONE) ASLAM_LDS_BARRIER();                                  // (pairs with the workers' barrier before the last publication)
 #ifdef ASLAM_WIN_STAMPS
-    if (lane == 0 && wd.piece == 1) {
+    if (lane == 0 && (ONE || wd.piece == 1)) {
         const int nc = NS - n_pred;
         printf("prepare T %d steps %d (%d predict): barrier %lld | rows wait %lld correct %lld | predict path %lld per predict | c %lld S+inv %lld Kt+hdr %lld per correction | operands+log %lld per step\n",
                T, NS, n_pred, stamp_acc[0] / (NS + 1), stamp_acc[7] / NS, stamp_acc[1] / NS, stamp_acc[2] / (n_pred ? n_pred : 1), stamp_acc[3] / (nc ? nc : 1), stamp_acc[4] / (nc ? nc : 1),
@@ -517,11 +582,11 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     // the last comparison is of the rows as they stand after step NS - 2: the step before the piece's last
     if (lane == 0) printf("pose-check T %d piece %d steps %d: max |prepare - accumulator| pose rows %.3e over the piece, %.3e at its end\n", T, wd.piece, NS, dmax, dend);
 #endif
-    // ---- mu_S for the next piece; back into the state at the window's end ----
+    // ---- mu_S for the next piece; back into the state at the window's end (one-launch window: by k_ekf_win_fix) ----
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         const int col = lane + 64 * c;
-        if (col < s) { muimg[col] = mu[c]; if (wd.last) E.d_mu[sS[col]] = mu[c]; }
+        if (col < s) { muimg[col] = mu[c]; if (wd.mu_out) E.d_mu[sS[col]] = mu[c]; }
     }
 }
 
@@ -537,8 +602,8 @@ template <int T> struct WinScanLds {
     double sRec[2][REC];
     double sT[2][4][WBW];                  // t (row 3 stays zero)
 };
-template <int T>
-__device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, unsigned char* smem) {
+template <int T, bool ONE>
+__device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, unsigned epoch, int* sAvail, unsigned char* smem) {
     constexpr int SP = 16 * T, EPT = SP * WBW / 256, REC = 3 * SP + kWinHdr;
     constexpr int RPT = (REC + 191) / 192;                         // record doubles per loading thread
     WinScanLds<T>& L = *reinterpret_cast<WinScanLds<T>*>(smem);
@@ -562,23 +627,43 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
     // PFD records in flight (registers), one per step of the unrolled loop
     constexpr int PFD = 3;
     double pf[PFD][RPT];
-#pragma unroll
-    for (int u = 0; u < PFD; u++)
-#pragma unroll
-        for (int q = 0; q < RPT; q++) { const int e = lt + 192 * q; pf[u][q] = (lt >= 0 && e < REC && u < nsteps) ? logp[(size_t)u * ls + e] : 0.0; }
     for (int e = tid; e < 2 * 4 * WBW; e += 256) (&sT[0][0][0])[e] = 0.0;
-    __syncthreads();
-    for (int n0 = 0; n0 < nsteps; n0 += PFD) {
+    // one-launch window: the steps arrive in batches, as the chain publishes them (the piece schedule: one batch, the whole log)
+    for (int done = 0; done < nsteps;) {
+      int avail = nsteps;
+      if constexpr (ONE) {
+        if (tid == 0) {                                             // ONE lane polls, relaxed; ONE acquire per batch
+            int got = win_count(E.d_win_sync, epoch);
+            const unsigned long long t0 = wall_clock64();
+            while (got <= done) {
+                __builtin_amdgcn_s_sleep(2);
+                got = win_count(E.d_win_sync, epoch);
+                if (got <= done && wall_clock64() - t0 > kWinSpinTicks) { win_fail(E, 1u); got = -1; break; }
+            }
+            *sAvail = got;
+            ASLAM_ACQUIRE_AGENT();
+            ASLAM_VMCNT(0);                                         // (holds the barrier until the invalidate is done)
+        }
+        __syncthreads();
+        avail = *sAvail;
+        if (avail < 0) return;
+      }
+#pragma unroll
+      for (int u = 0; u < PFD; u++)
+#pragma unroll
+        for (int q = 0; q < RPT; q++) { const int e = lt + 192 * q; pf[u][q] = (lt >= 0 && e < REC && done + u < avail) ? logp[(size_t)(done + u) * ls + e] : 0.0; }
+      __syncthreads();
+      for (int n0 = done; n0 < avail; n0 += PFD) {
 #pragma unroll
       for (int u = 0; u < PFD; u++) {
         const int n = n0 + u;
-        if (n >= nsteps) break;
+        if (n >= avail) break;
         double* rec = sRec[n & 1];
         double (*tt)[WBW] = sT[n & 1];
         if (lt >= 0) {
 #pragma unroll
             for (int q = 0; q < RPT; q++) { const int e = lt + 192 * q; if (e < REC) rec[e] = pf[u][q]; }
-            if (n + PFD < nsteps) {                                 // in flight while the next PFD steps are applied
+            if (n + PFD < avail) {                                  // in flight while the next PFD steps are applied
                 const double* nx = logp + (size_t)(n + PFD) * ls;
 #pragma unroll
                 for (int q = 0; q < RPT; q++) { const int e = lt + 192 * q; pf[u][q] = e < REC ? nx[e] : 0.0; }
@@ -620,7 +705,8 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
                     ps += t0 * w0 + t1 * w1 + t2 * w2;
                 }
             }
-            tlog[(size_t)n * ts + row * SP + c] = v;
+            if (ONE) st_wt(tlog + (size_t)n * ts + row * SP + c, v);
+            else tlog[(size_t)n * ts + row * SP + c] = v;
         }
         if (!is_predict) {
             // Lambda[r][c] += sum_k Aop[k][r] t[k][c]      (c is the same for all of a thread's entries)
@@ -633,6 +719,12 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
             }
         }
       }
+      }
+      if (ONE && tid < 64) {                                        // wave 0, the only one that stores t / u: its stores, then the count
+          ASLAM_VMCNT(0);
+          if (tid == 0) win_signal(E.d_win_sync + kWinSyncLine * (1 + b), epoch, avail);
+      }
+      done = avail;
     }
     __syncthreads();
     for (int e = tid; e < SP * WBW; e += 256) { const int r = e / WBW, c = e % WBW; Lam[(size_t)r * SP + WBW * b + c] = sLam[r][c]; }
@@ -642,9 +734,9 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
 
 // Psi (+)= sum over the piece's steps of t^T u on the f64 matrix cores: workgroup = tile row, wave w = tile columns w, w + 4, ...
 // The operands come straight from the t / u log (L2): four steps are fetched ahead of the four products.
-template <int T>
-__device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr) {
-    constexpr int SP = 16 * T, TW = (T + 3) / 4, UN = 4;
+template <int T, bool ONE>
+__device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr, unsigned epoch, int* sAvail) {
+    constexpr int SP = 16 * T, TW = (T + 3) / 4, UN = 4, NSCAN = SP / WBW;
     if (threadIdx.x >= 256) return;
     const int nsteps = wd.nsteps;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -661,11 +753,34 @@ __device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr) {
             acc[q][reg] = (wd.piece && tc < T) ? Psi[(size_t)(16 * tr + lk + 4 * reg) * SP + 16 * tc + li] : 0.0;
     }
     // A[i][k] = t[k][16 tr + i] (lane k * 16 + i), B[k][j] = u[k][16 tc + j]
-    for (int n0 = 0; n0 < nsteps; n0 += UN) {
+    for (int done = 0; done < nsteps;) {
+      int avail = nsteps;
+      if constexpr (ONE) {
+        // one-launch window: wave 0 polls the replay workgroups' counts (lane b: workgroup b), relaxed; ONE acquire per batch
+        if (wave == 0) {
+            const unsigned long long t0 = wall_clock64();
+            int got;
+            for (;;) {
+                got = lane < NSCAN ? win_count(E.d_win_sync + kWinSyncLine * (1 + lane), epoch) : nsteps;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) got = min(got, __shfl_xor(got, d));
+                if (got > done) break;
+                const int late = __shfl(wall_clock64() - t0 > kWinSpinTicks ? 1 : 0, 0);      // (lane 0 decides for the wave)
+                if (late) { if (lane == 0) win_fail(E, 2u); got = -1; break; }
+                __builtin_amdgcn_s_sleep(2);
+            }
+            if (lane == 0) { *sAvail = got; ASLAM_ACQUIRE_AGENT(); ASLAM_VMCNT(0); }
+        }
+        __syncthreads();
+        avail = *sAvail;
+        __syncthreads();                                            // (every wave has read it before wave 0 polls again)
+        if (avail < 0) return;
+      }
+    for (int n0 = done; n0 < avail; n0 += UN) {
         double a[UN], bv[UN][TW];
 #pragma unroll
         for (int u = 0; u < UN; u++) {
-            const bool ok = n0 + u < nsteps;
+            const bool ok = n0 + u < avail;
             const double* st = tlog + (size_t)(ok ? n0 + u : n0) * ts;
             a[u] = ok ? st[lk * SP + 16 * tr + li] : 0.0;
 #pragma unroll
@@ -675,6 +790,8 @@ __device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr) {
         for (int u = 0; u < UN; u++)
 #pragma unroll
             for (int q = 0; q < TW; q++) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], bv[u][q], acc[q], 0, 0, 0);
+    }
+      done = avail;
     }
 #pragma unroll
     for (int q = 0; q < TW; q++) {
@@ -691,16 +808,46 @@ __device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr) {
 // product of piece i - 2 (the last T workgroups).  The three depend on each other only through the PREVIOUS launch (the log of
 // piece i - 1 is complete when this launch starts: same stream), so no events are needed between the pieces of a window and the
 // replay is hidden behind the chain: with one event per piece the EKF alone ran 14 % slower (cfg2).
-template <int T, int RW>
+//
+// ONE = true: one launch = a whole window (wd.K frames, wd.nsteps steps), the same three roles running side by side.  The chain
+// publishes its step count every kWinPubEvery steps; each replay workgroup replays the published steps in batches and publishes
+// its own count; each Psi workgroup takes the steps every replay workgroup has published.  Publication: the log and the t / u log
+// are stored write-through (sc1); each storing wave waits for its stores of the published steps (a counted vmcnt: the chain's
+// workers issue no global load in the step loop, so the count is static and covers only the newest steps, which are not waited
+// for), the chain's waves then pass the step's barrier, and one lane stores {epoch, count} with a relaxed agent-scope store.  A
+// consumer polls with one lane (relaxed sc1 loads, s_sleep between polls), then makes ONE agent acquire, waits for it and passes
+// a barrier before its waves load the batch.  The counters carry the window's epoch (an older window's count reads as 0), so
+// nothing is reset between windows.  Forward progress: roles go by a ticket each workgroup takes when it starts (a CAS on an
+// epoch-tagged word: first = chain, then the replay workgroups, then Psi), not by blockIdx, and every wait is on a role with a
+// smaller ticket, i.e. on a workgroup that is already running.  Neither dispatch order nor co-residency of the whole grid is
+// assumed (at T = 12 the 37 workgroups need not all be resident).  Every spin gives up after kWinSpinTicks without progress:
+// the workgroup writes a code into E.d_win_err (the first code stays; read back with the call's counters) and leaves.
+__device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch) {
+    unsigned long long old = __hip_atomic_load((aslam_gu64*)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const bool cur = (unsigned)(old >> 32) == epoch;
+        const unsigned long long nw = cur ? old + 1 : ((unsigned long long)epoch << 32) | 1u;
+        const unsigned long long prev = atomicCAS(w, old, nw);
+        if (prev == old) return cur ? (int)(unsigned)old : 0;
+        old = prev;
+    }
+}
+template <int T, int RW, bool ONE>
 __global__ __launch_bounds__(((T + RW - 1) / RW + 1) * 64 > 256 ? ((T + RW - 1) / RW + 1) * 64 : 256)
 void k_ekf_win_step(EkfState E, SlamParams sp, WinDesc wd, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
-    constexpr size_t kLds = sizeof(WinChainLds<T>) > sizeof(WinScanLds<T>) ? sizeof(WinChainLds<T>) : sizeof(WinScanLds<T>);
+    constexpr size_t kLds = sizeof(WinChainLds<T, ONE>) > sizeof(WinScanLds<T>) ? sizeof(WinChainLds<T, ONE>) : sizeof(WinScanLds<T>);
     __shared__ __align__(16) unsigned char smem[kLds];
+    __shared__ int sTicket, sAvail;
     constexpr int NSCAN = 16 * T / WBW;
-    const int bx = blockIdx.x;
-    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW>(E, sp, wd, obs, enc, smem); }
-    else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T>(E, rs, bx - 1, smem); }
-    else if (rq.nsteps > 0) win_psi_role<T>(E, rq, bx - 1 - NSCAN);
+    int bx = blockIdx.x;
+    if constexpr (ONE) {
+        if (threadIdx.x == 0) sTicket = win_ticket(E.d_win_sync + (size_t)kWinSyncLine * (kWinSyncCounters - 1), wd.epoch);
+        __syncthreads();
+        bx = sTicket;
+    }
+    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE>(E, sp, wd, obs, enc, smem); }
+    else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
+    else if (rq.nsteps > 0) win_psi_role<T, ONE>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -756,7 +903,8 @@ __global__ __launch_bounds__(256) void k_ekf_win_thin(EkfState E, WinDesc wd) {
     if (blockIdx.y == 0 && tid < 64 && c0 + tid < N && E.d_win_sidx[c0 + tid] < 0) E.d_mu[c0 + tid] += macc;      // mu_R += Y_0^T psi
 }
 
-// Rows and columns S of Sigma after the Z pass: row S_p <- Y_K[p][:], column S_p <- the same (symmetry), (S_p, S_q) <- P_K[p][q].
+// Rows and columns S of Sigma after the Z pass: row S_p <- Y_K[p][:], column S_p <- the same (symmetry), (S_p, S_q) <- P_K[p][q];
+// mu_S back into the state (behind the previous window's flush: same stream).
 __global__ __launch_bounds__(256) void k_ekf_win_fix(EkfState E, WinDesc wd, int SP) {
     const int ld = E.ld;
     const int N = 3 + 3 * (*E.d_L);
@@ -765,6 +913,7 @@ __global__ __launch_bounds__(256) void k_ekf_win_fix(EkfState E, WinDesc wd, int
     if (t >= N) return;
     const int tp = E.d_win_sidx[t];
     const double* Pimg = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
+    if (blockIdx.y == 0 && t < s) E.d_mu[win_state_index(wd, t)] = E.d_win_small[wsm_MU(E.win_sp_max, wd.wpar) + t];   // mu_S as the chain left it
     for (int p = blockIdx.y; p < s; p += gridDim.y) {
         const int Sp = win_state_index(wd, p);
         const double v = tp >= 0 ? Pimg[(size_t)p * SP + tp] : E.d_V[(size_t)p * ld + t];
@@ -810,7 +959,7 @@ __global__ __launch_bounds__(256) void k_ekf_win_next_gather(EkfState E, WinDesc
     if (blockIdx.y == 0) {
         E.d_win_next_idx[a] = pa;
         if (a == 0) E.d_win_next_idx[SPm] = nx.nS;
-        mu2[a] = E.d_mu[ia];
+        mu2[a] = pa >= 0 ? E.d_win_small[wsm_MU(SPm, pv.wpar) + pa] : E.d_mu[ia];     // in S: as the chain left it (its image)
     }
     for (int p = blockIdx.y; p < SPp; p += gridDim.y) Vg[(size_t)p * SPm + a] = pa < 0 ? E.d_Wt[(size_t)p * ld + ia] : 0.0;
     for (int b = blockIdx.y; b < s2; b += gridDim.y) Ptmp[(size_t)b * SPm + a] = E.d_sigma[(size_t)win_state_index(nx, b) * ld + ia];
@@ -839,7 +988,7 @@ __global__ __launch_bounds__(256) void k_ekf_win_next_fix(EkfState E, WinDesc pv
 // Every workgroup of a step launch asks for more than half of a CU's LDS (an unused dynamic allocation on top of the static one), so
 // that no second workgroup - a replay workgroup of the same launch, or anything else - is placed on the chain workgroup's CU and
 // competes with the prepare wave for issue slots and LDS bandwidth (ASLAM_WIN_SHARE_CU: off, for comparison).
-template <int T, class K> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
+template <int T, bool ONE, class K> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const WinDesc& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
     const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, (size_t)20 * 1024);      // static + dynamic > 80 KB of the 160 KB
@@ -854,9 +1003,16 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps) {
     const WinReplay rs{s_piece, s_log0, s_nsteps, wd.wpar}, rq{q_piece, q_log0, q_nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
-    if (wd.T == 4) launch_step_kernel<4>(k_ekf_win_step<4, 2>, st, nb, 256, sizeof(WinChainLds<4>), E, sp, wd, rs, rq, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8>(k_ekf_win_step<8, 2>, st, nb, 320, sizeof(WinChainLds<8>), E, sp, wd, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
-    else launch_step_kernel<12>(k_ekf_win_step<12, 2>, st, nb, 448, sizeof(WinChainLds<12>), E, sp, wd, rs, rq, obs, enc);
+    if (wd.T == 4) launch_step_kernel<4, false>(k_ekf_win_step<4, 2, false>, st, nb, 256, sizeof(WinChainLds<4, false>), E, sp, wd, rs, rq, obs, enc);
+    else if (wd.T == 8) launch_step_kernel<8, false>(k_ekf_win_step<8, 2, false>, st, nb, 320, sizeof(WinChainLds<8, false>), E, sp, wd, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
+    else launch_step_kernel<12, false>(k_ekf_win_step<12, 2, false>, st, nb, 448, sizeof(WinChainLds<12, false>), E, sp, wd, rs, rq, obs, enc);
+}
+void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc) {
+    const WinReplay r{0, 0, wd.nsteps, wd.wpar};
+    const int nb = 1 + 16 * wd.T / WBW + wd.T;
+    if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wd, r, r, obs, enc);
+    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 320, sizeof(WinChainLds<8, true>), E, sp, wd, r, r, obs, enc);
+    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 448, sizeof(WinChainLds<12, true>), E, sp, wd, r, r, obs, enc);
 }
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd) {
     hipLaunchKernelGGL(k_ekf_win_gather, dim3((E.ld + 255) / 256, 16), dim3(256), 0, st, E, wd);       // y: rows of Y_0 in turn (one load in flight per thread otherwise)
