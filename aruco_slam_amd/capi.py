@@ -179,6 +179,8 @@ _SIGS = {
     "aslam_debug_inject_observations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp, _dp]),
     "aslam_debug_inject_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _fp]),
     "aslam_debug_run_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
+    "aslam_debug_run_identify": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "aslam_debug_get_identified": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _u8p, _llp]),
     "aslam_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_profile_reset": (C.c_int, [C.c_void_p]),
     "aslam_get_plan_stats": (C.c_int, [C.c_void_p, _llp]),
@@ -665,6 +667,23 @@ class Context:
         if rs is not None and rs.size != count:
             raise ValueError("one robot per slot")
         self._ck(self.lib.aslam_debug_run_pose(self.h, int(first), int(count), _ptr(rs, _ip)))
+
+    def run_identify(self, first, count):
+        """the identification stage alone on the slots' injected candidates, over the grey frames their last detection read"""
+        self._ck(self.lib.aslam_debug_run_identify(self.h, int(first), int(count)))
+
+    def get_identified(self, slot):
+        """what run_identify decided per candidate: ids (-1 rejected), rotations, cells (n x nc x nc, border included) and info
+        (n x 8: branch 0 Otsu / 1 all zero / 2 all one, Otsu T, border errors, inner sum, inner sum of squares, recorded id,
+        recorded rotation, nc)"""
+        n = C.c_int()
+        ids = np.zeros(CAND_MAX, np.int32); rots = np.zeros(CAND_MAX, np.int32)
+        cells = np.zeros((CAND_MAX, 81), np.uint8); info = np.zeros((CAND_MAX, 8), np.int64)
+        self._ck(self.lib.aslam_debug_get_identified(self.h, int(slot), CAND_MAX, C.byref(n), _ptr(ids, _ip), _ptr(rots, _ip),
+                                                     _ptr(cells, _u8p), _ptr(info, _llp)))
+        k = n.value
+        nc = int(info[0, 7]) if k else 0
+        return ids[:k].copy(), rots[:k].copy(), cells[:k, :nc * nc].reshape(k, nc, nc).copy(), info[:k].copy()
 
     def sync(self):
         self._ck(self.lib.aslam_sync(self.h))

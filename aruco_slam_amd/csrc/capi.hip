@@ -112,6 +112,7 @@ struct aslam_ctx {
     FinalCand* d_finals = nullptr;
     unsigned* d_nfinal = nullptr;
     IdentWork* d_work = nullptr;
+    IdentRecord* d_ident_rec = nullptr;    // k_identify_record's output, kCandMax per slot (allocated by the first aslam_debug_run_identify)
     unsigned long long* d_dict = nullptr;
     Marker* d_markers = nullptr;
     unsigned* d_nmarkers = nullptr;
@@ -453,6 +454,19 @@ void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int 
     prof_end(c);
 }
 
+// the grey frame of slot f0 a detection pass reads: a gray slot in place, a bgr8 slot as k_threshold converted it
+const uint8_t* slot_gray(const aslam_ctx* c, int f0) {
+    return c->channels == 1 ? c->d_in + (size_t)f0 * c->in_frame_bytes : c->d_gray + (size_t)f0 * c->rows * c->cols;
+}
+
+// k_identify over the work list of the frames from f0 on (rec: k_identify_record instead, writing the records of those frames)
+void launch_identify_stage(aslam_ctx* c, hipStream_t st, const DetectCfg& g, int f0, IdentRecord* rec = nullptr) {
+    prof_begin(c, P_IDENTIFY, st);
+    launch_identify(st, c->nwaves, g, c->d_ctr, slot_gray(c, f0), c->d_finals + (size_t)f0 * kCandMax, c->d_work, c->d_dict,
+                    rec ? rec + (size_t)f0 * kCandMax : nullptr);
+    prof_end(c);
+}
+
 // detection + pose of the call's frames (asynchronous on the stream).  latency: the configuration of a one-frame call (one rig step)
 int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = false, hipEvent_t wait_before = nullptr) {
     const int first = k.first, count = k.count;
@@ -487,7 +501,7 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
         launch_clear_counts(st, nf, c->d_ctr, c->d_nstarts + f0, c->d_ncontours + f0, c->d_npoints + f0, c->d_nwrite + f0, c->d_ncand + f0);
         const uint8_t* in = c->d_in + (size_t)f0 * c->in_frame_bytes;
         uint8_t* nbr = c->d_nbr + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch);
-        const uint8_t* gray = alias_gray ? in : c->d_gray + (size_t)f0 * frame_px;
+        const uint8_t* gray = slot_gray(c, f0);
         unsigned* starts = c->d_starts + (size_t)f0 * g.cap_starts;
         ContourRec* contours = c->d_contours + (size_t)f0 * g.cap_contours;
         unsigned* points = c->d_points + (size_t)f0 * g.cap_points;
@@ -520,9 +534,7 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
         launch_assemble(st, nf, g, c->d_ctr, c->d_cands + (size_t)f0 * kCandMax, c->d_ncand + f0,
                         c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_work);
         prof_end(c);
-        prof_begin(c, P_IDENTIFY, st);
-        launch_identify(st, c->nwaves, g, c->d_ctr, gray, c->d_finals + (size_t)f0 * kCandMax, c->d_work, c->d_dict);
-        prof_end(c);
+        launch_identify_stage(c, st, g, f0);
         const RefineCfg rf{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
                            g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
                            c->d_refine_mask, gray};
@@ -800,7 +812,7 @@ void aslam_destroy(aslam_ctx* c) {
     hipFree(c->d_nstarts); hipFree(c->d_ncontours); hipFree(c->d_npoints); hipFree(c->d_pre_trace); hipFree(c->d_pre_quads);
     hipFree(c->d_contours); hipFree(c->d_points); hipFree(c->d_cands); hipFree(c->d_ncand); hipFree(c->d_finals);
     hipFree(c->d_nfinal); hipFree(c->d_work); hipFree(c->d_dict); hipFree(c->d_markers); hipFree(c->d_nmarkers);
-    hipFree(c->d_obs); hipFree(c->d_enc); hipFree(c->d_synth);
+    hipFree(c->d_obs); hipFree(c->d_enc); hipFree(c->d_synth); hipFree(c->d_ident_rec);
     ekf_free(c->ekf);
     ekf_fleet_free(c->fslam);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
@@ -2787,6 +2799,78 @@ int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of
     for (int f0 = first; f0 < first + count; f0 += chunk) launch_pose_stage(c, k, st, f0, std::min(chunk, first + count - f0), rf);
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
     HIP_TRY(c, hipGetLastError());
+    return ASLAM_OK;
+}
+
+int aslam_debug_run_identify(aslam_ctx* c, int first, int count) {
+    if (!c) return ASLAM_E_INVALID;
+    int r = check_slot_range(c, first, count);
+    if (r) return r;
+    if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
+    for (int i = first; i < first + count; i++)
+        if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+            return fail(c, ASLAM_E_STATE, "slot has no frame of the current shape (stage one and run a detection pass on it first)");
+    r = sync_streams(c);
+    if (r) return r;
+    if (!c->d_ident_rec) HIP_TRY(c, dalloc(&c->d_ident_rec, (size_t)kCandMax * c->max_batch));
+    std::vector<unsigned> nf(count);
+    HIP_TRY(c, hipMemcpy(nf.data(), c->d_nfinal + first, count * sizeof(unsigned), hipMemcpyDeviceToHost));
+    hipStream_t st = c->stream;
+    if (c->last_detect && c->last_detect != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    c->last_detect = st;
+    c->last_first = first;
+    c->last_count = count;
+    // what run_detect launches at P_IDENTIFY, chunk by chunk: the work list k_assemble would have written (every candidate of
+    // every frame, frame by frame, in candidate order) and its counters
+    const int chunk = detect_chunk();
+    std::vector<IdentWork> work;
+    for (int f0 = first; f0 < first + count; f0 += chunk) {
+        const int n = std::min(chunk, first + count - f0);
+        work.clear();
+        for (int f = 0; f < n; f++)
+            for (unsigned i = 0; i < std::min(nf[f0 - first + f], (unsigned)kCandMax); i++) work.push_back(IdentWork{(unsigned)f, i});
+        const unsigned heads[2] = {(unsigned)work.size(), 0u};     // n_ident, q_ident
+        if (!work.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_work, work.data(), work.size() * sizeof(IdentWork), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(&c->d_ctr->n_ident, heads, sizeof(heads), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipStreamSynchronize(st));                      // (the host vectors are reused)
+        launch_identify_stage(c, st, c->cfg, f0, c->d_ident_rec);
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_detect, st));
+    HIP_TRY(c, hipGetLastError());
+    return ASLAM_OK;
+}
+
+int aslam_debug_get_identified(aslam_ctx* c, int slot, int max, int* n_out, int* ids, int* rots, uint8_t* cells, long long* info) {
+    if (!c || !n_out || max < 0) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slot_range(c, slot, 1);
+    if (r) return r;
+    if (!c->d_ident_rec) return fail(c, ASLAM_E_STATE, "no identification records (aslam_debug_run_identify)");
+    r = sync_streams(c);
+    if (r) return r;
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, c->d_nfinal + slot, sizeof(unsigned), hipMemcpyDeviceToHost));
+    n = std::min(n, (unsigned)kCandMax);
+    *n_out = (int)n;
+    const unsigned m = std::min(n, (unsigned)max);
+    std::vector<FinalCand> h(m);
+    std::vector<IdentRecord> rec(m);
+    if (m) {
+        HIP_TRY(c, hipMemcpy(h.data(), c->d_finals + (size_t)slot * kCandMax, m * sizeof(FinalCand), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(rec.data(), c->d_ident_rec + (size_t)slot * kCandMax, m * sizeof(IdentRecord), hipMemcpyDeviceToHost));
+    }
+    const int nc = c->cfg.marker_size + 2 * c->cfg.border_bits, ncell = nc * nc;
+    for (unsigned i = 0; i < m; i++) {
+        if (ids) ids[i] = h[i].id;
+        if (rots) rots[i] = h[i].pad[0];
+        if (cells)
+            for (int k = 0; k < kDictMaxCells * kDictMaxCells; k++)
+                cells[(size_t)i * kDictMaxCells * kDictMaxCells + k] = k < ncell ? (uint8_t)((rec[i].bits[k / 64] >> (k % 64)) & 1ull) : 0;
+        if (info) {
+            long long* o = info + (size_t)i * 8;
+            o[0] = rec[i].branch; o[1] = rec[i].T; o[2] = rec[i].border_err; o[3] = rec[i].sum; o[4] = rec[i].sq;
+            o[5] = rec[i].id; o[6] = rec[i].rot; o[7] = nc;
+        }
+    }
     return ASLAM_OK;
 }
 

@@ -120,6 +120,16 @@ struct FinalCand {                // candidate after _reorderCandidatesCorners +
 
 struct IdentWork { unsigned frame, idx; };
 
+struct IdentRecord {              // what k_identify decided for one candidate (k_identify<true> only: aslam_debug_get_identified)
+    unsigned long long bits[2];   // cell c = row * nc + column (border included) -> bit c % 64 of bits[c / 64]
+    long long sum, sq;            // inner region of the warped image (half a cell off every side): sum and sum of squares
+    int id, rot;                  // id (-1 rejected) and corner rotation, as written to the FinalCand
+    int branch;                   // 0 Otsu, 1 uniform dark (all bits 0), 2 uniform bright (all bits 1)
+    int T;                        // Otsu threshold (0 off the Otsu branch)
+    int border_err;               // _getBorderErrors
+    int pad[3];
+};
+
 struct Marker {                   // one detection: what detectMarkers + estimatePoseSingleMarkers return
     int id;
     int pad;

@@ -21,7 +21,7 @@ void launch_quads(hipStream_t st, int nwaves, const DetectCfg& cfg, int nframes,
 void launch_assemble(hipStream_t st, int nframes, const DetectCfg& cfg, Counters* ctr, const CandRec* cands,
                      const unsigned* n_cand, FinalCand* finals, unsigned* n_final, IdentWork* work);
 void launch_identify(hipStream_t st, int nwaves, const DetectCfg& cfg, Counters* ctr, const uint8_t* gray,
-                     FinalCand* finals, const IdentWork* work, const unsigned long long* dict_codes);
+                     FinalCand* finals, const IdentWork* work, const unsigned long long* dict_codes, IdentRecord* rec = nullptr);
 int max_frames_per_call();
 
 } // namespace aslam

@@ -368,6 +368,19 @@ int aslam_debug_inject_observations(aslam_ctx* ctx, int slot, int n, const int* 
  * fuses them. */
 int aslam_debug_inject_candidates(aslam_ctx* ctx, int slot, int n, const int* ids, const int* rots, const float* corners /* n x 8 */);
 int aslam_debug_run_pose(aslam_ctx* ctx, int first, int count, const int* robot_of_slot /* count entries, or NULL */);
+/* the identification stage on given quads (tests/test_identify_kernel.py).  aslam_debug_run_identify launches on slots [first,
+ * first + count) what a detection call launches at identification, with the context's dictionary and detector parameters: the
+ * perspective removal, the inner-region meanStdDev, Otsu, the cell votes, _getBorderErrors and Dictionary::identify, on every
+ * candidate aslam_debug_inject_candidates wrote (its corners; the injected ids and rotations are overwritten), reading the grey
+ * frame a detection pass reads: a gray slot as staged, a bgr8 slot as its last detection pass converted it.  It runs the
+ * instrumented build of the kernel, which also records every decision.  aslam_debug_get_identified returns slot's first
+ * min(n, max) candidates: ids[i] (-1 rejected), rots[i], cells[81 i .. 81 i + 80] (the nc x nc cell bits, border included,
+ * row-major, zero-padded to 9 x 9) and info[8 i .. 8 i + 7] = {branch (0 Otsu, 1 uniform dark: all bits 0, 2 uniform bright:
+ * all bits 1), Otsu threshold (0 off that branch), border errors, inner-region sum, inner-region sum of squares, recorded id,
+ * recorded rotation, nc}. */
+int aslam_debug_run_identify(aslam_ctx* ctx, int first, int count);
+int aslam_debug_get_identified(aslam_ctx* ctx, int slot, int max, int* n, int* ids, int* rots, uint8_t* cells /* max x 81 */,
+                               long long* info /* max x 8 */);
 /* HIP-event timing of each kernel family on the context's stream, accumulated since the last reset:
  * names[i] (static strings), calls[i], total_ms[i]; returns the number of entries. */
 int aslam_profile_enable(aslam_ctx* ctx, int on);

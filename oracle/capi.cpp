@@ -101,7 +101,8 @@ void orc_perspective_transform(const float src[8], const float dst[8], double M[
     get_perspective_transform(s, d, M);
 }
 
-void orc_extract_bits(const uint8_t* gray, int rows, int cols, const float corners[8], uint8_t* bits /*49*/) {
+// bits: (markerSize + 2 markerBorderBits)^2 bytes for the current dictionary and parameters (81 for a 7 x 7 dictionary)
+void orc_extract_bits(const uint8_t* gray, int rows, int cols, const float corners[8], uint8_t* bits) {
     const DetectorParams P = params();
     Pt2f c[4];
     for (int i = 0; i < 4; i++) c[i] = Pt2f{corners[2 * i], corners[2 * i + 1]};
@@ -117,6 +118,25 @@ int orc_identify(const uint8_t* gray, int rows, int cols, float corners[8], int*
     bool ok = identify_one_candidate(dict(), gray, rows, cols, c, *id, P);
     for (int i = 0; i < 4; i++) { corners[2 * i] = c[i].x; corners[2 * i + 1] = c[i].y; }
     return ok ? 1 : 0;
+}
+
+// cells per side of the current dictionary and parameters: markerSize + 2 markerBorderBits
+int orc_cells_per_side() { return dict().markerSize + 2 * params().markerBorderBits; }
+
+// _identifyOneCandidate on one candidate with every decision it made: bits (nc x nc, border included; nc returned), info = {branch
+// (0 Otsu, 1 all zero, 2 all one), Otsu T, border errors, inner sum, inner sum of squares, id (-1 rejected), rotation}
+int orc_identify_detail(const uint8_t* gray, int rows, int cols, const float corners[8], uint8_t* bits /* nc * nc */, long long info[7]) {
+    const DetectorParams P = params();
+    Pt2f c[4];
+    for (int i = 0; i < 4; i++) c[i] = Pt2f{corners[2 * i], corners[2 * i + 1]};
+    IdentDetail det;
+    std::vector<uint8_t> b;
+    int id = -1;
+    if (!identify_one_candidate(dict(), gray, rows, cols, c, id, P, &det, &b)) { det.id = -1; det.rotation = 0; }
+    std::memcpy(bits, b.data(), b.size());
+    const long long v[7] = {det.branch, det.T, det.border_err, det.sum, det.sq, det.id, det.rotation};
+    std::memcpy(info, v, sizeof(v));
+    return dict().markerSize + 2 * P.markerBorderBits;
 }
 
 // replace the dictionary used by the free functions below (Slam objects carry their own, see orc_slam_set_dictionary)

@@ -467,7 +467,7 @@ int otsu_threshold(const uint8_t* img, int n) {
 
 // aruco.cpp::_extractBits
 void extract_bits(const uint8_t* gray, int rows, int cols, const Pt2f corners[4], int markerSize,
-                  const DetectorParams& P, std::vector<uint8_t>& bits) {
+                  const DetectorParams& P, std::vector<uint8_t>& bits, IdentDetail* detail) {
     const int cellSize = P.perspectiveRemovePixelPerCell;
     const int sizeWB = markerSize + 2 * P.markerBorderBits;
     const int cellMarginPixels = int(P.perspectiveRemoveIgnoredMarginPerCell * cellSize);
@@ -488,11 +488,14 @@ void extract_bits(const uint8_t* gray, int rows, int cols, const Pt2f corners[4]
     const double mean = sum * scale;
     const double var = std::max(sq * scale - mean * mean, 0.);
     const double stddev = std::sqrt(var);
+    if (detail) { detail->sum = sum; detail->sq = sq; detail->branch = 0; detail->T = 0; }
     if (stddev < P.minOtsuStdDev) {
         if (mean > 127) std::fill(bits.begin(), bits.end(), 1);
+        if (detail) detail->branch = mean > 127 ? 2 : 1;
         return;
     }
     const int T = otsu_threshold(img.data(), S * S);
+    if (detail) detail->T = T;
     for (int y = 0; y < sizeWB; y++)
         for (int x = 0; x < sizeWB; x++) {
             int Xs = x * cellSize + cellMarginPixels, Ys = y * cellSize + cellMarginPixels;
@@ -589,17 +592,21 @@ static int border_errors(const uint8_t* bits, int markerSize, int borderSize) {
 
 // aruco.cpp::_identifyOneCandidate
 bool identify_one_candidate(const Dictionary& d, const uint8_t* gray, int rows, int cols, Pt2f corners[4],
-                            int& id, const DetectorParams& P) {
+                            int& id, const DetectorParams& P, IdentDetail* detail, std::vector<uint8_t>* bits_out) {
     std::vector<uint8_t> bits;
-    extract_bits(gray, rows, cols, corners, d.markerSize, P, bits);
+    extract_bits(gray, rows, cols, corners, d.markerSize, P, bits, detail);
+    if (bits_out) *bits_out = bits;
     int maximumErrorsInBorder = int(d.markerSize * d.markerSize * P.maxErroneousBitsInBorderRate);
-    if (border_errors(bits.data(), d.markerSize, P.markerBorderBits) > maximumErrorsInBorder) return false;
+    const int borderErrors = border_errors(bits.data(), d.markerSize, P.markerBorderBits);
+    if (detail) detail->border_err = borderErrors;
+    if (borderErrors > maximumErrorsInBorder) return false;
     int n = d.markerSize + 2 * P.markerBorderBits, b = P.markerBorderBits;
     std::vector<uint8_t> only((size_t)d.markerSize * d.markerSize);
     for (int y = 0; y < d.markerSize; y++)
         for (int x = 0; x < d.markerSize; x++) only[y * d.markerSize + x] = bits[(y + b) * n + x + b];
     int rotation;
     if (!dictionary_identify(d, only.data(), id, rotation, P.errorCorrectionRate)) return false;
+    if (detail) { detail->id = id; detail->rotation = rotation; }
     if (rotation != 0) std::rotate(corners, corners + 4 - rotation, corners + 4);
     return true;
 }

@@ -97,16 +97,24 @@ void filter_too_close_candidates(const std::vector<Candidate>& in, std::vector<C
 void get_perspective_transform(const Pt2f src[4], const Pt2f dst[4], double M[9]);
 void warp_perspective_nearest(const uint8_t* gray, int rows, int cols, const double M[9], int dsize, uint8_t* dst);
 int  otsu_threshold(const uint8_t* img, int n);
-// returns false if the candidate bits could not be extracted; bits is (markerSize+2b)^2 row-major 0/1
+// what _extractBits / _identifyOneCandidate decided on the way (filled when asked for: tests compare it with k_identify's record)
+struct IdentDetail {
+    int branch = 0;               // 0 Otsu, 1 uniform dark (all bits 0), 2 uniform bright (all bits 1)
+    int T = 0;                    // Otsu threshold (0 off that branch)
+    long long sum = 0, sq = 0;    // inner region: sum and sum of squares
+    int border_err = -1;          // _getBorderErrors (identify_one_candidate only)
+    int id = -1, rotation = 0;    // identify_one_candidate only
+};
+// bits is (markerSize+2b)^2 row-major 0/1
 void extract_bits(const uint8_t* gray, int rows, int cols, const Pt2f corners[4], int markerSize,
-                  const DetectorParams& p, std::vector<uint8_t>& bits);
+                  const DetectorParams& p, std::vector<uint8_t>& bits, IdentDetail* detail = nullptr);
 Dictionary make_dict_aruco_original();
 void get_rect_sub_pix_8u32f(const uint8_t* src, int rows, int cols, int win_w, int win_h, float cx, float cy, float* dst);
 void corner_sub_pix(const uint8_t* gray, int rows, int cols, Pt2f* corners, int count, int win, int maxCount, double epsilon);
 Dictionary make_dict_from_bits(int markerSize, int nMarkers, int maxCorrectionBits, const uint8_t* bits);
 bool dictionary_identify(const Dictionary& d, const uint8_t* onlyBits, int& idx, int& rotation, double rate);
 bool identify_one_candidate(const Dictionary& d, const uint8_t* gray, int rows, int cols, Pt2f corners[4],
-                            int& id, const DetectorParams& p);
+                            int& id, const DetectorParams& p, IdentDetail* detail = nullptr, std::vector<uint8_t>* bits_out = nullptr);
 void filter_detected_markers(std::vector<Detection>& d);
 // full cv::aruco::detectMarkers (channels = 1 gray or 3 BGR)
 void detect_markers(const uint8_t* img, int rows, int cols, int channels, size_t step, const Dictionary& dict,

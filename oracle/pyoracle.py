@@ -57,6 +57,8 @@ def load():
         L.orc_candidates.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _ip, _ip, _ip]
         L.orc_extract_bits.argtypes = [_u8p, C.c_int, C.c_int, _fp, _u8p]
         L.orc_identify.argtypes = [_u8p, C.c_int, C.c_int, _fp, _ip]
+        L.orc_identify_detail.argtypes = [_u8p, C.c_int, C.c_int, _fp, _u8p, _llp]
+        L.orc_cells_per_side.argtypes = []
         L.orc_detect.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, _ip, _fp]
         L.orc_dict_bytes.argtypes = [_u8p]
         L.orc_dict_bits.argtypes = [C.c_int, _u8p]
@@ -128,11 +130,24 @@ def candidates(gray, stage, maxn=8192):
 
 
 def extract_bits(gray, corners):
+    """_extractBits with the current dictionary and parameters: (nc, nc) cells, nc = markerSize + 2 markerBorderBits"""
     gray = np.ascontiguousarray(gray, np.uint8)
     c = np.ascontiguousarray(corners, np.float32).reshape(8)
-    bits = np.zeros(49, np.uint8)
+    nc = load().orc_cells_per_side()
+    bits = np.zeros(nc * nc, np.uint8)
     load().orc_extract_bits(_p(gray, _u8p), gray.shape[0], gray.shape[1], _p(c, _fp), _p(bits, _u8p))
-    return bits.reshape(7, 7)
+    return bits.reshape(nc, nc)
+
+
+def identify_detail(gray, corners):
+    """_identifyOneCandidate with every decision: (bits nc x nc, dict(branch, T, border_err, sum, sq, id, rot))"""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    c = np.ascontiguousarray(corners, np.float32).reshape(8)
+    nc = load().orc_cells_per_side()
+    bits = np.zeros(nc * nc, np.uint8)
+    info = np.zeros(7, np.int64)
+    load().orc_identify_detail(_p(gray, _u8p), gray.shape[0], gray.shape[1], _p(c, _fp), _p(bits, _u8p), _p(info, _llp))
+    return bits[:nc * nc].reshape(nc, nc).copy(), dict(zip(("branch", "T", "border_err", "sum", "sq", "id", "rot"), (int(v) for v in info)))
 
 
 def identify(gray, corners):

@@ -16,11 +16,12 @@ KERNELS = ["k_ekf_plan", "k_ekf_mid", "k_ekf_apply", "k_ekf_mid64", "k_ekf_T", "
 RES = ["VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "SGPRs Spill"]
 
 
-def compile_ekf(csrc, out):
-    """device-only compile of ekf.hip with the Makefile's flags: (disassembly per function, resource remarks per function)"""
-    co, elf = os.path.join(out, "ekf.co"), os.path.join(out, "ekf.elf")
+def compile_ekf(csrc, out, src="ekf.hip"):
+    """device-only compile of src (ekf.hip) with the Makefile's flags: (disassembly per function, resource remarks per function)"""
+    stem = os.path.splitext(src)[0]
+    co, elf = os.path.join(out, stem + ".co"), os.path.join(out, stem + ".elf")
     r = subprocess.run([f"{ROCM}/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-function",
-                        "-Wno-unused-value", "-Wno-unused-result", "--cuda-device-only", "-c", "ekf.hip", "-o", co,
+                        "-Wno-unused-value", "-Wno-unused-result", "--cuda-device-only", "-c", src, "-o", co,
                         "-Rpass-analysis=kernel-resource-usage"], cwd=csrc, capture_output=True, text=True, check=True)
     subprocess.run([f"{ROCM}/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", f"--input={co}",
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={elf}"], check=True)

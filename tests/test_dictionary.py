@@ -118,3 +118,52 @@ def test_6x6_dictionary_full_frame(dict6):
     ctx.set_dictionary(bits, maxcorr)
     img = run(ctx, rows, cols, K, ids, poses)
     pc.check_stages(ctx, 0, img, expect_ids=ids)
+
+
+# ---- marker sizes 3, 4 and 7 through the whole detector ---------------------------------------------------------------------------
+# (min_distance per size: what random_dictionary can still fill quickly; 3 x 3 has only 9 bits)
+SIZES = {3: (6, 3), 4: (12, 5), 7: (24, 13)}
+
+
+@pytest.fixture(params=sorted(SIZES))
+def dict_n(request):
+    ms = request.param
+    count, dist = SIZES[ms]
+    bits, maxcorr = synth.random_dictionary(ms, count, dist, seed=30 + ms)
+    orc.set_dictionary(bits, maxcorr)
+    yield ms, bits, maxcorr
+    orc.set_dictionary(None)
+
+
+def test_marker_sizes_3_4_7_match_oracle(dict_n):
+    """rendered scenes of 3 x 3, 4 x 4 and 7 x 7 markers (7 x 7 at the default 8 px per cell: a 72 px warp and 81 cells), the full
+    detector against the oracle stage by stage"""
+    ms, bits, maxcorr = dict_n
+    rows, cols, f = 240, 320, 300.0
+    n = min(3, len(bits))
+    ids, poses, K = scene(rows, cols, f, n, 10 + ms)
+    ids = np.arange(n, dtype=np.int32)
+    ctx = capi.Context(max_rows=rows, max_cols=cols, max_batch=1, persistent_waves=4, max_landmarks=16)
+    ctx.set_camera(K, np.zeros(5))
+    ctx.set_dictionary(bits, maxcorr)
+    img = run(ctx, rows, cols, K, ids, poses)
+    got, corners, rv, tv = pc.check_stages(ctx, 0, img, expect_ids=ids)
+    pc.check_poses(got, corners, rv, tv, K, np.zeros(5))
+
+
+@pytest.mark.gpu
+def test_7x7_dictionary_full_frame():
+    """7 x 7 markers at 8 px per cell over a 1280 x 720 frame, 20 markers"""
+    bits, maxcorr = synth.random_dictionary(7, 24, 13, seed=37)
+    orc.set_dictionary(bits, maxcorr)
+    try:
+        rows, cols, f = 720, 1280, 900.0
+        _, poses, K = synth.simple_scene(rows, cols, f, 20, seed=7, tz=(1.9, 2.6))
+        ids = np.arange(20, dtype=np.int32)
+        ctx = capi.Context(max_rows=rows, max_cols=cols, max_batch=1, max_landmarks=16)
+        ctx.set_camera(K, np.zeros(5))
+        ctx.set_dictionary(bits, maxcorr)
+        img = run(ctx, rows, cols, K, ids, poses)
+        pc.check_stages(ctx, 0, img, expect_ids=ids)
+    finally:
+        orc.set_dictionary(None)
