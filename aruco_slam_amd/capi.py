@@ -181,6 +181,9 @@ _SIGS = {
     "aslam_debug_run_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
     "aslam_debug_run_identify": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "aslam_debug_get_identified": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _u8p, _llp]),
+    "aslam_debug_inject_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
+    "aslam_debug_inject_quads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
+    "aslam_debug_run_quads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "aslam_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_profile_reset": (C.c_int, [C.c_void_p]),
     "aslam_get_plan_stats": (C.c_int, [C.c_void_p, _llp]),
@@ -684,6 +687,31 @@ class Context:
         k = n.value
         nc = int(info[0, 7]) if k else 0
         return ids[:k].copy(), rots[:k].copy(), cells[:k, :nc * nc].reshape(k, nc, nc).copy(), info[:k].copy()
+
+    def inject_contours(self, slot, contours, scales, keys):
+        """overwrite slot's kept-contour list: contours = closed point lists (m x 2 ints each), one scale and discovery key each"""
+        sizes = np.array([len(p) for p in contours], np.int32)
+        pts = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int64).reshape(-1, 2) for p in contours]) if len(contours) else
+                                   np.zeros((0, 2)), dtype=np.int32)
+        scales = np.ascontiguousarray(scales, dtype=np.int32).reshape(-1); keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        if not sizes.size == scales.size == keys.size:
+            raise ValueError("one scale and one key per contour")
+        self._ck(self.lib.aslam_debug_inject_contours(self.h, int(slot), int(sizes.size), _ptr(scales, _ip), _ptr(keys, _ip), _ptr(sizes, _ip),
+                                                      _ptr(pts, _ip)))
+
+    def inject_quads(self, slot, corners, sizes, scales, keys):
+        """overwrite slot's quad list (what the quad stage emits): corners n x 4 x 2 ints, contour point counts, scales, keys"""
+        corners = np.ascontiguousarray(corners, dtype=np.int32).reshape(-1, 8); sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1)
+        scales = np.ascontiguousarray(scales, dtype=np.int32).reshape(-1); keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        if not corners.shape[0] == sizes.size == scales.size == keys.size:
+            raise ValueError("4 corners, one size, one scale and one key per quad")
+        self._ck(self.lib.aslam_debug_inject_quads(self.h, int(slot), int(sizes.size), _ptr(corners, _ip), _ptr(sizes, _ip), _ptr(scales, _ip),
+                                                   _ptr(keys, _ip)))
+
+    def run_quads(self, first, count, stages):
+        """the quad stage (stages & 1) and candidate assembly (stages & 2) alone on the slots' injected lists; waits, and raises on
+        an overflowed list as sync() does"""
+        self._ck(self.lib.aslam_debug_run_quads(self.h, int(first), int(count), int(stages)))
 
     def sync(self):
         self._ck(self.lib.aslam_sync(self.h))

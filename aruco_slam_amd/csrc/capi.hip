@@ -2874,6 +2874,133 @@ int aslam_debug_get_identified(aslam_ctx* c, int slot, int max, int* n_out, int*
     return ASLAM_OK;
 }
 
+namespace {
+// Injected coordinates: the 16-bit packing holds [-32768, 32767], but k_quads' wave reductions carry squared distances and cross
+// products as 32-bit integers (wave_first_max_exact), which holds for differences below 2^15 (a detection pass: below 2^12)
+constexpr int kInjectCoordMin = -16384, kInjectCoordMax = 16383;
+// what both quad hooks ask of a slot: a frame of the current shape staged in it (its shape and DetectCfg are the launch's)
+int check_slots_staged(aslam_ctx* c, int first, int count) {
+    int r = check_slot_range(c, first, count);
+    if (r) return r;
+    if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
+    for (int i = first; i < first + count; i++)
+        if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+            return fail(c, ASLAM_E_STATE, "slot has no frame of the current shape (stage one first)");
+    return ASLAM_OK;
+}
+// a (scale, discovery key) list as k_link would have produced it: a window in force, a key of the frame, no pair twice
+int check_scale_keys(aslam_ctx* c, int n, const int* scales, const int* keys) {
+    std::vector<unsigned long long> seen(n);
+    for (int i = 0; i < n; i++) {
+        if (scales[i] < 0 || scales[i] >= c->cfg.n_scales) return fail(c, ASLAM_E_INVALID, "scale outside the threshold windows in force");
+        if (keys[i] < 0 || (long long)keys[i] > (long long)c->rows * c->cols) return fail(c, ASLAM_E_INVALID, "key outside [0, rows * cols]");
+        seen[i] = ((unsigned long long)scales[i] << 32) | (unsigned)keys[i];
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(c, ASLAM_E_INVALID, "(scale, key) twice in one slot");
+    return ASLAM_OK;
+}
+}
+
+int aslam_debug_inject_contours(aslam_ctx* c, int slot, int n, const int* scales, const int* keys, const int* sizes, const int* points_xy) {
+    if (!c || n < 0 || (n && (!scales || !keys || !sizes || !points_xy))) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slots_staged(c, slot, 1);
+    if (r) return r;
+    const DetectCfg& g = c->cfg;
+    if ((unsigned)n > g.cap_contours) return fail(c, ASLAM_E_INVALID, "more contours than cap_contours_per_frame");
+    r = check_scale_keys(c, n, scales, keys);
+    if (r) return r;
+    std::vector<ContourRec> recs(n);
+    std::vector<unsigned> pts;
+    size_t tot = 0;
+    for (int i = 0; i < n; i++) {
+        if (sizes[i] < 1 || sizes[i] > 65534) return fail(c, ASLAM_E_INVALID, "contour size outside [1, 65534]");
+        if (tot + (size_t)sizes[i] > g.cap_points) return fail(c, ASLAM_E_INVALID, "more points than cap_points_per_frame");
+        for (int k = 0; k < sizes[i]; k++) {
+            const int x = points_xy[2 * (tot + k)], y = points_xy[2 * (tot + k) + 1];
+            if (x < kInjectCoordMin || x > kInjectCoordMax || y < kInjectCoordMin || y > kInjectCoordMax)
+                return fail(c, ASLAM_E_INVALID, "point coordinate outside [-16384, 16383]");
+            pts.push_back((unsigned)(x & 0xFFFF) | ((unsigned)(y & 0xFFFF) << 16));
+        }
+        recs[i] = ContourRec{(unsigned)slot, (unsigned)scales[i], (unsigned)keys[i], (unsigned)sizes[i], (unsigned)tot,
+                             (short)points_xy[2 * tot], (short)points_xy[2 * tot + 1], 0, {0u, 0u}};
+        tot += (size_t)sizes[i];
+    }
+    r = sync_streams(c);
+    if (r) return r;
+    const unsigned un = (unsigned)n, up = (unsigned)tot;
+    if (n) HIP_TRY(c, hipMemcpy(c->d_contours + (size_t)slot * g.cap_contours, recs.data(), n * sizeof(ContourRec), hipMemcpyHostToDevice));
+    if (tot) HIP_TRY(c, hipMemcpy(c->d_points + (size_t)slot * g.cap_points, pts.data(), tot * sizeof(unsigned), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_ncontours + slot, &un, sizeof(unsigned), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_npoints + slot, &up, sizeof(unsigned), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int aslam_debug_inject_quads(aslam_ctx* c, int slot, int n, const int* corners, const int* sizes, const int* scales, const int* keys) {
+    if (!c || n < 0 || n > kCandMax || (n && (!corners || !sizes || !scales || !keys))) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slots_staged(c, slot, 1);
+    if (r) return r;
+    r = check_scale_keys(c, n, scales, keys);
+    if (r) return r;
+    std::vector<CandRec> h(n);
+    for (int i = 0; i < n; i++) {
+        if (sizes[i] < 1 || sizes[i] > 65534) return fail(c, ASLAM_E_INVALID, "contour size outside [1, 65534]");
+        for (int k = 0; k < 4; k++) {
+            const int x = corners[8 * i + 2 * k], y = corners[8 * i + 2 * k + 1];
+            if (x < kInjectCoordMin || x > kInjectCoordMax || y < kInjectCoordMin || y > kInjectCoordMax)
+                return fail(c, ASLAM_E_INVALID, "corner coordinate outside [-16384, 16383]");
+            h[i].x[k] = (short)x; h[i].y[k] = (short)y;
+        }
+        h[i].n = (unsigned)sizes[i];
+        h[i].ordkey = cand_ordkey((unsigned)scales[i], (unsigned)keys[i]);
+    }
+    r = sync_streams(c);
+    if (r) return r;
+    const unsigned un = (unsigned)n;
+    if (n) HIP_TRY(c, hipMemcpy(c->d_cands + (size_t)slot * kCandMax, h.data(), n * sizeof(CandRec), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_ncand + slot, &un, sizeof(unsigned), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+int aslam_debug_run_quads(aslam_ctx* c, int first, int count, int stages) {
+    if (!c) return ASLAM_E_INVALID;
+    if (stages < 1 || stages > 3) return fail(c, ASLAM_E_INVALID, "stages: 1 quads, 2 assemble, 3 both");
+    int r = check_slots_staged(c, first, count);
+    if (r) return r;
+    r = sync_streams(c);
+    if (r) return r;
+    hipStream_t st = c->stream;
+    if (c->last_detect && c->last_detect != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    c->last_detect = st;
+    c->last_first = first;
+    c->last_count = count;
+    // what run_detect launches at P_QUADS and P_ASSEMBLE, chunk by chunk.  Of the counters a detection pass clears (k_clear_counts)
+    // those these two stages use: the queue heads, and the candidate counts when k_quads is to fill them (the injected lists stay)
+    const DetectCfg& g = c->cfg;
+    const int chunk = detect_chunk();
+    for (int f0 = first; f0 < first + count; f0 += chunk) {
+        const int nf = std::min(chunk, first + count - f0);
+        HIP_TRY(c, hipMemsetAsync(c->d_ctr, 0, sizeof(unsigned) * kCounterHeads, st));
+        if (stages & 1) {
+            HIP_TRY(c, hipMemsetAsync(c->d_ncand + f0, 0, sizeof(unsigned) * nf, st));
+            prof_begin(c, P_QUADS, st);
+            launch_prefix(st, nf, c->d_ncontours + f0, g.cap_contours, 1u, c->d_pre_quads);
+            launch_quads(st, c->nwaves, g, nf, c->d_ctr, c->d_contours + (size_t)f0 * g.cap_contours, c->d_ncontours + f0, c->d_pre_quads,
+                         c->d_points + (size_t)f0 * g.cap_points, c->d_cands + (size_t)f0 * kCandMax, c->d_ncand + f0);
+            prof_end(c);
+        }
+        if (stages & 2) {
+            prof_begin(c, P_ASSEMBLE, st);
+            launch_assemble(st, nf, g, c->d_ctr, c->d_cands + (size_t)f0 * kCandMax, c->d_ncand + f0,
+                            c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_work);
+            prof_end(c);
+        }
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_detect, st));
+    HIP_TRY(c, hipGetLastError());
+    return sync_and_check(c);             // a candidate or pair list that overflowed: ASLAM_E_CAPACITY, as aslam_sync reports it
+}
+
 int aslam_debug_get_frame_counts(aslam_ctx* c, int slot, unsigned* out /* 6 */) {
     if (!c || !out || slot < 0 || slot >= c->max_batch) return ASLAM_E_INVALID;
     const unsigned* src[6] = {c->d_nstarts, c->d_ncontours, c->d_npoints, c->d_nwrite, c->d_ncand, c->d_link_todo};

@@ -108,8 +108,14 @@ struct WriteRec {                 // one write ticket: from `state` skip cnt >> 
 struct CandRec {                  // quad that passed _findMarkerContours
     short x[4], y[4];
     unsigned n;                   // contour point count ("perimeter" in 3.2.0)
-    unsigned ordkey;              // scale * 2^22 + (2^22 - 1 - key): ascending = OpenCV candidate order
+    unsigned ordkey;              // cand_ordkey(scale, key): ascending = OpenCV candidate order
 };
+// scale * 2^24 + (2^24 - 1 - key): scale ascending, reverse discovery inside a scale.  24 bits hold every key: a frame is at most
+// 4095 x 4095 and key <= rows * cols < 2^24; with at most kScales = 3 scales the sum stays below 2^26
+constexpr unsigned kOrdKeyBits = 24;
+__host__ __device__ inline unsigned cand_ordkey(unsigned scale, unsigned key) {
+    return scale * (1u << kOrdKeyBits) + ((1u << kOrdKeyBits) - 1u - key);
+}
 
 struct FinalCand {                // candidate after _reorderCandidatesCorners + _filterTooCloseCandidates
     float c[8];

@@ -1085,8 +1085,15 @@ __device__ int approx_poly_closed_body(const unsigned* __restrict__ gsrc, const 
         }
         if (new_count + top > 8) return -1;
     }
-    // final clean-up
+    // final clean-up.  The wave-uniform arrays above are safe without this care: every lane stores the same value to stack[] and to
+    // dst[new_count++] and reads back only what it or any other lane stored there, in whatever order the lanes run.  The clean-up is
+    // different: it overwrites slots of dst in place and later reads them again (read after overwrite), so a lane that ran it after
+    // another lane would start from that lane's result.  The 64 lanes of a wavefront run it in lockstep and agree; a build whose
+    // lanes run one after the other between collectives (the CPU emulation of the tests) does not.  One lane runs it, on every build
     QST(2);
+    __shared__ int s_new_count;
+    __syncthreads();                                            // (the workgroup is this one wavefront)
+    if (lane == 0) {
     int count2 = new_count;
     pos = count2 - 1;
     start_pt = dst[pos]; if (++pos >= count2) pos = 0;
@@ -1110,8 +1117,11 @@ __device__ int approx_poly_closed_body(const unsigned* __restrict__ gsrc, const 
         pt = end_pt;
     }
     for (int i = 0; i < new_count; i++) out[i] = dst[i];
+    s_new_count = new_count;
+    }
+    __syncthreads();
     QST(4);
-    return new_count;
+    return s_new_count;
 }
 
 // Returns the number of vertices (<= 8) written to out, or -1 when the result cannot have 4 vertices (see the body).
@@ -1234,7 +1244,7 @@ __global__ __launch_bounds__(64) void k_quads(DetectCfg cfg, int nframes, Counte
                     CandRec c;
                     for (int j = 0; j < 4; j++) { c.x[j] = (short)q[j].x; c.y[j] = (short)q[j].y; }
                     c.n = rec.n;
-                    c.ordkey = rec.scale * (1u << 22) + ((1u << 22) - 1u - rec.key);
+                    c.ordkey = cand_ordkey(rec.scale, rec.key);
                     cands[(size_t)f * kCandMax + k] = c;
                 } else {
                     atomicOr(&ctr->overflow, (unsigned)kOvfCands);

@@ -381,6 +381,26 @@ int aslam_debug_run_pose(aslam_ctx* ctx, int first, int count, const int* robot_
 int aslam_debug_run_identify(aslam_ctx* ctx, int first, int count);
 int aslam_debug_get_identified(aslam_ctx* ctx, int slot, int max, int* n, int* ids, int* rots, uint8_t* cells /* max x 81 */,
                                long long* info /* max x 8 */);
+/* the quad and assembly stages on given contours / quads (tests/test_quads_kernel.py).  The slots must hold staged frames of the
+ * current shape: their shape and the detector parameters in force are the launch's.
+ * aslam_debug_inject_contours overwrites a slot's kept-contour list with n closed point lists (contour i: sizes[i] points, packed one
+ * after the other in points_xy as x y pairs; scales[i] = its threshold window, keys[i] = its discovery key y * cols + x (+ 1 for a
+ * hole border)).  Refused with ASLAM_E_INVALID: n > cap_contours_per_frame, more points in all than cap_points_per_frame, a size
+ * outside [1, 65534], a scale that is not a threshold window in force, a key outside [0, rows * cols], a (scale, key) pair twice, a
+ * coordinate outside [-16384, 16383] (the 16-bit packing would hold twice that; the quad kernel's integer reductions need squared
+ * distances below 2^32).  The perimeter limits (minMarkerPerimeterRate, maxMarkerPerimeterRate) are NOT applied: they are the
+ * contour stage's, upstream of this list.
+ * aslam_debug_inject_quads overwrites a slot's quad list (what the quad stage would have emitted) with n <= 2048 quads: corners
+ * [8 i .. 8 i + 7] = x0 y0 .. x3 y3, sizes[i] = the contour's point count, scales / keys as above, the same checks.
+ * aslam_debug_run_quads launches on slots [first, first + count) what a detection call launches for the quad stage (stages & 1) and
+ * for candidate assembly (stages & 2), with the queue heads (and, with stages & 1, the quad counts) reset as a detection call
+ * resets them; it waits, and reports an overflowed quad or near-pair list as aslam_sync does (ASLAM_E_CAPACITY).  Results:
+ * aslam_debug_get_candidates, stage 0 (quads, sorted into candidate order) and stage 2. */
+int aslam_debug_inject_contours(aslam_ctx* ctx, int slot, int n, const int* scales, const int* keys, const int* sizes,
+                                const int* points_xy);
+int aslam_debug_inject_quads(aslam_ctx* ctx, int slot, int n, const int* corners /* n x 8 */, const int* sizes, const int* scales,
+                             const int* keys);
+int aslam_debug_run_quads(aslam_ctx* ctx, int first, int count, int stages);
 /* HIP-event timing of each kernel family on the context's stream, accumulated since the last reset:
  * names[i] (static strings), calls[i], total_ms[i]; returns the number of entries. */
 int aslam_profile_enable(aslam_ctx* ctx, int on);

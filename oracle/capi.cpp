@@ -95,6 +95,39 @@ int orc_candidates(const uint8_t* gray, int rows, int cols, int stage, int max, 
     return export_candidates(a, max, corners, sizes, scales, keys);
 }
 
+// _findMarkerContours' loop body on given contours (no perimeter limits), joined as _detectInitialCandidates joins them: scale
+// ascending, inside a scale in OpenCV's contour order (key descending).  stage as orc_candidates.  Contour i: sizes[i] points packed
+// in points_xy.  With sizes == NULL the n inputs are quads already (corners_in n x 8, contour_sizes) and only the stages apply.
+int orc_quads_from_contours(int rows, int cols, int n, const int* scales, const int* keys, const int* sizes, const int* points_xy,
+                            const int* corners_in, const int* contour_sizes, int stage, int max, float* corners, int* out_sizes,
+                            int* out_scales, int* out_keys) {
+    const DetectorParams P = params();
+    std::vector<int> order(n);
+    for (int i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return scales[a] != scales[b] ? scales[a] < scales[b] : keys[a] > keys[b]; });
+    std::vector<long long> off(n + 1, 0);
+    for (int i = 0; i < n; i++) off[i + 1] = off[i] + (sizes ? sizes[i] : 0);
+    std::vector<Candidate> a, b;
+    for (int i : order) {
+        if (sizes) {
+            Contour c;
+            c.is_hole = 0;
+            c.key = keys[i];
+            c.pts.resize(sizes[i]);
+            for (int k = 0; k < sizes[i]; k++) c.pts[k] = Pt{points_xy[2 * (off[i] + k)], points_xy[2 * (off[i] + k) + 1]};
+            marker_contour_candidate(c, rows, cols, P, scales[i], a);
+        } else {
+            Candidate cand;
+            for (int k = 0; k < 4; k++) cand.c[k] = Pt2f{(float)corners_in[8 * i + 2 * k], (float)corners_in[8 * i + 2 * k + 1]};
+            cand.contour_size = contour_sizes[i]; cand.scale = scales[i]; cand.key = keys[i];
+            a.push_back(cand);
+        }
+    }
+    if (stage >= 1) reorder_candidate_corners(a);
+    if (stage >= 2) { filter_too_close_candidates(a, b, P.minMarkerDistanceRate); a.swap(b); }
+    return export_candidates(a, max, corners, out_sizes, out_scales, out_keys);
+}
+
 void orc_perspective_transform(const float src[8], const float dst[8], double M[9]) {
     Pt2f s[4], d[4];
     for (int i = 0; i < 4; i++) { s[i] = Pt2f{src[2 * i], src[2 * i + 1]}; d[i] = Pt2f{dst[2 * i], dst[2 * i + 1]}; }

@@ -270,6 +270,33 @@ bool is_contour_convex(const std::vector<Pt>& p) {
     return true;
 }
 
+// aruco.cpp::_findMarkerContours, the body of its loop after the perimeter limits: one contour -> at most one candidate
+void marker_contour_candidate(const Contour& c, int rows, int cols, const DetectorParams& P, int scale, std::vector<Candidate>& out) {
+    std::vector<Pt> approx;
+    approx_poly_dp_closed(c.pts, double(c.pts.size()) * P.polygonalApproxAccuracyRate, approx);
+    if (approx.size() != 4 || !is_contour_convex(approx)) return;
+    double minDistSq = (double)std::max(cols, rows) * std::max(cols, rows);
+    for (int j = 0; j < 4; j++) {
+        double d = (double)(approx[j].x - approx[(j + 1) % 4].x) * (double)(approx[j].x - approx[(j + 1) % 4].x) +
+                   (double)(approx[j].y - approx[(j + 1) % 4].y) * (double)(approx[j].y - approx[(j + 1) % 4].y);
+        minDistSq = std::min(minDistSq, d);
+    }
+    double minCornerDistancePixels = double(c.pts.size()) * P.minCornerDistanceRate;
+    if (minDistSq < minCornerDistancePixels * minCornerDistancePixels) return;
+    bool tooNearBorder = false;
+    for (int j = 0; j < 4; j++)
+        if (approx[j].x < P.minDistanceToBorder || approx[j].y < P.minDistanceToBorder ||
+            approx[j].x > cols - 1 - P.minDistanceToBorder || approx[j].y > rows - 1 - P.minDistanceToBorder)
+            tooNearBorder = true;
+    if (tooNearBorder) return;
+    Candidate cand;
+    for (int j = 0; j < 4; j++) cand.c[j] = Pt2f{(float)approx[j].x, (float)approx[j].y};
+    cand.contour_size = (int)c.pts.size();
+    cand.scale = scale;
+    cand.key = c.key;
+    out.push_back(cand);
+}
+
 // aruco.cpp::_findMarkerContours
 void find_marker_contours(const uint8_t* thresh, int rows, int cols, const DetectorParams& P, int scale,
                           std::vector<Candidate>& out) {
@@ -279,29 +306,7 @@ void find_marker_contours(const uint8_t* thresh, int rows, int cols, const Detec
     find_contours_list_none(thresh, rows, cols, contours);
     for (const Contour& c : contours) {
         if (c.pts.size() < minPerimeterPixels || c.pts.size() > maxPerimeterPixels) continue;
-        std::vector<Pt> approx;
-        approx_poly_dp_closed(c.pts, double(c.pts.size()) * P.polygonalApproxAccuracyRate, approx);
-        if (approx.size() != 4 || !is_contour_convex(approx)) continue;
-        double minDistSq = (double)std::max(cols, rows) * std::max(cols, rows);
-        for (int j = 0; j < 4; j++) {
-            double d = (double)(approx[j].x - approx[(j + 1) % 4].x) * (double)(approx[j].x - approx[(j + 1) % 4].x) +
-                       (double)(approx[j].y - approx[(j + 1) % 4].y) * (double)(approx[j].y - approx[(j + 1) % 4].y);
-            minDistSq = std::min(minDistSq, d);
-        }
-        double minCornerDistancePixels = double(c.pts.size()) * P.minCornerDistanceRate;
-        if (minDistSq < minCornerDistancePixels * minCornerDistancePixels) continue;
-        bool tooNearBorder = false;
-        for (int j = 0; j < 4; j++)
-            if (approx[j].x < P.minDistanceToBorder || approx[j].y < P.minDistanceToBorder ||
-                approx[j].x > cols - 1 - P.minDistanceToBorder || approx[j].y > rows - 1 - P.minDistanceToBorder)
-                tooNearBorder = true;
-        if (tooNearBorder) continue;
-        Candidate cand;
-        for (int j = 0; j < 4; j++) cand.c[j] = Pt2f{(float)approx[j].x, (float)approx[j].y};
-        cand.contour_size = (int)c.pts.size();
-        cand.scale = scale;
-        cand.key = c.key;
-        out.push_back(cand);
+        marker_contour_candidate(c, rows, cols, P, scale, out);
     }
 }
 

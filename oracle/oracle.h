@@ -88,6 +88,7 @@ void adaptive_threshold_mean_inv(const uint8_t* gray, int rows, int cols, int k,
 void find_contours_list_none(const uint8_t* bin, int rows, int cols, std::vector<Contour>& out);
 void approx_poly_dp_closed(const std::vector<Pt>& src, double eps, std::vector<Pt>& dst);
 bool is_contour_convex(const std::vector<Pt>& p);
+void marker_contour_candidate(const Contour& c, int rows, int cols, const DetectorParams& p, int scale, std::vector<Candidate>& out);
 void find_marker_contours(const uint8_t* thresh, int rows, int cols, const DetectorParams& p, int scale,
                           std::vector<Candidate>& out);
 void detect_initial_candidates(const uint8_t* gray, int rows, int cols, const DetectorParams& p,

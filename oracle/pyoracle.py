@@ -55,6 +55,7 @@ def load():
         L.orc_bgr2gray.argtypes = [_u8p, C.c_int, C.c_int, C.c_size_t, _u8p]
         L.orc_approx_poly.argtypes = [_ip, C.c_int, C.c_double, _ip, C.c_int]
         L.orc_candidates.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _ip, _ip, _ip]
+        L.orc_quads_from_contours.argtypes = [C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _fp, _ip, _ip, _ip]
         L.orc_extract_bits.argtypes = [_u8p, C.c_int, C.c_int, _fp, _u8p]
         L.orc_identify.argtypes = [_u8p, C.c_int, C.c_int, _fp, _ip]
         L.orc_identify_detail.argtypes = [_u8p, C.c_int, C.c_int, _fp, _u8p, _llp]
@@ -127,6 +128,25 @@ def candidates(gray, stage, maxn=8192):
     corners = np.zeros((maxn, 4, 2), np.float32); sizes = np.zeros(maxn, np.int32); scales = np.zeros(maxn, np.int32); keys = np.zeros(maxn, np.int32)
     n = load().orc_candidates(_p(gray, _u8p), gray.shape[0], gray.shape[1], int(stage), maxn, _p(corners, _fp), _p(sizes, _ip), _p(scales, _ip), _p(keys, _ip))
     return corners[:n].copy(), sizes[:n].copy(), scales[:n].copy(), keys[:n].copy()
+
+
+def quads(rows, cols, scales, keys, contours=None, quads_in=None, stage=0, maxn=8192):
+    """_findMarkerContours' per-contour body on given contours (closed point lists; no perimeter limits), or on given quads
+    (quads_in = (corners n x 4 x 2 ints, contour sizes)), joined in candidate order, with the current detector parameters; stage
+    as candidates().  Returns corners, sizes, scales, keys."""
+    scales = np.ascontiguousarray(scales, np.int32).reshape(-1); keys = np.ascontiguousarray(keys, np.int32).reshape(-1)
+    n = scales.size
+    sizes = pts = cin = csz = None
+    if contours is not None:
+        sizes = np.array([len(p) for p in contours], np.int32)
+        pts = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int64).reshape(-1, 2) for p in contours]) if n else np.zeros((0, 2)), dtype=np.int32)
+    else:
+        cin = np.ascontiguousarray(quads_in[0], dtype=np.int32).reshape(-1, 8); csz = np.ascontiguousarray(quads_in[1], dtype=np.int32).reshape(-1)
+    corners = np.zeros((maxn, 4, 2), np.float32); osz = np.zeros(maxn, np.int32); osc = np.zeros(maxn, np.int32); ok = np.zeros(maxn, np.int32)
+    opt = lambda a: _p(a, _ip) if a is not None else None
+    m = load().orc_quads_from_contours(int(rows), int(cols), n, _p(scales, _ip), _p(keys, _ip), opt(sizes), opt(pts), opt(cin), opt(csz),
+                                       int(stage), maxn, _p(corners, _fp), _p(osz, _ip), _p(osc, _ip), _p(ok, _ip))
+    return corners[:m].copy(), osz[:m].copy(), osc[:m].copy(), ok[:m].copy()
 
 
 def extract_bits(gray, corners):
