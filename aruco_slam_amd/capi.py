@@ -20,6 +20,7 @@ E_NAMES = {-1: "INVALID", -2: "NO_DEVICE", -3: "HIP", -4: "CAPACITY", -5: "STATE
 MAP_RECORD_BYTES = 104
 MARKER_MAX = 128
 CAND_MAX = 2048
+ID_TABLE_SIZE = 1024
 
 
 class AslamInit(C.Structure):
@@ -135,6 +136,10 @@ _SIGS = {
     "aslam_fleet_get_state": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
     "aslam_fleet_set_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]),
     "aslam_fleet_get_landmark_ids": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "aslam_merge_map_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp,
+                                          _ip, _ip, _dp]),
+    "aslam_fleet_merge_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _ip, _ip, _dp]),
+    "aslam_merge_scratch_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -478,6 +483,40 @@ class Context:
         self._ck(self.lib.aslam_fleet_get_landmark_ids(self.h, int(robot), C.byref(n), _ptr(ids, _ip)))
         return ids[: n.value].copy()
 
+    # -- map merge: one shared map from N maps in N frames -----------------------------------------------------
+    def _merged(self, call, n_maps):
+        """run call(max, n, ids, xyth, sigmas, n_seen, rounds, T) -> (ids, xyth n x 3, sigmas n x 3 x 3, n_seen, rounds, T n_maps x 3)"""
+        n = C.c_int()
+        ids = np.zeros(ID_TABLE_SIZE, np.int32); seen = np.zeros(ID_TABLE_SIZE, np.int32)
+        xyth = np.zeros((ID_TABLE_SIZE, 3)); sig = np.zeros((ID_TABLE_SIZE, 3, 3))
+        rounds = np.zeros(n_maps, np.int32); T = np.zeros((n_maps, 3))
+        self._ck(call(ID_TABLE_SIZE, C.byref(n), _ptr(ids, _ip), _ptr(xyth, _dp), _ptr(sig, _dp), _ptr(seen, _ip), _ptr(rounds, _ip), _ptr(T, _dp)))
+        k = n.value
+        return ids[:k].copy(), xyth[:k].copy(), sig[:k].copy(), seen[:k].copy(), rounds, T
+
+    def merge_map_records(self, records, n_maps, per_map, anchor=0, min_common=2, on_device=False):
+        """align n_maps maps of per_map 104-byte records each into map `anchor`'s frame and fuse them per marker id.  records: a numpy
+        array holding the records (e.g. of dist.MAP_DTYPE), or with on_device=True the address of a device buffer"""
+        if on_device:
+            ptr = C.c_void_p(int(records))
+        else:
+            records = np.ascontiguousarray(records)
+            if records.nbytes != int(n_maps) * int(per_map) * MAP_RECORD_BYTES:
+                raise ValueError("records must hold n_maps x per_map records of MAP_RECORD_BYTES bytes")
+            ptr = records.ctypes.data_as(C.c_void_p)
+        return self._merged(lambda *out: self.lib.aslam_merge_map_records(self.h, ptr, 1 if on_device else 0, int(n_maps), int(per_map),
+                                                                          int(anchor), int(min_common), *out), int(n_maps))
+
+    def fleet_merge_maps(self, anchor=0, min_common=2):
+        """merge_map_records on the maps of the active SLAM fleet's robots (map r = robot r)"""
+        return self._merged(lambda *out: self.lib.aslam_fleet_merge_maps(self.h, int(anchor), int(min_common), *out), max(self.is_fleet(), 1))
+
+    def merge_scratch_bytes(self):
+        """device memory the merge calls hold at present (0 before the first merge and after fleet_end)"""
+        b = C.c_longlong()
+        self._ck(self.lib.aslam_merge_scratch_bytes(self.h, C.byref(b)))
+        return b.value
+
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))
 
@@ -751,6 +790,10 @@ class Context:
         out = np.zeros(self._comm_world * int(self.init.max_landmarks) * MAP_RECORD_BYTES, np.uint8)
         self._ck(self.lib.aslam_comm_gather_maps(self.h, out.ctypes.data_as(C.c_void_p), 0))
         return out
+
+    def comm_gather_maps_to_device(self, device_ptr):
+        """the gathered records (world x max_landmarks, rank-major) into a device buffer, e.g. for merge_map_records(on_device=True)"""
+        self._ck(self.lib.aslam_comm_gather_maps(self.h, C.c_void_p(int(device_ptr)), 1))
 
     def comm_destroy(self):
         self._ck(self.lib.aslam_comm_destroy(self.h))

@@ -145,6 +145,7 @@ struct aslam_ctx {
     // fleet SLAM (aslam_fleet_slam_begin): every robot a complete SLAM filter (ekf_fleet_slam.h), allocated for the R
     // requested; the cameras, armed flags and work-list buffers above serve it as they serve fleet localization
     FleetSlam fslam{};
+    MergeBufs merge{};                    // map merge: tables allocated by the first merge, freed at aslam_fleet_end / aslam_destroy
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -815,6 +816,7 @@ void aslam_destroy(aslam_ctx* c) {
     hipFree(c->d_obs); hipFree(c->d_enc); hipFree(c->d_synth); hipFree(c->d_ident_rec);
     ekf_free(c->ekf);
     ekf_fleet_free(c->fslam);
+    merge_free(c->merge);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
     hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
     pinned_free(c->fleet_camidx_up);
@@ -2287,6 +2289,7 @@ int aslam_fleet_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
     if (int r = allow(c, kFleet)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
+    merge_free(c->merge);                               // the map merge's tables and record buffer, if a merge made them
     return enter_mode(c, Mode::Slam);
 }
 
@@ -2339,6 +2342,76 @@ int aslam_fleet_get_landmark_ids(aslam_ctx* c, int robot, int* L, int* ids) {
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     { int rs = sync_streams(c); if (rs) return rs; }
     return read_landmark_ids(c, ekf_fleet_robot(c->fslam, robot), L, ids);
+}
+
+// ---- map merge: one shared map from N maps in N frames (include/aruco_slam_hip.h) -------------------------------
+namespace {
+int merge_check(aslam_ctx* c, int n_maps, int anchor, int min_common, int max) {
+    if (n_maps < 1 || n_maps > ASLAM_MAX_ROBOTS) return fail(c, ASLAM_E_INVALID, "a merge takes 1..ASLAM_MAX_ROBOTS maps");
+    if (anchor < 0 || anchor >= n_maps) return fail(c, ASLAM_E_INVALID, "anchor outside the maps");
+    if (min_common < 2 || min_common > kIdTableSize) return fail(c, ASLAM_E_INVALID, "min_common 2..1024");
+    if (max < 0) return fail(c, ASLAM_E_INVALID, "negative max");
+    return ASLAM_OK;
+}
+
+// the merge of n_maps x per_map device records on the EKF stream, and its results to the caller's (host) arrays: rounds, transforms,
+// count and entries come back as one copy of the tables' tail into page-locked memory, after one wait
+int merge_records(aslam_ctx* c, const MapRecord* d_rec, int n_maps, int per_map, int anchor, int min_common, int max, int* n, int* ids,
+                  double* xyth, double* sigmas, int* n_seen, int* map_round, double* map_T) {
+    const MergeBufs& M = c->merge;
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, merge_run(st, M, d_rec, n_maps, per_map, anchor, min_common, nullptr));
+    HIP_TRY(c, hipMemcpyAsync(M.h_out, M.round, M.out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    auto host = [&M](const void* d) { return M.h_out + (static_cast<const char*>(d) - reinterpret_cast<const char*>(M.round)); };
+    int total = 0;
+    std::memcpy(&total, host(M.out_n), sizeof(int));
+    if (n) *n = total;
+    if (map_round) std::memcpy(map_round, host(M.round), sizeof(int) * n_maps);
+    if (map_T) std::memcpy(map_T, host(M.T), sizeof(double) * 3 * n_maps);
+    const size_t k = (size_t)std::min(total, max);
+    if (ids) std::memcpy(ids, host(M.out_ids), sizeof(int) * k);
+    if (n_seen) std::memcpy(n_seen, host(M.out_seen), sizeof(int) * k);
+    if (xyth) std::memcpy(xyth, host(M.out_xyth), sizeof(double) * 3 * k);
+    if (sigmas) std::memcpy(sigmas, host(M.out_sigma), sizeof(double) * 9 * k);
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_merge_map_records(aslam_ctx* c, const void* records, int records_on_device, int n_maps, int per_map, int anchor, int min_common,
+                            int max, int* n, int* ids, double* xyth, double* sigmas, int* n_seen, int* map_round, double* map_T) {
+    if (!c || !records) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (per_map < 1 || per_map > kIdTableSize) return fail(c, ASLAM_E_INVALID, "1..1024 records per map");
+    if (int r = merge_check(c, n_maps, anchor, min_common, max)) return r;
+    HIP_TRY(c, merge_alloc(c->merge));
+    const MapRecord* d_rec = static_cast<const MapRecord*>(records);
+    if (!records_on_device) {
+        const size_t count = (size_t)n_maps * per_map;
+        HIP_TRY(c, merge_reserve_records(c->merge, count));
+        HIP_TRY(c, hipMemcpyAsync(c->merge.rec, records, count * sizeof(MapRecord), hipMemcpyHostToDevice, c->stream_ekf));
+        d_rec = c->merge.rec;
+    }
+    return merge_records(c, d_rec, n_maps, per_map, anchor, min_common, max, n, ids, xyth, sigmas, n_seen, map_round, map_T);
+}
+
+int aslam_fleet_merge_maps(aslam_ctx* c, int anchor, int min_common, int max, int* n, int* ids, double* xyth, double* sigmas, int* n_seen,
+                           int* robot_round, double* robot_T) {
+    if (!c) return ASLAM_E_INVALID;
+    if (int r = allow(c, kFleetSlam)) return r;
+    const int R = c->fleet_n, per_map = c->ekf.max_landmarks;
+    if (int r = merge_check(c, R, anchor, min_common, max)) return r;     // per_map is the context's own capacity: any size
+    { int rs = sync_and_check(c); if (rs) return rs; }
+    HIP_TRY(c, merge_alloc(c->merge));
+    HIP_TRY(c, merge_reserve_records(c->merge, (size_t)R * per_map));
+    launch_fleet_export_maps(c->stream_ekf, c->fslam, c->merge.rec);
+    HIP_TRY(c, hipGetLastError());
+    return merge_records(c, c->merge.rec, R, per_map, anchor, min_common, max, n, ids, xyth, sigmas, n_seen, robot_round, robot_T);
+}
+
+int aslam_merge_scratch_bytes(aslam_ctx* c, long long* bytes) {
+    if (!c || !bytes) return fail(c, ASLAM_E_INVALID, "null argument");
+    *bytes = (long long)(c->merge.mem_bytes + c->merge.rec_cap * sizeof(MapRecord));
+    return ASLAM_OK;
 }
 
 // MapLoader markers -> planar landmarks: heading of the marker's +z axis (third column of Matrix3x3(orientation)), which is what an

@@ -147,6 +147,36 @@ void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R);
 void launch_ekf_gather(hipStream_t st, const FleetRound& R);
 void launch_ekf_small(hipStream_t st, const FleetRound& R);
 void launch_ekf_T(hipStream_t st, const FleetRound& R);
+// map merge (fleet_merge.h): n_maps <= kMergeMaxMaps maps of per_map MapRecord records each, aligned
+// into the anchor map's frame and fused per marker id.  The tables are one allocation made on first use (merge_alloc); rec is the
+// context's own record buffer (host records uploaded, or a fleet's export), grown on demand.
+constexpr int kMergeMaxMaps = 256;
+struct MergeBufs {
+    int* index;                        // n_maps x kIdTableSize: position of the id's record in its map, or -1
+    int* present;                      // reference table, per id: 1 = has a mean
+    double* mean;                      // ... (x, y, theta) in the anchor frame
+    int* round;                        // per map: round it was aligned in (0 the anchor, -1 not aligned)
+    double* T;                         // per map: (t_x, t_y, phi) into the anchor frame
+    int* aligned;                      // maps aligned so far
+    int* out_n;                        // ids in the table = output entries
+    int *out_ids, *out_seen;           // per output entry, ascending id: marker id, contributions fused
+    double *out_xyth, *out_sigma;      // ... mean (3) and covariance (9, row-major)
+    void* mem;                         // the allocation holding the tables above (nullptr: none), in the order above
+    size_t mem_bytes;
+    char* h_out;                       // page-locked copy of the allocation's tail, round ... out_sigma: what a merge returns
+    size_t out_bytes;
+    int* h_aligned;                    // page-locked word *aligned is read back into after every round
+    MapRecord* rec;
+    size_t rec_cap;                    // records rec holds
+};
+hipError_t merge_alloc(MergeBufs& M);
+void merge_free(MergeBufs& M);
+hipError_t merge_reserve_records(MergeBufs& M, size_t count);
+void launch_fleet_export_maps(hipStream_t st, const FleetSlam& F, MapRecord* out);   // F.n x max_landmarks records, robot-major
+// the whole merge of rec (device) on st; waits for st once per round and leaves the results in M.out_* (enqueued, not waited for);
+// *rounds = alignment rounds run
+hipError_t merge_run(hipStream_t st, const MergeBufs& M, const MapRecord* rec, int n_maps, int per_map, int anchor, int min_common,
+                     int* rounds);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,

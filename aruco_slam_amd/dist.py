@@ -90,6 +90,16 @@ class MapGather:
             self.torch.cuda.current_stream().synchronize()
         return self.all
 
+    def merge(self, anchor=0, min_common=2):
+        """one map from the gathered ones (Context.merge_map_records: map r = rank r, aligned into rank `anchor`'s frame).  After a
+        GPU gather the records are merged where they lie, in device memory; the collective that wrote them must have completed
+        (gather() followed by a synchronize of torch's stream, or flush())."""
+        n = int(self.ctx.init.max_landmarks)
+        if self.on_gpu:
+            self.torch.cuda.current_stream().synchronize()
+            return self.ctx.merge_map_records(self.all.data_ptr(), self.world, n, anchor, min_common, on_device=True)
+        return self.ctx.merge_map_records(self.all.numpy(), self.world, n, anchor, min_common)
+
     def records(self):
         """gathered maps as a (world, max_landmarks) structured array (host copy)"""
         buf = self.all.cpu().numpy().tobytes()

@@ -297,6 +297,50 @@ int aslam_fleet_get_state(aslam_ctx* ctx, int robot, int* N, double* mu, double*
 int aslam_fleet_set_state(aslam_ctx* ctx, int robot, int N, const double* mu, const double* sigma, const int* landmark_ids);
 int aslam_fleet_get_landmark_ids(aslam_ctx* ctx, int robot, int* L, int* ids);
 
+/* ---- map merge: one shared map from the robots of a SLAM fleet or from gathered GPUs (no reference counterpart) ----
+ * Input: n_maps maps (1 <= n_maps <= ASLAM_MAX_ROBOTS) of per_map records each (1 <= per_map <= 1024), map-major, every record the
+ * ASLAM_MAP_RECORD_BYTES record of aslam_export_map { int32 id, int32 index, f64 x, y, theta, f64 S[9] }.  A record whose id is outside
+ * [0, 1024) is unused (id = -1 included); of two records of one map with the same id the one at the lower position counts.  Every
+ * map is in a frame of its own (a SLAM robot's map is in its start frame).  anchor in [0, n_maps) names the map whose frame the
+ * result is in; min_common in [2, 1024] is the number of shared ids an alignment needs.
+ * A reference table holds per marker id a presence flag and a mean (x, y, theta) in the anchor frame.  It starts as the anchor's
+ * records; the anchor has round 0 and the identity transform.  Rounds k = 1, 2, ...: first every map not yet aligned is tested
+ * against the table as the round found it.  With K the ids both have (ascending), p_j the map's positions and q_j the table's:
+ * |K| < min_common, the map waits; otherwise, in f64, pm / qm the centroids, a = sum (p_j - pm) x (q_j - qm) (2-D cross product),
+ * b = sum (p_j - pm) . (q_j - qm); a = b = 0 (every common landmark on one point), the map waits; otherwise phi = atan2(a, b),
+ * t = qm - R(phi) pm and the map is aligned in round k with T = (t_x, t_y, phi).  Headings do not enter the alignment.  Then every
+ * id the table lacks is inserted from the lowest-indexed map aligned in this round that has it, as (R(phi)(x, y) + t,
+ * wrap(theta + phi)), wrap being the library's single normAngle wrap, which maps into [-pi, pi): a heading of exactly pi comes out
+ * as -pi.  The rounds end when one aligns no map or all are aligned;
+ * a map never aligned has round -1, T = (0, 0, 0) and contributes nothing.
+ * Fusion, once per id of the table, over the aligned maps that hold it in ascending map order: C = (S + S^T) / 2, C' = J C J^T with
+ * J = blockdiag(R(phi), 1), m' the transformed mean; a contribution whose C' has a non-finite entry or a leading principal minor
+ * <= 0 is skipped.  With m0 the table's mean and d = m' - m0 (theta component wrapped): Lambda = sum C'^-1,
+ * m = m0 + Lambda^-1 sum C'^-1 d (theta wrapped), covariance Lambda^-1, n_seen = contributions used; none usable: m0, a zero
+ * covariance, n_seen 0.  Deliberately dropped: the uncertainty of the alignment itself, and the correlations between different
+ * landmarks of one map (a frozen localization map has Sigma_ll = 0 anyway).  No floating-point atomics: the same input gives the
+ * same bits.
+ * Output, one entry per id of the table in ascending id order: ids, xyth (n x 3), sigmas (n x 9, row-major), n_seen - exactly what
+ * aslam_localize_begin / aslam_fleet_begin take as a map; per map map_round and map_T (3 per map).  *n receives the number of
+ * entries available, at most max are written; any output pointer may be NULL. */
+/* a pure function of its input: allowed in every mode, touches no filter, synchronous.  records_on_device != 0: records is a
+   device pointer, e.g. the destination of aslam_comm_gather_maps (n_maps = world, per_map = max_landmarks).  ASLAM_E_INVALID: a null
+   context or records, n_maps, per_map, anchor or min_common outside the ranges above, max < 0.  The limit on per_map holds for
+   device records too: a gather from contexts created with max_landmarks > 1024 is refused here (a map holds at most 1024 distinct
+   ids, so such a buffer can be compacted to 1024 records per map first). */
+int aslam_merge_map_records(aslam_ctx* ctx, const void* records, int records_on_device, int n_maps, int per_map, int anchor,
+                            int min_common, int max, int* n, int* ids, double* xyth, double* sigmas, int* n_seen, int* map_round,
+                            double* map_T);
+/* the same on the R maps of the active SLAM fleet (map r = robot r, per_map = max_landmarks): does what aslam_sync does and returns
+   its error if any, exports all robots' maps with one launch and merges them; no robot's filter changes.  ASLAM_E_STATE outside
+   fleet SLAM; ASLAM_E_INVALID: a null context, anchor outside [0, R), min_common outside [2, 1024], max < 0.  max_landmarks is not
+   limited here: a fleet of any capacity merges.  The scratch tables and the record buffer of both calls are allocated on first use
+   and freed by aslam_fleet_end / aslam_destroy. */
+int aslam_fleet_merge_maps(aslam_ctx* ctx, int anchor, int min_common, int max, int* n, int* ids, double* xyth, double* sigmas,
+                           int* n_seen, int* robot_round, double* robot_T);
+/* device memory the two calls above hold at present: tables plus record buffer, 0 before the first merge and after aslam_fleet_end */
+int aslam_merge_scratch_bytes(aslam_ctx* ctx, long long* bytes);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
@@ -336,7 +380,8 @@ int aslam_export_wait(aslam_ctx* ctx, int buffer);
  * torch - shares its copy).  Rank 0 calls aslam_comm_get_unique_id and hands the 128 bytes to the other ranks by any
  * out-of-band means (ROS parameter, file, socket); every rank then calls aslam_comm_create(ctx, id, world, rank).
  * aslam_comm_gather_maps exports this rank's map behind the EKF steps enqueued so far, all-gathers, and writes
- * world x max_landmarks records (rank-major) to dst (host, or device if dst_is_device).  Read-only: nothing is fused back. */
+ * world x max_landmarks records (rank-major) to dst (host, or device if dst_is_device).  Read-only: nothing is fused back into
+ * any filter (aslam_merge_map_records makes one map of the gathered ones). */
 #define ASLAM_COMM_ID_BYTES 128
 int aslam_comm_get_unique_id(void* id /* ASLAM_COMM_ID_BYTES */);
 int aslam_comm_create(aslam_ctx* ctx, const void* id, int world, int rank);
