@@ -98,6 +98,16 @@ class MarkerMsg(C.Structure):
                 ("orientation", C.c_double * 4), ("lifetime_sec", C.c_double)]
 
 
+class RelocalizeParams(C.Structure):
+    """mirror of aslam_relocalize_params"""
+    _fields_ = [("tol_xy", C.c_double), ("tol_th", C.c_double), ("min_inliers", C.c_int)]
+
+
+# mirror of aslam_relocalize_result: what Context.relocalize / fleet_relocalize return (sigma row-major 3 x 3)
+RELOC_DTYPE = np.dtype([("status", "<i4"), ("n_candidates", "<i4"), ("n_inliers", "<i4"), ("runner_up", "<i4"), ("best", "<i4"),
+                        ("pose", "<f8", (3,)), ("sigma", "<f8", (3, 3))], align=True)
+
+
 class AslamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aslam error {code} ({E_NAMES.get(code, '?')}): {msg}")
@@ -140,6 +150,9 @@ _SIGS = {
                                           _ip, _ip, _dp]),
     "aslam_fleet_merge_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _ip, _ip, _dp]),
     "aslam_merge_scratch_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "aslam_default_relocalize_params": (None, [_P(RelocalizeParams)]),
+    "aslam_relocalize": (C.c_int, [C.c_void_p, C.c_int, _P(RelocalizeParams), C.c_int, C.c_void_p]),
+    "aslam_fleet_relocalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _P(RelocalizeParams), C.c_int, C.c_void_p]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -516,6 +529,33 @@ class Context:
         b = C.c_longlong()
         self._ck(self.lib.aslam_merge_scratch_bytes(self.h, C.byref(b)))
         return b.value
+
+    # -- relocalization: lost poses from one frame against the frozen map ---------------------------------------
+    def _reloc_params(self, params):
+        """None when no parameter is given (the library's defaults), else the defaults with the given fields replaced"""
+        if not params:
+            return None
+        p = RelocalizeParams()
+        self.lib.aslam_default_relocalize_params(C.byref(p))
+        for k, v in params.items():
+            if k not in ("tol_xy", "tol_th", "min_inliers"):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return C.byref(p)
+
+    def relocalize(self, slot, apply=True, **params):
+        """the localizing filter's pose from slot's observation list; params: tol_xy, tol_th, min_inliers.  A RELOC_DTYPE record"""
+        out = np.zeros(1, RELOC_DTYPE)
+        self._ck(self.lib.aslam_relocalize(self.h, int(slot), self._reloc_params(params), 1 if apply else 0, out.ctypes.data_as(C.c_void_p)))
+        return out[0]
+
+    def fleet_relocalize(self, first, robots, apply=True, **params):
+        """slot first + i is robot robots[i]'s frame; one RELOC_DTYPE record per slot"""
+        rs = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(rs.size, 1), RELOC_DTYPE)
+        self._ck(self.lib.aslam_fleet_relocalize(self.h, int(first), int(rs.size), _ptr(rs, _ip), self._reloc_params(params), 1 if apply else 0,
+                                                 out.ctypes.data_as(C.c_void_p)))
+        return out[:rs.size]
 
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))

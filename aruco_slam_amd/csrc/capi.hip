@@ -146,6 +146,7 @@ struct aslam_ctx {
     // requested; the cameras, armed flags and work-list buffers above serve it as they serve fleet localization
     FleetSlam fslam{};
     MergeBufs merge{};                    // map merge: tables allocated by the first merge, freed at aslam_fleet_end / aslam_destroy
+    RelocBufs reloc{};                    // relocalization: result records, allocated by the first call, freed at the same two places
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -218,6 +219,7 @@ int allow(aslam_ctx* c, unsigned allowed) {
     if ((now & kFleet) && !(allowed & kFleet)) why = "a fleet is active: this call reads or writes the single filter or camera (aslam_fleet_end first)";
     else if (c->mode == Mode::FleetSlam) why = "fleet SLAM: a robot's pose is correlated with its map (aslam_fleet_set_state)";
     else if (allowed == kFleetSlam) why = "no fleet SLAM (aslam_fleet_slam_begin first)";
+    else if (allowed == kLocalize) why = "not localizing (aslam_localize_begin first)";
     else if (!(allowed & kSingle)) why = "no fleet (aslam_fleet_begin first)";
     else if (allowed & kFleet) why = "localizing: one filter is active (aslam_localize_end first)";     // a call that starts a fleet
     else why = "localizing: the map is frozen (aslam_localize_end first)";
@@ -817,6 +819,7 @@ void aslam_destroy(aslam_ctx* c) {
     ekf_free(c->ekf);
     ekf_fleet_free(c->fslam);
     merge_free(c->merge);
+    reloc_free(c->reloc);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
     hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
     pinned_free(c->fleet_camidx_up);
@@ -2290,6 +2293,7 @@ int aslam_fleet_end(aslam_ctx* c) {
     if (int r = allow(c, kFleet)) return r;
     { int rs = sync_streams(c); if (rs) return rs; }
     merge_free(c->merge);                               // the map merge's tables and record buffer, if a merge made them
+    reloc_free(c->reloc);                               // the relocalization's result records, if a call made them
     return enter_mode(c, Mode::Slam);
 }
 
@@ -2411,6 +2415,84 @@ int aslam_fleet_merge_maps(aslam_ctx* c, int anchor, int min_common, int max, in
 int aslam_merge_scratch_bytes(aslam_ctx* c, long long* bytes) {
     if (!c || !bytes) return fail(c, ASLAM_E_INVALID, "null argument");
     *bytes = (long long)(c->merge.mem_bytes + c->merge.rec_cap * sizeof(MapRecord));
+    return ASLAM_OK;
+}
+
+// ---- relocalization: lost poses from one frame against the frozen map (include/aruco_slam_hip.h) ----------------
+void aslam_default_relocalize_params(aslam_relocalize_params* p) {
+    if (!p) return;
+    p->tol_xy = 0.25;
+    p->tol_th = 0.2;
+    p->min_inliers = 2;
+}
+
+namespace {
+int reloc_params(aslam_ctx* c, const aslam_relocalize_params* params, RelocParams& out) {
+    aslam_relocalize_params p;
+    aslam_default_relocalize_params(&p);
+    if (params) p = *params;
+    if (!std::isfinite(p.tol_xy) || !(p.tol_xy > 0.0)) return fail(c, ASLAM_E_INVALID, "tol_xy must be finite and positive");
+    if (!std::isfinite(p.tol_th) || !(p.tol_th > 0.0) || p.tol_th >= 3.14159265358979323846)
+        return fail(c, ASLAM_E_INVALID, "tol_th must be finite, positive and below pi");
+    if (p.min_inliers < 1 || p.min_inliers > kMarkerMax) return fail(c, ASLAM_E_INVALID, "min_inliers 1..128");
+    out.tol_xy2 = p.tol_xy * p.tol_xy;
+    out.tol_th = p.tol_th;
+    out.min_inliers = p.min_inliers;
+    return ASLAM_OK;
+}
+
+// k_relocalize on slots [first, first + count) on the EKF stream, behind the detection that produced their lists and every EKF step
+// enqueued so far: one launch, one copy of the records into page-locked memory, one wait.  d_robots: the robots' indices on the
+// device (a fleet), or nullptr (the single filter).
+int relocalize_slots(aslam_ctx* c, int first, int count, const int* d_robots, const RelocParams& prm, int apply, aslam_relocalize_result* out) {
+    HIP_TRY(c, reloc_alloc(c->reloc, c->max_batch));
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    launch_relocalize(st, c->ekf, c->fleet, prm, c->d_obs, c->d_nmarkers, first, count, d_robots, apply, c->reloc.d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->reloc.h, c->reloc.d, sizeof(RelocRecord) * count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int i = 0; i < count; i++) {
+        const RelocRecord& r = c->reloc.h[i];
+        aslam_relocalize_result& o = out[i];
+        o.status = r.status; o.n_candidates = r.n_candidates; o.n_inliers = r.n_inliers; o.runner_up = r.runner_up; o.best = r.best;
+        std::memcpy(o.pose, r.pose, sizeof(o.pose));
+        std::memcpy(o.sigma, r.sigma, sizeof(o.sigma));
+    }
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_relocalize(aslam_ctx* c, int slot, const aslam_relocalize_params* params, int apply, aslam_relocalize_result* out) {
+    if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kLocalize)) return r;
+    RelocParams prm{};
+    if (int r = reloc_params(c, params, prm)) return r;
+    if (int r = check_slot_range(c, slot, 1)) return r;
+    if (int r = finalize_pending(c)) return r;
+    return relocalize_slots(c, slot, 1, nullptr, prm, apply ? 1 : 0, out);
+}
+
+int aslam_fleet_relocalize(aslam_ctx* c, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params, int apply,
+                           aslam_relocalize_result* out) {
+    if (!c || !robot_of_slot || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (c->mode == Mode::FleetSlam) return fail(c, ASLAM_E_STATE, "fleet SLAM: every robot has a map of its own, there is no shared map to relocalize against");
+    if (int r = allow(c, kFleetLocalize)) return r;
+    RelocParams prm{};
+    if (int r = reloc_params(c, params, prm)) return r;
+    if (int r = check_slot_range(c, first, count)) return r;
+    std::vector<char> seen(c->fleet_n, 0);
+    for (int i = 0; i < count; i++) {
+        if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+        if (seen[robot_of_slot[i]]) return fail(c, ASLAM_E_INVALID, "a robot named twice in one aslam_fleet_relocalize");
+        seen[robot_of_slot[i]] = 1;
+    }
+    if (int r = finalize_pending(c)) return r;
+    if (int r = pinned_upload(c, c->fleet_work_up, c->d_fleet_work, robot_of_slot, count, c->stream_ekf)) return r;
+    if (int r = relocalize_slots(c, first, count, c->d_fleet_work, prm, apply ? 1 : 0, out)) return r;
+    if (apply)
+        for (int i = 0; i < count; i++)
+            if (out[i].status == 0) c->fleet_armed[robot_of_slot[i]] = 0;      // seated as by aslam_fleet_set_pose: its next frame only arms it
     return ASLAM_OK;
 }
 

@@ -177,6 +177,28 @@ void launch_fleet_export_maps(hipStream_t st, const FleetSlam& F, MapRecord* out
 // *rounds = alignment rounds run
 hipError_t merge_run(hipStream_t st, const MergeBufs& M, const MapRecord* rec, int n_maps, int per_map, int anchor, int min_common,
                      int* rounds);
+// relocalization (relocalize.h): per slot of a call one 128-byte result record (16 doubles: the five counts as int32
+// in the first four, then pose and covariance), in a device buffer made on first use together with its page-locked copy
+struct RelocParams {
+    double tol_xy2, tol_th;            // tol_xy squared; heading tolerance
+    int min_inliers;
+};
+struct RelocRecord {
+    int status, n_candidates, n_inliers, runner_up, best, pad[3];
+    double pose[3];
+    double sigma[9];                   // row-major
+};
+struct RelocBufs {
+    RelocRecord* d;                    // one record per slot of a call (nullptr: none)
+    RelocRecord* h;                    // page-locked: what a call reads back
+    int cap;                           // records each holds
+};
+hipError_t reloc_alloc(RelocBufs& B, int slots);
+void reloc_free(RelocBufs& B);
+// slots [first, first + count), workgroup i on slot first + i, its record out[i].  robot_of_slot (device, count entries): with apply
+// a solved slot seats that robot's pose block in F; nullptr: the single filter's (mu_x, Sigma_xx of E, last-observed length 0)
+void launch_relocalize(hipStream_t st, const EkfState& E, const FleetState& F, const RelocParams& prm, const ObsRaw* obs,
+                       const unsigned* n_markers, int first, int count, const int* robot_of_slot, int apply, RelocRecord* out);
 int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,

@@ -1528,3 +1528,4 @@ void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
 #include "ekf_localize.h"     // localization against a frozen map: k_loc_steps and its launcher
 #include "ekf_fleet.h"        // fleet localization: k_fleet_steps, one workgroup per robot, and its launcher
 #include "fleet_merge.h"      // map merge: k_fleet_export_maps, k_merge_*, and their launchers
+#include "relocalize.h"       // relocalization: k_relocalize, one workgroup per slot, and its launcher

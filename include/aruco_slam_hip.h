@@ -341,6 +341,50 @@ int aslam_fleet_merge_maps(aslam_ctx* ctx, int anchor, int min_common, int max, 
 /* device memory the two calls above hold at present: tables plus record buffer, 0 before the first merge and after aslam_fleet_end */
 int aslam_merge_scratch_bytes(aslam_ctx* ctx, long long* bytes);
 
+/* ---- relocalization: lost poses from one frame against the frozen map (no reference counterpart) ---------------
+ * Localization and fleet localization need a pose and a Sigma_xx from the caller before the first frame, and a filter whose pose is
+ * wrong by a metre never converges (its corrections are linearised at that pose).  These calls turn one slot's observation list
+ * (what aslam_get_slot_raw_observations returns: already in the base frame) and the frozen map into a pose and a covariance, on the
+ * device, for any number of slots in one launch.  Read-only apart from the optional seating of the pose (apply != 0).
+ * Parameters: tol_xy (m) and tol_th (rad) bound the distance between two pose hypotheses that support each other, min_inliers is
+ * the consensus a solution needs.  The defaults (0.25 m, 0.2 rad, 2) are the maintainer's choice; nobody has measured them.
+ * ASLAM_E_INVALID: tol_xy or tol_th not finite or not positive, tol_th >= pi, min_inliers outside [1, 128].
+ * For one slot, over its first nM = min(number of observations, 128) observations in list order:
+ * 1. Candidates.  Observation j is a candidate iff valid != 0, 0 <= id < 1024, the id is in the map, x, y, theta are finite and
+ *    r0, r1, r2 are finite and > 0.  An id seen twice gives two candidates.
+ * 2. Hypotheses.  With the id's landmark (lx, ly, lt): theta_j = wrap(lt - theta), c = cos theta_j, s = sin theta_j,
+ *    x_j = lx - (c x - s y), y_j = ly - (s x + c y): the pose at which the localization step's z_hat equals the observation.  wrap is
+ *    the library's single normAngle wrap, into [-pi, pi).
+ * 3. Consensus.  Candidate k supports candidate j iff (x_k - x_j)^2 + (y_k - y_j)^2 <= tol_xy^2 and |wrap(theta_k - theta_j)| <=
+ *    tol_th; a candidate supports itself.  count_j = supporters of j.  The winner b has the greatest count, ties to the lowest list
+ *    position.  runner_up = the greatest count among the candidates that do not support b, 0 if there is none: reported only, so that
+ *    a caller can reject an ambiguous frame (two places of the map that look alike).
+ * 4. Status.  1: no candidate (n_candidates = n_inliers = runner_up = 0, best = -1).  2: count_b < min_inliers (n_inliers = count_b,
+ *    best, runner_up and n_candidates as found).  0: solved.  With status != 0 pose and sigma are zero and nothing is seated.
+ * 5. Fusion over the supporters of b in ascending list position, in information form around m0 = hypothesis b:
+ *    J = [[-c, s, -(s x + c y)], [-s, -c, c x - s y], [0, 0, -1]] (the hypothesis' derivative by the observation), C = J diag(r) J^T,
+ *    Lambda = sum C^-1, m = m0 + Lambda^-1 sum C^-1 d with d = m_j - m0, its theta component wrapped (headings fuse across the wrap);
+ *    pose = m with theta wrapped, sigma = Lambda^-1 (row-major), n_inliers = count_b, best = b's list position.
+ * Every sum has a fixed order and there is no floating-point atomic: the same input gives the same bits, whatever else the call
+ * carries.  Dropped: the map's own uncertainty (zero in a frozen map) and any accumulation over several frames. */
+typedef struct { double tol_xy, tol_th; int min_inliers; } aslam_relocalize_params;
+typedef struct { int status, n_candidates, n_inliers, runner_up, best; double pose[3], sigma[9]; } aslam_relocalize_result;
+void aslam_default_relocalize_params(aslam_relocalize_params* params);
+/* Both calls are synchronous.  Their one kernel launch runs behind the detection and the EKF steps submitted so far, so they may
+   follow aslam_run_staged / aslam_fleet_run_staged (with_ekf = 0) or an injection directly; the results come back in one copy.
+   params NULL = the defaults.  The result records live in a device buffer allocated by the first call and freed by aslam_fleet_end /
+   aslam_destroy.
+   aslam_relocalize: the single filter, only while localizing (ASLAM_E_STATE otherwise); a bad slot is ASLAM_E_INVALID.  With apply
+   and status 0 the pose and Sigma_xx are replaced and the last-observed list is emptied; the arming is left as aslam_localize_begin
+   leaves it. */
+int aslam_relocalize(aslam_ctx* ctx, int slot, const aslam_relocalize_params* params, int apply, aslam_relocalize_result* out);
+/* slot first + i belongs to robot robot_of_slot[i], its result is out[i].  Only in fleet localization (ASLAM_E_STATE otherwise: a
+   SLAM fleet has no shared map); ASLAM_E_INVALID: a slot range outside [0, max_batch), a robot index outside the fleet, a robot named
+   twice.  With apply every solved robot is seated as by aslam_fleet_set_pose (pose, Sigma_xx, list emptied, disarmed: its next frame
+   only arms it); unsolved robots are untouched. */
+int aslam_fleet_relocalize(aslam_ctx* ctx, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params,
+                           int apply, aslam_relocalize_result* out /* count */);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
