@@ -116,6 +116,7 @@ class AslamError(RuntimeError):
 
 _P = C.POINTER
 _u8p, _ip, _fp, _dp, _llp = _P(C.c_uint8), _P(C.c_int), _P(C.c_float), _P(C.c_double), _P(C.c_longlong)
+_up = _P(C.c_uint)
 
 _SIGS = {
     "aslam_default_init": (None, [_P(AslamInit)]),
@@ -202,6 +203,10 @@ _SIGS = {
     "aslam_debug_inject_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "aslam_debug_inject_quads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "aslam_debug_run_quads": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "aslam_debug_run_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "aslam_debug_get_nodes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _up, _up, _up, _ip]),
+    "aslam_debug_get_write_tickets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _up, _up, _up, _up]),
+    "aslam_debug_get_link_todo": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "aslam_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_profile_reset": (C.c_int, [C.c_void_p]),
     "aslam_get_plan_stats": (C.c_int, [C.c_void_p, _llp]),
@@ -791,6 +796,35 @@ class Context:
         """the quad stage (stages & 1) and candidate assembly (stages & 2) alone on the slots' injected lists; waits, and raises on
         an overflowed list as sync() does"""
         self._ck(self.lib.aslam_debug_run_quads(self.h, int(first), int(count), int(stages)))
+
+    def run_contours(self, first, count, cut_grid=0, lds_nodes=-1):
+        """the contour stage alone on staged frames (threshold, border nodes, segments, cycle resolution, point writer); waits, and
+        raises on an overflowed list as sync() does.  cut_grid 0 / 32 / 64; lds_nodes >= 0: node count above which the serial form
+        resolves a frame"""
+        self._ck(self.lib.aslam_debug_run_contours(self.h, int(first), int(count), int(cut_grid), int(lds_nodes)))
+
+    def debug_nodes(self, slot):
+        """(state, next, steps, area) of the slot's node list: packed states as listed (0xFFFFFFFF = unused entry) and segment records"""
+        n = C.c_int()
+        self.lib.aslam_debug_get_nodes(self.h, int(slot), 0, C.byref(n), None, None, None, None)     # (the size; E_CAPACITY unless empty)
+        k = n.value
+        state = np.zeros(k, np.uint32); nxt = np.zeros(k, np.uint32); steps = np.zeros(k, np.uint32); area = np.zeros(k, np.int32)
+        self._ck(self.lib.aslam_debug_get_nodes(self.h, int(slot), k, C.byref(n), _ptr(state, _up), _ptr(nxt, _up), _ptr(steps, _up), _ptr(area, _ip)))
+        return state, nxt, steps, area
+
+    def debug_write_tickets(self, slot):
+        """(state, contour, rel, cnt) of the slot's write tickets; cnt = points | steps skipped first << 16"""
+        n = C.c_int()
+        self.lib.aslam_debug_get_write_tickets(self.h, int(slot), 0, C.byref(n), None, None, None, None)
+        k = n.value
+        state = np.zeros(k, np.uint32); ci = np.zeros(k, np.uint32); rel = np.zeros(k, np.uint32); cnt = np.zeros(k, np.uint32)
+        self._ck(self.lib.aslam_debug_get_write_tickets(self.h, int(slot), k, C.byref(n), _ptr(state, _up), _ptr(ci, _up), _ptr(rel, _up), _ptr(cnt, _up)))
+        return state, ci, rel, cnt
+
+    def debug_link_todo(self, slot):
+        v = C.c_int()
+        self._ck(self.lib.aslam_debug_get_link_todo(self.h, int(slot), C.byref(v)))
+        return v.value
 
     def sync(self):
         self._ck(self.lib.aslam_sync(self.h))

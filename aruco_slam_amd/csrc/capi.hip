@@ -470,6 +470,48 @@ void launch_identify_stage(aslam_ctx* c, hipStream_t st, const DetectCfg& g, int
     prof_end(c);
 }
 
+// pitch of the cut lattice of a call of `count` frames (latency: the configuration of a one-frame call): one frame gets a finer
+// lattice - its longest segment sets the latency of k_seg / k_trace_write, and the extra nodes (x 1.6) still fit k_link's LDS image
+// for frames up to a megapixel or so
+int cut_grid_of_call(const DetectCfg& g, int count, bool latency) {
+    return (count == 1 || latency) && (size_t)g.rows * g.cols <= (size_t)1200 * 1000 ? kCutGridSingle : kCutGrid;
+}
+
+// The contour stage of frames [f0, f0 + nf) on stream st: counts cleared, k_threshold, k_prefix, k_seg, k_link, k_link_serial, k_prefix,
+// k_trace_write.  g carries the call's cut lattice; lds_nodes < 0: k_link's own hand-over limit.  run_detect and
+// aslam_debug_run_contours both launch it from here.
+void launch_contour_stage(aslam_ctx* c, hipStream_t st, const DetectCfg& g, int f0, int nf, int lds_nodes = -1) {
+    const size_t frame_px = (size_t)g.rows * g.cols;
+    const bool alias_gray = c->channels == 1;              // staged gray frames are tight: the detector reads them in place
+    // queue heads, work count and the per-frame list sizes of these frames, in one launch (the overflow mask is sticky)
+    launch_clear_counts(st, nf, c->d_ctr, c->d_nstarts + f0, c->d_ncontours + f0, c->d_npoints + f0, c->d_nwrite + f0, c->d_ncand + f0);
+    const uint8_t* in = c->d_in + (size_t)f0 * c->in_frame_bytes;
+    uint8_t* nbr = c->d_nbr + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch);
+    unsigned* starts = c->d_starts + (size_t)f0 * g.cap_starts;
+    ContourRec* contours = c->d_contours + (size_t)f0 * g.cap_contours;
+    unsigned* points = c->d_points + (size_t)f0 * g.cap_points;
+    prof_begin(c, P_THRESH, st);
+    launch_threshold(st, in, c->channels, c->in_frame_bytes, (size_t)g.cols * c->channels, nf,
+                     alias_gray ? nullptr : c->d_gray + (size_t)f0 * frame_px, nbr, g, starts, c->d_nstarts + f0,
+                     c->d_nodeplane + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch), c->d_ctr);
+    prof_end(c);
+    prof_begin(c, P_SEG, st);
+    launch_prefix(st, nf, c->d_nstarts + f0, g.cap_starts, 1u, c->d_pre_trace);
+    NodeRec* nodes = c->d_nodes + (size_t)f0 * g.cap_starts;
+    WriteRec* wlist = c->d_wlist + (size_t)f0 * g.cap_write;
+    launch_seg(st, c->nwaves, nbr, g, nf, starts, c->d_nstarts + f0, c->d_nodeplane + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch),
+               c->d_pre_trace, c->d_ctr, nodes);
+    prof_end(c);
+    prof_begin(c, P_LINK, st);
+    launch_link(st, g, nf, c->d_nstarts + f0, c->d_ctr, nodes, c->d_link_todo + f0, contours, c->d_ncontours + f0, c->d_npoints + f0, wlist,
+                c->d_nwrite + f0, lds_nodes);
+    prof_end(c);
+    prof_begin(c, P_WRITE, st);
+    launch_prefix(st, nf, c->d_nwrite + f0, g.cap_write, 1u, c->d_pre_write);
+    launch_trace_write(st, std::max(64, c->nwaves / 4), nbr, g, nf, c->d_pre_write, c->d_ctr, contours, wlist, c->d_nwrite + f0, points);
+    prof_end(c);
+}
+
 // detection + pose of the call's frames (asynchronous on the stream).  latency: the configuration of a one-frame call (one rig step)
 int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = false, hipEvent_t wait_before = nullptr) {
     const int first = k.first, count = k.count;
@@ -482,11 +524,7 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
     c->last_detect = st;
     if (wait_before) HIP_TRY(c, hipStreamWaitEvent(st, wait_before, 0));          // frames still in flight on the copy stream
     DetectCfg g = c->cfg;
-    // one frame (the drop-in call): a finer cut lattice - its longest segment sets the latency of k_seg / k_trace_write, and the extra nodes
-    // (x 1.6) still fit k_link's LDS image for frames up to a megapixel or so
-    g.cut_mask = ((count == 1 || latency) && (size_t)g.rows * g.cols <= (size_t)1200 * 1000 ? kCutGridSingle : kCutGrid) - 1;
-    const size_t frame_px = (size_t)g.rows * g.cols;
-    const bool alias_gray = c->channels == 1;              // staged gray frames are tight: the detector reads them in place
+    g.cut_mask = cut_grid_of_call(g, count, latency) - 1;
     c->last_first = first;
     c->last_count = count;
     if (c->ekf_count > 0 && first < c->ekf_hi && c->ekf_lo < first + count) {
@@ -500,34 +538,10 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
     const int chunk = detect_chunk();
     for (int f0 = first; f0 < first + count; f0 += chunk) {
         const int nf = std::min(chunk, first + count - f0);
-        // queue heads, work count and the per-frame list sizes of these frames, in one launch (the overflow mask is sticky)
-        launch_clear_counts(st, nf, c->d_ctr, c->d_nstarts + f0, c->d_ncontours + f0, c->d_npoints + f0, c->d_nwrite + f0, c->d_ncand + f0);
-        const uint8_t* in = c->d_in + (size_t)f0 * c->in_frame_bytes;
-        uint8_t* nbr = c->d_nbr + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch);
+        launch_contour_stage(c, st, g, f0, nf);
         const uint8_t* gray = slot_gray(c, f0);
-        unsigned* starts = c->d_starts + (size_t)f0 * g.cap_starts;
-        ContourRec* contours = c->d_contours + (size_t)f0 * g.cap_contours;
-        unsigned* points = c->d_points + (size_t)f0 * g.cap_points;
-        prof_begin(c, P_THRESH, st);
-        launch_threshold(st, in, c->channels, c->in_frame_bytes, (size_t)g.cols * c->channels, nf,
-                         alias_gray ? nullptr : c->d_gray + (size_t)f0 * frame_px, nbr, g, starts, c->d_nstarts + f0,
-                         c->d_nodeplane + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch), c->d_ctr);
-        prof_end(c);
-        prof_begin(c, P_SEG, st);
-        launch_prefix(st, nf, c->d_nstarts + f0, g.cap_starts, 1u, c->d_pre_trace);
-        NodeRec* nodes = c->d_nodes + (size_t)f0 * g.cap_starts;
-        WriteRec* wlist = c->d_wlist + (size_t)f0 * g.cap_write;
-        launch_seg(st, c->nwaves, nbr, g, nf, starts, c->d_nstarts + f0, c->d_nodeplane + (size_t)f0 * kScales * nbr_plane_bytes(g.rows, g.pitch),
-                   c->d_pre_trace, c->d_ctr, nodes);
-        prof_end(c);
-        prof_begin(c, P_LINK, st);
-        launch_link(st, g, nf, c->d_nstarts + f0, c->d_ctr, nodes, c->d_link_todo + f0, contours, c->d_ncontours + f0, c->d_npoints + f0, wlist,
-                    c->d_nwrite + f0);
-        prof_end(c);
-        prof_begin(c, P_WRITE, st);
-        launch_prefix(st, nf, c->d_nwrite + f0, g.cap_write, 1u, c->d_pre_write);
-        launch_trace_write(st, std::max(64, c->nwaves / 4), nbr, g, nf, c->d_pre_write, c->d_ctr, contours, wlist, c->d_nwrite + f0, points);
-        prof_end(c);
+        const ContourRec* contours = c->d_contours + (size_t)f0 * g.cap_contours;
+        const unsigned* points = c->d_points + (size_t)f0 * g.cap_points;
         prof_begin(c, P_QUADS, st);
         launch_prefix(st, nf, c->d_ncontours + f0, g.cap_contours, 1u, c->d_pre_quads);
         launch_quads(st, c->nwaves, g, nf, c->d_ctr, contours, c->d_ncontours + f0, c->d_pre_quads, points,
@@ -3154,6 +3168,87 @@ int aslam_debug_run_quads(aslam_ctx* c, int first, int count, int stages) {
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
     HIP_TRY(c, hipGetLastError());
     return sync_and_check(c);             // a candidate or pair list that overflowed: ASLAM_E_CAPACITY, as aslam_sync reports it
+}
+
+int aslam_debug_run_contours(aslam_ctx* c, int first, int count, int cut_grid, int lds_nodes) {
+    if (!c) return ASLAM_E_INVALID;
+    if (cut_grid != 0 && cut_grid != kCutGridSingle && cut_grid != kCutGrid) return fail(c, ASLAM_E_INVALID, "cut_grid: 0 (the call's own), 32 or 64");
+    int r = check_slots_staged(c, first, count);
+    if (r) return r;
+    r = sync_streams(c);
+    if (r) return r;
+    hipStream_t st = c->stream;
+    if (c->last_detect && c->last_detect != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    c->last_detect = st;
+    c->last_first = first;
+    c->last_count = count;
+    DetectCfg g = c->cfg;
+    g.cut_mask = (cut_grid ? cut_grid : cut_grid_of_call(g, count, count == 1)) - 1;
+    // every ticket of these slots reads "unused" until a link kernel writes it: one it should have written and did not then shows in
+    // the list, whatever an earlier call left there
+    HIP_TRY(c, hipMemsetAsync(c->d_wlist + (size_t)first * g.cap_write, 0xFF, sizeof(WriteRec) * (size_t)count * g.cap_write, st));
+    const int chunk = detect_chunk();
+    for (int f0 = first; f0 < first + count; f0 += chunk) launch_contour_stage(c, st, g, f0, std::min(chunk, first + count - f0), lds_nodes);
+    HIP_TRY(c, hipEventRecord(c->ev_detect, st));
+    HIP_TRY(c, hipGetLastError());
+    return sync_and_check(c);             // a node, contour or point list that overflowed: ASLAM_E_CAPACITY, as aslam_sync reports it
+}
+
+int aslam_debug_get_nodes(aslam_ctx* c, int slot, int max, int* n_out, unsigned* state, unsigned* next, unsigned* steps, int* area) {
+    if (!c || !n_out || max < 0) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slot_range(c, slot, 1);
+    if (r) return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, c->d_nstarts + slot, sizeof(unsigned), hipMemcpyDeviceToHost));
+    n = std::min(n, c->cfg.cap_starts);
+    *n_out = (int)n;
+    if (n > (unsigned)max) return fail(c, ASLAM_E_CAPACITY, "debug buffer too small");
+    std::vector<unsigned> st(n);
+    std::vector<NodeRec> rec(n);
+    if (n) {
+        HIP_TRY(c, hipMemcpy(st.data(), c->d_starts + (size_t)slot * c->cfg.cap_starts, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(rec.data(), c->d_nodes + (size_t)slot * c->cfg.cap_starts, n * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    }
+    for (unsigned i = 0; i < n; i++) {
+        if (state) state[i] = st[i];
+        if (next) next[i] = rec[i].nxt;
+        if (steps) steps[i] = rec[i].len;
+        if (area) area[i] = rec[i].area;
+    }
+    return ASLAM_OK;
+}
+
+int aslam_debug_get_write_tickets(aslam_ctx* c, int slot, int max, int* n_out, unsigned* state, unsigned* contour, unsigned* rel, unsigned* cnt) {
+    if (!c || !n_out || max < 0) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slot_range(c, slot, 1);
+    if (r) return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, c->d_nwrite + slot, sizeof(unsigned), hipMemcpyDeviceToHost));
+    n = std::min(n, c->cfg.cap_write);
+    *n_out = (int)n;
+    if (n > (unsigned)max) return fail(c, ASLAM_E_CAPACITY, "debug buffer too small");
+    std::vector<WriteRec> rec(n);
+    if (n) HIP_TRY(c, hipMemcpy(rec.data(), c->d_wlist + (size_t)slot * c->cfg.cap_write, n * sizeof(WriteRec), hipMemcpyDeviceToHost));
+    for (unsigned i = 0; i < n; i++) {
+        if (state) state[i] = rec[i].state;
+        if (contour) contour[i] = rec[i].ci;
+        if (rel) rel[i] = rec[i].rel;
+        if (cnt) cnt[i] = rec[i].cnt;
+    }
+    return ASLAM_OK;
+}
+
+int aslam_debug_get_link_todo(aslam_ctx* c, int slot, int* flag) {
+    if (!c || !flag) return fail(c, ASLAM_E_INVALID, "bad arguments");
+    int r = check_slot_range(c, slot, 1);
+    if (r) return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    unsigned v = 0;
+    HIP_TRY(c, hipMemcpy(&v, c->d_link_todo + slot, sizeof(unsigned), hipMemcpyDeviceToHost));
+    *flag = (int)v;
+    return ASLAM_OK;
 }
 
 int aslam_debug_get_frame_counts(aslam_ctx* c, int slot, unsigned* out /* 6 */) {

@@ -560,6 +560,11 @@ __global__ __launch_bounds__(64) void k_seg(const uint8_t* __restrict__ nbr, Det
 __device__ __forceinline__ int node_key(unsigned state, int cols) {
     return (int)((state >> 12) & 0xFFFu) * cols + (int)(state & 0xFFFu) + (((state >> 29) & 3u) == kNodeHole ? 1 : 0);
 }
+// A border that overflowed a list still holds the write tickets it reserved (k_trace_write takes every ticket below the frame's count):
+// mark those that lie inside the list as unused, or the writer replays whatever the memory held
+__device__ __forceinline__ void void_tickets(WriteRec* wl, unsigned wbase, unsigned wcap, unsigned cap_write) {
+    for (unsigned long long t = wbase; t < (unsigned long long)wbase + wcap && t < cap_write; t++) wl[t] = WriteRec{0u, kNone, 0u, 0u};
+}
 constexpr int kLinkThreads = 1024;
 constexpr unsigned kLinkLdsNodes = 32000;        // x (4 B + 1 bit) = 129 KB; node indices < 0x8000
 constexpr unsigned kLinkSlots = 1536;            // x 16 B = 24 KB
@@ -703,9 +708,11 @@ __global__ __launch_bounds__(kLinkThreads) void k_link(DetectCfg cfg, const unsi
         const int cx = ckey % cols - (is_hole ? 1 : 0), cy = ckey / cols;
         if (ci >= cfg.cap_contours) {
             atomicOr(&ctr->overflow, (unsigned)kOvfContours);
+            void_tickets(wlist + (size_t)f * cfg.cap_write, wbase, wcap, cfg.cap_write);
         } else if ((unsigned long long)off + n > cfg.cap_points || (unsigned long long)wbase + wcap > cfg.cap_write) {
             atomicOr(&ctr->overflow, (unsigned)kOvfPoints);
             contours[(size_t)f * cfg.cap_contours + ci] = ContourRec{(unsigned)f, sc, (unsigned)ckey, 0u, 0u, (short)cx, (short)cy, 0, {0u, 0u}};
+            void_tickets(wlist + (size_t)f * cfg.cap_write, wbase, wcap, cfg.cap_write);
         } else {
             contours[(size_t)f * cfg.cap_contours + ci] = ContourRec{(unsigned)f, sc, (unsigned)ckey, n, off, (short)cx, (short)cy,
                                                                     (int)((r.state >> 24) & 7u), {0u, 0u}};
@@ -817,9 +824,11 @@ __global__ __launch_bounds__(512) void k_link_serial(DetectCfg cfg, const unsign
                     const int cx = ckey % cols - (is_hole ? 1 : 0), cy = ckey / cols;
                     if (ci >= cfg.cap_contours) {
                         atomicOr(&ctr->overflow, (unsigned)kOvfContours);
+                        void_tickets(wlist + (size_t)f * cfg.cap_write, wbase, wcap, cfg.cap_write);
                     } else if ((unsigned long long)off + n > cfg.cap_points || (unsigned long long)wbase + wcap > cfg.cap_write) {
                         atomicOr(&ctr->overflow, (unsigned)kOvfPoints);
                         contours[(size_t)f * cfg.cap_contours + ci] = ContourRec{(unsigned)f, sc, (unsigned)ckey, 0u, 0u, (short)cx, (short)cy, 0, {0u, 0u}};
+                        void_tickets(wlist + (size_t)f * cfg.cap_write, wbase, wcap, cfg.cap_write);
                     } else {
                         id = self; pos = 0; hops = 0; wcount = 0; chunk_len = 0; s_canon = 0;
                         mode = 2;
@@ -1465,10 +1474,13 @@ void launch_seg(hipStream_t st, int nwaves, const uint8_t* nbr, const DetectCfg&
     hipLaunchKernelGGL(k_seg, dim3(nwaves), dim3(64), 0, st, nbr, cfg, nframes, starts, n_starts, nodeplane, pre, ctr, nodes);
 }
 void launch_link(hipStream_t st, const DetectCfg& cfg, int nframes, const unsigned* n_starts, Counters* ctr, const NodeRec* nodes,
-                 unsigned* link_todo, ContourRec* contours, unsigned* n_contours, unsigned* n_points, WriteRec* wlist, unsigned* n_write) {
-    // ASLAM_LINK_LDS_NODES: nodes of a frame the LDS image holds (a test knob: 0 sends every frame through k_link_serial)
+                 unsigned* link_todo, ContourRec* contours, unsigned* n_contours, unsigned* n_points, WriteRec* wlist, unsigned* n_write,
+                 int lds_nodes_arg) {
+    // nodes of a frame the LDS image holds: the caller's (aslam_debug_run_contours), else ASLAM_LINK_LDS_NODES (a test knob: 0 sends
+    // every frame through k_link_serial), else all of it
     const char* env = std::getenv("ASLAM_LINK_LDS_NODES");
-    const unsigned lds_nodes = env ? std::min((unsigned)std::atoi(env), kLinkLdsNodes) : kLinkLdsNodes;
+    const unsigned lds_nodes = lds_nodes_arg >= 0 ? std::min((unsigned)lds_nodes_arg, kLinkLdsNodes)
+                                                  : env ? std::min((unsigned)std::atoi(env), kLinkLdsNodes) : kLinkLdsNodes;
     const size_t dyn = (size_t)kLinkLdsNodes * 4u + sizeof(LinkSlot) * kLinkSlots + (kLinkLdsNodes + 31u) / 32u * 4u;
     static bool attr_done = false;
     if (!attr_done) {

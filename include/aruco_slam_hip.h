@@ -490,6 +490,27 @@ int aslam_debug_inject_contours(aslam_ctx* ctx, int slot, int n, const int* scal
 int aslam_debug_inject_quads(aslam_ctx* ctx, int slot, int n, const int* corners /* n x 8 */, const int* sizes, const int* scales,
                              const int* keys);
 int aslam_debug_run_quads(aslam_ctx* ctx, int first, int count, int stages);
+/* the contour stage on staged frames (tests/test_contours_kernel.py).  aslam_debug_run_contours launches on slots [first, first +
+ * count), which must hold staged frames of the current shape, exactly what a detection call launches up to and including the contour
+ * points: the counts cleared, the threshold and border-node kernel, the segment walks, both forms of the cycle resolution and the
+ * point writer; then it waits, and reports an overflowed node, contour or point list as aslam_sync does (ASLAM_E_CAPACITY).
+ * cut_grid: 0 = the cut lattice a detection call of `count` frames would choose, 32 or 64 = that pitch (anything else:
+ * ASLAM_E_INVALID).  lds_nodes < 0: the default; otherwise a frame with more nodes than that is resolved by the serial form (0: every
+ * frame with a node).  The slots' ticket lists are filled with unused tickets first, so that a ticket no kernel wrote reads as unused.
+ * No camera is needed.  Results: aslam_debug_get_nbr, aslam_debug_get_contours, aslam_debug_get_frame_counts and
+ *   aslam_debug_get_nodes: the slot's node list as the threshold kernel wrote it - state[i] = x | y << 12 | s << 24 | scale << 27 |
+ *     type << 29 (type 0 cut state, 1 outer start candidate, 2 hole start candidate; 0xFFFFFFFF = an unused staged entry) - and for each
+ *     node the segment record: next[i] = index of the next node of its border (0xFFFFFFFF: the walk was cut beyond the largest kept
+ *     perimeter, or an unused entry), steps[i], area[i] = the shoelace partial sum over those steps;
+ *   aslam_debug_get_write_tickets: state[i], contour[i] (index into the slot's contour list in emission order; 0xFFFFFFFF = a reserved
+ *     ticket that is not used), rel[i] = offset of its first point in the contour, cnt[i] = points | steps skipped first << 16;
+ *   aslam_debug_get_link_todo: 1 when the serial form resolved the slot's frame, 0 when the LDS form did.
+ * The getters fail with ASLAM_E_CAPACITY (and set *n) when the list has more than max entries. */
+int aslam_debug_run_contours(aslam_ctx* ctx, int first, int count, int cut_grid, int lds_nodes);
+int aslam_debug_get_nodes(aslam_ctx* ctx, int slot, int max, int* n, unsigned* state, unsigned* next, unsigned* steps, int* area);
+int aslam_debug_get_write_tickets(aslam_ctx* ctx, int slot, int max, int* n, unsigned* state, unsigned* contour, unsigned* rel,
+                                  unsigned* cnt);
+int aslam_debug_get_link_todo(aslam_ctx* ctx, int slot, int* flag);
 /* HIP-event timing of each kernel family on the context's stream, accumulated since the last reset:
  * names[i] (static strings), calls[i], total_ms[i]; returns the number of entries. */
 int aslam_profile_enable(aslam_ctx* ctx, int on);

@@ -42,9 +42,33 @@ struct dim3 {
 };
 struct uint3_emu { unsigned x, y, z; };
 
+// Switching lanes: swapcontext saves and restores the signal mask with two system calls per switch, which was most of the
+// emulation's run time.  On x86-64 the switch is six callee-saved registers and the stack pointer; elsewhere ucontext stays.
+#if defined(__x86_64__) && !defined(HIPEMU_UCONTEXT)
+#define HIPEMU_FAST_SWITCH 1
+extern "C" void hipemu_switch(void** save_sp, void* to_sp);
+asm(".text\n"
+    ".weak hipemu_switch\n"
+    ".type hipemu_switch,@function\n"
+    "hipemu_switch:\n"
+    "    pushq %rbp\n    pushq %rbx\n    pushq %r12\n    pushq %r13\n    pushq %r14\n    pushq %r15\n"
+    "    movq %rsp, (%rdi)\n"
+    "    movq %rsi, %rsp\n"
+    "    popq %r15\n    popq %r14\n    popq %r13\n    popq %r12\n    popq %rbx\n    popq %rbp\n"
+    "    ret\n"
+    ".size hipemu_switch,.-hipemu_switch\n");
+#endif
+
 namespace hipemu {
+#ifdef HIPEMU_FAST_SWITCH
+struct LaneCtx { void* sp = nullptr; };
+inline void switch_ctx(LaneCtx* from, LaneCtx* to) { hipemu_switch(&from->sp, to->sp); }
+#else
+typedef ucontext_t LaneCtx;
+inline void switch_ctx(LaneCtx* from, LaneCtx* to) { swapcontext(from, to); }
+#endif
 struct Lane {
-    ucontext_t ctx;
+    LaneCtx ctx;
     char* stack = nullptr;
     bool done = false;
     uint3_emu tidx;
@@ -61,7 +85,8 @@ struct WaveCtx {
 struct BlockCtx {
     std::vector<Lane> lanes;
     std::vector<WaveCtx> waves;
-    ucontext_t sched;
+    LaneCtx sched;
+    void* body = nullptr;  // the launch closure (fast switch: the lanes' entry reads it here)
     int cur = 0;
     int live = 0;         // threads that have not returned
     int arrived = 0;
@@ -74,7 +99,7 @@ inline thread_local BlockCtx* t_block;
 inline dim3 g_blockDim, g_gridDim;
 inline void yield_lane() {                     // back to the block scheduler, which resumes the next live lane
     BlockCtx* b = t_block;
-    swapcontext(&b->lanes[b->cur].ctx, &b->sched);
+    switch_ctx(&b->lanes[b->cur].ctx, &b->sched);
 }
 }
 
@@ -245,8 +270,9 @@ inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *
 namespace hipemu {
 constexpr size_t kStackBytes = 96 * 1024;
 template <class F> struct Tramp {
-    static void entry(unsigned lo, unsigned hi) {
-        F* f = reinterpret_cast<F*>(((unsigned long long)hi << 32) | lo);
+    static void entry(unsigned lo, unsigned hi) { run(reinterpret_cast<F*>(((unsigned long long)hi << 32) | lo)); }
+    static void entry_fast() { run(static_cast<F*>(t_block->body)); }
+    static void run(F* f) {
         (*f)();
         BlockCtx* b = t_block;
         Lane& me = b->lanes[b->cur];
@@ -257,10 +283,22 @@ template <class F> struct Tramp {
         // a lane that returns may complete a pending barrier / collective of the others
         if (b->live > 0 && b->arrived >= b->live) { b->arrived = 0; b->gen++; }
         if (w.live > 0 && w.arrived >= w.live) { w.arrived = 0; w.gen++; }
-        swapcontext(&me.ctx, &b->sched);
+        switch_ctx(&me.ctx, &b->sched);
+        __builtin_unreachable();
     }
 };
-template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by, unsigned bz, std::vector<char>& stacks) {
+// the lanes' stacks of one worker: plain malloc, never filled - a page a lane does not reach is never touched (a zero-filled vector
+// of 1024 x 96 KB per launch of a 1024-lane workgroup was most of the emulation's run time)
+struct StackPool {
+    char* p = nullptr;
+    size_t n = 0;
+    ~StackPool() { std::free(p); }
+    char* get(size_t need) {
+        if (n < need) { std::free(p); p = static_cast<char*>(std::malloc(need)); n = need; }
+        return p;
+    }
+};
+template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by, unsigned bz, StackPool& stacks) {
     const int T = (int)(block.x * block.y * block.z);
     const int nw = (T + 63) / 64;
     BlockCtx ctx;
@@ -268,7 +306,8 @@ template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by,
     ctx.waves.resize(nw);
     ctx.live = T;
     ctx.bidx = uint3_emu{bx, by, bz};
-    if (stacks.size() < (size_t)T * kStackBytes) stacks.resize((size_t)T * kStackBytes);
+    ctx.body = &body;
+    char* const stack_base = stacks.get((size_t)T * kStackBytes);
     for (int w = 0; w < nw; w++) { ctx.waves[w].lanes = std::min(64, T - 64 * w); ctx.waves[w].live = ctx.waves[w].lanes; }
     t_block = &ctx;
     t_blockIdx = ctx.bidx;
@@ -278,11 +317,22 @@ template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by,
         l.tidx = uint3_emu{(unsigned)(t % block.x), (unsigned)((t / block.x) % block.y), (unsigned)(t / (block.x * block.y))};
         l.lane = t & 63;
         l.wave = t >> 6;
+#ifdef HIPEMU_FAST_SWITCH
+        // what hipemu_switch pops: six registers, then the entry as its return address.  The return address lies on a 16-byte boundary, so
+        // the entry starts with the stack pointer at 8 mod 16, as after a call (the ABI's alignment)
+        void** top = reinterpret_cast<void**>((reinterpret_cast<uintptr_t>(stack_base + (size_t)(t + 1) * kStackBytes) & ~(uintptr_t)15) - 64);
+        top[-1] = nullptr;                                                        // (a return from the entry would fault at once; it never returns)
+        void (*entry)() = &Tramp<F>::entry_fast;
+        top[-2] = reinterpret_cast<void*>(entry);
+        for (int r = 3; r <= 8; r++) top[-r] = nullptr;
+        l.ctx.sp = top - 8;
+#else
         getcontext(&l.ctx);
-        l.ctx.uc_stack.ss_sp = stacks.data() + (size_t)t * kStackBytes;
+        l.ctx.uc_stack.ss_sp = stack_base + (size_t)t * kStackBytes;
         l.ctx.uc_stack.ss_size = kStackBytes;
         l.ctx.uc_link = nullptr;
         makecontext(&l.ctx, reinterpret_cast<void (*)()>(&Tramp<F>::entry), 2, (unsigned)(fp & 0xffffffffu), (unsigned)(fp >> 32));
+#endif
     }
     while (ctx.live > 0) {
         for (int t = 0; t < T; t++) {
@@ -292,7 +342,7 @@ template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by,
             t_threadIdx = l.tidx;
             t_lane = l.lane;
             t_wave = l.wave;
-            swapcontext(&ctx.sched, &l.ctx);
+            switch_ctx(&ctx.sched, &l.ctx);
         }
     }
     t_block = nullptr;
@@ -316,7 +366,7 @@ template <class F> void run_grid(const char*, dim3 grid, dim3 block, F&& body) {
         }
     }
     auto worker = [&]() {
-        std::vector<char> stacks;
+        StackPool stacks;
         for (;;) {
             unsigned long long i = next.fetch_add(1);
             if (i >= nblocks) break;

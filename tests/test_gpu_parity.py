@@ -69,10 +69,12 @@ def test_contours_on_degenerate_images(link, monkeypatch):
     if link == "serial":
         monkeypatch.setenv("ASLAM_LINK_LDS_NODES", "0")
     rows, cols = 240, 320
-    ctx = capi.Context(max_rows=rows, max_cols=cols, max_batch=1, max_landmarks=4, cap_contours_per_frame=1 << 15,
-                       cap_points_per_frame=1 << 21, cap_starts_per_frame=1 << 17)
+    caps = dict(nodes=1 << 17, contours=1 << 15, points=1 << 21)
+    ctx = capi.Context(max_rows=rows, max_cols=cols, max_batch=1, max_landmarks=4, cap_contours_per_frame=caps["contours"],
+                       cap_points_per_frame=caps["points"], cap_starts_per_frame=caps["nodes"])
     ctx.set_camera(synth.camera_matrix(rows, cols, 200.0), np.zeros(5))
     rng = np.random.RandomState(7)
+    checked = expected = 0
     for trial in range(21):
         kind = trial % 7
         if kind == 0:
@@ -98,17 +100,24 @@ def test_contours_on_degenerate_images(link, monkeypatch):
             img = np.clip(128 + 900 * g, 0, 255).astype(np.uint8)           # smooth blobs: curved borders, touching the frame
         long_borders = kind >= 4
         ctx.set_detector_params(maxMarkerPerimeterRate=40.0 if long_borders else 4.0)
+        # a case may be left out only where the oracle's own counts overflow a list of the context (one frame: lattice 32)
+        over = pc.exceeds_capacity(img, (0.03, 40.0 if long_borders else 4.0), caps, 32)     # (kept per image: both link forms draw the same)
+        expected += not over
         ctx.stage_frames(img)
         try:
             ctx.run_staged(0, 1, with_ekf=False)
             ctx.sync()
         except capi.AslamError as e:
-            assert e.code == -4            # candidate-list capacity on pure-noise input is reported, never silent
+            # a list's capacity on pure-noise input is reported, never silent - and only where the oracle's counts overflow it too
+            assert pc.capacity_error_is_excused(e, over), f"trial {trial}: {e}; the oracle's counts overflow {over}"
             continue
+        assert not over, f"trial {trial}: the oracle's counts overflow {over}, and no error was reported"
         if long_borders:
             pc.check_contours(ctx, 0, img, perim_rates=(0.03, 40.0))
         else:
             pc.check_stages(ctx, 0, img)
+        checked += 1
+    assert checked == expected >= 15
 
 
 def test_slam_sequence_cfg1_literal_oracle():

@@ -71,9 +71,10 @@ def test_contours_degenerate_images(link, monkeypatch):
     if link == "serial":
         monkeypatch.setenv("ASLAM_LINK_LDS_NODES", "0")
     rng = np.random.RandomState(0)
-    checked = 0
+    checked = expected = 0
+    caps = dict(nodes=1 << 16, contours=1 << 13, points=1 << 19)
     for rows, cols, trials in ((64, 96, 6), (150, 200, 5)):
-        ctx = small_ctx(rows, cols, cap_starts_per_frame=1 << 16, cap_contours_per_frame=1 << 13, cap_points_per_frame=1 << 19)
+        ctx = small_ctx(rows, cols, cap_starts_per_frame=caps["nodes"], cap_contours_per_frame=caps["contours"], cap_points_per_frame=caps["points"])
         ctx.set_camera(synth.camera_matrix(rows, cols, 100.0), np.zeros(5))
         ctx.set_detector_params(maxMarkerPerimeterRate=40.0)       # keep the long borders: they are the point
         for trial in range(trials):
@@ -92,16 +93,20 @@ def test_contours_degenerate_images(link, monkeypatch):
                 for _ in range(25):
                     x0, y0 = rng.randint(0, cols), rng.randint(0, rows)
                     img[y0:y0 + rng.randint(1, 30), x0:x0 + rng.randint(1, 30)] = rng.randint(0, 256)
+            # a case may be left out only where the oracle's own counts overflow a list of the context (one frame: lattice 32)
+            over = pc.exceeds_capacity(img, (0.03, 40.0), caps, 32)
+            expected += not over
             ctx.stage_frames(img)
             try:
                 ctx.run_staged(0, 1, with_ekf=False)
                 ctx.sync()
             except capi.AslamError as e:
-                assert e.code == -4
+                assert pc.capacity_error_is_excused(e, over), f"trial {trial}: {e}; the oracle's counts overflow {over}"
                 continue
+            assert not over, f"trial {trial}: the oracle's counts overflow {over}, and no error was reported"
             pc.check_contours(ctx, 0, img, perim_rates=(0.03, 40.0))
             checked += 1
-    assert checked >= 8
+    assert checked == expected >= 8
 
 
 def test_empty_and_blank_frames():
