@@ -108,6 +108,19 @@ RELOC_DTYPE = np.dtype([("status", "<i4"), ("n_candidates", "<i4"), ("n_inliers"
                         ("pose", "<f8", (3,)), ("sigma", "<f8", (3, 3))], align=True)
 
 
+class GateParams(C.Structure):
+    """mirror of aslam_gate_params"""
+    _fields_ = [("gate_d2", C.c_double), ("min_attempted", C.c_int), ("min_accept_percent", C.c_int), ("lost_after", C.c_int),
+                ("pad", C.c_int)]
+
+
+# mirrors of aslam_slot_health / aslam_track_health: what Context.get_slot_health / get_track_health / fleet_get_health return
+SLOT_HEALTH_DTYPE = np.dtype([("attempted", "<i4"), ("accepted", "<i4"), ("rejected", "<i4"), ("ref_flagged", "<i4"), ("nis_sum", "<f8"),
+                              ("d2_max", "<f8"), ("worst_id", "<i4"), ("pad", "<i4")], align=True)
+TRACK_HEALTH_DTYPE = np.dtype([("frames", "<i4"), ("accepted_total", "<i4"), ("rejected_total", "<i4"), ("bad_streak", "<i4"),
+                               ("lost", "<i4"), ("pad", "<i4", (3,))], align=True)
+
+
 class AslamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aslam error {code} ({E_NAMES.get(code, '?')}): {msg}")
@@ -154,6 +167,12 @@ _SIGS = {
     "aslam_default_relocalize_params": (None, [_P(RelocalizeParams)]),
     "aslam_relocalize": (C.c_int, [C.c_void_p, C.c_int, _P(RelocalizeParams), C.c_int, C.c_void_p]),
     "aslam_fleet_relocalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _P(RelocalizeParams), C.c_int, C.c_void_p]),
+    "aslam_default_gate_params": (None, [_P(GateParams)]),
+    "aslam_set_innovation_gate": (C.c_int, [C.c_void_p, _P(GateParams)]),
+    "aslam_get_innovation_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
+    "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
     "aslam_save_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_load_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "aslam_stream_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -561,6 +580,50 @@ class Context:
         self._ck(self.lib.aslam_fleet_relocalize(self.h, int(first), int(rs.size), _ptr(rs, _ip), self._reloc_params(params), 1 if apply else 0,
                                                  out.ctypes.data_as(C.c_void_p)))
         return out[:rs.size]
+
+    # -- innovation gate and lost-track detection ---------------------------------------------------------------
+    def set_innovation_gate(self, params=True, **kw):
+        """set_innovation_gate(gate_d2=..., min_attempted=..., min_accept_percent=..., lost_after=...): the library's defaults with the
+        given fields replaced (gate_d2=inf: monitor only); set_innovation_gate(None): off"""
+        if params is None:
+            if kw:
+                raise ValueError("set_innovation_gate(None) takes no parameters")
+            self._ck(self.lib.aslam_set_innovation_gate(self.h, None))
+            return
+        p = GateParams()
+        self.lib.aslam_default_gate_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in ("gate_d2", "min_attempted", "min_accept_percent", "lost_after"):
+                raise KeyError(k)
+            setattr(p, k, v)
+        self._ck(self.lib.aslam_set_innovation_gate(self.h, C.byref(p)))
+
+    def get_innovation_gate(self):
+        """None while the gate is off, else its parameters as a dict"""
+        on, p = C.c_int(), GateParams()
+        self._ck(self.lib.aslam_get_innovation_gate(self.h, C.byref(on), C.byref(p)))
+        if not on.value:
+            return None
+        return dict(gate_d2=p.gate_d2, min_attempted=p.min_attempted, min_accept_percent=p.min_accept_percent, lost_after=p.lost_after)
+
+    def get_slot_health(self, first, count):
+        """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""
+        out = np.zeros(max(int(count), 1), SLOT_HEALTH_DTYPE)
+        self._ck(self.lib.aslam_get_slot_health(self.h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:max(int(count), 0)]
+
+    def get_track_health(self):
+        """the single localizing filter's TRACK_HEALTH_DTYPE record"""
+        out = np.zeros(1, TRACK_HEALTH_DTYPE)
+        self._ck(self.lib.aslam_get_track_health(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out[0]
+
+    def fleet_get_health(self):
+        """one TRACK_HEALTH_DTYPE record per robot of the localization fleet"""
+        n = C.c_int()
+        out = np.zeros(MAX_ROBOTS, TRACK_HEALTH_DTYPE)
+        self._ck(self.lib.aslam_fleet_get_health(self.h, MAX_ROBOTS, C.byref(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n.value].copy()
 
     def save_state(self, path):
         self._ck(self.lib.aslam_save_state(self.h, str(path).encode()))

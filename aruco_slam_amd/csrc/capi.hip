@@ -147,6 +147,14 @@ struct aslam_ctx {
     FleetSlam fslam{};
     MergeBufs merge{};                    // map merge: tables allocated by the first merge, freed at aslam_fleet_end / aslam_destroy
     RelocBufs reloc{};                    // relocalization: result records, allocated by the first call, freed at the same two places
+    // innovation gate (aslam_set_innovation_gate): off unless set; only the localization and localization-fleet steps
+    // look at it.  The health records (one per EKF slot, one track record per robot and one for the single filter) and their
+    // page-locked copies are made by the first aslam_set_innovation_gate and freed by aslam_destroy.
+    bool gate_on = false;
+    aslam_gate_params gate_prm{};
+    GateState gate{};                     // the parameters in force and the device records, as the gated kernels take them
+    SlotHealth* h_slot_health = nullptr;  // page-locked: 2 max_batch
+    TrackHealth* h_track_health = nullptr;   // page-locked: ASLAM_MAX_ROBOTS + 1
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -617,7 +625,7 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     hipStream_t st = c->stream_ekf;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_LOC_STEPS, st);
-    launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0);
+    launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0, c->gate_on ? &c->gate : nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
@@ -834,6 +842,9 @@ void aslam_destroy(aslam_ctx* c) {
     ekf_fleet_free(c->fslam);
     merge_free(c->merge);
     reloc_free(c->reloc);
+    hipFree(c->gate.slot); hipFree(c->gate.track);
+    if (c->h_slot_health) hipHostFree(c->h_slot_health);
+    if (c->h_track_health) hipHostFree(c->h_track_health);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
     hipFree(c->d_fleet_cams); hipFree(c->d_fleet_camidx); hipFree(c->d_fleet_work);
     pinned_free(c->fleet_camidx_up);
@@ -2008,6 +2019,15 @@ int install_frozen_map(aslam_ctx* c, int n, const int* ids, const double* xyth, 
     return ASLAM_OK;
 }
 
+// a seat clears the track records [first, first + count) of the innovation gate (if it was ever set): at once, or behind the work
+// enqueued on st
+int clear_track_health(aslam_ctx* c, int first, int count, hipStream_t st = nullptr) {
+    if (!c->gate.track) return ASLAM_OK;
+    if (st) HIP_TRY(c, hipMemsetAsync(c->gate.track + first, 0, sizeof(TrackHealth) * count, st));
+    else HIP_TRY(c, hipMemset(c->gate.track + first, 0, sizeof(TrackHealth) * count));
+    return ASLAM_OK;
+}
+
 int check_pose(aslam_ctx* c, const double* pose, const double* sigma) {
     for (int k = 0; k < 3; k++) if (!std::isfinite(pose[k])) return fail(c, ASLAM_E_INVALID, "non-finite pose");
     for (int i = 0; i < 3; i++)
@@ -2099,6 +2119,7 @@ int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth
         HIP_TRY(c, hipMemcpy(c->ekf.d_sigma + (size_t)col * ld, v, sizeof(v), hipMemcpyHostToDevice));
     }
     HIP_TRY(c, hipMemcpy(c->ekf.d_mu, pose, 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (int rt = clear_track_health(c, kTrackSingle, 1)) return rt;
     return enter_mode(c, Mode::Localize);
 }
 
@@ -2125,7 +2146,7 @@ int fleet_seat(aslam_ctx* c, int robot, const double* pose, const double* sigma)
     HIP_TRY(c, hipMemcpy(c->fleet.pose + (size_t)kFleetState * robot, st, sizeof(st), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->fleet.nlast + robot, 0, sizeof(int)));
     c->fleet_armed[robot] = 0;
-    return ASLAM_OK;
+    return clear_track_health(c, robot, 1);
 }
 
 // fleet steps of frame slots [first, first + count), slot first + i belonging to robot robots[i]: one k_fleet_steps workgroup per
@@ -2152,7 +2173,7 @@ int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_FLEET_STEPS, st);
-    launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng);
+    launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng, c->gate_on ? &c->gate : nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_ekf, st));
@@ -2484,7 +2505,9 @@ int aslam_relocalize(aslam_ctx* c, int slot, const aslam_relocalize_params* para
     if (int r = reloc_params(c, params, prm)) return r;
     if (int r = check_slot_range(c, slot, 1)) return r;
     if (int r = finalize_pending(c)) return r;
-    return relocalize_slots(c, slot, 1, nullptr, prm, apply ? 1 : 0, out);
+    if (int r = relocalize_slots(c, slot, 1, nullptr, prm, apply ? 1 : 0, out)) return r;
+    if (apply && out->status == 0) return clear_track_health(c, kTrackSingle, 1, c->stream_ekf);      // seated
+    return ASLAM_OK;
 }
 
 int aslam_fleet_relocalize(aslam_ctx* c, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params, int apply,
@@ -2506,8 +2529,107 @@ int aslam_fleet_relocalize(aslam_ctx* c, int first, int count, const int* robot_
     if (int r = relocalize_slots(c, first, count, c->d_fleet_work, prm, apply ? 1 : 0, out)) return r;
     if (apply)
         for (int i = 0; i < count; i++)
-            if (out[i].status == 0) c->fleet_armed[robot_of_slot[i]] = 0;      // seated as by aslam_fleet_set_pose: its next frame only arms it
+            if (out[i].status == 0) {                                          // seated as by aslam_fleet_set_pose: its next frame only arms it
+                c->fleet_armed[robot_of_slot[i]] = 0;
+                if (int r = clear_track_health(c, robot_of_slot[i], 1, c->stream_ekf)) return r;
+            }
     return ASLAM_OK;
+}
+
+// ---- innovation gate and lost-track detection (include/aruco_slam_hip.h) -------------------------------------------
+static_assert(kTrackSingle == ASLAM_MAX_ROBOTS, "the single filter's track record follows the robots'");
+static_assert(sizeof(SlotHealth) == sizeof(aslam_slot_health) && sizeof(TrackHealth) == sizeof(aslam_track_health), "records are copied as they are");
+
+void aslam_default_gate_params(aslam_gate_params* p) {
+    if (!p) return;
+    p->gate_d2 = 16.266;                 // the 0.999 quantile of chi-square with 3 degrees of freedom
+    p->min_attempted = 2;
+    p->min_accept_percent = 50;
+    p->lost_after = 3;
+    p->pad = 0;
+}
+
+int aslam_set_innovation_gate(aslam_ctx* c, const aslam_gate_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (!params) { c->gate_on = false; return ASLAM_OK; }
+    const aslam_gate_params& p = *params;
+    if (!(p.gate_d2 > 0.0)) return fail(c, ASLAM_E_INVALID, "gate_d2 must be positive, or +inf to monitor only");
+    if (p.min_attempted < 1) return fail(c, ASLAM_E_INVALID, "min_attempted >= 1");
+    if (p.min_accept_percent < 0 || p.min_accept_percent > 100) return fail(c, ASLAM_E_INVALID, "min_accept_percent 0..100");
+    if (p.lost_after < 1) return fail(c, ASLAM_E_INVALID, "lost_after >= 1");
+    if (!c->gate.track) {
+        const size_t ns = (size_t)c->ekf.max_slots, nt = (size_t)kTrackSingle + 1;
+        SlotHealth* d_slot = nullptr;
+        HIP_TRY(c, dalloc(&d_slot, ns));
+        c->gate.slot = d_slot;
+        HIP_TRY(c, hipMemset(c->gate.slot, 0, ns * sizeof(SlotHealth)));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_slot_health), ns * sizeof(SlotHealth), hipHostMallocDefault));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_track_health), nt * sizeof(TrackHealth), hipHostMallocDefault));
+        TrackHealth* d_track = nullptr;
+        HIP_TRY(c, dalloc(&d_track, nt));
+        HIP_TRY(c, hipMemset(d_track, 0, nt * sizeof(TrackHealth)));
+        c->gate.track = d_track;         // set last: the records exist exactly when this is set
+    }
+    c->gate_prm = p;
+    c->gate_prm.pad = 0;
+    c->gate.gate_d2 = p.gate_d2;
+    c->gate.min_attempted = p.min_attempted;
+    c->gate.min_accept_percent = p.min_accept_percent;
+    c->gate.lost_after = p.lost_after;
+    c->gate_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_get_innovation_gate(aslam_ctx* c, int* on, aslam_gate_params* out) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->gate_on ? 1 : 0;
+    if (out) {
+        if (c->gate_on) *out = c->gate_prm;
+        else aslam_default_gate_params(out);
+    }
+    return ASLAM_OK;
+}
+
+namespace {
+// what every health getter checks first: the gate is set and the mode is one it works in
+int gate_readable(aslam_ctx* c, unsigned modes) {
+    if (!c->gate_on) return fail(c, ASLAM_E_STATE, "no innovation gate set (aslam_set_innovation_gate first)");
+    return allow(c, modes);
+}
+
+// bytes of records from the device array d into the page-locked h behind the EKF steps enqueued so far, then to out
+int read_health(aslam_ctx* c, const void* d, void* h, size_t bytes, void* out) {
+    { int rs = sync_streams(c); if (rs) return rs; }
+    HIP_TRY(c, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream_ekf));
+    HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
+    std::memcpy(out, h, bytes);
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_get_slot_health(aslam_ctx* c, int first, int count, aslam_slot_health* out) {
+    if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = gate_readable(c, kLocalize | kFleetLocalize)) return r;
+    if (first < 0 || count < 1 || count > c->ekf.max_slots || first > c->ekf.max_slots - count)
+        return fail(c, ASLAM_E_INVALID, "EKF slot range outside [0, 2 max_batch)");
+    return read_health(c, c->gate.slot + first, c->h_slot_health, sizeof(SlotHealth) * count, out);
+}
+
+int aslam_get_track_health(aslam_ctx* c, aslam_track_health* out) {
+    if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = gate_readable(c, kLocalize)) return r;
+    return read_health(c, c->gate.track + kTrackSingle, c->h_track_health, sizeof(TrackHealth), out);
+}
+
+int aslam_fleet_get_health(aslam_ctx* c, int max, int* n_robots, aslam_track_health* out) {
+    if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (max < 0 || (max > 0 && !out)) return fail(c, ASLAM_E_INVALID, "max records need an output array");
+    if (c->mode == Mode::FleetSlam) return fail(c, ASLAM_E_STATE, "fleet SLAM: the innovation gate covers localization fleets only");
+    if (int r = gate_readable(c, kFleetLocalize)) return r;
+    *n_robots = c->fleet_n;
+    const int n = std::min(max, c->fleet_n);
+    if (n == 0) return ASLAM_OK;
+    return read_health(c, c->gate.track, c->h_track_health, sizeof(TrackHealth) * n, out);
 }
 
 // MapLoader markers -> planar landmarks: heading of the marker's +z axis (third column of Matrix3x3(orientation)), which is what an

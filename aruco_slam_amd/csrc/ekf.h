@@ -8,7 +8,7 @@ namespace aslam {
 constexpr int kIdTableSize = 1024;     // marker id -> landmark index (std::map<int,int> aruco_id_map, aruco_slam.h:164)
 
 struct PopRec {                        // one popped observation (aruco_slam.cpp:92-95) and what was done with it
-    int id, index, action, det;        // action: 0 augment, 1 update, 2 stationary no-op; det: position in the frame's observation list
+    int id, index, action, det;        // action: 0 augment, 1 update, 2 stationary no-op, 3 update rejected by the innovation gate; det: position in the frame's observation list
     double z[3];
     double r[3];
 };
@@ -106,10 +106,28 @@ void launch_ekf_gather(hipStream_t st, const EkfState& E);
 void launch_ekf_small(hipStream_t st, const EkfState& E);
 void launch_ekf_T(hipStream_t st, const EkfState& E);
 void launch_ekf_export_map(hipStream_t st, const EkfState& E);
+// innovation gate of the localization steps (ekf_localize.h): the parameters in force and where the gated kernels
+// leave their records.  SlotHealth / TrackHealth have the layout of aslam_slot_health / aslam_track_health.
+struct SlotHealth {                    // one gated step: what became of its prepared corrections
+    int attempted, accepted, rejected, ref_flagged;
+    double nis_sum, d2_max;
+    int worst_id, pad;
+};
+struct TrackHealth {                   // one filter since it was last seated
+    int frames, accepted_total, rejected_total, bad_streak, lost, pad[3];
+};
+constexpr int kTrackSingle = 256;      // the single filter's track record; a fleet's robot r has record r (< ASLAM_MAX_ROBOTS = 256)
+struct GateState {
+    double gate_d2;                    // > 0, or +inf: monitor only
+    int min_attempted, min_accept_percent, lost_after;
+    SlotHealth* slot;                  // per EKF slot (max_slots records)
+    TrackHealth* track;                // kTrackSingle + 1 records
+};
 // localization steps of EKF slots [first, first + count) in one launch (ekf_localize.h): the map stays frozen, only the pose block
-// is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder)
+// is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder).
+// gate != nullptr: the gated kernel (k_loc_steps_gated, k_fleet_steps_gated) with those parameters
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first);
+                      const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr);
 // fleet localization (ekf_fleet.h): one workgroup per robot of the work list (n_groups robots), each on its own filter in F
 constexpr int kFleetState = 12;        // doubles per robot: mu_x (3), then Sigma_xx row-major (9)
 struct FleetState {
@@ -118,7 +136,7 @@ struct FleetState {
     int* nlast;                        // R: their lengths
 };
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
-                        const unsigned* n_markers, const double* enc, const int* work, int n_groups);
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate = nullptr);
 // fleet SLAM (ekf_fleet_slam.h): R complete filters with the single filter's chain layouts in one allocation; robot r's buffers lie
 // r * stride bytes past robot 0's.  No window buffers; d_slot_stat and max_slots are the context's.
 struct FleetSlam {

@@ -22,6 +22,7 @@ struct LocFleet {
     const int* slots;
     int count, predict_first;
     static constexpr bool kPopList = false;          // aslam_get_observations describes the single filter, not a robot
+    __device__ __forceinline__ int track() const { return robot; }
     __device__ __forceinline__ int n() const { return count; }
     __device__ __forceinline__ int slot(int k) const { return slots[k]; }
     __device__ __forceinline__ bool predict(int k) const { return k > 0 || predict_first; }
@@ -48,9 +49,20 @@ __global__ __launch_bounds__(kMarkerMax) void k_fleet_steps(EkfState E, FleetSta
     loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc);
 }
 
+// the same with the innovation gate: every robot's workgroup gates its own corrections and keeps its own records
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                 const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                 const int* __restrict__ work, int n_groups, GateState g) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g});
+}
+
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
-                        const unsigned* n_markers, const double* enc, const int* work, int n_groups) {
-    hipLaunchKernelGGL(k_fleet_steps, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups);
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate) {
+    if (gate)
+        hipLaunchKernelGGL(k_fleet_steps_gated, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate);
+    else
+        hipLaunchKernelGGL(k_fleet_steps, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups);
 }
 
 } // namespace aslam

@@ -11,6 +11,13 @@
 //
 // The body is loc_steps<Src>: Src says which slots the workgroup steps through and where the filter it corrects lives.  LocSingle
 // is the context's one filter (k_loc_steps); a fleet's workgroup uses LocFleet, its robot's own filter (ekf_fleet.h).
+//
+// loc_steps<Src, G> takes a compile-time gate policy G (include/aruco_slam_hip.h).  NoGate, the default, is the
+// chain above and nothing else: every gated statement sits under `if constexpr (G::kOn)`.  Gated (k_loc_steps_gated,
+// k_fleet_steps_gated) adds on lane 0, per correction, d2 = ze^T S^-1 ze, the reference's logged test (aruco_slam.cpp:156), the
+// skip of a correction whose d2 exceeds a finite gate, the slot's health sums in pop order and the filter's track record, which
+// stays in registers across the slots of a launch; a rejected flag per popped observation lives in LDS, and after the chain all
+// lanes compact the last-observed list with two ballots so that it holds the accepted updates and the no-ops only.
 #pragma once
 #include "common.h"
 #include "ekf.h"
@@ -30,6 +37,7 @@ struct LocSingle {
     const EkfState& E;
     int first, count, predict_first;
     static constexpr bool kPopList = true;
+    __device__ __forceinline__ int track() const { return kTrackSingle; }
     __device__ __forceinline__ int n() const { return count; }
     __device__ __forceinline__ int slot(int k) const { return first + k; }
     __device__ __forceinline__ bool predict(int k) const { return k > 0 || predict_first; }
@@ -51,9 +59,15 @@ struct LocSingle {
     __device__ __forceinline__ int* nlast() const { return E.d_nlast; }
 };
 
-template <class Src>
+struct NoGate { static constexpr bool kOn = false; };
+struct Gated {
+    static constexpr bool kOn = true;
+    GateState g;
+};
+
+template <class Src, class G = NoGate>
 __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                                          const double* enc) {
+                                          const double* enc, const G& gate = G{}) {
     __shared__ LastObs sLast[kMarkerMax];       // last_observed_marker_ of the previous step
     __shared__ int sIndex[kMarkerMax];          // landmark index per observation slot (-2: dropped)
     __shared__ int sOrder[kMarkerMax];          // pop order
@@ -63,11 +77,23 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
     __shared__ int sDup, sNl, sCnt[2], sUpdCnt[2], sStatCnt[2];
     const int tid = threadIdx.x;
     const int count = src.n();
+    int* sCorrPop = nullptr;                    // gated: pop position of every correction, rejected flag of every popped observation
+    int* sRej = nullptr;
+    int* sKeepCnt = nullptr;
+    if constexpr (G::kOn) {
+        __shared__ int sGateCorrPop[kMarkerMax], sGateRej[kMarkerMax], sGateKeepCnt[2];
+        sCorrPop = sGateCorrPop; sRej = sGateRej; sKeepCnt = sGateKeepCnt;
+    }
 
     double mx = 0, my = 0, mt = 0, P[9];        // lane 0: the pose and Sigma_xx, in registers for the whole launch
+    int trFrames = 0, trAcc = 0, trRej = 0, trStreak = 0, trLost = 0;   // gated, lane 0: the filter's track record, likewise
     if (tid == 0) {
         src.load(mx, my, mt, P);
         sNl = min(*src.nlast(), kMarkerMax);
+        if constexpr (G::kOn) {
+            const TrackHealth* t = gate.g.track + src.track();
+            trFrames = t->frames; trAcc = t->accepted_total; trRej = t->rejected_total; trStreak = t->bad_streak;
+        }
     }
     sLast[tid] = src.last()[tid];               // entries beyond the list length are never read
     __syncthreads();
@@ -225,6 +251,7 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             cr.H[6] = 0.0;       cr.H[7] = 0.0;       cr.H[8] = -1.0;
             cr.r[0] = po.r[0]; cr.r[1] = po.r[1]; cr.r[2] = po.r[2];
             sCorr[up] = cr;
+            if constexpr (G::kOn) sCorrPop[up] = tid;
         }
         // last_observed_marker_ = observed_marker (aruco_slam.cpp:263); last_observation_ is set in the update branch only
         if (tid < np) {
@@ -233,9 +260,14 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             if (act == 1) { lo.z[0] = po.x; lo.z[1] = po.y; lo.z[2] = po.th; }
             else { lo.z[0] = lo.z[1] = lo.z[2] = nan(""); }
             sLast[tid] = lo;
+            if constexpr (G::kOn) sRej[tid] = 0;
         }
         __syncthreads();
         if (tid == 0) {
+            // gated: the slot's health record, summed in pop order
+            int hAcc = 0, hRej = 0, hFlag = 0, hWorst = -1;
+            bool hHave = false;
+            double hNis = 0.0, hMax = 0.0;
             // the dependent chain: m sequential corrections of the pose block (aruco_slam.cpp:145-205 with zero landmark blocks)
             for (int q = 0; q < m; q++) {
                 const LocCorr& cr = sCorr[q];
@@ -253,22 +285,79 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
                     }
                 inv3_reg(S, Si);
                 mul3(PHt, Si, K);                                        // K_x = P H^T S^-1
-                mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
-                my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
-                mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
-                mul3(K, H, A);                                           // I - K H
+                bool fuse = true;
+                if constexpr (G::kOn) {
+                    const double z0 = cr.ze[0], z1 = cr.ze[1], z2 = cr.ze[2];
+                    const double d2 = z0 * (Si[0] * z0 + Si[1] * z1 + Si[2] * z2) + z1 * (Si[3] * z0 + Si[4] * z1 + Si[5] * z2) +
+                                      z2 * (Si[6] * z0 + Si[7] * z1 + Si[8] * z2);            // ze^T S^-1 ze
+                    double kk = 0.0;
 #pragma unroll
-                for (int i = 0; i < 9; i++) A[i] = ((i % 4) == 0 ? 1.0 : 0.0) - A[i];
-                mul3(A, P, Pn);
+                    for (int i = 0; i < 9; i++) kk += K[i] * K[i];
+                    hFlag += (sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;   // aruco_slam.cpp:156
+                    const int pop = sCorrPop[q];
+                    if (d2 == d2 && (!hHave || d2 > hMax)) { hHave = true; hMax = d2; hWorst = sLast[pop].id; }
+                    if (gate.g.gate_d2 < HUGE_VAL && !(d2 <= gate.g.gate_d2)) {       // a NaN d2 rejects
+                        fuse = false;
+                        hRej++;
+                        sRej[pop] = 1;
+                    } else {
+                        hAcc++;
+                        hNis += d2;
+                    }
+                }
+                if (fuse) {
+                    mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
+                    my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
+                    mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
+                    mul3(K, H, A);                                       // I - K H
 #pragma unroll
-                for (int i = 0; i < 9; i++) P[i] = Pn[i];
+                    for (int i = 0; i < 9; i++) A[i] = ((i % 4) == 0 ? 1.0 : 0.0) - A[i];
+                    mul3(A, P, Pn);
+#pragma unroll
+                    for (int i = 0; i < 9; i++) P[i] = Pn[i];
+                }
             }
-            sNl = np;
+            const int fused = G::kOn ? hAcc : m;
+            if constexpr (!G::kOn) sNl = np;
             if (slot < E.max_slots) {                                    // detections, appended (never), corrections, no-ops
                 int* st = E.d_slot_stat + 4 * slot;
-                st[0] = nM; st[1] = 0; st[2] = m; st[3] = sStatCnt[0] + sStatCnt[1];
+                st[0] = nM; st[1] = 0; st[2] = fused; st[3] = sStatCnt[0] + sStatCnt[1];
             }
-            if (Src::kPopList && k == count - 1) { *E.d_npop = np; *E.d_m = m; }
+            if (Src::kPopList && k == count - 1) { *E.d_npop = np; *E.d_m = fused; }
+            if constexpr (G::kOn) {
+                if (slot < E.max_slots) {
+                    SlotHealth* h = gate.g.slot + slot;
+                    h->attempted = m; h->accepted = hAcc; h->rejected = hRej; h->ref_flagged = hFlag;
+                    h->nis_sum = hNis; h->d2_max = hMax; h->worst_id = hWorst; h->pad = 0;
+                }
+                trFrames++;
+                trAcc += hAcc;
+                trRej += hRej;
+                if (m >= gate.g.min_attempted) trStreak = 100 * hAcc < gate.g.min_accept_percent * m ? trStreak + 1 : 0;
+                trLost = trStreak >= gate.g.lost_after ? 1 : 0;
+            }
+        }
+        if constexpr (G::kOn) {
+            // the rejected observations leave the list (the reference's commented-out `continue` before aruco_slam.cpp:261): the kept
+            // entries move up in pop order, placed by the two-wave prefix that places sCorr[up]
+            __syncthreads();                                             // lane 0's chain wrote sRej
+            int loId = 0;
+            double lz0 = 0.0, lz1 = 0.0, lz2 = 0.0;
+            bool keep = false, rej = false;
+            if (tid < np) {
+                rej = sRej[tid] != 0;
+                keep = !rej;
+                loId = sLast[tid].id; lz0 = sLast[tid].z[0]; lz1 = sLast[tid].z[1]; lz2 = sLast[tid].z[2];
+            }
+            const unsigned long long bK = __ballot(keep);
+            if ((tid & 63) == 0) sKeepCnt[tid >> 6] = __popcll(bK);
+            if (Src::kPopList && k == count - 1 && rej) E.d_pop[tid].action = 3;
+            __syncthreads();                                             // every lane holds its entry
+            if (keep) {
+                LastObs& lo = sLast[(tid >= 64 ? sKeepCnt[0] : 0) + __popcll(bK & ((1ull << (tid & 63)) - 1ull))];
+                lo.id = loId; lo.pad = 0; lo.z[0] = lz0; lo.z[1] = lz1; lo.z[2] = lz2;
+            }
+            if (tid == 0) sNl = sKeepCnt[0] + sKeepCnt[1];
         }
         __syncthreads();
     }
@@ -276,6 +365,11 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
     if (tid == 0) {
         *src.nlast() = sNl;
         src.store(mx, my, mt, P);
+        if constexpr (G::kOn) {
+            TrackHealth* t = gate.g.track + src.track();
+            t->frames = trFrames; t->accepted_total = trAcc; t->rejected_total = trRej; t->bad_streak = trStreak; t->lost = trLost;
+            t->pad[0] = t->pad[1] = t->pad[2] = 0;
+        }
     }
 }
 
@@ -285,9 +379,18 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams
     loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc);
 }
 
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                               const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                               int first, int count, int predict_first, GateState g) {
+    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g});
+}
+
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first) {
-    hipLaunchKernelGGL(k_loc_steps, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
+                      const double* enc, int first, int count, int predict_first, const GateState* gate) {
+    if (gate)
+        hipLaunchKernelGGL(k_loc_steps_gated, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate);
+    else
+        hipLaunchKernelGGL(k_loc_steps, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
 }
 
 } // namespace aslam

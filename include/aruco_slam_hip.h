@@ -128,7 +128,8 @@ int aslam_set_state(aslam_ctx* ctx, int N, const double* mu, const double* sigma
  * call; corners M*8 floats (x0,y0,...,x3,y3), rvecs/tvecs M*3 doubles.  Arrays may be NULL. */
 int aslam_get_detections(aslam_ctx* ctx, int* M, int* ids, float* corners, double* rvecs, double* tvecs);
 /* the observations popped from obs_ in pop order (aruco_slam.cpp:92-95) for the last frame: id, landmark index
- * at push time (-1 new), action (0 augment, 1 update, 2 stationary no-op), (x,y,theta), diag(R). */
+ * at push time (-1 new), action (0 augment, 1 update, 2 stationary no-op, 3 update rejected by the innovation gate of a localizing
+ * filter), (x,y,theta), diag(R). */
 int aslam_get_observations(aslam_ctx* ctx, int* n, int* ids, int* idx, int* action, double* xyth, double* Rdiag);
 /* aruco_id_map inverted: ids[i] = marker id of landmark index i (aruco_slam.h:164) */
 int aslam_get_landmark_ids(aslam_ctx* ctx, int* L, int* ids);
@@ -384,6 +385,65 @@ int aslam_relocalize(aslam_ctx* ctx, int slot, const aslam_relocalize_params* pa
    only arms it); unsolved robots are untouched. */
 int aslam_fleet_relocalize(aslam_ctx* ctx, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params,
                            int apply, aslam_relocalize_result* out /* count */);
+
+/* ---- innovation gate and lost-track detection for localization and localization fleets ------------------------
+ * The reference tests every correction with `ze.norm() >= 1 || K.norm() >= 10` (aruco_slam.cpp:156-175) but only prints the result
+ * ("Outlier test logs only"; the skip is a commented-out `continue`).  Here the test becomes a chi-square gate
+ * with a consequence, and every filter keeps a record from which a caller sees that it is lost and should be relocalized.
+ * The gate is off by default, and with it off every kernel, call and result is what it is without this section.  It can be set in
+ * any mode and persists, but takes effect only in the localization steps of the single localizing filter (aslam_localize_begin;
+ * single-camera and rig steps) and of a localization fleet (aslam_fleet_begin).  SLAM, rig SLAM and fleet SLAM ignore it: their
+ * chains compose a frame's corrections into one factorisation, where a per-correction gate has no place.
+ * With a gate set those steps run a gated variant of the chain.  Everything up to the chain is unchanged: the predict, the lookup of
+ * ids, the pop order, the "stationary" test against the previous step's list and every correction's H, ze and R from the
+ * frame-start pose.  Then for each prepared correction (action 1), in pop order:
+ * 1. S = H P H^T + R from the live P, S^-1 and K = P H^T S^-1, exactly as without the gate.
+ * 2. d2 = ze^T S^-1 ze, the squared Mahalanobis distance of the innovation.
+ * 3. The correction is rejected iff gate_d2 is finite and !(d2 <= gate_d2); a NaN d2 therefore rejects.
+ * 4. A rejected correction changes neither the pose nor P.
+ * 5. With gate_d2 = +inf (monitor only) nothing is rejected, and pose, Sigma_xx, last-observed list, pop list and EKF stats are
+ *    bit for bit those of the ungated call.
+ * 6. The correction counts as ref_flagged iff ||ze||_2 >= 1 || ||K||_F >= 10, accepted or not: the reference's own test, K being
+ *    the 3 x 3 pose gain (the frozen map zeroes the landmark rows of the reference's K).
+ * A rejected observation is left out of the list the step leaves as last_observed_marker_ (what the reference's `continue` would
+ * do): that list holds the accepted updates and the stationary no-ops, in pop order.  Stationary no-ops are not corrections: they
+ * are neither attempted nor gated.  aslam_get_observations reports a rejected observation with action 3; count [2] of
+ * aslam_get_slot_ekf_stats ("corrections fused") counts the accepted corrections only.
+ * Per EKF slot the step leaves an aslam_slot_health: attempted = corrections the step prepared, accepted = fused, rejected =
+ * skipped by the gate, ref_flagged as above, nis_sum = sum of d2 over the accepted in pop order, d2_max = the greatest non-NaN d2
+ * over the attempted (0 if none), worst_id = the id of the observation with d2_max (the first in pop order of equal ones; -1 if
+ * none).  A record describes the last gated step of its slot (zero before any).
+ * Per filter (one per robot; one for the single filter) an aslam_track_health: frames = gated frames stepped since the last seat,
+ * accepted_total / rejected_total = corrections fused / skipped since then, bad_streak = consecutive bad frames, lost =
+ * bad_streak >= lost_after.  In integers: a frame is bad iff attempted >= min_attempted and 100 accepted < min_accept_percent
+ * attempted; good iff attempted >= min_attempted and not bad.  A good frame sets bad_streak to 0, a bad one adds 1, a frame with
+ * fewer than min_attempted corrections leaves it; the streak is carried across the slots of a call and across calls.  Every seat
+ * clears the record: aslam_localize_begin, aslam_fleet_begin, aslam_fleet_set_pose, and a solved apply != 0 of aslam_relocalize /
+ * aslam_fleet_relocalize (the solved robots only).  `lost` only reports: the gate works the same way afterwards, and recovery is the
+ * caller's aslam_relocalize / aslam_fleet_relocalize.
+ * Defaults: gate_d2 = 16.266, the 0.999 quantile of chi-square with 3 degrees of freedom; min_attempted 2, min_accept_percent 50,
+ * lost_after 3.  They are the maintainer's choice; nobody has measured them.  ASLAM_E_INVALID: gate_d2 not > 0 (NaN included; +inf
+ * is allowed), min_attempted < 1, min_accept_percent outside [0, 100], lost_after < 1.
+ * No floating-point atomics and a fixed order of every sum: a robot's results do not depend on the other robots of the call. */
+typedef struct { double gate_d2; int min_attempted, min_accept_percent, lost_after, pad; } aslam_gate_params;
+void aslam_default_gate_params(aslam_gate_params* params);
+/* params NULL: the gate is off again.  Allowed in every mode; the first call with parameters allocates the health records
+   (2 max_batch slot records, ASLAM_MAX_ROBOTS + 1 track records, and a page-locked copy of each), aslam_destroy frees them.  The
+   track records are not touched by this call. */
+int aslam_set_innovation_gate(aslam_ctx* ctx, const aslam_gate_params* params /* NULL: off */);
+/* *on = 1 while a gate is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
+int aslam_get_innovation_gate(aslam_ctx* ctx, int* on, aslam_gate_params* out);
+typedef struct { int attempted, accepted, rejected, ref_flagged; double nis_sum, d2_max; int worst_id, pad; } aslam_slot_health;
+/* The getters wait for the submitted work as aslam_get_slot_ekf_stats does and refuse with ASLAM_E_STATE while no gate is set or in
+   a mode the gate does not work in (the slot records: localization and fleet localization; aslam_get_track_health: localization;
+   aslam_fleet_get_health: fleet localization).
+   aslam_get_slot_health: EKF slots [first, first + count) within [0, 2 max_batch) - a frame slot for single-camera and fleet calls,
+   max_batch + step for a rig step (step as in aslam_get_rig_step_ekf_stats). */
+int aslam_get_slot_health(aslam_ctx* ctx, int first, int count, aslam_slot_health* out);
+typedef struct { int frames, accepted_total, rejected_total, bad_streak, lost, pad[3]; } aslam_track_health;
+int aslam_get_track_health(aslam_ctx* ctx, aslam_track_health* out);                          /* the single localizing filter */
+/* *n_robots = robots of the fleet; the records of the first min(max, *n_robots) robots go to out */
+int aslam_fleet_get_health(aslam_ctx* ctx, int max, int* n_robots, aslam_track_health* out);  /* a localization fleet */
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
