@@ -10,14 +10,18 @@
 
 // In-launch hand-offs between workgroups (ekf_window.hip, one-launch window): an agent-scope acquire, a wait for this wave's older
 // vector-memory operations, and global-address-space 64-bit words for write-through (sc1) stores and counters.  The CPU emulation
-// of the tests has sequentially consistent atomics and no memory counters.
+// of the tests has sequentially consistent atomics and no memory counters.  ASLAM_WAVE_LOCKSTEP marks a place where one lane acts on
+// what the other lanes of its wave did before it in program order: nothing on the device, where a wave executes in lockstep; the
+// emulation runs the lanes of a wave one after the other between barriers and has to bring them together there.
 #if defined(__HIP__)
 #define ASLAM_ACQUIRE_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
 #define ASLAM_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define ASLAM_WAVE_LOCKSTEP() do { } while (0)
 typedef __attribute__((address_space(1))) unsigned long long aslam_gu64;
 #else
 #define ASLAM_ACQUIRE_AGENT() __threadfence()
 #define ASLAM_VMCNT(n) do { } while (0)
+#define ASLAM_WAVE_LOCKSTEP() hipemu::wave_sync()
 typedef unsigned long long aslam_gu64;
 #endif
 

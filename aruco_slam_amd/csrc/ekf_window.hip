@@ -721,6 +721,7 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
       }
       }
       if (ONE && tid < 64) {                                        // wave 0, the only one that stores t / u: its stores, then the count
+          ASLAM_WAVE_LOCKSTEP();                                    // (every lane's stores of the batch, not only lane 0's)
           ASLAM_VMCNT(0);
           if (tid == 0) win_signal(E.d_win_sync + kWinSyncLine * (1 + b), epoch, avail);
       }

@@ -50,7 +50,10 @@ typedef struct {
     int    persistent_waves;             /* wavefronts of the work-queue kernels; 0 = default (4096) */
     int    max_updates_per_frame;        /* EKF corrections fused per frame; <= 24 selects the 3-kernel fast chain,
                                             larger values (up to 128) the general 5-kernel chain; exceeding it at run
-                                            time is reported as ASLAM_E_CAPACITY */
+                                            time is reported as ASLAM_E_CAPACITY.  A frame over the cap keeps its prediction
+                                            and its new landmarks and applies none of its corrections: its statistics count
+                                            0 fused corrections, while its pop list (action 1) and the last-observed list
+                                            are written as if they had been fused */
     unsigned cap_starts_per_frame;       /* 0 = defaults */
     unsigned cap_contours_per_frame;
     unsigned cap_points_per_frame;
@@ -504,7 +507,9 @@ int aslam_debug_get_candidates(aslam_ctx* ctx, int slot, int stage /*0 quads (un
                                int* n, float* corners, int* sizes, int* ids);
 /* overwrite a slot's per-marker observations (id, passed-the-gates flag, (x,y,theta), diag R); together with
  * aslam_run_staged(..., with_ekf = 2) = "EKF steps only" this replays recorded observation sequences through the
- * device EKF without the detector (tests/test_ekf_golden.py). */
+ * device EKF without the detector (tests/test_ekf_golden.py).  Only this call can deliver an id outside [0, 1024) (a dictionary
+ * holds at most 1024 markers): with the flag set, such an observation is a new landmark in every frame, nothing is written to the
+ * id table, and aslam_get_landmark_ids reports the id as given (tests/test_plan_kernel.py). */
 int aslam_debug_inject_observations(aslam_ctx* ctx, int slot, int n, const int* ids, const int* valid, const double* xyth,
                                     const double* Rdiag);
 /* the pose stage on given quads, without the detector (tests/test_pose_kernel.py).  aslam_debug_inject_candidates overwrites a slot's

@@ -176,55 +176,63 @@ class LiteralSlam:
         self.log = []
         while q.c:
             ob = q.pop()
-            Rk = ob["R"]
-            if ob["index"] >= 0:
-                N = self.mu.size
-                i3 = 3 + 3 * ob["index"]
-                F = np.zeros((6, N)); F[:3, :3] = np.eye(3); F[3:, i3:i3 + 3] = np.eye(3)
-                mx, my, mth = mu[i3], mu[i3 + 1], mu[i3 + 2]
-                x, y, th = mu[0], mu[1], mu[2]
-                s, c = math.sin(th), math.cos(th)
-                gdx, gdy = mx - x, my - y
-                gdth = norm_angle(mth - th)
-                z_hat = np.array([gdx * c + gdy * s, -gdx * s + gdy * c, gdth])
-                z = ob["z"].copy()
-                ze = z - z_hat
-                ze[2] = norm_angle(ze[2])
-                Gxm = np.array([[-c, -s, -gdx * s + gdy * c, c, s, 0],
-                                [s, -c, -gdx * c - gdy * s, -s, c, 0],
-                                [0, 0, -1, 0, 0, 1]], float)
-                Gx = Gxm @ F
-                Kg = self.sigma @ Gx.T @ np.linalg.inv(Gx @ self.sigma @ Gx.T + Rk)
-                last = next((o for o in self.last_observed if o["id"] == ob["id"]), None)
-                if last is not None and np.linalg.norm(last["last"] - z) < 0.01:
-                    action = 2                                  # 3x0 block: nothing happens
-                else:
-                    action = 1
-                    ob["last"] = z
-                    self.mu = self.mu + Kg @ ze
-                    self.sigma = (np.eye(N) - Kg @ Gx) @ self.sigma
-            else:
-                action = 0
-                sinth = float(np.float32(math.sin(mu[2])))
-                costh = float(np.float32(math.cos(mu[2])))
-                N = self.mu.size
-                map_x = mu[0] + costh * ob["z"][0] - sinth * ob["z"][1]
-                map_y = mu[1] + sinth * ob["z"][0] + costh * ob["z"][1]
-                map_th = norm_angle(mu[2] + ob["z"][2])
-                dx, dy = map_x - mu[0], map_y - mu[1]
-                sigma_s = self.sigma[:3, :3]
-                Gsk = np.array([[-costh, -sinth, -sinth * dx + costh * dy], [sinth, -costh, -dx * costh - dy * sinth], [0, 0, -1]], float)
-                Gmi = np.array([[costh, sinth, 0], [-sinth, costh, 0], [0, 0, 1]], float)
-                sigma_mm = Gmi @ (Gsk @ sigma_s @ Gsk.T + Rk).T @ Gmi.T
-                sigma_mx = -Gmi @ Gsk @ self.sigma[:3, :]
-                tmp = np.zeros((N + 3, N + 3))
-                tmp[:N, :N] = self.sigma
-                tmp[:N, N:] = sigma_mx.T
-                tmp[N:, :N] = sigma_mx
-                tmp[N:, N:] = sigma_mm
-                self.sigma = tmp
-                self.mu = np.concatenate([self.mu, [map_x, map_y, map_th]])
-                self.id_map.setdefault(ob["id"], (self.mu.size - 3) // 3 - 1)
+            action = self.correct(ob, mu) if ob["index"] >= 0 else self.augment(ob, mu)
             observed.append(ob)
             self.log.append((ob["id"], ob["index"], action))
         self.last_observed = observed
+
+    # aruco_slam.cpp:108-207, one popped observation of a mapped marker; mu = the pre-frame mean (:88); returns the branch taken
+    def correct(self, ob, mu):
+        Rk = ob["R"]
+        N = self.mu.size
+        i3 = 3 + 3 * ob["index"]
+        F = np.zeros((6, N)); F[:3, :3] = np.eye(3); F[3:, i3:i3 + 3] = np.eye(3)
+        mx, my, mth = mu[i3], mu[i3 + 1], mu[i3 + 2]
+        x, y, th = mu[0], mu[1], mu[2]
+        s, c = math.sin(th), math.cos(th)
+        gdx, gdy = mx - x, my - y
+        gdth = norm_angle(mth - th)
+        z_hat = np.array([gdx * c + gdy * s, -gdx * s + gdy * c, gdth])
+        z = ob["z"].copy()
+        ze = z - z_hat
+        ze[2] = norm_angle(ze[2])
+        Gxm = np.array([[-c, -s, -gdx * s + gdy * c, c, s, 0],
+                        [s, -c, -gdx * c - gdy * s, -s, c, 0],
+                        [0, 0, -1, 0, 0, 1]], float)
+        Gx = Gxm @ F
+        Kg = self.sigma @ Gx.T @ np.linalg.inv(Gx @ self.sigma @ Gx.T + Rk)
+        last = next((o for o in self.last_observed if o["id"] == ob["id"]), None)
+        if last is not None and np.linalg.norm(last["last"] - z) < 0.01:
+            action = 2                                  # 3x0 block: nothing happens
+        else:
+            action = 1
+            ob["last"] = z
+            self.mu = self.mu + Kg @ ze
+            self.sigma = (np.eye(N) - Kg @ Gx) @ self.sigma
+        return action
+
+    # aruco_slam.cpp:208-260, one popped observation of a new marker
+    def augment(self, ob, mu):
+        Rk = ob["R"]
+        action = 0
+        sinth = float(np.float32(math.sin(mu[2])))
+        costh = float(np.float32(math.cos(mu[2])))
+        N = self.mu.size
+        map_x = mu[0] + costh * ob["z"][0] - sinth * ob["z"][1]
+        map_y = mu[1] + sinth * ob["z"][0] + costh * ob["z"][1]
+        map_th = norm_angle(mu[2] + ob["z"][2])
+        dx, dy = map_x - mu[0], map_y - mu[1]
+        sigma_s = self.sigma[:3, :3]
+        Gsk = np.array([[-costh, -sinth, -sinth * dx + costh * dy], [sinth, -costh, -dx * costh - dy * sinth], [0, 0, -1]], float)
+        Gmi = np.array([[costh, sinth, 0], [-sinth, costh, 0], [0, 0, 1]], float)
+        sigma_mm = Gmi @ (Gsk @ sigma_s @ Gsk.T + Rk).T @ Gmi.T
+        sigma_mx = -Gmi @ Gsk @ self.sigma[:3, :]
+        tmp = np.zeros((N + 3, N + 3))
+        tmp[:N, :N] = self.sigma
+        tmp[:N, N:] = sigma_mx.T
+        tmp[N:, :N] = sigma_mx
+        tmp[N:, N:] = sigma_mm
+        self.sigma = tmp
+        self.mu = np.concatenate([self.mu, [map_x, map_y, map_th]])
+        self.id_map.setdefault(ob["id"], (self.mu.size - 3) // 3 - 1)
+        return action
