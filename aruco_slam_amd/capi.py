@@ -217,6 +217,7 @@ _SIGS = {
     "aslam_debug_inject_observations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp, _dp]),
     "aslam_debug_inject_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _fp]),
     "aslam_debug_run_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
+    "aslam_debug_run_pose_refined": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip]),
     "aslam_debug_run_identify": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "aslam_debug_get_identified": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _u8p, _llp]),
     "aslam_debug_inject_contours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
@@ -811,12 +812,14 @@ class Context:
             raise ValueError("one id, one rotation and 4 corners per candidate")
         self._ck(self.lib.aslam_debug_inject_candidates(self.h, int(slot), int(ids.size), _ptr(ids, _ip), _ptr(rots, _ip), _ptr(corners, _fp)))
 
-    def run_pose(self, first, count, robot_of_slot=None):
-        """the pose stage alone on the slots' injected candidates (robot_of_slot: a fleet's robot of each slot)"""
+    def run_pose(self, first, count, robot_of_slot=None, refine=False):
+        """the pose stage alone on the slots' injected candidates (robot_of_slot: a fleet's robot of each slot); refine: with the
+        corner refinement of a detection call, over the slots' staged frames"""
         rs = None if robot_of_slot is None else np.ascontiguousarray(robot_of_slot, dtype=np.int32).reshape(-1)
         if rs is not None and rs.size != count:
             raise ValueError("one robot per slot")
-        self._ck(self.lib.aslam_debug_run_pose(self.h, int(first), int(count), _ptr(rs, _ip)))
+        fn = self.lib.aslam_debug_run_pose_refined if refine else self.lib.aslam_debug_run_pose
+        self._ck(fn(self.h, int(first), int(count), _ptr(rs, _ip)))
 
     def run_identify(self, first, count):
         """the identification stage alone on the slots' injected candidates, over the grey frames their last detection read"""

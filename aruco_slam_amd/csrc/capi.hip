@@ -470,6 +470,15 @@ const uint8_t* slot_gray(const aslam_ctx* c, int f0) {
     return c->channels == 1 ? c->d_in + (size_t)f0 * c->in_frame_bytes : c->d_gray + (size_t)f0 * c->rows * c->cols;
 }
 
+// k_pose's corner refinement for a launch whose first frame is slot f0 (run_detect and aslam_debug_run_pose_refined): the detector
+// parameters' window, cv::cornerSubPix's iteration count (clamped to 1..100) and squared accuracy, the mask aslam_set_detector_params
+// uploaded and the grey frames from slot f0 on
+RefineCfg refine_cfg(const aslam_ctx* c, int f0) {
+    const double eps = std::max(c->dp.cornerRefinementMinAccuracy, 0.0);
+    return RefineCfg{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
+                     c->cfg.rows, c->cfg.cols, eps * eps, c->d_refine_mask, slot_gray(c, f0)};
+}
+
 // k_identify over the work list of the frames from f0 on (rec: k_identify_record instead, writing the records of those frames)
 void launch_identify_stage(aslam_ctx* c, hipStream_t st, const DetectCfg& g, int f0, IdentRecord* rec = nullptr) {
     prof_begin(c, P_IDENTIFY, st);
@@ -547,7 +556,6 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
     for (int f0 = first; f0 < first + count; f0 += chunk) {
         const int nf = std::min(chunk, first + count - f0);
         launch_contour_stage(c, st, g, f0, nf);
-        const uint8_t* gray = slot_gray(c, f0);
         const ContourRec* contours = c->d_contours + (size_t)f0 * g.cap_contours;
         const unsigned* points = c->d_points + (size_t)f0 * g.cap_points;
         prof_begin(c, P_QUADS, st);
@@ -560,10 +568,7 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
                         c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_work);
         prof_end(c);
         launch_identify_stage(c, st, g, f0);
-        const RefineCfg rf{c->dp.doCornerRefinement ? 1 : 0, c->dp.cornerRefinementWinSize, std::min(std::max(c->dp.cornerRefinementMaxIterations, 1), 100),
-                           g.rows, g.cols, std::max(c->dp.cornerRefinementMinAccuracy, 0.0) * std::max(c->dp.cornerRefinementMinAccuracy, 0.0),
-                           c->d_refine_mask, gray};
-        launch_pose_stage(c, k, st, f0, nf, rf);
+        launch_pose_stage(c, k, st, f0, nf, refine_cfg(c, f0));
     }
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
     HIP_TRY(c, hipGetLastError());
@@ -3060,7 +3065,10 @@ int aslam_debug_inject_candidates(aslam_ctx* c, int slot, int n, const int* ids,
     return ASLAM_OK;
 }
 
-int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of_slot) {
+namespace {
+// both pose hooks: what run_detect launches at P_POSE for the call's frames, chunk by chunk (slot first + i: camera i % n of a rig),
+// without corner refinement (no grey frame is needed) or with the detection call's own (refine)
+int debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of_slot, bool refine) {
     if (!c) return ASLAM_E_INVALID;
     int r = check_slot_range(c, first, count);
     if (r) return r;
@@ -3070,10 +3078,30 @@ int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of
         for (int i = 0; i < count; i++)
             if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     if (!robot_of_slot && c->rig_n == 0 && !c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
+    if (refine) {
+        if (!c->dp.doCornerRefinement) return fail(c, ASLAM_E_STATE, "corner refinement is not enabled (aslam_set_detector_params)");
+        if (c->rows == 0) return fail(c, ASLAM_E_STATE, "no frames staged");
+        for (int i = first; i < first + count; i++)
+            if ((int)c->slot_shape.size() <= i || c->slot_shape[i] != frame_shape(c))
+                return fail(c, ASLAM_E_STATE, "slot has no frame of the current shape (stage one and run a detection pass on it first)");
+    }
     r = sync_streams(c);
     if (r) return r;
-    // what run_detect launches at P_POSE for the call's frames, chunk by chunk (slot first + i: camera i % n of a rig), without
-    // corner refinement (there is no grey frame)
+    if (refine) {
+        // cornerSubPix starts inside the image: a detection pass never hands it anything else, and the loop relies on it
+        std::vector<FinalCand> h;
+        for (int i = first; i < first + count; i++) {
+            unsigned n = 0;
+            HIP_TRY(c, hipMemcpy(&n, c->d_nfinal + i, sizeof(unsigned), hipMemcpyDeviceToHost));
+            n = std::min(n, (unsigned)kCandMax);
+            h.resize(n);
+            if (n) HIP_TRY(c, hipMemcpy(h.data(), c->d_finals + (size_t)i * kCandMax, n * sizeof(FinalCand), hipMemcpyDeviceToHost));
+            for (const FinalCand& f : h)
+                for (int q = 0; q < 4 && f.id >= 0; q++)
+                    if (!(f.c[2 * q] >= 0 && f.c[2 * q] < (float)c->cfg.cols && f.c[2 * q + 1] >= 0 && f.c[2 * q + 1] < (float)c->cfg.rows))
+                        return fail(c, ASLAM_E_INVALID, "identified candidate with a corner outside the frame");
+        }
+    }
     const Call k{first, count, c->rig_n > 0 ? &c->rig : nullptr, robot_of_slot, first, count};
     hipStream_t st = c->stream;
     if (c->last_detect && c->last_detect != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
@@ -3084,13 +3112,23 @@ int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of
         r = pinned_upload(c, c->fleet_camidx_up, c->d_fleet_camidx + first, robot_of_slot, count, st);
         if (r) return r;
     }
-    RefineCfg rf{};
-    rf.on = 0;
+    RefineCfg off{};
+    off.on = 0;
     const int chunk = detect_chunk();
-    for (int f0 = first; f0 < first + count; f0 += chunk) launch_pose_stage(c, k, st, f0, std::min(chunk, first + count - f0), rf);
+    for (int f0 = first; f0 < first + count; f0 += chunk)
+        launch_pose_stage(c, k, st, f0, std::min(chunk, first + count - f0), refine ? refine_cfg(c, f0) : off);
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
+}
+} // namespace
+
+int aslam_debug_run_pose(aslam_ctx* c, int first, int count, const int* robot_of_slot) {
+    return debug_run_pose(c, first, count, robot_of_slot, false);
+}
+
+int aslam_debug_run_pose_refined(aslam_ctx* c, int first, int count, const int* robot_of_slot) {
+    return debug_run_pose(c, first, count, robot_of_slot, true);
 }
 
 int aslam_debug_run_identify(aslam_ctx* c, int first, int count) {

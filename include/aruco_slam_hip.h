@@ -516,12 +516,19 @@ int aslam_debug_inject_observations(aslam_ctx* ctx, int slot, int n, const int* 
  * final candidate list with n <= 2048 quads: ids[i] (-1 = rejected), rots[i] in 0..3 (the corner rotation identification found) and
  * corners[8 i .. 8 i + 7] (x0 y0 .. x3 y3 before the rotation).  aslam_debug_run_pose then launches on slots [first, first + count)
  * what a detection call launches after identification: the ordered list of identified candidates (at most 128), the same-id
- * inside-quad filter, solvePnP, the observation and its gates, without corner refinement.  Slot first + i is camera i % n of the rig
+ * inside-quad filter, solvePnP, the observation and its gates, without corner refinement (aslam_debug_run_pose_refined runs it).  Slot first + i is camera i % n of the rig
  * when one is set (the single camera otherwise); robot_of_slot[i] names its robot while a fleet is active (NULL otherwise).  The
  * results read back through aslam_get_slot_detections / aslam_get_slot_raw_observations, and aslam_run_staged(..., with_ekf = 2)
  * fuses them. */
 int aslam_debug_inject_candidates(aslam_ctx* ctx, int slot, int n, const int* ids, const int* rots, const float* corners /* n x 8 */);
 int aslam_debug_run_pose(aslam_ctx* ctx, int first, int count, const int* robot_of_slot /* count entries, or NULL */);
+/* the same with the corner refinement of a detection call between the filter and solvePnP (tests/test_subpix_kernel.py): cv::cornerSubPix
+ * on the 4 corners of every kept marker with the detector parameters in force (window, iteration count clamped to 1..100, accuracy),
+ * reading the grey frame a detection pass reads: a gray slot as staged, a bgr8 slot as its last detection pass converted it.  Refused
+ * with ASLAM_E_STATE when doCornerRefinement is not set or a slot of the range holds no frame of the current shape, and with
+ * ASLAM_E_INVALID when an identified candidate (id >= 0) has a corner outside [0, cols) x [0, rows): a detection pass never produces
+ * one, and the refinement starts from a point inside the image. */
+int aslam_debug_run_pose_refined(aslam_ctx* ctx, int first, int count, const int* robot_of_slot /* count entries, or NULL */);
 /* the identification stage on given quads (tests/test_identify_kernel.py).  aslam_debug_run_identify launches on slots [first,
  * first + count) what a detection call launches at identification, with the context's dictionary and detector parameters: the
  * perspective removal, the inner-region meanStdDev, Otsu, the cell votes, _getBorderErrors and Dictionary::identify, on every
