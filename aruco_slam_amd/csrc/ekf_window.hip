@@ -28,7 +28,7 @@
 //             j + 2 as they stand after step j, the prepare wave applies step j + 1's correction to them and to the pose rows it
 //             carries in its own registers, forms c, S, S^-1, Kt and hands the operands to the workers: one barrier per step.  The
 //             workers log -Kt (the A operand they read) and worker wave 0 the header the prepare wave leaves in LDS (S^-1, ze, the
-//             Jacobian scalars);
+//             Jacobian scalars); in the one-launch window a logger wave of its own copies both from LDS to the log;
 //     replay  (SP / 8 workgroups) replays the log of piece i - 1, each on its own 8 columns of Lambda (all rows; in LDS) and its
 //             part of psi, and logs t and u;
 //     Psi     (T workgroups) adds the t^T u of piece i - 2 to Psi on the matrix cores.
@@ -56,16 +56,18 @@ constexpr unsigned long long kWinSpinTicks = 6000000000ull;   // (the CPU emulat
 #endif
 // a wait that gave up: the FIRST code stays (a replay that stalls makes its Psi workgroups give up after it)
 __device__ __forceinline__ void win_fail(const EkfState& E, unsigned code) { atomicCAS(E.d_win_err, 0u, code); }
-// at the end of a publication step: this wave's stores of every step but the last kWinPubLag complete.  A worker wave issues RW
-// log stores per step, worker wave 0 one more (the header) and its count stores: all but the newest RW kWinPubLag (wave 0:
-// (RW + 1) kWinPubLag) store instructions are older than those steps' stores
-template <int RW> __device__ __forceinline__ void win_vmcnt_lag(bool wave0) {
-    static_assert(RW == 2 && kWinPubLag == 4, "the counts below are (RW + 1) kWinPubLag and RW kWinPubLag");
-    if (wave0) ASLAM_VMCNT(12);
-    else ASLAM_VMCNT(8);
+// at the end of a publication step: the logger wave's stores of every step but the last kWinPubLag complete.  The logger wave
+// issues 3 NC + 1 log stores per step (the three operand rows in NC chunks of 64 columns, the header), its count stores and no
+// load: all but the newest (3 NC + 1) kWinPubLag store instructions are older than those steps' stores
+template <int NC> __device__ __forceinline__ void win_vmcnt_lag() {
+    static_assert(kWinPubLag == 4 && NC >= 1 && NC <= 3, "the counts below are (3 NC + 1) kWinPubLag");
+    static_assert((3 * NC + 1) * kWinPubLag <= 63, "vmcnt has six bits");
+    if constexpr (NC == 1) ASLAM_VMCNT(16);
+    else if constexpr (NC == 2) ASLAM_VMCNT(28);
+    else ASLAM_VMCNT(40);
 }
 
-// development aid (make FLAGS+=-DASLAM_WIN_STAMPS): cycle stamps of the prepare wave's step phases and of the workers, summed over a piece
+// development aid (make FLAGS+=-DASLAM_WIN_STAMPS): cycle stamps of the prepare wave's step phases, of the workers and of the logger wave, summed over a piece
 #ifdef ASLAM_WIN_STAMPS
 #define WSTAMP(i) do { const long long t_ = clock64(); stamp_acc[i] += t_ - stamp_last; stamp_last = t_; } while (0)
 #else
@@ -138,7 +140,8 @@ __device__ __forceinline__ void win_publish(const v4d (&acc)[RW][T], int p, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// T tiles per side, RW tile rows per worker wave: ceil(T / RW) worker waves + 1 prepare wave.  With T = 4 (2 x 2 rows on two
+// T tiles per side, RW tile rows per worker wave: ceil(T / RW) worker waves + 1 prepare wave (+ 1 logger wave in the one-launch
+// window: it stores the step log and publishes the step count, so that neither lies on the workers' path).  With T = 4 (2 x 2 rows on two
 // workers) the prepare wave - the kernel's critical path - has a SIMD to itself (measured: -11 % per step); at T = 8 the same idea
 // (3 + 3 + 2 rows on three workers) makes the workers the bottleneck (measured: +12 %), so it keeps one worker per SIMD.
 template <int T, bool ONE> struct WinChainLds {
@@ -146,7 +149,7 @@ template <int T, bool ONE> struct WinChainLds {
     double sA[2][4][SPP];                  // a step's A operand rows  Aop[k][row]   (P += Aop^T Bop)
     double sB[2][4][SPP];                  // ... and B operand rows   Bop[k][column]
     double sPub[2][3][SPP];                // the landmark rows of the step after next
-    double sHdr[2][kWinHdr];               // a step's log header, from the prepare wave to worker wave 0 (which stores it)
+    double sHdr[2][kWinHdr];               // a step's log header, from the prepare wave to the wave that stores it (logger; pieces: worker wave 0)
 #ifdef ASLAM_WIN_POSE_CHECK
     double sDbg[2][3][SPP];                // the accumulators' pose rows, to compare with the prepare wave's own
 #endif
@@ -159,7 +162,7 @@ template <int T, int RW, bool ONE>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
-    constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + 1) * 64;
+    constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
     auto& sA = L.sA; auto& sB = L.sB; auto& sPub = L.sPub; auto& sMu = L.sMu; auto& sS = L.sS; auto& sOff = L.sOff;
     auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sFrm = L.sFrm;
@@ -259,33 +262,27 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #endif
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
-            // one-launch window: steps 0 .. j - 1 - kWinPubLag are complete in every worker wave (each waited for them at the end of
-            // step j - 1, before the barrier just passed): one lane publishes their count for the replay workgroups
-            if (ONE && j > kWinPubLag && j % kWinPubEvery == 0 && tid == 0) win_signal(E.d_win_sync, wd.epoch, j - kWinPubLag);
             if (j >= 0) {
                 const int cb = j & 1;
                 double* const log = logbase + (size_t)j * win_log_stride(T);
                 double b[T];
 #pragma unroll
                 for (int t = 0; t < T; t++) b[t] = sB[cb][lk][16 * t + li];
+#ifdef ASLAM_WIN_STAMPS
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (stamps only: the B operand's reads apart from the products)
+                WSTAMP(1);
+#endif
 #pragma unroll
                 for (int rr = 0; rr < RW; rr++) {
                     if (T % RW != 0 && wave * RW + rr >= T) break;
                     const double a = sA[cb][lk][16 * (wave * RW + rr) + li];
 #pragma unroll
                     for (int t = 0; t < T; t++) acc[rr][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[t], acc[rr][t], 0, 0, 0);
-                    if (lk < 3) {                                                  // the step's log rows: -Kt (predict: its rows 0..2)
-                        if (ONE) st_wt(log + lk * SP + 16 * (wave * RW + rr) + li, a);
-                        else log[lk * SP + 16 * (wave * RW + rr) + li] = a;
-                    }
+                    // pieces: the step's log rows, -Kt (predict: its rows 0..2).  One launch: the logger wave stores the log
+                    if (!ONE && lk < 3) log[lk * SP + 16 * (wave * RW + rr) + li] = a;
                 }
-                if (wave == 0 && lane < kWinHdr) {
-                    if (ONE) st_wt(log + 3 * SP + lane, L.sHdr[cb][lane]);
-                    else log[3 * SP + lane] = L.sHdr[cb][lane];
-                }
-                // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete.
-                // The wave issues RW log stores per step (wave 0 one more, and its count stores) and no load: a static count
-                if (ONE && (j + 1) % kWinPubEvery == 0) win_vmcnt_lag<RW>(wave == 0);
+                if (!ONE && wave == 0 && lane < kWinHdr) log[3 * SP + lane] = L.sHdr[cb][lane];
+                WSTAMP(2);
                 if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
 #ifdef ASLAM_WIN_POSE_CHECK
                     if (wave == 0 && lk < 3) {
@@ -297,16 +294,13 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     if (pn != 255) win_publish<T, RW>(acc, 3 + 3 * pn, wave, lk, li, &sPub[cb][0][0], SPP);
                 }
             }
-            WSTAMP(1);
+            WSTAMP(3);
             ASLAM_LDS_BARRIER();
-        }
-        if (ONE) {                                                  // the whole log: after every worker wave's last stores
-            ASLAM_VMCNT(0);
-            ASLAM_LDS_BARRIER();
-            if (tid == 0) win_signal(E.d_win_sync, wd.epoch, NS);
         }
 #ifdef ASLAM_WIN_STAMPS
-        if (lane == 0 && (ONE || wd.piece == 1)) printf("worker %d T %d steps %d: barrier-wait %lld work %lld cycles per step\n", wave, T, NS, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1));
+        if (lane == 0 && (ONE || wd.piece == 1))
+            printf("worker %d T %d steps %d: barrier-wait %lld | B reads %lld A reads + products%s %lld publish %lld cycles per step\n", wave, T, NS, stamp_acc[0] / (NS + 1),
+                   stamp_acc[1] / (NS + 1), ONE ? "" : " + log", stamp_acc[2] / (NS + 1), stamp_acc[3] / (NS + 1));
 #endif
         // P_K for the next piece / the flush
         double* Pout = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
@@ -317,6 +311,42 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #pragma unroll
                 for (int reg = 0; reg < 4; reg++)
                     if (T % RW == 0 || wave * RW + rr < T) Pout[(size_t)(16 * (wave * RW + rr) + lk + 4 * reg) * SP + 16 * t + li] = acc[rr][t][reg];
+        return;
+    }
+
+    if (ONE && wave == NWK + 1) {
+        // ============================ logger wave (one-launch window): the step log and its publication ============================
+        // In phase j the operand rows and the header of step j lie in the parity buffers sA[j & 1], sHdr[j & 1], which nobody writes
+        // before the phase's barrier: this wave copies them to the log (write-through) and is the only wave of the role that stores
+        // to the log in the loop, so the publication needs this wave's store counter alone.  Steps 0 .. j - 1 - kWinPubLag are complete
+        // when it has waited for them at the end of step j - 1; it then passes the barrier (as every wave that read or wrote those
+        // steps' operands has) and one of its lanes publishes their count for the replay workgroups.
+        ASLAM_LDS_BARRIER();                                       // (pairs with the workers' barrier after their first publish)
+#ifdef ASLAM_WIN_STAMPS
+        long long stamp_acc[2] = {0, 0}, stamp_last = clock64();
+#endif
+        for (int j = -1; j < NS; j++) {
+            WSTAMP(0);
+            if (j > kWinPubLag && j % kWinPubEvery == 0 && lane == 0) win_signal(E.d_win_sync, wd.epoch, j - kWinPubLag);
+            if (j >= 0) {
+                const int cb = j & 1;
+                double* const log = logbase + (size_t)j * win_log_stride(T);
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+#pragma unroll
+                    for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, sA[cb][k][lane + 64 * c]);
+                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, L.sHdr[cb][lane]);
+                // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete
+                if ((j + 1) % kWinPubEvery == 0) win_vmcnt_lag<NC>();
+            }
+            WSTAMP(1);
+            ASLAM_LDS_BARRIER();
+        }
+        ASLAM_VMCNT(0);                                            // the whole log: after this wave's last stores
+        if (lane == 0) win_signal(E.d_win_sync, wd.epoch, NS);
+#ifdef ASLAM_WIN_STAMPS
+        if (lane == 0) printf("logger T %d steps %d: barrier-wait %lld work %lld cycles per step\n", T, NS, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1));
+#endif
         return;
     }
 
@@ -546,7 +576,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     for (int c = 0; c < NC; c++) { sA[nb][3][lane + 64 * c] = 0.0; sB[nb][3][lane + 64 * c] = 0.0; }
                     if (nb) dirty1 = false; else dirty0 = false;
                 }
-                // header of the logged step (to LDS: worker wave 0 stores it to the log)
+                // header of the logged step (to LDS: the logger wave, in the piece schedule worker wave 0, stores it to the log)
                 if (lane == 0) {
                     hdr[WH_TYPE] = 1.0; hdr[WH_POS] = (double)pos;
 #pragma unroll
@@ -555,7 +585,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 }
                 WSTAMP(5);
             }
-            // operands to the workers (who also log them), and this wave's own copy
+            // operands to the workers and the logger wave (pieces: to the workers, who also log them), and this wave's own copy
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 const int col = lane + 64 * c;
@@ -569,7 +599,6 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         }
         ASLAM_LDS_BARRIER();
     }
-    if (ONE) ASLAM_LDS_BARRIER();                                  // (pairs with the workers' barrier before the last publication)
 #ifdef ASLAM_WIN_STAMPS
     if (lane == 0 && (ONE || wd.piece == 1)) {
         const int nc = NS - n_pred;
@@ -814,8 +843,9 @@ __device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr, uns
 // publishes its step count every kWinPubEvery steps; each replay workgroup replays the published steps in batches and publishes
 // its own count; each Psi workgroup takes the steps every replay workgroup has published.  Publication: the log and the t / u log
 // are stored write-through (sc1); each storing wave waits for its stores of the published steps (a counted vmcnt: the chain's
-// workers issue no global load in the step loop, so the count is static and covers only the newest steps, which are not waited
-// for), the chain's waves then pass the step's barrier, and one lane stores {epoch, count} with a relaxed agent-scope store.  A
+// logger wave, the only wave of the chain that stores to the log, issues no global load in the step loop, so the count is static
+// and covers only the newest steps, which are not waited for), then passes the step's barrier, and one of its lanes stores
+// {epoch, count} with a relaxed agent-scope store.  A
 // consumer polls with one lane (relaxed sc1 loads, s_sleep between polls), then makes ONE agent acquire, waits for it and passes
 // a barrier before its waves load the batch.  The counters carry the window's epoch (an older window's count reads as 0), so
 // nothing is reset between windows.  Forward progress: roles go by a ticket each workgroup takes when it starts (a CAS on an
@@ -834,7 +864,7 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
     }
 }
 template <int T, int RW, bool ONE>
-__global__ __launch_bounds__(((T + RW - 1) / RW + 1) * 64 > 256 ? ((T + RW - 1) / RW + 1) * 64 : 256)
+__global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
 void k_ekf_win_step(EkfState E, SlamParams sp, WinDesc wd, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
     constexpr size_t kLds = sizeof(WinChainLds<T, ONE>) > sizeof(WinScanLds<T>) ? sizeof(WinChainLds<T, ONE>) : sizeof(WinScanLds<T>);
     __shared__ __align__(16) unsigned char smem[kLds];
@@ -1011,9 +1041,10 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc) {
     const WinReplay r{0, 0, wd.nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
+    // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
     if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wd, r, r, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 320, sizeof(WinChainLds<8, true>), E, sp, wd, r, r, obs, enc);
-    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 448, sizeof(WinChainLds<12, true>), E, sp, wd, r, r, obs, enc);
+    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wd, r, r, obs, enc);
+    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wd, r, r, obs, enc);
 }
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd) {
     hipLaunchKernelGGL(k_ekf_win_gather, dim3((E.ld + 255) / 256, 16), dim3(256), 0, st, E, wd);       // y: rows of Y_0 in turn (one load in flight per thread otherwise)
