@@ -160,6 +160,8 @@ _SIGS = {
     "aslam_fleet_get_state": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
     "aslam_fleet_set_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]),
     "aslam_fleet_get_landmark_ids": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "aslam_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "aslam_fleet_remove_landmarks": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int, _ip, _ip]),
     "aslam_merge_map_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp,
                                           _ip, _ip, _dp]),
     "aslam_fleet_merge_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _ip, _ip, _dp]),
@@ -520,6 +522,29 @@ class Context:
         ids = np.zeros(max(int(self.init.max_landmarks), 1), np.int32)
         self._ck(self.lib.aslam_fleet_get_landmark_ids(self.h, int(robot), C.byref(n), _ptr(ids, _ip)))
         return ids[: n.value].copy()
+
+    # -- landmark removal: marginalise landmarks out of a SLAM map on the device ---------------------------------
+    def remove_landmarks(self, ids):
+        """remove every landmark whose marker id is in ids from the SLAM map (mu, Sigma, id tables, last-observed list), in place
+        on the device; returns the number of landmarks removed"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        removed = C.c_int()
+        self._ck(self.lib.aslam_remove_landmarks(self.h, int(ids.size), _ptr(ids, _ip) if ids.size else None, C.byref(removed)))
+        return removed.value
+
+    def fleet_remove_landmarks(self, ids, robots=None):
+        """remove_landmarks on the listed robots of the active SLAM fleet (None: every robot) in one call; returns the number of
+        landmarks removed per listed robot, in list order"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if robots is None:
+            n_robots, rp = max(self.is_fleet(), 0), None
+        else:
+            robots = np.ascontiguousarray(robots, dtype=np.int32).ravel()
+            n_robots, rp = int(robots.size), _ptr(robots, _ip) if robots.size else _ptr(np.zeros(1, np.int32), _ip)
+        removed = np.zeros(max(n_robots, 1), np.int32)
+        self._ck(self.lib.aslam_fleet_remove_landmarks(self.h, int(ids.size), _ptr(ids, _ip) if ids.size else None, n_robots, rp,
+                                                       _ptr(removed, _ip)))
+        return removed[:n_robots].copy()
 
     # -- map merge: one shared map from N maps in N frames (DESIGN.md §16) -----------------------------------------------------
     def _merged(self, call, n_maps):

@@ -31,11 +31,12 @@ constexpr int kWinWidenFrames = 16;     // a window of at least this many frames
 constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (its log is replayed meanwhile); <= kWinPieceMax
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
-              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS, P_COUNT };
+              P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
+              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
-                                   "k_fleet_steps"};
+                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -147,6 +148,7 @@ struct aslam_ctx {
     FleetSlam fslam{};
     MergeBufs merge{};                    // map merge: tables allocated by the first merge, freed at aslam_fleet_end / aslam_destroy
     RelocBufs reloc{};                    // relocalization: result records, allocated by the first call, freed at the same two places
+    MapEditBufs map_edit{};               // landmark removal: src_of / meta tables, allocated by the first call, freed at aslam_destroy
     // innovation gate (aslam_set_innovation_gate): off unless set; only the localization and localization-fleet steps
     // look at it.  The health records (one per EKF slot, one track record per robot and one for the single filter) and their
     // page-locked copies are made by the first aslam_set_innovation_gate and freed by aslam_destroy.
@@ -847,6 +849,7 @@ void aslam_destroy(aslam_ctx* c) {
     ekf_fleet_free(c->fslam);
     merge_free(c->merge);
     reloc_free(c->reloc);
+    map_edit_free(c->map_edit);
     hipFree(c->gate.slot); hipFree(c->gate.track);
     if (c->h_slot_health) hipHostFree(c->h_slot_health);
     if (c->h_track_health) hipHostFree(c->h_track_health);
@@ -2386,6 +2389,87 @@ int aslam_fleet_get_landmark_ids(aslam_ctx* c, int robot, int* L, int* ids) {
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     { int rs = sync_streams(c); if (rs) return rs; }
     return read_landmark_ids(c, ekf_fleet_robot(c->fslam, robot), L, ids);
+}
+
+// ---- landmark removal: marginalise landmarks out of a SLAM map on the device (include/aruco_slam_hip.h) ----------
+namespace {
+// the ids of a removal as the kernels take them (one bit per marker id); false: an id outside the table
+bool removal_set(int n, const int* ids, unsigned* bits) {
+    std::memset(bits, 0, sizeof(unsigned) * (kIdTableSize / 32));
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= kIdTableSize) return false;
+        bits[ids[i] >> 5] |= 1u << (ids[i] & 31);
+    }
+    return true;
+}
+
+// the removal J.ids on the J.n filters of J (tables not yet set), streams synchronised by the caller: three launches on the EKF
+// stream, the meta rows back in one copy, one wait.  removed: J.n entries or nullptr
+int run_map_edit(aslam_ctx* c, MapEdit& J, int* removed) {
+    HIP_TRY(c, map_edit_reserve(c->map_edit, J.n, J.base.ld));
+    J.src_of = c->map_edit.src_of;
+    J.meta = c->map_edit.meta;
+    hipStream_t st = c->stream_ekf;
+    prof_begin(c, P_MAP_PLAN, st);
+    launch_map_plan(st, J);
+    prof_end(c);
+    prof_begin(c, P_MAP_COLS, st);
+    launch_map_cols(st, J);
+    prof_end(c);
+    prof_begin(c, P_MAP_ROWS, st);
+    launch_map_rows(st, J);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->map_edit.h_meta, J.meta, sizeof(int) * 4 * J.n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (removed)
+        for (int k = 0; k < J.n; k++) removed[k] = c->map_edit.h_meta[4 * k + 2];
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_remove_landmarks(aslam_ctx* c, int n, const int* ids, int* removed) {
+    if (!c) return ASLAM_E_INVALID;
+    if (int r = allow(c, kSlam)) return r;
+    if (n < 0 || (n > 0 && !ids)) return fail(c, ASLAM_E_INVALID, "remove landmarks: n >= 0 ids");
+    MapEdit J{};
+    if (!removal_set(n, ids, J.ids)) return fail(c, ASLAM_E_INVALID, "landmark id out of range");
+    if (removed) *removed = 0;
+    if (n == 0) return ASLAM_OK;
+    { int rs = sync_streams(c); if (rs) return rs; }
+    J.base = c->ekf;
+    J.stride = 0;
+    J.n = 1;
+    int r = run_map_edit(c, J, removed);
+    if (r) return r;
+    c->mirror_dirty = true;
+    return ASLAM_OK;
+}
+
+int aslam_fleet_remove_landmarks(aslam_ctx* c, int n, const int* ids, int n_robots, const int* robots, int* removed) {
+    if (!c) return ASLAM_E_INVALID;
+    if (int r = allow(c, kFleetSlam)) return r;
+    if (n < 0 || (n > 0 && !ids)) return fail(c, ASLAM_E_INVALID, "remove landmarks: n >= 0 ids");
+    MapEdit J{};
+    if (!removal_set(n, ids, J.ids)) return fail(c, ASLAM_E_INVALID, "landmark id out of range");
+    const int R = c->fleet_n;
+    if (!robots) n_robots = R;
+    if (n_robots < 0) return fail(c, ASLAM_E_INVALID, "negative robot count");
+    std::vector<char> listed(R, 0);
+    for (int k = 0; k < n_robots; k++) {
+        const int r = robots ? robots[k] : k;
+        if (r < 0 || r >= R) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+        if (listed[r]) return fail(c, ASLAM_E_INVALID, "robot listed twice");
+        listed[r] = 1;
+        J.robot[k] = (unsigned char)r;                 // R <= ASLAM_MAX_ROBOTS = kMapEditMaxFilters
+    }
+    if (removed) std::fill(removed, removed + n_robots, 0);
+    if (n == 0 || n_robots == 0) return ASLAM_OK;
+    { int rs = sync_streams(c); if (rs) return rs; }
+    J.base = c->fslam.base;
+    J.stride = c->fslam.stride;
+    J.n = n_robots;
+    return run_map_edit(c, J, removed);
 }
 
 // ---- map merge: one shared map from N maps in N frames (include/aruco_slam_hip.h) -------------------------------

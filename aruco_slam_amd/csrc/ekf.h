@@ -195,6 +195,30 @@ void launch_fleet_export_maps(hipStream_t st, const FleetSlam& F, MapRecord* out
 // *rounds = alignment rounds run
 hipError_t merge_run(hipStream_t st, const MergeBufs& M, const MapRecord* rec, int n_maps, int per_map, int anchor, int min_common,
                      int* rounds);
+// map edit (map_edit.h): landmarks removed from n filters in place, filter k = robot[k] of a SLAM fleet (base, stride
+// as in FleetSlam) or the single filter (n = 1, stride 0, robot[0] = 0).  The tables are made on first use: per filter of a call
+// src_of (ld entries: new state index -> old state index) and a meta row {N before, N after, landmarks removed, 0}.
+constexpr int kMapEditMaxFilters = 256;
+struct MapEdit {                       // kernel argument of the three map-edit kernels
+    EkfState base;                     // robot 0's filter, or the single filter
+    size_t stride;
+    int n;                             // filters of the call = gridDim.z
+    unsigned ids[kIdTableSize / 32];   // bit id set: landmarks with this marker id go
+    unsigned char robot[kMapEditMaxFilters];
+    int* src_of;
+    int* meta;
+};
+struct MapEditBufs {
+    int* src_of;                       // cap x ld
+    int* meta;                         // cap x 4
+    int* h_meta;                       // page-locked copy of meta: what a call reads back
+    int cap;                           // filters the tables hold (0: none)
+};
+hipError_t map_edit_reserve(MapEditBufs& B, int filters, int ld);
+void map_edit_free(MapEditBufs& B);
+void launch_map_plan(hipStream_t st, const MapEdit& J);
+void launch_map_cols(hipStream_t st, const MapEdit& J);
+void launch_map_rows(hipStream_t st, const MapEdit& J);
 // relocalization (relocalize.h): per slot of a call one 128-byte result record (16 doubles: the five counts as int32
 // in the first four, then pose and covariance), in a device buffer made on first use together with its page-locked copy
 struct RelocParams {

@@ -1529,3 +1529,4 @@ void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
 #include "ekf_fleet.h"        // fleet localization: k_fleet_steps, one workgroup per robot, and its launcher
 #include "fleet_merge.h"      // map merge: k_fleet_export_maps, k_merge_*, and their launchers
 #include "relocalize.h"       // relocalization: k_relocalize, one workgroup per slot, and its launcher
+#include "map_edit.h"         // landmark removal: k_map_plan, k_map_cols, k_map_rows, and their launchers

@@ -301,6 +301,39 @@ int aslam_fleet_get_state(aslam_ctx* ctx, int robot, int* N, double* mu, double*
 int aslam_fleet_set_state(aslam_ctx* ctx, int robot, int N, const double* mu, const double* sigma, const int* landmark_ids);
 int aslam_fleet_get_landmark_ids(aslam_ctx* ctx, int robot, int* L, int* ids);
 
+/* ---- landmark removal: take landmarks out of a SLAM map on the device -------------------------------------------
+ * The reference can only grow its map: after its outlier test it carries "// TODO: Remove map point?" (aruco_slam.cpp:156-175) and
+ * never does.  These calls marginalise landmarks out of a SLAM filter, which for a Gaussian is exact and needs no arithmetic: the
+ * landmark's three rows and columns of mu and Sigma are deleted, in place on the device, with no copy of mu or Sigma to the host.
+ * Which landmarks to remove is the caller's decision (aslam_export_map gives every landmark's 3 x 3 covariance to select on).
+ * For one filter, with L landmarks and N = 3 + 3 L before the call:
+ * - The call first does what aslam_set_state does: the pending batch is finalised and the streams are synchronised.  On return the
+ *   removal has happened.
+ * - Landmark i is removed iff its marker id (entry i of aslam_get_landmark_ids) is in ids.  An id that is not in the map is ignored;
+ *   an id listed twice counts once; a map that aslam_set_state seeded with one id twice loses both landmarks.  The kept landmarks
+ *   keep their relative order; L' is their number, N' = 3 + 3 L'.
+ * - mu' and Sigma' are the kept entries bit for bit: with map(a) the old state index of new state index a (pose block first),
+ *   mu'[a] = mu[map(a)] and Sigma'[a, b] = Sigma[map(a), map(b)].  Every entry of the device array with row or column in [N', N) is
+ *   0.0, as aslam_set_state leaves the unused part, so the filter goes on exactly as one seeded with (mu', Sigma', kept ids).
+ * - Landmark ids: entry i < L' is the i-th kept id.  A kept id that occurs twice is still looked up at its first landmark.  A removed
+ *   id seen again is appended at index L' like any new id (action 0), and a full map that lost k landmarks takes k new ones.
+ * - last_observed_marker_: entries of removed ids are deleted, the others stay, unchanged and in order.  This is the one difference
+ *   from aslam_get_state, deleting on the host and aslam_set_state, which empties the list: a kept marker seen again at the same
+ *   place is still the reference's "stationary" no-op on the next frame.
+ * - Left alone: the pop list of the last frame (aslam_get_observations) and the per-slot statistics are history, and the landmark
+ *   indices in them refer to the map BEFORE the removal; the armed flag and the time of the last encoder sample; the innovation gate.
+ * ASLAM_E_INVALID, with the state untouched: a null context, n < 0, n > 0 with ids == NULL, an id outside [0, 1024).  n == 0 is
+ * ASLAM_OK and changes nothing.  *removed (may be NULL) receives L - L'. */
+/* SLAM mode only (a camera rig is SLAM mode); ASLAM_E_STATE while localizing (the map is the caller's there: pass a shorter one to
+   aslam_localize_begin) or while a fleet is active */
+int aslam_remove_landmarks(aslam_ctx* ctx, int n, const int* ids, int* removed);
+/* the same id set removed from every listed robot of the active SLAM fleet, each robot's filter on its own as above, in one launch of
+   each kernel for all of them; robots not listed are untouched.  robots == NULL: every robot of the fleet (n_robots is not read);
+   removed (may be NULL): one entry per listed robot, in list order (R entries with robots == NULL).  ASLAM_E_STATE outside fleet
+   SLAM.  ASLAM_E_INVALID in addition to the above: n_robots < 0, a robot outside [0, R), a robot listed twice.  n_robots == 0 is
+   ASLAM_OK and changes nothing. */
+int aslam_fleet_remove_landmarks(aslam_ctx* ctx, int n, const int* ids, int n_robots, const int* robots, int* removed);
+
 /* ---- map merge: one shared map from the robots of a SLAM fleet or from gathered GPUs (no reference counterpart) ----
  * Input: n_maps maps (1 <= n_maps <= ASLAM_MAX_ROBOTS) of per_map records each (1 <= per_map <= 1024), map-major, every record the
  * ASLAM_MAP_RECORD_BYTES record of aslam_export_map { int32 id, int32 index, f64 x, y, theta, f64 S[9] }.  A record whose id is outside
