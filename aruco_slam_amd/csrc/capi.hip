@@ -166,6 +166,7 @@ struct aslam_ctx {
     bool win_pieces = false;              // ASLAM_WIN_PIECE set: the piece schedule (several launches per window) instead of one launch per window
     unsigned win_epoch = 0;               // one-launch windows enqueued so far: the tag of a window's hand-off counters
     bool win_no_early = false;            // ASLAM_WIN_NO_EARLY: every window waits for its own flush (test / comparison knob)
+    bool win_next_split = false;          // ASLAM_WIN_NEXT_SPLIT: the early start as four launches instead of one kernel (comparison knob)
     struct Pending { bool active = false; int first = 0, count = 0, ev = 0; } pend;
     hipEvent_t ev_obs[2] = {nullptr, nullptr}, ev_idx = nullptr;
     hipStream_t stream_win = nullptr;     // scan / flush of the windows, beside the chain on stream_ekf
@@ -747,6 +748,7 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
 
     c->win_enabled = std::getenv("ASLAM_NO_WINDOWS") == nullptr;
     c->win_no_early = std::getenv("ASLAM_WIN_NO_EARLY") != nullptr;
+    c->win_next_split = std::getenv("ASLAM_WIN_NEXT_SPLIT") != nullptr;
     if (const char* e = std::getenv("ASLAM_WIN_PIECE")) { c->win_piece = std::min(kWinChainFrames, std::max(1, std::atoi(e))); c->win_pieces = true; }
     const int B = c->max_batch;
     const size_t px = (size_t)init->max_rows * init->max_cols;
@@ -1159,7 +1161,7 @@ int finalize_pending(aslam_ctx* c) {
             // the previous window's mu outside its S (and P_K, mu images of this parity) are as the flush before it leaves them
             if (pf.ev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, pf.ev_flush, 0));
             prof_begin(c, P_EKF_WIN_NEXT, sa);                       // (the previous window's Lambda, Psi, psi are complete: same stream)
-            launch_ekf_win_next(sa, c->ekf, pf.wd, wd);
+            launch_ekf_win_next(sa, c->ekf, pf.wd, wd, c->win_next_split);
             prof_end(c);
             hipEvent_t ev_next = new_event();
             HIP_TRY(c, hipEventRecord(ev_next, sa));

@@ -53,7 +53,7 @@ struct WinDesc {                       // one chain piece / one window (kernel a
     int piece, log0;                   // index of the piece within its window; steps logged by the earlier pieces
     int last;                          // 1 = the window's last piece: mu_S goes back to the state, the last frame's pop list / last-observation list are left behind
     int wpar;                          // parity of the window within its batch: which of the two P / mu hand-over images it uses
-    int from_image;                    // first piece of a window whose P and mu_S were prepared in the image (k_ekf_win_next_*) instead of read from Sigma / mu
+    int from_image;                    // first piece of a window whose P and mu_S were prepared in the image (k_ekf_win_next) instead of read from Sigma / mu
     int mu_out;                        // the chain writes mu_S back into the state (piece schedule: the window's last piece); otherwise k_ekf_win_fix does
     unsigned epoch;                    // one-launch window: tag of its hand-off counters (unique per window of the context, never 0)
     int nsteps;                        // one-launch window: steps of the whole window (frames + corrections)
@@ -80,7 +80,7 @@ struct EkfState {
     double* d_win_log;                 // per window step: operand rows -K^T (3 x SP) + header (ekf_window.hip)
     double* d_win_tlog;                // per window step: t = H Lambda and u = S^-1 t (4 x SP each, 4th row zero)
     double* d_win_small;               // two P images and mu_S images (hand-over between the pieces of a window), Lambda, Psi images (SP x SP) and psi
-    double* d_win_next;                // early start of the next window: Y_0 columns S' (Vg), Psi Vg, Lambda Vg, Sigma[S',S'] (each SPm x SPm)
+    double* d_win_next;                // early start of the next window, four-launch path only (ASLAM_WIN_NEXT_SPLIT): Y_0 columns S' (Vg), Psi Vg, Lambda Vg, Sigma[S',S'] (each SPm x SPm)
     int* d_win_next_idx;               // ... position in the previous S of every entry of S' (or -1), and nS' (at [SPm])
     int* d_win_sidx;                   // per state index: position in S or -1
     WinFrame* d_win_frames;            // per staged slot: the host's plan of the frame
@@ -250,7 +250,7 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps);
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd);               // Y_0 = rows S of Sigma, position table
 // P and mu_S of the NEXT window (set nx) from the previous window's (pv) P_K, Lambda, Psi, psi, Y_0 and the not yet flushed Sigma / mu
-void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx);
+void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx, bool split);   // split: the four-launch path (comparison)
 void launch_ekf_win_flush(hipStream_t st, const EkfState& E, const WinDesc& wd);                 // thin products, Sigma pass, rows / columns of S
 
 } // namespace aslam

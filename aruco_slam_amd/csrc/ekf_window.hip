@@ -36,7 +36,7 @@
 //   k_ekf_win_gather  Y_0 = rows S of Sigma (second stream, behind the previous window's flush)
 //   k_ekf_win_thin    [Psi; Lambda] Y_0 as one tiled product (U = Psi Y_0, Y_K = Lambda Y_0), mu_R += Y_0^T psi;
 //   k_ekf_update_mfma (ekf.hip) Sigma -= Y_0^T U: the ONE pass over Sigma per window;  k_ekf_win_fix writes rows / columns S and P_K.
-//   k_ekf_win_next_*  the next window's P and mu_S from this window's small results, before its flush has run.
+//   k_ekf_win_next    the next window's P and mu_S from this window's small results, before its flush has run.
 #include "common.h"
 #include "ekf.h"
 #include "ekf_dev.h"
@@ -139,6 +139,27 @@ __device__ __forceinline__ void win_publish(const v4d (&acc)[RW][T], int p, int 
     }
 }
 
+// What a window's last frame leaves behind for whatever follows: pop list, last_observed_marker_ (aruco_slam.cpp:202, 263).
+// One wave, lane = popped observation; fm = corrections of the frame.
+__device__ __forceinline__ void win_last_frame(const EkfState& E, const WinFrame& fr, const ObsRaw* __restrict__ fobs, int fm, int lane) {
+    const int npop = fr.npop;
+    if (lane < npop) {
+        const ObsRaw o = fobs[fr.pdet[lane]];
+        const bool upd = fr.pact[lane] == 1;
+        PopRec pr;
+        pr.id = o.id; pr.index = fr.pidx[lane]; pr.action = upd ? 1 : 2; pr.det = fr.pdet[lane];
+        pr.z[0] = o.x; pr.z[1] = o.y; pr.z[2] = o.th;
+        pr.r[0] = o.r[0]; pr.r[1] = o.r[1]; pr.r[2] = o.r[2];
+        E.d_pop[lane] = pr;
+        LastObs lo;
+        lo.id = o.id; lo.pad = 0;
+        const double nanv = __builtin_nan("");
+        lo.z[0] = upd ? o.x : nanv; lo.z[1] = upd ? o.y : nanv; lo.z[2] = upd ? o.th : nanv;   // stationary: last_observation_ stays unset
+        E.d_last[lane] = lo;
+    }
+    if (lane == 0) { *E.d_nlast = npop; *E.d_npop = npop; *E.d_m = fm; }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // T tiles per side, RW tile rows per worker wave: ceil(T / RW) worker waves + 1 prepare wave (+ 1 logger wave in the one-launch
 // window: it stores the step log and publishes the step count, so that neither lies on the workers' path).  With T = 4 (2 x 2 rows on two
@@ -157,6 +178,7 @@ template <int T, bool ONE> struct WinChainLds {
     int sS[SP];
     int sOff[KMAX + 1];
     unsigned char sPos[NSMAX], sIdx[NSMAX], sFrm[NSMAX];   // per step: landmark position (255 = predict), correction index, frame
+    unsigned char sDet[NSMAX];             // ... and the correction's detection in its frame's observation list
 };
 template <int T, int RW, bool ONE>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* __restrict__ obs,
@@ -165,7 +187,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
     auto& sA = L.sA; auto& sB = L.sB; auto& sPub = L.sPub; auto& sMu = L.sMu; auto& sS = L.sS; auto& sOff = L.sOff;
-    auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sFrm = L.sFrm;
+    auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sFrm = L.sFrm; auto& sDet = L.sDet;
     if (threadIdx.x >= NT) return;                                  // (the launch's block is sized for its widest role)
     const int tid = threadIdx.x;
     const int nS = wd.nS, s = 3 + 3 * nS;
@@ -179,16 +201,24 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     for (int e = tid; e < 2 * 3 * SPP; e += NT) (&sPub[0][0][0])[e] = 0.0;
     for (int e = tid; e < 2 * kWinHdr; e += NT) (&L.sHdr[0][0])[e] = 0.0;
     if constexpr (ONE) {
-        // the step tables of the whole window (K <= 64 frames): thread k loads frame k's count and its 64 landmark positions at
-        // once, wave 0 forms the running sum with a lane scan, thread k writes its frame's steps
+        // the step tables of the whole window (K <= 64 frames): thread k loads frame k's head, its 64 landmark positions and its 64
+        // detection indices at once, wave 0 forms the running sum with a lane scan, thread k writes its frame's steps.  The head
+        // is all the frame's slot statistics need: thread k stores them here, off the chain
         int cnt = 0;
-        unsigned cp[16];
+        unsigned cp[16], cd[16];
         if (tid < wd.K) {
-            const WinFrame& fr = frames[wd.first_slot + tid];
-            cnt = 1 + fr.m;
+            const int slot = wd.first_slot + tid;
+            const WinFrame& fr = frames[slot];
+            const int fm = fr.m, fnpop = fr.npop, fnm = fr.n_markers;
+            cnt = 1 + fm;
             const unsigned* c4 = reinterpret_cast<const unsigned*>(fr.cpos);
+            const unsigned* d4 = reinterpret_cast<const unsigned*>(fr.cdet);
 #pragma unroll
-            for (int q = 0; q < 16; q++) cp[q] = c4[q];
+            for (int q = 0; q < 16; q++) { cp[q] = c4[q]; cd[q] = d4[q]; }
+            if (slot < E.max_slots) {
+                int* st = E.d_slot_stat + 4 * slot;
+                st[0] = fnm; st[1] = 0; st[2] = fm; st[3] = fnpop - fm;
+            }
         }
         if (wave == 0) {
             int inc = cnt;
@@ -200,16 +230,28 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         __syncthreads();
         if (tid < wd.K) {
             const int o = sOff[tid], m = cnt - 1;
-            sPos[o] = 255; sIdx[o] = 0; sFrm[o] = (unsigned char)tid;
+            sPos[o] = 255; sIdx[o] = 0; sFrm[o] = (unsigned char)tid; sDet[o] = 0;
 #pragma unroll
             for (int a = 0; a < 63; a++)
-                if (a < m) { sPos[o + 1 + a] = (unsigned char)(cp[a >> 2] >> (8 * (a & 3))); sIdx[o + 1 + a] = (unsigned char)a; sFrm[o + 1 + a] = (unsigned char)tid; }
+                if (a < m) {
+                    sPos[o + 1 + a] = (unsigned char)(cp[a >> 2] >> (8 * (a & 3))); sDet[o + 1 + a] = (unsigned char)(cd[a >> 2] >> (8 * (a & 3)));
+                    sIdx[o + 1 + a] = (unsigned char)a; sFrm[o + 1 + a] = (unsigned char)tid;
+                }
         }
         __syncthreads();
     } else {
         // steps per frame (1 predict + m corrections), every frame's count loaded by its own thread (one thread walking the plan would
         // pay one dependent global load per frame), then the running sum
-        if (tid < wd.K) sOff[tid + 1] = 1 + frames[wd.first_slot + tid].m;
+        if (tid < wd.K) {
+            const int slot = wd.first_slot + tid;
+            const WinFrame& fr = frames[slot];
+            const int fm = fr.m, fnpop = fr.npop, fnm = fr.n_markers;
+            sOff[tid + 1] = 1 + fm;
+            if (slot < E.max_slots) {                               // the frame's slot statistics
+                int* st = E.d_slot_stat + 4 * slot;
+                st[0] = fnm; st[1] = 0; st[2] = fm; st[3] = fnpop - fm;
+            }
+        }
         if (tid == 0) sOff[0] = 0;
         __syncthreads();
         if (tid == 0)
@@ -221,6 +263,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 const int st = sOff[k] + a;
                 sPos[st] = a == 0 ? 255 : fr.cpos[a - 1];
                 sIdx[st] = a == 0 ? 0 : (unsigned char)(a - 1);
+                sDet[st] = a == 0 ? 0 : fr.cdet[a - 1];
                 sFrm[st] = (unsigned char)k;
             }
         }
@@ -322,6 +365,10 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         // when it has waited for them at the end of step j - 1; it then passes the barrier (as every wave that read or wrote those
         // steps' operands has) and one of its lanes publishes their count for the replay workgroups.
         ASLAM_LDS_BARRIER();                                       // (pairs with the workers' barrier after their first publish)
+        // What the window's last frame leaves behind for whatever follows: pop list, last_observed_marker_ (aruco_slam.cpp:202,
+        // 263).  Nothing of it depends on the chain, and this wave has no log to store while the first predict is prepared: it
+        // does the two-level load here.  The stores need the loaded values, so no load is in flight when the loop begins.
+        win_last_frame(E, frames[wd.first_slot + wd.K - 1], obs + (size_t)(wd.first_slot + wd.K - 1) * kMarkerMax, sOff[wd.K] - sOff[wd.K - 1] - 1, lane);
 #ifdef ASLAM_WIN_STAMPS
         long long stamp_acc[2] = {0, 0}, stamp_last = clock64();
 #endif
@@ -381,12 +428,12 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     bool dirty0 = false, dirty1 = false;                           // operand buffer 0 / 1 holds a predict's fourth depth row
     // the first frame's inputs
     ObsRaw nObs{};
-    if (lane < sOff[1] - 1) nObs = obs[(size_t)wd.first_slot * kMarkerMax + frames[wd.first_slot].cdet[lane]];
+    if (lane < sOff[1] - 1) nObs = obs[(size_t)wd.first_slot * kMarkerMax + sDet[1 + lane]];
     double e_wl, e_wr, e_dt;
     { const double* e = enc + (size_t)3 * wd.first_slot; e_wl = e[0]; e_wr = e[1]; e_dt = e[2]; }
     ASLAM_LDS_BARRIER();                                           // (pairs with the workers' barrier after their first publish)
 #ifdef ASLAM_WIN_STAMPS
-    long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = clock64();
+    long long stamp_acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = clock64();
     int n_pred = 0;
 #endif
     for (int j = -1; j < NS; j++) {
@@ -455,6 +502,10 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 for (int c = 0; c < NC; c++) sMu[lane + 64 * c] = mu[c];
                 __builtin_amdgcn_wave_barrier();
                 const double m0 = sMu[0], m1 = sMu[1], m2 = sMu[2];
+#ifdef ASLAM_WIN_STAMPS
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (stamps only: the mean's round trip through LDS apart from the sincos)
+                WSTAMP(8);
+#endif
                 double th = m2 + delta_theta;
                 wrap1(th);
                 // the two sincos of the frame in one call: even lanes the mid-step heading, odd lanes the new heading
@@ -462,6 +513,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 sincos((lane & 1) ? th : m2 + 0.5 * delta_theta, &sv, &cv);
                 const double cm = ASLAM_WAVE_BCAST(cv, 0), sm = ASLAM_WAVE_BCAST(sv, 0);
                 cth = ASLAM_WAVE_BCAST(cv, 1); sth = ASLAM_WAVE_BCAST(sv, 1);
+                WSTAMP(9);
                 const double ua = -delta_s * sm, ub = delta_s * cm;                 // H3 = I + [ua ub 0]^T e2^T
                 const double f = 0.5 * kl * e_dt;                                    // kl for BOTH wheels (quirk Q7)
                 const double su0 = Qk * fabs(e_wl), su1 = Qk * fabs(e_wr);
@@ -498,34 +550,15 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     rR0 = nObs.r[0]; rR1 = nObs.r[1]; rR2 = nObs.r[2];
                 }
                 __builtin_amdgcn_wave_barrier();
-                const WinFrame& fr = frames[slot];
-                if (lane == 0 && slot < E.max_slots) {
-                    int* st = E.d_slot_stat + 4 * slot;
-                    st[0] = fr.n_markers; st[1] = 0; st[2] = fm; st[3] = fr.npop - fm;
-                }
-                if (wd.last && k == wd.K - 1) {
-                    // what the window's last frame leaves behind for whatever follows: pop list, last_observed_marker_ (aruco_slam.cpp:202, 263)
-                    const int npop = fr.npop;
-                    if (lane < npop) {
-                        const ObsRaw o = obs[(size_t)slot * kMarkerMax + fr.pdet[lane]];
-                        const bool upd = fr.pact[lane] == 1;
-                        PopRec pr;
-                        pr.id = o.id; pr.index = fr.pidx[lane]; pr.action = upd ? 1 : 2; pr.det = fr.pdet[lane];
-                        pr.z[0] = o.x; pr.z[1] = o.y; pr.z[2] = o.th;
-                        pr.r[0] = o.r[0]; pr.r[1] = o.r[1]; pr.r[2] = o.r[2];
-                        E.d_pop[lane] = pr;
-                        LastObs lo;
-                        lo.id = o.id; lo.pad = 0;
-                        const double nanv = __builtin_nan("");
-                        lo.z[0] = upd ? o.x : nanv; lo.z[1] = upd ? o.y : nanv; lo.z[2] = upd ? o.th : nanv;   // stationary: last_observation_ stays unset
-                        E.d_last[lane] = lo;
-                    }
-                    if (lane == 0) { *E.d_nlast = npop; *E.d_npop = npop; *E.d_m = fm; }
+                WSTAMP(10);
+                if constexpr (!ONE) {
+                    // piece schedule: the window's last frame leaves its pop list behind here (one launch: the logger wave does)
+                    if (wd.last && k == wd.K - 1) win_last_frame(E, frames[slot], obs + (size_t)slot * kMarkerMax, fm, lane);
                 }
                 // the next frame's inputs are fetched while this one is solved
                 if (k + 1 < wd.K) {
                     const int fmn = sOff[k + 2] - sOff[k + 1] - 1;
-                    if (lane < fmn) nObs = obs[(size_t)(slot + 1) * kMarkerMax + frames[slot + 1].cdet[lane]];
+                    if (lane < fmn) nObs = obs[(size_t)(slot + 1) * kMarkerMax + sDet[sOff[k + 1] + 1 + lane]];      // (index from LDS: one load level)
                     const double* e = enc + (size_t)3 * (slot + 1);
                     e_wl = e[0]; e_wr = e[1]; e_dt = e[2];
                 }
@@ -602,8 +635,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
     if (lane == 0 && (ONE || wd.piece == 1)) {
         const int nc = NS - n_pred;
-        printf("prepare T %d steps %d (%d predict): barrier %lld | rows wait %lld correct %lld | predict path %lld per predict | c %lld S+inv %lld Kt+hdr %lld per correction | operands+log %lld per step\n",
-               T, NS, n_pred, stamp_acc[0] / (NS + 1), stamp_acc[7] / NS, stamp_acc[1] / NS, stamp_acc[2] / (n_pred ? n_pred : 1), stamp_acc[3] / (nc ? nc : 1), stamp_acc[4] / (nc ? nc : 1),
+        printf("prepare T %d steps %d (%d predict): barrier %lld | rows wait %lld correct %lld | predict path %lld (mean through LDS %lld sincos %lld operands + records %lld global loads, bookkeeping, header %lld) per predict | c %lld S+inv %lld Kt+hdr %lld per correction | operands+log %lld per step\n",
+               T, NS, n_pred, stamp_acc[0] / (NS + 1), stamp_acc[7] / NS, stamp_acc[1] / NS, (stamp_acc[2] + stamp_acc[8] + stamp_acc[9] + stamp_acc[10]) / (n_pred ? n_pred : 1), stamp_acc[8] / (n_pred ? n_pred : 1),
+               stamp_acc[9] / (n_pred ? n_pred : 1), stamp_acc[10] / (n_pred ? n_pred : 1), stamp_acc[2] / (n_pred ? n_pred : 1), stamp_acc[3] / (nc ? nc : 1), stamp_acc[4] / (nc ? nc : 1),
                stamp_acc[5] / (nc ? nc : 1), stamp_acc[6] / NS);
     }
 #endif
@@ -974,9 +1008,10 @@ __global__ __launch_bounds__(256) void k_ekf_win_gather(EkfState E, WinDesc wd) 
 // flush; both follow from the previous window's small results without the pass over Sigma:
 //     (a, b in S)      P_K                 (a in S, b not)   (Lambda Y_0)[a][b]            (neither)   Sigma_old[a][b] - (Y_0^T Psi Y_0)[a][b]
 //     mu: in S as the chain left it, otherwise mu_old + Y_0^T psi.
-// k_ekf_win_next_gather collects Y_0's columns S' (Vg, zero where the entry is in S), Sigma_old[S', S'] and mu_old[S'] into
-// small dense buffers with the index tables a miniature EkfState view needs; k_ekf_win_thin and k_ekf_update_mfma then run on that
-// view (N := s'), and k_ekf_win_next_fix assembles the image the chain loads.  The flush of the previous window runs meanwhile.
+// The flush of the previous window runs meanwhile.  k_ekf_win_next (below) does it in one launch.  The four-launch form it replaced
+// stays as the comparison path (ASLAM_WIN_NEXT_SPLIT): k_ekf_win_next_gather collects Y_0's columns S' (Vg, zero where the entry
+// is in S), Sigma_old[S', S'] and mu_old[S'] into small dense buffers with the index tables a miniature EkfState view needs;
+// k_ekf_win_thin and k_ekf_update_mfma then run on that view (N := s'), and k_ekf_win_next_fix assembles the image the chain loads.
 __global__ __launch_bounds__(256) void k_ekf_win_next_gather(EkfState E, WinDesc pv, WinDesc nx) {
     const int ld = E.ld, SPm = E.win_sp_max;
     const int s2 = 3 + 3 * nx.nS, SPp = 16 * pv.T;
@@ -1015,14 +1050,125 @@ __global__ __launch_bounds__(256) void k_ekf_win_next_fix(EkfState E, WinDesc pv
     }
 }
 
+// The same in ONE launch (the default; the four launches above stay behind ASLAM_WIN_NEXT_SPLIT for comparison): their 40 us were
+// launch floor and the gaps between dependent kernels, not work.  Workgroup t owns columns 16 t .. 16 t + 15 of S' and depends on
+// no other workgroup: it gathers its columns of Vg into LDS, forms (Psi Vg) and (Lambda Vg) for them, then
+// Sigma_old[S', tile] - Vg^T (Psi Vg)[:, tile] with the whole of Vg as the other operand, and writes
+//     every entry of its image columns but those with the row outside S and the column inside: such an entry is the mirror of
+//     (Lambda Vg)[a][b], a in S, b outside, and is written with it by the tile that owns b.
+// Every entry goes through the matrix-core sequence it had in the four launches (k_ekf_win_thin: accumulator from zero, depth
+// ascending in fours; k_ekf_update_mfma: accumulator from Sigma_old, the (Psi Vg) operand negated; mu: multiply, then add, by
+// ascending depth), so the image is the same to the bit.  The operands that come from global memory (Psi, Lambda; Vg's other
+// columns) are read by the lane that feeds them to the matrix core: at 16 columns per workgroup a staging pass through LDS would
+// only add barriers, and with none in the depth loops the compiler keeps several groups of loads in flight.
+constexpr int kWinNextSP = 16 * 12;                                 // the widest window
+__global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, WinDesc nx) {
+    __shared__ double sVt[kWinNextSP][16];                          // Vg[:, tile]
+    __shared__ double sTt[kWinNextSP][16];                          // (Psi Vg)[:, tile]
+    __shared__ int sIa[kWinNextSP], sPa[kWinNextSP], sInv[kWinNextSP];   // of position a of S': state offset; position in S, -1 outside, -2 padding; of position p of S: its position in S' or -1
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int ld = E.ld, SPm = E.win_sp_max;
+    const int Tp = pv.T, Tn = nx.T, SPp = 16 * Tp, SPn = 16 * Tn;
+    const int s1 = 3 + 3 * pv.nS, s2 = 3 + 3 * nx.nS;
+    const int c0 = 16 * blockIdx.x;
+    const double* Pprev = E.d_win_small + wsm_P(SPm, pv.wpar);
+    double* Pout = E.d_win_small + wsm_P(SPm, nx.wpar);
+    if (tid < kWinNextSP) sInv[tid] = -1;
+    __syncthreads();
+    if (tid < SPn) {
+        const int ia = tid < s2 ? win_state_index(nx, tid) : 0;
+        const int pa = tid < s2 ? E.d_win_sidx[ia] : -2;
+        sIa[tid] = ia; sPa[tid] = pa;
+        if (pa >= 0) sInv[pa] = tid;
+    }
+    __syncthreads();
+    for (int e = tid; e < 16 * SPp; e += 256) {
+        const int p = e >> 4, a = c0 + (e & 15);
+        sVt[p][e & 15] = sPa[a] == -1 ? E.d_Wt[(size_t)p * ld + sIa[a]] : 0.0;
+    }
+    // the image columns' entries that need no product: zero in the padding, P_K where row and column are both in S
+    for (int e = tid; e < 16 * SPn; e += 256) {
+        const int a = e >> 4, b = c0 + (e & 15);
+        const int pa = sPa[a], pb = sPa[b];
+        if (pa == -2 || pb == -2) Pout[(size_t)a * SPn + b] = 0.0;
+        else if (pa >= 0 && pb >= 0) Pout[(size_t)a * SPn + b] = Pprev[(size_t)pa * SPp + pb];
+    }
+    __syncthreads();
+    // [Psi; Lambda] Vg[:, tile]: the 2 Tp row tiles in turn over the waves
+    for (int rt = wave; rt < 2 * Tp; rt += 4) {
+        const bool lam = rt >= Tp;
+        const int q = lam ? rt - Tp : rt;
+        const double* M = E.d_win_small + (lam ? wsm_LAM(SPm, pv.wpar) : wsm_PSI(SPm, pv.wpar)) + (size_t)(16 * q + li) * SPp + lk;
+        v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+        for (int pc = 0; pc < SPp; pc += 64) {                      // (SPp is a multiple of 64: sixteen groups' loads in flight at once)
+            double av[16];
+#pragma unroll
+            for (int g = 0; g < 16; g++) av[g] = M[pc + 4 * g];
+#pragma unroll
+            for (int g = 0; g < 16; g++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[g], sVt[pc + 4 * g + lk][li], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int p = 16 * q + lk + 4 * reg;
+            if (!lam) sTt[p][li] = acc[reg];
+            else {
+                const int a = sInv[p], b = c0 + li;                 // (Lambda Vg)[p][b]: image entry (a, b) and its mirror
+                if (a >= 0 && sPa[b] == -1) { Pout[(size_t)a * SPn + b] = acc[reg]; Pout[(size_t)b * SPn + a] = acc[reg]; }
+            }
+        }
+    }
+    // mu_S': in S as the chain left it (its image), otherwise mu_old + Y_0^T psi
+    if (wave == 3 && lane < 16 && c0 + lane < s2) {
+        const int a = c0 + lane, pa = sPa[a];
+        double v;
+        if (pa >= 0) v = E.d_win_small[wsm_MU(SPm, pv.wpar) + pa];
+        else {
+            const double* psi = E.d_win_small + wsm_psi(SPm, pv.wpar);
+            double macc = 0.0;
+            for (int p = 0; p < s1; p++) macc += sVt[p][lane] * psi[p];
+            v = E.d_mu[sIa[a]] + macc;
+        }
+        E.d_win_small[wsm_MU(SPm, nx.wpar) + a] = v;
+    }
+    __syncthreads();
+    // Sigma_old[S', tile] - Vg^T (Psi Vg)[:, tile], formed transposed as k_ekf_update_mfma does: D'[c][r], c in the tile
+    for (int ri = wave; ri < Tn; ri += 4) {
+        const int r = 16 * ri + li;
+        const int pr = sPa[r];
+        const double* W = E.d_Wt + (size_t)lk * ld + sIa[r];
+        v4d acc;
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int c = c0 + lk + 4 * reg;
+            acc[reg] = (c < s2 && r < s2) ? E.d_sigma[(size_t)sIa[c] * ld + sIa[r]] : 0.0;
+        }
+        for (int pc = 0; pc < SPp; pc += 64) {
+            double bv[16];
+#pragma unroll
+            for (int g = 0; g < 16; g++) bv[g] = W[(size_t)(pc + 4 * g) * ld];     // (a valid address whatever r is; used where r lies outside S)
+#pragma unroll
+            for (int g = 0; g < 16; g++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-sTt[pc + 4 * g + lk][li], pr == -1 ? bv[g] : 0.0, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int c = c0 + lk + 4 * reg;
+            if (pr == -1 && sPa[c] == -1) Pout[(size_t)r * SPn + c] = acc[reg];
+        }
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------
 // Every workgroup of a step launch asks for more than half of a CU's LDS (an unused dynamic allocation on top of the static one), so
 // that no second workgroup - a replay workgroup of the same launch, or anything else - is placed on the chain workgroup's CU and
-// competes with the prepare wave for issue slots and LDS bandwidth (ASLAM_WIN_SHARE_CU: off, for comparison).
+// competes with the prepare wave for issue slots and LDS bandwidth (ASLAM_WIN_SHARE_CU: off, for comparison).  The claim is no
+// larger than that needs: at SP = 64 the one-launch window leaves 70 388 of the CU's 163 840 bytes, which a k_ekf_win_thin workgroup
+// of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
+// waited for up to a whole window (measured: DESIGN.md).
 template <int T, bool ONE, class K> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const WinDesc& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
-    const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, (size_t)20 * 1024);      // static + dynamic > 80 KB of the 160 KB
+    const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, (size_t)24 * 1024);      // static + dynamic > 80 KB of the 160 KB
     static bool attr_done = false;
     if (!attr_done && dyn > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
@@ -1055,7 +1201,11 @@ static void launch_thin(hipStream_t st, const EkfState& E, const WinDesc& wd, in
     else if (wd.T == 8) hipLaunchKernelGGL(k_ekf_win_thin<8>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd);
     else hipLaunchKernelGGL(k_ekf_win_thin<12>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd);
 }
-void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx) {
+void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx, bool split) {
+    if (!split) {
+        hipLaunchKernelGGL(k_ekf_win_next, dim3(nx.T), dim3(256), 0, st, E, pv, nx);
+        return;
+    }
     const int SPm = E.win_sp_max, s2 = 3 + 3 * nx.nS, SPn = 16 * nx.T;
     hipLaunchKernelGGL(k_ekf_win_next_gather, dim3((s2 + 255) / 256, 64), dim3(256), 0, st, E, pv, nx);
     // the miniature state the previous window's thin products and the Sigma pass run on: N := s', Sigma := Sigma_old[S', S']
