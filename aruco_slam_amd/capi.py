@@ -147,6 +147,10 @@ _SIGS = {
     "aslam_localize_begin": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp]),
     "aslam_localize_end": (C.c_int, [C.c_void_p]),
     "aslam_is_localizing": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_localize_begin_uncertain": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _dp]),
+    "aslam_fleet_begin_uncertain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _dp]),
+    "aslam_is_map_uncertain": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_fleet_get_cross": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
     "aslam_landmarks_from_markers": (C.c_int, [C.c_int, C.c_void_p, _ip, _dp]),
     "aslam_fleet_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _ip, _dp, _dp, _dp]),
     "aslam_fleet_add_images": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _P(C.c_void_p), C.c_int, C.c_int, C.c_int, _P(C.c_size_t)]),
@@ -434,6 +438,42 @@ class Context:
         on = C.c_int(0)
         self._ck(self.lib.aslam_is_localizing(self.h, C.byref(on)))
         return bool(on.value)
+    # -- localization on an uncertain map: Schmidt-Kalman steps (include/aruco_slam_hip.h) ----------------
+    def localize_begin_uncertain(self, ids, xyth, map_sigmas, pose, pose_sigma):
+        """localize_begin with one 3 x 3 covariance per landmark (n x 3 x 3 or n x 9, as a map merge returns them)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        xyth = np.ascontiguousarray(xyth, dtype=np.float64).reshape(-1, 3)
+        ms = np.ascontiguousarray(map_sigmas, dtype=np.float64).reshape(-1, 9)
+        if xyth.shape[0] != ids.size or ms.shape[0] != ids.size:
+            raise ValueError("one (x, y, theta) row and one covariance per landmark id")
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3)
+        ps = np.ascontiguousarray(pose_sigma, dtype=np.float64).reshape(9)
+        self._ck(self.lib.aslam_localize_begin_uncertain(self.h, int(ids.size), _ptr(ids, _ip), _ptr(xyth, _dp), _ptr(ms, _dp),
+                                                         _ptr(pose, _dp), _ptr(ps, _dp)))
+    def fleet_begin_uncertain(self, cams, ids, xyth, map_sigmas, poses, pose_sigmas):
+        """fleet_begin with one shared table of landmark covariances (n x 3 x 3 or n x 9)"""
+        cams = [c if isinstance(c, Camera) else Camera.make(*c) for c in cams]
+        arr = (Camera * max(len(cams), 1))(*cams)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        xyth = np.ascontiguousarray(xyth, dtype=np.float64).reshape(-1, 3)
+        ms = np.ascontiguousarray(map_sigmas, dtype=np.float64).reshape(-1, 9)
+        if xyth.shape[0] != ids.size or ms.shape[0] != ids.size:
+            raise ValueError("one (x, y, theta) row and one covariance per landmark id")
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        sig = np.ascontiguousarray(pose_sigmas, dtype=np.float64).reshape(-1, 9)
+        self._ck(self.lib.aslam_fleet_begin_uncertain(self.h, len(cams), arr, int(ids.size), _ptr(ids, _ip), _ptr(xyth, _dp), _ptr(ms, _dp),
+                                                      _ptr(poses, _dp), _ptr(sig, _dp)))
+    def is_map_uncertain(self):
+        on = C.c_int(0)
+        self._ck(self.lib.aslam_is_map_uncertain(self.h, C.byref(on)))
+        return bool(on.value)
+    def fleet_get_cross(self, robot):
+        """robot's Sigma_xl, 3 x 3L"""
+        L = C.c_int()
+        self._ck(self.lib.aslam_fleet_get_cross(self.h, int(robot), C.byref(L), None))
+        cross = np.zeros((3, 3 * L.value))
+        self._ck(self.lib.aslam_fleet_get_cross(self.h, int(robot), C.byref(L), _ptr(cross, _dp)))
+        return cross
     # -- fleet localization: many robots, one camera each, on one frozen map (DESIGN.md §12) ----------------------------
     def fleet_begin(self, cams, ids, xyth, poses, pose_sigmas):
         """cams: one Camera (or (K, D, mount) tuple) per robot; poses R x 3, pose_sigmas R x 3 x 3; map as localize_begin"""

@@ -156,6 +156,12 @@ struct aslam_ctx {
     aslam_gate_params gate_prm{};
     GateState gate{};                     // the parameters in force and the device records, as the gated kernels take them
     SlotHealth* h_slot_health = nullptr;  // page-locked: 2 max_batch
+    // uncertain map (aslam_localize_begin_uncertain / aslam_fleet_begin_uncertain): on exactly while the active
+    // localization or localization fleet was begun with landmark covariances.  The C table (max_landmarks x 9) is made by the first
+    // such begin and freed by aslam_destroy; a fleet's cross strips (R x 3 x 3n) live from its begin to aslam_fleet_end / aslam_destroy.
+    bool umap_on = false;
+    MapCov umap{};                        // the C table, the fleet's strips (nullptr: the single filter's strip is in Sigma), landmarks
+    double* d_map_c = nullptr;
     TrackHealth* h_track_health = nullptr;   // page-locked: ASLAM_MAX_ROBOTS + 1
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
@@ -633,7 +639,8 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     hipStream_t st = c->stream_ekf;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_LOC_STEPS, st);
-    launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0, c->gate_on ? &c->gate : nullptr);
+    launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0, c->gate_on ? &c->gate : nullptr,
+                     c->umap_on ? &c->umap : nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
@@ -852,6 +859,8 @@ void aslam_destroy(aslam_ctx* c) {
     merge_free(c->merge);
     reloc_free(c->reloc);
     map_edit_free(c->map_edit);
+    if (c->umap.cross) hipFree(c->umap.cross);
+    if (c->d_map_c) hipFree(c->d_map_c);
     hipFree(c->gate.slot); hipFree(c->gate.track);
     if (c->h_slot_health) hipHostFree(c->h_slot_health);
     if (c->h_track_health) hipHostFree(c->h_track_health);
@@ -2047,6 +2056,49 @@ int check_pose(aslam_ctx* c, const double* pose, const double* sigma) {
         }
     return ASLAM_OK;
 }
+
+// the landmark covariances of an uncertain map: checked, and C = (S + S^T) / 2 per landmark into out (n x 9)
+int check_map_sigmas(aslam_ctx* c, int n, const int* ids, const double* map_sigmas, std::vector<double>& out) {
+    out.resize((size_t)9 * n);
+    for (int k = 0; k < n; k++) {
+        const double* S = map_sigmas + 9 * (size_t)k;
+        double* C = &out[9 * (size_t)k];
+        const std::string who = "landmark " + std::to_string(ids[k]);
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(S[i])) return fail(c, ASLAM_E_INVALID, who + ": non-finite covariance");
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) C[i * 3 + j] = 0.5 * (S[i * 3 + j] + S[j * 3 + i]);
+        for (int i = 0; i < 3; i++) {
+            if (C[i * 4] < 0.0) return fail(c, ASLAM_E_INVALID, who + ": negative variance");
+            for (int j = i + 1; j < 3; j++)
+                if (C[i * 3 + j] * C[i * 3 + j] > C[i * 4] * C[j * 4]) return fail(c, ASLAM_E_INVALID, who + ": covariance exceeds its variances");
+        }
+    }
+    return ASLAM_OK;
+}
+
+// the C table on the device (made on first use for max_landmarks blocks)
+int upload_map_sigmas(aslam_ctx* c, const std::vector<double>& C) {
+    if (!c->d_map_c) HIP_TRY(c, dalloc(&c->d_map_c, (size_t)9 * c->ekf.max_landmarks));
+    HIP_TRY(c, hipMemcpy(c->d_map_c, C.data(), sizeof(double) * C.size(), hipMemcpyHostToDevice));
+    return ASLAM_OK;
+}
+
+// a seat of a pose on an uncertain map drops its correlation with the map: Sigma_xl := 0 of the single filter (robot < 0) or of one
+// robot, at once (st = nullptr) or behind the work enqueued on st
+int clear_cross(aslam_ctx* c, int robot, hipStream_t st = nullptr) {
+    if (!c->umap_on) return ASLAM_OK;
+    if (robot < 0) {
+        launch_umap_clear_cross(st, c->ekf, c->umap.L);
+        HIP_TRY(c, hipGetLastError());
+        if (!st) HIP_TRY(c, hipStreamSynchronize(nullptr));
+        return ASLAM_OK;
+    }
+    const size_t n = (size_t)9 * c->umap.L;
+    if (st) HIP_TRY(c, hipMemsetAsync(c->umap.cross + n * robot, 0, sizeof(double) * n, st));
+    else HIP_TRY(c, hipMemset(c->umap.cross + n * robot, 0, sizeof(double) * n));
+    return ASLAM_OK;
+}
 }  // namespace
 
 namespace {
@@ -2077,6 +2129,9 @@ int enter_mode(aslam_ctx* c, Mode m, const std::vector<RigCam>& cams = {}) {
         if (r) return r;
     }
     ekf_fleet_free(c->fslam);
+    if (c->umap.cross) hipFree(c->umap.cross);          // an uncertain-map fleet's strips; the begin that wants them makes them anew
+    c->umap = MapCov{};
+    c->umap_on = false;
     c->mode = Mode::Slam;
     c->fleet_n = 0;
     c->fleet_armed.clear();
@@ -2133,6 +2188,32 @@ int aslam_localize_begin(aslam_ctx* c, int n, const int* ids, const double* xyth
     return enter_mode(c, Mode::Localize);
 }
 
+int aslam_localize_begin_uncertain(aslam_ctx* c, int n, const int* ids, const double* xyth, const double* map_sigmas, const double pose[3],
+                                   const double pose_sigma[9]) {
+    if (!c || !ids || !xyth || !map_sigmas || !pose || !pose_sigma) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kSingle)) return r;
+    if (int r = install_frozen_map(c, n, ids, xyth, false)) return r;
+    if (int r = check_pose(c, pose, pose_sigma)) return r;
+    std::vector<double> C;
+    if (int r = check_map_sigmas(c, n, ids, map_sigmas, C)) return r;
+    if (int r = aslam_localize_begin(c, n, ids, xyth, pose, pose_sigma)) return r;
+    // Sigma := blockdiag(pose_sigma, C_0 ... C_{n-1}): the blocks beside the frozen-map state; Sigma_xl = 0 already
+    if (int r = upload_map_sigmas(c, C)) return r;
+    const size_t ld = (size_t)c->ekf.ld;
+    for (int k = 0; k < n; k++)
+        HIP_TRY(c, hipMemcpy2D(c->ekf.d_sigma + (size_t)(3 + 3 * k) * ld + 3 + 3 * k, ld * sizeof(double), &C[9 * (size_t)k], 3 * sizeof(double),
+                               3 * sizeof(double), 3, hipMemcpyHostToDevice));
+    c->umap = MapCov{c->d_map_c, nullptr, n};
+    c->umap_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_is_map_uncertain(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->umap_on ? 1 : 0;
+    return ASLAM_OK;
+}
+
 int aslam_localize_end(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
@@ -2156,6 +2237,7 @@ int fleet_seat(aslam_ctx* c, int robot, const double* pose, const double* sigma)
     HIP_TRY(c, hipMemcpy(c->fleet.pose + (size_t)kFleetState * robot, st, sizeof(st), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->fleet.nlast + robot, 0, sizeof(int)));
     c->fleet_armed[robot] = 0;
+    if (int r = clear_cross(c, robot)) return r;
     return clear_track_health(c, robot, 1);
 }
 
@@ -2183,7 +2265,8 @@ int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_FLEET_STEPS, st);
-    launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng, c->gate_on ? &c->gate : nullptr);
+    launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng, c->gate_on ? &c->gate : nullptr,
+                       c->umap_on ? &c->umap : nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_ekf, st));
@@ -2269,6 +2352,47 @@ int aslam_fleet_begin(aslam_ctx* c, int n_robots, const aslam_camera* cams, int 
         r = fleet_seat(c, k, poses + 3 * k, pose_sigmas + 9 * k);
         if (r) return r;
     }
+    return ASLAM_OK;
+}
+
+int aslam_fleet_begin_uncertain(aslam_ctx* c, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth,
+                                const double* map_sigmas, const double* poses, const double* pose_sigmas) {
+    if (!c || !cams || !ids || !xyth || !map_sigmas || !poses || !pose_sigmas) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kSlam | kFleet)) return r;
+    {   // every check of aslam_fleet_begin before anything changes, then the covariances
+        std::vector<RigCam> rc;
+        if (int r = fleet_cameras(c, n_robots, cams, rc)) return r;
+        if (int r = install_frozen_map(c, n, ids, xyth, false)) return r;
+        for (int k = 0; k < n_robots; k++)
+            if (int r = check_pose(c, poses + 3 * k, pose_sigmas + 9 * k)) return r;
+    }
+    std::vector<double> C;
+    if (int r = check_map_sigmas(c, n, ids, map_sigmas, C)) return r;
+    if (int r = aslam_fleet_begin(c, n_robots, cams, n, ids, xyth, poses, pose_sigmas)) return r;
+    if (int r = upload_map_sigmas(c, C)) return r;
+    double* cross = nullptr;
+    const size_t count = (size_t)9 * n * n_robots;
+    hipError_t e = dalloc(&cross, count);
+    if (e == hipSuccess && (e = hipMemset(cross, 0, sizeof(double) * count)) != hipSuccess) hipFree(cross);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        enter_mode(c, Mode::Slam);
+        return fail(c, ASLAM_E_CAPACITY, std::to_string(n_robots) + " cross strips of " + std::to_string(n) + " landmarks do not fit: " + hipGetErrorString(e));
+    }
+    c->umap = MapCov{c->d_map_c, cross, n};
+    c->umap_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_fleet_get_cross(aslam_ctx* c, int robot, int* L, double* cross) {
+    if (!c || !L) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kFleetLocalize)) return r;
+    if (!c->umap_on) return fail(c, ASLAM_E_STATE, "the fleet's map is exact (aslam_fleet_begin_uncertain first)");
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    *L = c->umap.L;
+    const size_t n = (size_t)9 * c->umap.L;
+    if (cross) HIP_TRY(c, hipMemcpy(cross, c->umap.cross + n * robot, sizeof(double) * n, hipMemcpyDeviceToHost));
     return ASLAM_OK;
 }
 
@@ -2597,7 +2721,10 @@ int aslam_relocalize(aslam_ctx* c, int slot, const aslam_relocalize_params* para
     if (int r = check_slot_range(c, slot, 1)) return r;
     if (int r = finalize_pending(c)) return r;
     if (int r = relocalize_slots(c, slot, 1, nullptr, prm, apply ? 1 : 0, out)) return r;
-    if (apply && out->status == 0) return clear_track_health(c, kTrackSingle, 1, c->stream_ekf);      // seated
+    if (apply && out->status == 0) {                                            // seated
+        if (int r = clear_cross(c, -1, c->stream_ekf)) return r;
+        return clear_track_health(c, kTrackSingle, 1, c->stream_ekf);
+    }
     return ASLAM_OK;
 }
 
@@ -2622,6 +2749,7 @@ int aslam_fleet_relocalize(aslam_ctx* c, int first, int count, const int* robot_
         for (int i = 0; i < count; i++)
             if (out[i].status == 0) {                                          // seated as by aslam_fleet_set_pose: its next frame only arms it
                 c->fleet_armed[robot_of_slot[i]] = 0;
+                if (int r = clear_cross(c, robot_of_slot[i], c->stream_ekf)) return r;
                 if (int r = clear_track_health(c, robot_of_slot[i], 1, c->stream_ekf)) return r;
             }
     return ASLAM_OK;

@@ -123,11 +123,20 @@ struct GateState {
     SlotHealth* slot;                  // per EKF slot (max_slots records)
     TrackHealth* track;                // kTrackSingle + 1 records
 };
+// uncertain map of the localization steps (ekf_localize.h): the landmarks' fixed covariance blocks and, for a fleet,
+// the robots' pose <-> landmark cross strips.  The single filter's strip lives in Sigma itself (rows 0..2, mirrored into columns 0..2).
+struct MapCov {
+    const double* C;                   // L x 9: block C_i of landmark index i, row-major, symmetric
+    double* cross;                     // fleet: robot r's strip Sigma_xl (3 x 3L row-major) at cross + 9 L r; nullptr for the single filter
+    int L;                             // landmarks of the map
+};
 // localization steps of EKF slots [first, first + count) in one launch (ekf_localize.h): the map stays frozen, only the pose block
 // is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder).
-// gate != nullptr: the gated kernel (k_loc_steps_gated, k_fleet_steps_gated) with those parameters
+// gate != nullptr: the gated kernel (k_loc_steps_gated, k_fleet_steps_gated) with those parameters; umap != nullptr: the
+// Schmidt-Kalman kernels (k_loc_steps_umap[_gated], k_fleet_steps_umap[_gated]) on that map
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr);
+                      const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr, const MapCov* umap = nullptr);
+void launch_umap_clear_cross(hipStream_t st, const EkfState& E, int L);   // the single filter's Sigma_xl := 0 (a seat of its pose)
 // fleet localization (ekf_fleet.h): one workgroup per robot of the work list (n_groups robots), each on its own filter in F
 constexpr int kFleetState = 12;        // doubles per robot: mu_x (3), then Sigma_xx row-major (9)
 struct FleetState {
@@ -136,7 +145,8 @@ struct FleetState {
     int* nlast;                        // R: their lengths
 };
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
-                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate = nullptr);
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate = nullptr,
+                        const MapCov* umap = nullptr);
 // fleet SLAM (ekf_fleet_slam.h): R complete filters with the single filter's chain layouts in one allocation; robot r's buffers lie
 // r * stride bytes past robot 0's.  No window buffers; d_slot_stat and max_slots are the context's.
 struct FleetSlam {

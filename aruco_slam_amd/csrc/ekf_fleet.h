@@ -40,6 +40,17 @@ struct LocFleet {
     }
     __device__ __forceinline__ LastObs* last() const { return F.last + (size_t)kMarkerMax * robot; }
     __device__ __forceinline__ int* nlast() const { return F.nlast + robot; }
+    // uncertain map: the robot's own cross strip, 3 x W row-major, in LDS (sX) as in memory
+    template <class M> __device__ __forceinline__ void load_cross(const M& um, double* sX) const {
+        const int n = 9 * um.m.L;
+        const double* g = um.m.cross + (size_t)n * robot;
+        for (int j = threadIdx.x; j < n; j += kMarkerMax) sX[j] = g[j];
+    }
+    template <class M> __device__ __forceinline__ void store_cross(const M& um, const double* sX) const {
+        const int n = 9 * um.m.L;
+        double* g = um.m.cross + (size_t)n * robot;
+        for (int j = threadIdx.x; j < n; j += kMarkerMax) g[j] = sX[j];
+    }
 };
 
 __global__ __launch_bounds__(kMarkerMax) void k_fleet_steps(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
@@ -57,8 +68,35 @@ __global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_gated(EkfState E, Fl
     loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g});
 }
 
+// the same two on an uncertain map: every robot's workgroup carries its own Sigma_xl in dynamic LDS
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                const int* __restrict__ work, int n_groups, MapCov mc) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                      const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                      const int* __restrict__ work, int n_groups, GateState g, MapCov mc) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
+}
+
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
-                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate) {
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate, const MapCov* umap) {
+    if (umap) {
+        static bool allowed[2] = {false, false};
+        const size_t dyn = umap_lds_bytes(umap->L);
+        if (gate) {
+            umap_allow_lds(k_fleet_steps_umap_gated, allowed[1]);
+            hipLaunchKernelGGL(k_fleet_steps_umap_gated, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate, *umap);
+        } else {
+            umap_allow_lds(k_fleet_steps_umap, allowed[0]);
+            hipLaunchKernelGGL(k_fleet_steps_umap, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *umap);
+        }
+        return;
+    }
     if (gate)
         hipLaunchKernelGGL(k_fleet_steps_gated, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate);
     else

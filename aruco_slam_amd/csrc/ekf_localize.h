@@ -18,6 +18,15 @@
 // skip of a correction whose d2 exceeds a finite gate, the slot's health sums in pop order and the filter's track record, which
 // stays in registers across the slots of a launch; a rejected flag per popped observation lives in LDS, and after the chain all
 // lanes compact the last-observed list with two ballots so that it holds the accepted updates and the no-ops only.
+//
+// loc_steps<Src, G, M> takes a compile-time map policy M (include/aruco_slam_hip.h).  FixedMap, the default, is the
+// filter above: every new statement sits under `if constexpr (M::kOn)`.  UncertainMap (k_loc_steps_umap[_gated],
+// k_fleet_steps_umap[_gated]) is the Schmidt-Kalman filter on a map whose landmarks carry fixed covariance blocks C_i: the strip
+// X = [Sigma_xx | Sigma_xl] replaces P.  Sigma_xl (3 x 3L) lives in dynamic LDS for the whole launch (Src says where it is loaded
+// from and stored to), Sigma_xx stays in lane 0's registers.  The front half of the slot body is shared; per correction lane 0 forms
+// S, K and the decision from the six columns it needs (pose block and block i), updates those six itself and publishes K and the
+// fuse flag; behind one barrier every lane subtracts K (Hx X[:, j]) from its own columns, behind a second one the chain goes on.  A
+// rejected correction costs the first barrier only.
 #pragma once
 #include "common.h"
 #include "ekf.h"
@@ -57,6 +66,23 @@ struct LocSingle {
     }
     __device__ __forceinline__ LastObs* last() const { return E.d_last; }
     __device__ __forceinline__ int* nlast() const { return E.d_nlast; }
+    // uncertain map: the strip's landmark columns, 3 x W row-major in sX (LDS) <-> rows 0..2 of Sigma, mirrored into columns 0..2
+    template <class M> __device__ __forceinline__ void load_cross(const M& um, double* sX) const {
+        const int W = 3 * um.m.L;
+        for (int j = threadIdx.x; j < W; j += kMarkerMax)
+#pragma unroll
+            for (int i = 0; i < 3; i++) sX[i * W + j] = E.d_sigma[(size_t)(3 + j) * E.ld + i];
+    }
+    template <class M> __device__ __forceinline__ void store_cross(const M& um, const double* sX) const {
+        const int W = 3 * um.m.L;
+        for (int j = threadIdx.x; j < W; j += kMarkerMax)
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const double v = sX[i * W + j];
+                E.d_sigma[(size_t)(3 + j) * E.ld + i] = v;
+                E.d_sigma[(size_t)i * E.ld + 3 + j] = v;
+            }
+    }
 };
 
 struct NoGate { static constexpr bool kOn = false; };
@@ -64,10 +90,15 @@ struct Gated {
     static constexpr bool kOn = true;
     GateState g;
 };
+struct FixedMap { static constexpr bool kOn = false; };
+struct UncertainMap {
+    static constexpr bool kOn = true;
+    MapCov m;
+};
 
-template <class Src, class G = NoGate>
+template <class Src, class G = NoGate, class M = FixedMap>
 __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                                          const double* enc, const G& gate = G{}) {
+                                          const double* enc, const G& gate = G{}, const M& umap = M{}) {
     __shared__ LastObs sLast[kMarkerMax];       // last_observed_marker_ of the previous step
     __shared__ int sIndex[kMarkerMax];          // landmark index per observation slot (-2: dropped)
     __shared__ int sOrder[kMarkerMax];          // pop order
@@ -83,6 +114,24 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
     if constexpr (G::kOn) {
         __shared__ int sGateCorrPop[kMarkerMax], sGateRej[kMarkerMax], sGateKeepCnt[2];
         sCorrPop = sGateCorrPop; sRej = sGateRej; sKeepCnt = sGateKeepCnt;
+    }
+    // uncertain map: Sigma_xl (3 x W row-major, W = 3 L) for the whole launch, every prepared correction's C_i and landmark block,
+    // and lane 0's verdict per correction (gain and fuse flag, two copies used alternately)
+    double* sX = nullptr;
+    double* sMapC = nullptr;
+    double* sGain = nullptr;
+    double* sPred = nullptr;
+    int* sBlock = nullptr;
+    int* sFuse = nullptr;
+    int W = 0;
+    if constexpr (M::kOn) {
+        ASLAM_DYN_LDS(umap_lds);
+        __shared__ double sUmapC[kMarkerMax * 9], sUmapGain[2 * 9], sUmapPred[2];
+        __shared__ int sUmapBlock[kMarkerMax], sUmapFuse[2];
+        sX = reinterpret_cast<double*>(umap_lds);
+        sMapC = sUmapC; sGain = sUmapGain; sPred = sUmapPred; sBlock = sUmapBlock; sFuse = sUmapFuse;
+        W = 3 * umap.m.L;
+        src.load_cross(umap, sX);
     }
 
     double mx = 0, my = 0, mt = 0, P[9];        // lane 0: the pose and Sigma_xx, in registers for the whole launch
@@ -141,6 +190,7 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
                 for (int i = 0; i < 3; i++)
                     for (int j = 0; j < 3; j++)
                         P[i * 3 + j] = (T[i * 3] * Hp[j * 3] + T[i * 3 + 1] * Hp[j * 3 + 1] + T[i * 3 + 2] * Hp[j * 3 + 2]) + Q[i * 3 + j];
+                if constexpr (M::kOn) { sPred[0] = Hp[2]; sPred[1] = Hp[5]; }
             }
             sPose[0] = mx; sPose[1] = my; sPose[2] = mt;
         }
@@ -149,6 +199,17 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             if ((tid & 63) == 0) sCnt[tid >> 6] = __popcll(b);
         }
         __syncthreads();
+        if constexpr (M::kOn) {
+            // Sigma_xl <- D Sigma_xl, every lane its own columns: D = Hp differs from I in (0,2) and (1,2) only
+            if (src.predict(k)) {
+                const double d0 = sPred[0], d1 = sPred[1];
+                for (int j = tid; j < W; j += kMarkerMax) {
+                    const double x2 = sX[2 * W + j];
+                    sX[j] = sX[j] + d0 * x2;
+                    sX[W + j] = sX[W + j] + d1 * x2;
+                }
+            }
+        }
         // pop order: every key is a landmark index >= 0, so unless one id was detected twice it is ascending index -> rank in parallel
         if (myIndex >= 0) {
             int rank = 0;
@@ -252,6 +313,12 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             cr.r[0] = po.r[0]; cr.r[1] = po.r[1]; cr.r[2] = po.r[2];
             sCorr[up] = cr;
             if constexpr (G::kOn) sCorrPop[up] = tid;
+            if constexpr (M::kOn) {                                      // its landmark's block and C_i: loaded off the chain
+                sBlock[up] = 3 * pidx;
+                const double* cg = umap.m.C + (size_t)9 * pidx;
+#pragma unroll
+                for (int i = 0; i < 9; i++) sMapC[9 * up + i] = cg[i];
+            }
         }
         // last_observed_marker_ = observed_marker (aruco_slam.cpp:263); last_observation_ is set in the update branch only
         if (tid < np) {
@@ -263,7 +330,7 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             if constexpr (G::kOn) sRej[tid] = 0;
         }
         __syncthreads();
-        if (tid == 0) {
+        if (tid == 0 || M::kOn) {                                        // uncertain map: every lane walks the chain, lane 0 decides
             // gated: the slot's health record, summed in pop order
             int hAcc = 0, hRej = 0, hFlag = 0, hWorst = -1;
             bool hHave = false;
@@ -271,70 +338,142 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
             // the dependent chain: m sequential corrections of the pose block (aruco_slam.cpp:145-205 with zero landmark blocks)
             for (int q = 0; q < m; q++) {
                 const LocCorr& cr = sCorr[q];
-                double H[9], HP[9], PHt[9], S[9], Si[9], K[9], A[9], Pn[9];
+                if (!M::kOn || tid == 0) {
+                    double H[9], HP[9], PHt[9], S[9], Si[9], K[9], A[9], Pn[9];
 #pragma unroll
-                for (int i = 0; i < 9; i++) H[i] = cr.H[i];
-                mul3(H, P, HP);                                          // H P
+                    for (int i = 0; i < 9; i++) H[i] = cr.H[i];
+                    if constexpr (M::kOn) {
+                        // Schmidt-Kalman: cst = Gxm Sigma on the pose columns (HP) and on block i (A), Gxm = [Hx | Hl at block i];
+                        // Hl = [[c, s, 0], [-s, c, 0], [0, 0, 1]] is Hx's rotation part negated
+                        const double Hl[9] = {-H[0], -H[1], 0.0, -H[3], -H[4], 0.0, 0.0, 0.0, 1.0};
+                        const double* Ci = sMapC + 9 * q;
+                        const double* Xb = sX + sBlock[q];
+                        double B[9];
 #pragma unroll
-                for (int i = 0; i < 3; i++)
+                        for (int i = 0; i < 3; i++)
 #pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        PHt[i * 3 + j] = P[i * 3] * H[j * 3] + P[i * 3 + 1] * H[j * 3 + 1] + P[i * 3 + 2] * H[j * 3 + 2];   // P H^T
-                        S[i * 3 + j] = HP[i * 3] * H[j * 3] + HP[i * 3 + 1] * H[j * 3 + 1] + HP[i * 3 + 2] * H[j * 3 + 2]       // H P H^T
-                                       + (i == j ? cr.r[i] : 0.0);
-                    }
-                inv3_reg(S, Si);
-                mul3(PHt, Si, K);                                        // K_x = P H^T S^-1
-                bool fuse = true;
-                if constexpr (G::kOn) {
-                    const double z0 = cr.ze[0], z1 = cr.ze[1], z2 = cr.ze[2];
-                    const double d2 = z0 * (Si[0] * z0 + Si[1] * z1 + Si[2] * z2) + z1 * (Si[3] * z0 + Si[4] * z1 + Si[5] * z2) +
-                                      z2 * (Si[6] * z0 + Si[7] * z1 + Si[8] * z2);            // ze^T S^-1 ze
-                    double kk = 0.0;
+                            for (int j = 0; j < 3; j++) B[i * 3 + j] = Xb[i * W + j];
 #pragma unroll
-                    for (int i = 0; i < 9; i++) kk += K[i] * K[i];
-                    hFlag += (sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;   // aruco_slam.cpp:156
-                    const int pop = sCorrPop[q];
-                    if (d2 == d2 && (!hHave || d2 > hMax)) { hHave = true; hMax = d2; hWorst = sLast[pop].id; }
-                    if (gate.g.gate_d2 < HUGE_VAL && !(d2 <= gate.g.gate_d2)) {       // a NaN d2 rejects
-                        fuse = false;
-                        hRej++;
-                        sRej[pop] = 1;
+                        for (int i = 0; i < 3; i++)
+#pragma unroll
+                            for (int j = 0; j < 3; j++) {
+                                HP[i * 3 + j] = (H[i * 3] * P[j] + H[i * 3 + 1] * P[3 + j] + H[i * 3 + 2] * P[6 + j]) +
+                                                (Hl[i * 3] * B[j * 3] + Hl[i * 3 + 1] * B[j * 3 + 1] + Hl[i * 3 + 2] * B[j * 3 + 2]);
+                                A[i * 3 + j] = (H[i * 3] * B[j] + H[i * 3 + 1] * B[3 + j] + H[i * 3 + 2] * B[6 + j]) +
+                                               (Hl[i * 3] * Ci[j] + Hl[i * 3 + 1] * Ci[3 + j] + Hl[i * 3 + 2] * Ci[6 + j]);
+                            }
+#pragma unroll
+                        for (int i = 0; i < 3; i++)
+#pragma unroll
+                            for (int j = 0; j < 3; j++) {
+                                PHt[i * 3 + j] = HP[j * 3 + i];                  // (cst's pose columns)^T
+                                S[i * 3 + j] = (HP[i * 3] * H[j * 3] + HP[i * 3 + 1] * H[j * 3 + 1] + HP[i * 3 + 2] * H[j * 3 + 2]) +
+                                               (A[i * 3] * Hl[j * 3] + A[i * 3 + 1] * Hl[j * 3 + 1] + A[i * 3 + 2] * Hl[j * 3 + 2]) +
+                                               (i == j ? cr.r[i] : 0.0);
+                            }
                     } else {
-                        hAcc++;
-                        hNis += d2;
+                        mul3(H, P, HP);                                          // H P
+#pragma unroll
+                        for (int i = 0; i < 3; i++)
+#pragma unroll
+                            for (int j = 0; j < 3; j++) {
+                                PHt[i * 3 + j] = P[i * 3] * H[j * 3] + P[i * 3 + 1] * H[j * 3 + 1] + P[i * 3 + 2] * H[j * 3 + 2];   // P H^T
+                                S[i * 3 + j] = HP[i * 3] * H[j * 3] + HP[i * 3 + 1] * H[j * 3 + 1] + HP[i * 3 + 2] * H[j * 3 + 2]       // H P H^T
+                                               + (i == j ? cr.r[i] : 0.0);
+                            }
+                    }
+                    inv3_reg(S, Si);
+                    mul3(PHt, Si, K);                                        // K_x = P H^T S^-1
+                    bool fuse = true;
+                    if constexpr (G::kOn) {
+                        const double z0 = cr.ze[0], z1 = cr.ze[1], z2 = cr.ze[2];
+                        const double d2 = z0 * (Si[0] * z0 + Si[1] * z1 + Si[2] * z2) + z1 * (Si[3] * z0 + Si[4] * z1 + Si[5] * z2) +
+                                          z2 * (Si[6] * z0 + Si[7] * z1 + Si[8] * z2);            // ze^T S^-1 ze
+                        double kk = 0.0;
+#pragma unroll
+                        for (int i = 0; i < 9; i++) kk += K[i] * K[i];
+                        hFlag += (sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;   // aruco_slam.cpp:156
+                        const int pop = sCorrPop[q];
+                        if (d2 == d2 && (!hHave || d2 > hMax)) { hHave = true; hMax = d2; hWorst = sLast[pop].id; }
+                        if (gate.g.gate_d2 < HUGE_VAL && !(d2 <= gate.g.gate_d2)) {       // a NaN d2 rejects
+                            fuse = false;
+                            hRej++;
+                            sRej[pop] = 1;
+                        } else {
+                            hAcc++;
+                            hNis += d2;
+                        }
+                    }
+                    if (fuse) {
+                        mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
+                        my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
+                        mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
+                        if constexpr (M::kOn) {
+                            // X <- X - K cst on the six columns lane 0 holds: Sigma_xx in registers, block i in place (no other
+                            // lane reads or writes block i's columns during this correction)
+                            double* Xw = sX + sBlock[q];
+#pragma unroll
+                            for (int i = 0; i < 3; i++)
+#pragma unroll
+                                for (int j = 0; j < 3; j++) {
+                                    P[i * 3 + j] = P[i * 3 + j] - (K[i * 3] * HP[j] + K[i * 3 + 1] * HP[3 + j] + K[i * 3 + 2] * HP[6 + j]);
+                                    Xw[i * W + j] = Xw[i * W + j] - (K[i * 3] * A[j] + K[i * 3 + 1] * A[3 + j] + K[i * 3 + 2] * A[6 + j]);
+                                }
+#pragma unroll
+                            for (int i = 0; i < 9; i++) sGain[9 * (q & 1) + i] = K[i];
+                        } else {
+                            mul3(K, H, A);                                       // I - K H
+#pragma unroll
+                            for (int i = 0; i < 9; i++) A[i] = ((i % 4) == 0 ? 1.0 : 0.0) - A[i];
+                            mul3(A, P, Pn);
+#pragma unroll
+                            for (int i = 0; i < 9; i++) P[i] = Pn[i];
+                        }
+                    }
+                    if constexpr (M::kOn) sFuse[q & 1] = fuse ? 1 : 0;
+                }
+                if constexpr (M::kOn) {
+                    // the strip pass of a fused correction: X[:, j] -= K (Hx X[:, j]) on every landmark column outside block i.
+                    // A rejected correction costs the one barrier and no pass.
+                    __syncthreads();                                         // lane 0's verdict is out
+                    if (sFuse[q & 1]) {
+                        double K[9], H[9];
+#pragma unroll
+                        for (int i = 0; i < 9; i++) { K[i] = sGain[9 * (q & 1) + i]; H[i] = cr.H[i]; }
+                        const int b = sBlock[q];
+                        for (int j = tid; j < W; j += kMarkerMax) {
+                            if (j >= b && j < b + 3) continue;
+                            const double x0 = sX[j], x1 = sX[W + j], x2 = sX[2 * W + j];
+                            const double c0 = H[0] * x0 + H[1] * x1 + H[2] * x2, c1 = H[3] * x0 + H[4] * x1 + H[5] * x2,
+                                         c2 = H[6] * x0 + H[7] * x1 + H[8] * x2;
+                            sX[j] = x0 - (K[0] * c0 + K[1] * c1 + K[2] * c2);
+                            sX[W + j] = x1 - (K[3] * c0 + K[4] * c1 + K[5] * c2);
+                            sX[2 * W + j] = x2 - (K[6] * c0 + K[7] * c1 + K[8] * c2);
+                        }
+                        __syncthreads();                                     // the strip is whole again before lane 0 reads the next block
                     }
                 }
-                if (fuse) {
-                    mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
-                    my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
-                    mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
-                    mul3(K, H, A);                                       // I - K H
-#pragma unroll
-                    for (int i = 0; i < 9; i++) A[i] = ((i % 4) == 0 ? 1.0 : 0.0) - A[i];
-                    mul3(A, P, Pn);
-#pragma unroll
-                    for (int i = 0; i < 9; i++) P[i] = Pn[i];
-                }
             }
-            const int fused = G::kOn ? hAcc : m;
-            if constexpr (!G::kOn) sNl = np;
-            if (slot < E.max_slots) {                                    // detections, appended (never), corrections, no-ops
-                int* st = E.d_slot_stat + 4 * slot;
-                st[0] = nM; st[1] = 0; st[2] = fused; st[3] = sStatCnt[0] + sStatCnt[1];
-            }
-            if (Src::kPopList && k == count - 1) { *E.d_npop = np; *E.d_m = fused; }
-            if constexpr (G::kOn) {
-                if (slot < E.max_slots) {
-                    SlotHealth* h = gate.g.slot + slot;
-                    h->attempted = m; h->accepted = hAcc; h->rejected = hRej; h->ref_flagged = hFlag;
-                    h->nis_sum = hNis; h->d2_max = hMax; h->worst_id = hWorst; h->pad = 0;
+            if (!M::kOn || tid == 0) {
+                const int fused = G::kOn ? hAcc : m;
+                if constexpr (!G::kOn) sNl = np;
+                if (slot < E.max_slots) {                                    // detections, appended (never), corrections, no-ops
+                    int* st = E.d_slot_stat + 4 * slot;
+                    st[0] = nM; st[1] = 0; st[2] = fused; st[3] = sStatCnt[0] + sStatCnt[1];
                 }
-                trFrames++;
-                trAcc += hAcc;
-                trRej += hRej;
-                if (m >= gate.g.min_attempted) trStreak = 100 * hAcc < gate.g.min_accept_percent * m ? trStreak + 1 : 0;
-                trLost = trStreak >= gate.g.lost_after ? 1 : 0;
+                if (Src::kPopList && k == count - 1) { *E.d_npop = np; *E.d_m = fused; }
+                if constexpr (G::kOn) {
+                    if (slot < E.max_slots) {
+                        SlotHealth* h = gate.g.slot + slot;
+                        h->attempted = m; h->accepted = hAcc; h->rejected = hRej; h->ref_flagged = hFlag;
+                        h->nis_sum = hNis; h->d2_max = hMax; h->worst_id = hWorst; h->pad = 0;
+                    }
+                    trFrames++;
+                    trAcc += hAcc;
+                    trRej += hRej;
+                    if (m >= gate.g.min_attempted) trStreak = 100 * hAcc < gate.g.min_accept_percent * m ? trStreak + 1 : 0;
+                    trLost = trStreak >= gate.g.lost_after ? 1 : 0;
+                }
             }
         }
         if constexpr (G::kOn) {
@@ -362,6 +501,7 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
         __syncthreads();
     }
     if (tid < sNl) src.last()[tid] = sLast[tid];
+    if constexpr (M::kOn) src.store_cross(umap, sX);
     if (tid == 0) {
         *src.nlast() = sNl;
         src.store(mx, my, mt, P);
@@ -385,8 +525,56 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps_gated(EkfState E, Slam
     loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g});
 }
 
+// the same two on an uncertain map: Sigma_xl in dynamic LDS, 24 * 3 L bytes
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                              const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                              int first, int count, int predict_first, MapCov mc) {
+    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                    const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                    int first, int count, int predict_first, GateState g, MapCov mc) {
+    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
+}
+
+// Sigma_xl := 0 of the single filter (rows 0..2 and their mirror in columns 0..2): what a seat of its pose does on an uncertain map
+__global__ void k_umap_clear_cross(EkfState E, int L) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 3 * L) return;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        E.d_sigma[(size_t)(3 + j) * E.ld + i] = 0.0;
+        E.d_sigma[(size_t)i * E.ld + 3 + j] = 0.0;
+    }
+}
+
+void launch_umap_clear_cross(hipStream_t st, const EkfState& E, int L) {
+    hipLaunchKernelGGL(k_umap_clear_cross, dim3((3 * L + 255) / 256), dim3(256), 0, st, E, L);
+}
+
+// dynamic LDS of an uncertain-map kernel: the strip's landmark columns; above 64 KB a kernel has to be told once
+inline size_t umap_lds_bytes(int L) { return sizeof(double) * 9 * (size_t)L; }
+template <class Kern> void umap_allow_lds(Kern kernel, bool& done) {
+    if (done) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)umap_lds_bytes(kIdTableSize));
+    done = true;
+}
+
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first, const GateState* gate) {
+                      const double* enc, int first, int count, int predict_first, const GateState* gate, const MapCov* umap) {
+    if (umap) {
+        static bool allowed[2] = {false, false};
+        const size_t dyn = umap_lds_bytes(umap->L);
+        if (gate) {
+            umap_allow_lds(k_loc_steps_umap_gated, allowed[1]);
+            hipLaunchKernelGGL(k_loc_steps_umap_gated, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate, *umap);
+        } else {
+            umap_allow_lds(k_loc_steps_umap, allowed[0]);
+            hipLaunchKernelGGL(k_loc_steps_umap, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *umap);
+        }
+        return;
+    }
     if (gate)
         hipLaunchKernelGGL(k_loc_steps_gated, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate);
     else

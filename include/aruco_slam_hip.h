@@ -273,6 +273,53 @@ int aslam_fleet_end(aslam_ctx* ctx);
 /* *n_robots = R of the active fleet (either kind), 0 outside fleet mode */
 int aslam_is_fleet(aslam_ctx* ctx, int* n_robots);
 
+/* ---- localization on an uncertain map: Schmidt-Kalman ("consider") steps, single filter and fleet ---------------
+ * A map surveyed by SLAM comes with a covariance per landmark (aslam_fleet_merge_maps / aslam_merge_map_records: sigmas, n x 9).
+ * The two calls below start localization / a localization fleet that takes it into account: the landmarks are still not estimated
+ * (their means and covariances never change), but their covariance enters every S and the pose <-> landmark cross-covariance is
+ * carried.  This is the reference's update (aruco_slam.cpp:88-207) with the landmark rows of K set to zero and the covariance
+ * updated consistently for that gain; with every landmark covariance zero it is the frozen-map filter above.
+ *
+ * Per filter X = [Sigma_xx | Sigma_xl] is a 3 x (3 + 3L) strip.  Sigma_ll is fixed and block-diagonal, one 3 x 3 block C_i per
+ * landmark; correlations between different landmarks are dropped, as the merge drops them.  Exactly as in the frozen-map steps:
+ * the predict's pose arithmetic, the id lookup (unknown ids dropped), the pop order including the heap replay for an id seen twice,
+ * the "stationary" no-op, ze and the pose Jacobian Hx from the frame-start pose, and R.  New:
+ *   predict     X <- D X on all columns (D = the predict's pose Jacobian, differing from I in (0,2) and (1,2) only), then
+ *               Sigma_xx <- (D Sigma_xx) D^T + Q in the frozen-map filter's expression order.
+ *   correction  on landmark i, in pop order, with Hl = [[c, s, 0], [-s, c, 0], [0, 0, 1]] (c, s of the frame-start heading: the
+ *               landmark part of the reference's Gxm):
+ *                   cst = Hx X                                (3 x (3 + 3L))
+ *                   cst[:, block i] += Hl C_i
+ *                   cst[:, 0:3]     += Hl (X[:, block i])^T
+ *                   S = cst[:, 0:3] Hx^T + cst[:, block i] Hl^T + diag(R)
+ *                   K = (cst[:, 0:3])^T S^-1                  (3 x 3)
+ *                   mu_x += K ze,   X <- X - K cst
+ *   gate        when set (aslam_set_innovation_gate): d2 = ze^T S^-1 ze with this S; a rejected correction leaves mu_x and the
+ *               whole strip untouched; slot and track records, action 3 and the compaction of the last-observed list as for the
+ *               frozen map; ref_flagged uses this K.
+ *   reseat      every seat of a pose zeroes that filter's Sigma_xl: aslam_fleet_set_pose and a solved apply != 0 of aslam_relocalize /
+ *               aslam_fleet_relocalize.  A relocalized pose IS correlated with the map it was solved against; that correlation is
+ *               deliberately dropped (relocalization uses the map means only).
+ * The calls that started on an exact map (aslam_localize_begin, aslam_fleet_begin) keep their filter and their kernels.  Every mode
+ * rule of localization and of fleets holds unchanged. */
+/* aslam_localize_begin with landmark covariances: its checks, and map_sigmas finite; C_i = (S_i + S_i^T) / 2 is used (as the merge
+   does), its diagonal must be >= 0 and C_jk^2 <= C_jj C_kk for each pair, else ASLAM_E_INVALID naming the id, the state untouched.
+   An all-zero block is legal (what the merge returns for n_seen = 0).  State := [pose, map], Sigma := blockdiag(pose_sigma, C_0 ..
+   C_{n-1}); the strip lives in rows 0..2 of Sigma, mirrored into columns 0..2, so aslam_get_state, aslam_export_map (which reports
+   C_i) and aslam_save_state work unchanged, and aslam_localize_end leaves a valid SLAM state whose later steps move the landmarks. */
+int aslam_localize_begin_uncertain(aslam_ctx* ctx, int n, const int* ids, const double* xyth /* n x 3 */,
+                                   const double* map_sigmas /* n x 9 row-major */, const double pose[3], const double pose_sigma[9]);
+/* aslam_fleet_begin with one shared table of landmark covariances (checked as above); every robot gets a zeroed cross strip of
+   3 x 3n doubles, freed by aslam_fleet_end / aslam_destroy (and by the next begin).  ASLAM_E_CAPACITY if the strips do not fit:
+   then no fleet is active. */
+int aslam_fleet_begin_uncertain(aslam_ctx* ctx, int n_robots, const aslam_camera* cams, int n, const int* ids, const double* xyth,
+                                const double* map_sigmas /* n x 9 */, const double* poses /* R x 3 */, const double* pose_sigmas /* R x 9 */);
+/* *on = 1 while the active localization or localization fleet runs on an uncertain map */
+int aslam_is_map_uncertain(aslam_ctx* ctx, int* on);
+/* one robot's Sigma_xl (waits for the enqueued work as the other fleet getters do): *L = landmarks, cross (may be NULL) receives
+   3 x 3L doubles, row-major.  ASLAM_E_STATE outside an uncertain-map fleet. */
+int aslam_fleet_get_cross(aslam_ctx* ctx, int robot, int* L, double* cross /* 3 x 3L */);
+
 /* ---- fleet SLAM: many robots, each building its own map, in one context (no reference counterpart) -----------
  * A SLAM fleet is R robots, 1 <= R <= min(max_batch, ASLAM_MAX_ROBOTS), each with one camera (aslam_camera) and a complete EKF-SLAM
  * filter of its own: mu and Sigma of capacity init.max_landmarks, id <-> index tables, last-observed list, pop list and armed flag.
