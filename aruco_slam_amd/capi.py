@@ -176,6 +176,8 @@ _SIGS = {
     "aslam_default_gate_params": (None, [_P(GateParams)]),
     "aslam_set_innovation_gate": (C.c_int, [C.c_void_p, _P(GateParams)]),
     "aslam_get_innovation_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
+    "aslam_set_slam_gate": (C.c_int, [C.c_void_p, _P(GateParams)]),
+    "aslam_get_slam_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -672,6 +674,31 @@ class Context:
             return None
         return dict(gate_d2=p.gate_d2, min_attempted=p.min_attempted, min_accept_percent=p.min_accept_percent, lost_after=p.lost_after)
 
+    # -- innovation gate of the SLAM chains ----------------------------------------------------------------------
+    def set_slam_gate(self, params=True, **kw):
+        """set_slam_gate(gate_d2=..., min_attempted=..., min_accept_percent=..., lost_after=...): the library's defaults with the given
+        fields replaced (gate_d2=inf: monitor only); set_slam_gate(None): off"""
+        if params is None:
+            if kw:
+                raise ValueError("set_slam_gate(None) takes no parameters")
+            self._ck(self.lib.aslam_set_slam_gate(self.h, None))
+            return
+        p = GateParams()
+        self.lib.aslam_default_gate_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in ("gate_d2", "min_attempted", "min_accept_percent", "lost_after"):
+                raise KeyError(k)
+            setattr(p, k, v)
+        self._ck(self.lib.aslam_set_slam_gate(self.h, C.byref(p)))
+
+    def get_slam_gate(self):
+        """None while the SLAM gate is off, else its parameters as a dict"""
+        on, p = C.c_int(), GateParams()
+        self._ck(self.lib.aslam_get_slam_gate(self.h, C.byref(on), C.byref(p)))
+        if not on.value:
+            return None
+        return dict(gate_d2=p.gate_d2, min_attempted=p.min_attempted, min_accept_percent=p.min_accept_percent, lost_after=p.lost_after)
+
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""
         out = np.zeros(max(int(count), 1), SLOT_HEALTH_DTYPE)
@@ -679,13 +706,13 @@ class Context:
         return out[:max(int(count), 0)]
 
     def get_track_health(self):
-        """the single localizing filter's TRACK_HEALTH_DTYPE record"""
+        """the single filter's TRACK_HEALTH_DTYPE record (localizing: the innovation gate's; SLAM, rig SLAM: the SLAM gate's)"""
         out = np.zeros(1, TRACK_HEALTH_DTYPE)
         self._ck(self.lib.aslam_get_track_health(self.h, out.ctypes.data_as(C.c_void_p)))
         return out[0]
 
     def fleet_get_health(self):
-        """one TRACK_HEALTH_DTYPE record per robot of the localization fleet"""
+        """one TRACK_HEALTH_DTYPE record per robot of the fleet (localization fleet: the innovation gate's; SLAM fleet: the SLAM gate's)"""
         n = C.c_int()
         out = np.zeros(MAX_ROBOTS, TRACK_HEALTH_DTYPE)
         self._ck(self.lib.aslam_fleet_get_health(self.h, MAX_ROBOTS, C.byref(n), out.ctypes.data_as(C.c_void_p)))

@@ -32,11 +32,11 @@ constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
-              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_COUNT };
+              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
-                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows"};
+                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -156,6 +156,12 @@ struct aslam_ctx {
     aslam_gate_params gate_prm{};
     GateState gate{};                     // the parameters in force and the device records, as the gated kernels take them
     SlotHealth* h_slot_health = nullptr;  // page-locked: 2 max_batch
+    // SLAM innovation gate (aslam_set_slam_gate): a switch of its own; only the per-frame chains of SLAM, rig SLAM and
+    // fleet SLAM look at it, and while it is set aslam_run_staged plans no windows.  The records are the ones above, made by whichever
+    // setter runs first; the verdict buffer (2 kMarkerMax doubles per filter of a launch) is made by the first aslam_set_slam_gate.
+    bool slam_gate_on = false;
+    aslam_gate_params slam_gate_prm{};
+    SlamGateArg slam_gate{};
     // uncertain map (aslam_localize_begin_uncertain / aslam_fleet_begin_uncertain): on exactly while the active
     // localization or localization fleet was begun with landmark covariances.  The C table (max_landmarks x 9) is made by the first
     // such begin and freed by aslam_destroy; a fleet's cross strips (R x 3 x 3n) live from its begin to aslam_fleet_end / aslam_destroy.
@@ -241,6 +247,15 @@ int allow(aslam_ctx* c, unsigned allowed) {
     else if (allowed & kFleet) why = "localizing: one filter is active (aslam_localize_end first)";     // a call that starts a fleet
     else why = "localizing: the map is frozen (aslam_localize_end first)";
     return fail(c, ASLAM_E_STATE, why);
+}
+
+// a seat clears the track records [first, first + count) of the innovation gate (if it was ever set): at once, or behind the work
+// enqueued on st
+int clear_track_health(aslam_ctx* c, int first, int count, hipStream_t st = nullptr) {
+    if (!c->gate.track) return ASLAM_OK;
+    if (st) HIP_TRY(c, hipMemsetAsync(c->gate.track + first, 0, sizeof(TrackHealth) * count, st));
+    else HIP_TRY(c, hipMemset(c->gate.track + first, 0, sizeof(TrackHealth) * count));
+    return ASLAM_OK;
 }
 
 int pinned_alloc(aslam_ctx* c, PinnedPair& p, size_t n) {
@@ -585,21 +600,31 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
 }
 
 // the per-frame chain behind k_ekf_plan, sized by max_updates_per_frame: on the single filter (s = c->ekf) or on one round of a fleet
-// SLAM call (s = FleetRound)
-template <class S> int run_chain(aslam_ctx* c, const S& s) {
+// SLAM call (s = FleetRound).  With the SLAM gate set the solve kernel is the gated one and k_ekf_gate_finish follows it (slot: the
+// single filter's EKF slot; a round's slots are in its work list).
+template <class S> int run_chain(aslam_ctx* c, const S& s, int slot = 0) {
     hipStream_t st = c->stream_ekf;
     const bool fast = c->init.max_updates_per_frame <= ekf_fast_max_updates();
+    const SlamGateArg* gate = c->slam_gate_on ? &c->slam_gate : nullptr;
+    auto finish = [&]() {
+        if (!gate) return;
+        prof_begin(c, P_EKF_GATE_FINISH, st);
+        launch_ekf_gate_finish(st, s, *gate, slot);
+        prof_end(c);
+    };
     if (fast) {
         prof_begin(c, P_EKF_MID, st);
-        launch_ekf_mid(st, s);
+        launch_ekf_mid(st, s, gate);
         prof_end(c);
+        finish();
         prof_begin(c, P_EKF_APPLY, st);
         launch_ekf_apply(st, s);
         prof_end(c);
     } else if (c->init.max_updates_per_frame <= ekf_mid_max_updates()) {
         prof_begin(c, P_EKF_MID64, st);
-        launch_ekf_mid64(st, s);
+        launch_ekf_mid64(st, s, gate);
         prof_end(c);
+        finish();
         prof_begin(c, P_EKF_T, st);
         launch_ekf_T(st, s);
         prof_end(c);
@@ -611,8 +636,9 @@ template <class S> int run_chain(aslam_ctx* c, const S& s) {
         launch_ekf_gather(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_SMALL, st);
-        launch_ekf_small(st, s);
+        launch_ekf_small(st, s, gate);
         prof_end(c);
+        finish();
         prof_begin(c, P_EKF_T, st);
         launch_ekf_T(st, s);
         prof_end(c);
@@ -630,7 +656,7 @@ int run_ekf_frame(aslam_ctx* c, int slot, double wl, double wr, double dt, bool 
     launch_ekf_plan(st, c->ekf, c->sp, wl, wr, dt, do_predict ? 1 : 0, c->d_obs + (size_t)slot * kMarkerMax, c->d_nmarkers + slot, c->d_ctr,
                     c->init.max_updates_per_frame, slot);
     prof_end(c);
-    return run_chain(c, c->ekf);
+    return run_chain(c, c->ekf, slot);
 }
 
 // localization steps of EKF slots [first, first + count) on the EKF stream, behind the detection that produced their lists: one
@@ -861,7 +887,7 @@ void aslam_destroy(aslam_ctx* c) {
     map_edit_free(c->map_edit);
     if (c->umap.cross) hipFree(c->umap.cross);
     if (c->d_map_c) hipFree(c->d_map_c);
-    hipFree(c->gate.slot); hipFree(c->gate.track);
+    hipFree(c->gate.slot); hipFree(c->gate.track); hipFree(c->slam_gate.verdicts);
     if (c->h_slot_health) hipHostFree(c->h_slot_health);
     if (c->h_track_health) hipHostFree(c->h_track_health);
     hipFree(c->fleet.pose); hipFree(c->fleet.last); hipFree(c->fleet.nlast);
@@ -1282,9 +1308,12 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         note_ekf_range(c, first, count);
         return ASLAM_OK;
     }
-    if (!c->win_enabled) {                     // every frame on the per-frame chain, enqueued at once
+    if (!c->win_enabled || c->slam_gate_on) {  // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
+        // the SLAM gate: the window planner runs the "stationary" test on the host from a mirror of the last-observed
+        // list, which a rejection on the device changes; the mirror is stale from here on
+        if (c->slam_gate_on) c->mirror_dirty = true;
         HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
         for (int i = 0; i < count; i++) {
             const double* e = &c->enc_host[(size_t)3 * (first + i)];
@@ -1795,7 +1824,7 @@ int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, 
     int r = write_state(c, c->ekf, N, mu, sigma, landmark_ids);
     if (r) return r;
     c->mirror_dirty = true;
-    return ASLAM_OK;
+    return clear_track_health(c, kTrackSingle, 1);
 }
 
 // ---- host-side result surface (what the node publishes; pure host arithmetic on a few values read back) ---------------
@@ -2038,15 +2067,6 @@ int install_frozen_map(aslam_ctx* c, int n, const int* ids, const double* xyth, 
     return ASLAM_OK;
 }
 
-// a seat clears the track records [first, first + count) of the innovation gate (if it was ever set): at once, or behind the work
-// enqueued on st
-int clear_track_health(aslam_ctx* c, int first, int count, hipStream_t st = nullptr) {
-    if (!c->gate.track) return ASLAM_OK;
-    if (st) HIP_TRY(c, hipMemsetAsync(c->gate.track + first, 0, sizeof(TrackHealth) * count, st));
-    else HIP_TRY(c, hipMemset(c->gate.track + first, 0, sizeof(TrackHealth) * count));
-    return ASLAM_OK;
-}
-
 int check_pose(aslam_ctx* c, const double* pose, const double* sigma) {
     for (int k = 0; k < 3; k++) if (!std::isfinite(pose[k])) return fail(c, ASLAM_E_INVALID, "non-finite pose");
     for (int i = 0; i < 3; i++)
@@ -2163,6 +2183,9 @@ int enter_mode(aslam_ctx* c, Mode m, const std::vector<RigCam>& cams = {}) {
     c->mode = m;
     c->fleet_n = fleet ? R : 0;
     c->fleet_armed.assign(c->fleet_n, 0);
+    // a seat of every SLAM filter the mode starts with (the localization modes' begins clear their own records)
+    if (m == Mode::Slam) return clear_track_health(c, kTrackSingle, 1);
+    if (m == Mode::FleetSlam) return clear_track_health(c, 0, R);
     return ASLAM_OK;
 }
 }  // namespace
@@ -2506,7 +2529,8 @@ int aslam_fleet_set_state(aslam_ctx* c, int robot, int N, const double* mu, cons
     if (L > c->ekf.max_landmarks) return fail(c, ASLAM_E_CAPACITY, "state larger than max_landmarks");
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
     { int rs = sync_streams(c); if (rs) return rs; }
-    return write_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma, landmark_ids);
+    if (int r = write_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma, landmark_ids)) return r;
+    return clear_track_health(c, robot, 1);
 }
 
 int aslam_fleet_get_landmark_ids(aslam_ctx* c, int robot, int* L, int* ids) {
@@ -2569,7 +2593,7 @@ int aslam_remove_landmarks(aslam_ctx* c, int n, const int* ids, int* removed) {
     int r = run_map_edit(c, J, removed);
     if (r) return r;
     c->mirror_dirty = true;
-    return ASLAM_OK;
+    return clear_track_health(c, kTrackSingle, 1);
 }
 
 int aslam_fleet_remove_landmarks(aslam_ctx* c, int n, const int* ids, int n_robots, const int* robots, int* removed) {
@@ -2595,7 +2619,10 @@ int aslam_fleet_remove_landmarks(aslam_ctx* c, int n, const int* ids, int n_robo
     J.base = c->fslam.base;
     J.stride = c->fslam.stride;
     J.n = n_robots;
-    return run_map_edit(c, J, removed);
+    if (int r = run_map_edit(c, J, removed)) return r;
+    for (int k = 0; k < n_robots; k++)
+        if (int r = clear_track_health(c, J.robot[k], 1)) return r;
+    return ASLAM_OK;
 }
 
 // ---- map merge: one shared map from N maps in N frames (include/aruco_slam_hip.h) -------------------------------
@@ -2768,14 +2795,17 @@ void aslam_default_gate_params(aslam_gate_params* p) {
     p->pad = 0;
 }
 
-int aslam_set_innovation_gate(aslam_ctx* c, const aslam_gate_params* params) {
-    if (!c) return ASLAM_E_INVALID;
-    if (!params) { c->gate_on = false; return ASLAM_OK; }
-    const aslam_gate_params& p = *params;
+namespace {
+int check_gate_params(aslam_ctx* c, const aslam_gate_params& p) {
     if (!(p.gate_d2 > 0.0)) return fail(c, ASLAM_E_INVALID, "gate_d2 must be positive, or +inf to monitor only");
     if (p.min_attempted < 1) return fail(c, ASLAM_E_INVALID, "min_attempted >= 1");
     if (p.min_accept_percent < 0 || p.min_accept_percent > 100) return fail(c, ASLAM_E_INVALID, "min_accept_percent 0..100");
     if (p.lost_after < 1) return fail(c, ASLAM_E_INVALID, "lost_after >= 1");
+    return ASLAM_OK;
+}
+
+// the health records and their page-locked copies, made by whichever gate is set first
+int alloc_health(aslam_ctx* c) {
     if (!c->gate.track) {
         const size_t ns = (size_t)c->ekf.max_slots, nt = (size_t)kTrackSingle + 1;
         SlotHealth* d_slot = nullptr;
@@ -2789,6 +2819,16 @@ int aslam_set_innovation_gate(aslam_ctx* c, const aslam_gate_params* params) {
         HIP_TRY(c, hipMemset(d_track, 0, nt * sizeof(TrackHealth)));
         c->gate.track = d_track;         // set last: the records exist exactly when this is set
     }
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_set_innovation_gate(aslam_ctx* c, const aslam_gate_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (!params) { c->gate_on = false; return ASLAM_OK; }
+    const aslam_gate_params& p = *params;
+    if (int r = check_gate_params(c, p)) return r;
+    if (int r = alloc_health(c)) return r;
     c->gate_prm = p;
     c->gate_prm.pad = 0;
     c->gate.gate_d2 = p.gate_d2;
@@ -2809,11 +2849,52 @@ int aslam_get_innovation_gate(aslam_ctx* c, int* on, aslam_gate_params* out) {
     return ASLAM_OK;
 }
 
+// ---- innovation gate of the SLAM chains (include/aruco_slam_hip.h) --------------------------------------------------
+int aslam_set_slam_gate(aslam_ctx* c, const aslam_gate_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (params)
+        if (int r = check_gate_params(c, *params)) return r;
+    // a batch still pending was submitted under the setting in force so far: its windows (or per-frame steps) are enqueued first
+    if (int r = finalize_pending(c)) return r;
+    if (!params) { c->slam_gate_on = false; return ASLAM_OK; }
+    if (int r = alloc_health(c)) return r;
+    if (!c->slam_gate.verdicts) {
+        const size_t filters = (size_t)std::max(1, std::min(c->max_batch, ASLAM_MAX_ROBOTS));   // the single filter, or the robots of a round
+        HIP_TRY(c, dalloc(&c->slam_gate.verdicts, filters * 2 * kMarkerMax));
+        HIP_TRY(c, hipMemset(c->slam_gate.verdicts, 0, filters * 2 * kMarkerMax * sizeof(double)));
+    }
+    const aslam_gate_params& p = *params;
+    c->slam_gate_prm = p;
+    c->slam_gate_prm.pad = 0;
+    c->slam_gate.g = c->gate;            // the records; the parameters are this gate's own
+    c->slam_gate.g.gate_d2 = p.gate_d2;
+    c->slam_gate.g.min_attempted = p.min_attempted;
+    c->slam_gate.g.min_accept_percent = p.min_accept_percent;
+    c->slam_gate.g.lost_after = p.lost_after;
+    c->slam_gate_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_get_slam_gate(aslam_ctx* c, int* on, aslam_gate_params* out) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->slam_gate_on ? 1 : 0;
+    if (out) {
+        if (c->slam_gate_on) *out = c->slam_gate_prm;
+        else aslam_default_gate_params(out);
+    }
+    return ASLAM_OK;
+}
+
 namespace {
-// what every health getter checks first: the gate is set and the mode is one it works in
-int gate_readable(aslam_ctx* c, unsigned modes) {
-    if (!c->gate_on) return fail(c, ASLAM_E_STATE, "no innovation gate set (aslam_set_innovation_gate first)");
-    return allow(c, modes);
+// what every health getter checks first.  In a SLAM mode (SLAM, fleet SLAM) the records are the SLAM gate's: readable while it is set
+// and the getter serves that mode (slam_modes).  In the localization modes they are the innovation gate's, as before (loc_modes).
+int gate_readable(aslam_ctx* c, unsigned loc_modes, unsigned slam_modes) {
+    if (in(c->mode) & slam_modes) {
+        if (c->slam_gate_on) return ASLAM_OK;
+        return fail(c, ASLAM_E_STATE, "no SLAM gate set (aslam_set_slam_gate first; the innovation gate covers the localization modes only)");
+    }
+    if ((in(c->mode) & loc_modes) && !c->gate_on) return fail(c, ASLAM_E_STATE, "no innovation gate set (aslam_set_innovation_gate first)");
+    return allow(c, loc_modes);
 }
 
 // bytes of records from the device array d into the page-locked h behind the EKF steps enqueued so far, then to out
@@ -2828,7 +2909,7 @@ int read_health(aslam_ctx* c, const void* d, void* h, size_t bytes, void* out) {
 
 int aslam_get_slot_health(aslam_ctx* c, int first, int count, aslam_slot_health* out) {
     if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (int r = gate_readable(c, kLocalize | kFleetLocalize)) return r;
+    if (int r = gate_readable(c, kLocalize | kFleetLocalize, kSlam | kFleetSlam)) return r;
     if (first < 0 || count < 1 || count > c->ekf.max_slots || first > c->ekf.max_slots - count)
         return fail(c, ASLAM_E_INVALID, "EKF slot range outside [0, 2 max_batch)");
     return read_health(c, c->gate.slot + first, c->h_slot_health, sizeof(SlotHealth) * count, out);
@@ -2836,15 +2917,14 @@ int aslam_get_slot_health(aslam_ctx* c, int first, int count, aslam_slot_health*
 
 int aslam_get_track_health(aslam_ctx* c, aslam_track_health* out) {
     if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
-    if (int r = gate_readable(c, kLocalize)) return r;
+    if (int r = gate_readable(c, kLocalize, kSlam)) return r;
     return read_health(c, c->gate.track + kTrackSingle, c->h_track_health, sizeof(TrackHealth), out);
 }
 
 int aslam_fleet_get_health(aslam_ctx* c, int max, int* n_robots, aslam_track_health* out) {
     if (!c || !n_robots) return fail(c, ASLAM_E_INVALID, "null argument");
     if (max < 0 || (max > 0 && !out)) return fail(c, ASLAM_E_INVALID, "max records need an output array");
-    if (c->mode == Mode::FleetSlam) return fail(c, ASLAM_E_STATE, "fleet SLAM: the innovation gate covers localization fleets only");
-    if (int r = gate_readable(c, kFleetLocalize)) return r;
+    if (int r = gate_readable(c, kFleetLocalize, kFleetSlam)) return r;
     *n_robots = c->fleet_n;
     const int n = std::min(max, c->fleet_n);
     if (n == 0) return ASLAM_OK;

@@ -96,14 +96,15 @@ void ekf_free(EkfState& E);
 void launch_ekf_predict_only(hipStream_t st, const EkfState& E, const SlamParams& sp, double wl, double wr, double dt);
 void launch_ekf_plan(hipStream_t st, const EkfState& E, const SlamParams& sp, double wl, double wr, double dt, int do_predict,
                      const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m, int slot);
-void launch_ekf_mid(hipStream_t st, const EkfState& E);
+struct SlamGateArg;                    // below: the SLAM gate of a launch; nullptr = the ungated kernel
+void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
 void launch_ekf_apply(hipStream_t st, const EkfState& E);
 int ekf_fast_max_updates();
 int ekf_mid_max_updates();
-void launch_ekf_mid64(hipStream_t st, const EkfState& E);
+void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
 void launch_ekf_update_mfma(hipStream_t st, const EkfState& E, int depth = -1);   // depth >= 0: rows of d_T / d_Wt to contract instead of 3 * *d_m
 void launch_ekf_gather(hipStream_t st, const EkfState& E);
-void launch_ekf_small(hipStream_t st, const EkfState& E);
+void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
 void launch_ekf_T(hipStream_t st, const EkfState& E);
 void launch_ekf_export_map(hipStream_t st, const EkfState& E);
 // innovation gate of the localization steps (ekf_localize.h): the parameters in force and where the gated kernels
@@ -123,6 +124,14 @@ struct GateState {
     SlotHealth* slot;                  // per EKF slot (max_slots records)
     TrackHealth* track;                // kTrackSingle + 1 records
 };
+// innovation gate of the SLAM chains (ekf_slam_gate.h): the parameters and records as above, and the buffer in which
+// a gated solve kernel leaves d2 and its verdict per correction for k_ekf_gate_finish (2 kMarkerMax doubles per filter of a launch)
+struct SlamGateArg {
+    GateState g;
+    double* verdicts;
+};
+// behind a gated solve of the single filter's frame in EKF slot `slot`: actions, last-observed list, slot record, track record
+void launch_ekf_gate_finish(hipStream_t st, const EkfState& E, const SlamGateArg& gate, int slot);
 // uncertain map of the localization steps (ekf_localize.h): the landmarks' fixed covariance blocks and, for a fleet,
 // the robots' pose <-> landmark cross strips.  The single filter's strip lives in Sigma itself (rows 0..2, mirrored into columns 0..2).
 struct MapCov {
@@ -168,12 +177,13 @@ struct FleetRound {
     int n;
 };
 void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m);
-void launch_ekf_mid(hipStream_t st, const FleetRound& R);
+void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
 void launch_ekf_apply(hipStream_t st, const FleetRound& R);
-void launch_ekf_mid64(hipStream_t st, const FleetRound& R);
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
 void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R);
 void launch_ekf_gather(hipStream_t st, const FleetRound& R);
-void launch_ekf_small(hipStream_t st, const FleetRound& R);
+void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
+void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateArg& gate, int slot = 0);   // every robot of the round; slot: unused (the work list's)
 void launch_ekf_T(hipStream_t st, const FleetRound& R);
 // map merge (fleet_merge.h): n_maps <= kMergeMaxMaps maps of per_map MapRecord records each, aligned
 // into the anchor map's frame and fused per marker id.  The tables are one allocation made on first use (merge_alloc); rec is the

@@ -15,6 +15,7 @@
 #include "ekf.h"
 #include "ekf_dev.h"
 #include "ekf_fleet_slam.h"
+#include "ekf_slam_gate.h"
 #include <cmath>
 #include <algorithm>
 #include <type_traits>
@@ -452,12 +453,15 @@ static __global__ __launch_bounds__(256) void k_ekf_gather(Src S) {
 // where Sv_li = V_l H_i^T and Sw_il = H_i W_l are the 3x3 blocks of H Sigma0 H^T taken from rows / columns.
 // a template on k_ekf_small's state source only so that each instantiation has a callee of its own: shared by two kernels, the inliner
 // treated it differently and k_ekf_small<EkfSingle> no longer compiled to the instructions of the former k_ekf_small
-template <class Src>
-static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 2*9*kMarkerMax + 9*kMarkerMax + 9 doubles of LDS */) {
+// Gated (G = SlamGate, ekf_slam_gate.h): thread 0 judges correction i where it forms S_i^-1; a rejected one keeps gamma column block i = 0
+// (as initialised) and is left out of g, which is the sweep without it.
+template <class Src, class G>
+static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 3*9*kMarkerMax + 16 + kMarkerMax doubles of LDS */, const G& gate) {
     double* sC = scratch;
     double* sD = scratch + kMarkerMax * 9;
     double* sBeta = scratch + 2 * kMarkerMax * 9;
     double* sSinv = scratch + 3 * kMarkerMax * 9;
+    double* sRejected = scratch + 3 * kMarkerMax * 9 + 16;   // gated: per correction, 1.0 = rejected
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = *E.d_m;
     const int n3 = 3 * m;
@@ -525,13 +529,17 @@ static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >
                     S[a * 3 + b] = s + (a == b ? u.r[a] : 0.0);
                 }
             inv3_pp(S, sSinv);
+            if constexpr (G::kOn) sRejected[i] = 1.0 - slam_gate_verdict(gate, sSinv, u.ze[0], u.ze[1], u.ze[2], i);
         }
         __syncthreads();
+        bool rejected = false;
+        if constexpr (G::kOn) rejected = sRejected[i] != 0.0;           // uniform
         // (f) gamma column block i = beta_.i S_i^-1
-        for (int p = tid; p < 3 * w3; p += nt) {
-            const int r = p / 3, b = p - 3 * r;
-            ga[(size_t)r * n3 + 3 * i + b] = sBeta[r * 3] * sSinv[b] + sBeta[r * 3 + 1] * sSinv[3 + b] + sBeta[r * 3 + 2] * sSinv[6 + b];
-        }
+        if (!rejected)
+            for (int p = tid; p < 3 * w3; p += nt) {
+                const int r = p / 3, b = p - 3 * r;
+                ga[(size_t)r * n3 + 3 * i + b] = sBeta[r * 3] * sSinv[b] + sBeta[r * 3 + 1] * sSinv[3 + b] + sBeta[r * 3 + 2] * sSinv[6 + b];
+            }
         __syncthreads();
     }
     // G = gamma * alpha ; g = gamma * ze
@@ -543,7 +551,10 @@ static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >
     }
     for (int r = tid; r < n3; r += nt) {
         double s = 0;
-        for (int q = r / 3 * 3; q < n3; q++) s += ga[(size_t)r * n3 + q] * E.d_upd[q / 3].ze[q % 3];
+        for (int q = r / 3 * 3; q < n3; q++) {
+            if constexpr (G::kOn) { if (sRejected[q / 3] != 0.0) continue; }       // its gamma is zero, its ze may be NaN
+            s += ga[(size_t)r * n3 + q] * E.d_upd[q / 3].ze[q % 3];
+        }
         E.d_g[r] = s;
     }
 }
@@ -569,8 +580,10 @@ __device__ __forceinline__ void inv3_cof(const double* P, int n3, double* o) {  
     o[6] = C * id; o[7] = (b * g - a * h) * id; o[8] = (a * e - b * d) * id;
 }
 
-template <class Src>
-static __global__ __launch_bounds__(768) void k_ekf_small(Src S) {
+template <class Src, class G = NoSlamGate>
+static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
+    const Src& S = arg;
+    const G& gate = arg;
     const EkfState E = S.state();
     __shared__ double sA0[kSmallMax * kSmallMax];     // ping
     __shared__ double sA1[kSmallMax * kSmallMax];     // pong
@@ -581,7 +594,7 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Src S) {
     const int ld = E.ld;
     const int tc = tid % kSmallMax, tr = tid / kSmallMax;     // column, row group (0..7); rows r = tr + 8*i
     if (n3 > kSmallMax) {                              // uniform branch
-        ekf_small_general<Src>(E, sA0);
+        ekf_small_general<Src, G>(E, sA0, gate);
     } else if (m > 0) {
         // A[(3i+a)][(3j+b)] = (V_i H_j^T)[a][b] + delta_ij R_i[a][b]   (aruco_slam.cpp:146: (Gx*sigma_)*Gx^T + Rk)
         if (tc < n3) {
@@ -614,7 +627,26 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Src S) {
         double* nxt = sA1;
         for (int ib = 0; ib < m; ib++) {
             const int k0 = 3 * ib;
-            if (tc < n3) {
+            bool rejected = false;
+            if constexpr (G::kOn) {
+                // every thread forms S_i^-1 here, so every thread reaches the same verdict from the same LDS words; thread 0 leaves it
+                double Pg[9];
+                inv3_cof(cur + k0 * n3 + k0, n3, Pg);
+                if (tid == 0) rejected = slam_gate_verdict(gate, Pg, sZe[k0], sZe[k0 + 1], sZe[k0 + 2], ib) == 0.0;
+                else rejected = slam_gate_rejects(gate, slam_gate_d2(Pg, sZe[k0], sZe[k0 + 1], sZe[k0 + 2]));
+            }
+            if (rejected) {
+                // the pivot is not eliminated: its rows and columns become zero, the rest is copied; nu_i = 0 (its ze may be NaN)
+                if (tc < n3) {
+                    const bool cin = tc >= k0 && tc < k0 + 3;
+#pragma unroll
+                    for (int i = 0; i < SMR; i++) {
+                        const int r = tr + 8 * i;
+                        if (r < n3) nxt[r * n3 + tc] = (cin || (r >= k0 && r < k0 + 3)) ? 0.0 : cur[r * n3 + tc];
+                    }
+                }
+                if (tid < 3) sNu[k0 + tid] = 0.0;
+            } else if (tc < n3) {
                 double Pi[9];
                 inv3_cof(cur + k0 * n3 + k0, n3, Pi);                         // S_i^-1 (every thread, from LDS broadcast reads)
                 const bool cin = tc >= k0 && tc < k0 + 3;
@@ -734,12 +766,14 @@ constexpr int kFastN3 = 3 * kFastM;      // 72
 constexpr int MIDT = 576;                // kFastM x kFastM: one thread per 3x3 block of the innovation matrix
 
 // <= 128 VGPRs (4 waves per SIMD) so that the workgroup always finds room beside the persistent detection waves of the other stream
-template <class Src>
-static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
+template <class Src, class G = NoSlamGate>
+static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G> arg) {
+    const Src& S = arg;
+    const G& gate = arg;
     const EkfState E = S.state();
     __shared__ __align__(16) double sCol[2][kFastM][10];   // pivot column blocks (bi, ib); rows padded to 80 B for 128-bit LDS reads
     __shared__ __align__(16) double sRow[2][kFastM][10];   // pivot row blocks (ib, bj), unscaled
-    __shared__ __align__(16) double sPinv[2][10];          // S_ib^-1 (from the owner of the pivot block, one step ahead)
+    __shared__ __align__(16) double sPinv[2][10];          // S_ib^-1 (from the owner of the pivot block, one step ahead); gated: [9] = its verdict, 0.0 = rejected
     __shared__ double sZe[kFastN3], sNu[kFastN3];
     __shared__ double sPart[kFastM][kFastM][3];
     const int tid = threadIdx.x;
@@ -819,6 +853,7 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
             double Pn[9];
             inv3_reg(A, Pn);
             for (int k = 0; k < 9; k++) sPinv[0][k] = Pn[k];
+            if constexpr (G::kOn) sPinv[0][9] = slam_gate_verdict(gate, Pn, sUpd[0].ze[0], sUpd[0].ze[1], sUpd[0].ze[2], 0);
         }
     }
     __syncthreads();
@@ -829,7 +864,17 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
     // Y_bj = S^-1 R_bj (27 flops, redundant down each column) instead of waiting for the pivot row to do it.
     for (int ib = 0; ib < m; ib++) {
         const int cb = ib & 1;
-        if (act) {
+        bool rejected = false;
+        if constexpr (G::kOn) rejected = sPinv[cb][9] == 0.0;               // uniform; behind the barrier that published S_ib^-1
+        if (act && rejected) {
+            // the pivot is not eliminated (ekf_slam_gate.h): its block row and column become zero, nu_ib = 0 (its ze may be NaN)
+            if (bi == ib || bj == ib) {
+#pragma unroll
+                for (int k = 0; k < 9; k++) A[k] = 0.0;
+            }
+            if (bi == ib && bj == ib) sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;
+        }
+        if (act && !rejected) {
             double Pi[9], Y[9];
 #pragma unroll
             for (int k = 0; k < 9; k++) Pi[k] = sPinv[cb][k];
@@ -864,6 +909,8 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
                     for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[a * 3] * z0 + A[a * 3 + 1] * z1 + A[a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
                 }
             }
+        }
+        if (act) {
             // what step ib + 1 needs
             if (bi == ib + 1) { for (int k = 0; k < 9; k++) sRow[cb ^ 1][bj][k] = A[k]; }
             if (bj == ib + 1) { for (int k = 0; k < 9; k++) sCol[cb ^ 1][bi][k] = A[k]; }
@@ -872,6 +919,7 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Src S) {
                 inv3_reg(A, Pn);
 #pragma unroll
                 for (int k = 0; k < 9; k++) sPinv[cb ^ 1][k] = Pn[k];
+                if constexpr (G::kOn) sPinv[cb ^ 1][9] = slam_gate_verdict(gate, Pn, sZe[3 * ib + 3], sZe[3 * ib + 4], sZe[3 * ib + 5], ib + 1);
             }
         }
         __syncthreads();
@@ -1038,14 +1086,21 @@ constexpr int M64T = 512;                // threads of k_ekf_mid64: 8 wavefronts
 constexpr int M64B = (kMidM * kMidM + M64T - 1) / M64T;   // 3x3 blocks per thread (8)
 
 // The fast chain's Gauss-Jordan with up to M64B blocks per thread, dense block index e = tid + M64T k -> (e / m, e % m).
-template <class Src>
-static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
+template <class Src, class G = NoSlamGate>
+static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
+    const Src& S = arg;
+    const G& gate = arg;
     const EkfState E = S.state();
     __shared__ __align__(16) double sCol[2][kMidM][10];
     __shared__ __align__(16) double sY[kMidM][10];
     __shared__ double sPinv[9];
     __shared__ double sZe[3 * kMidM], sNu[3 * kMidM];
     __shared__ double sPart[kMidM][kMidM][3];
+    double* sVerdict = nullptr;                        // gated: the verdict on the pivot whose inverse sPinv holds, 0.0 = rejected
+    if constexpr (G::kOn) {
+        __shared__ double sGateVerdict[1];
+        sVerdict = sGateVerdict;
+    }
     const int tid = threadIdx.x;
     const int m = *E.d_m;
     const int ld = E.ld;
@@ -1110,6 +1165,7 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
                 double Pn[9];
                 inv3_reg(A[k], Pn);
                 for (int q = 0; q < 9; q++) sPinv[q] = Pn[q];
+                if constexpr (G::kOn) *sVerdict = slam_gate_verdict(gate, Pn, ui.ze[0], ui.ze[1], ui.ze[2], 0);
             }
         }
     }
@@ -1117,6 +1173,8 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
     // block Gauss-Jordan with 3x3 pivots (see k_ekf_mid)
     for (int ib = 0; ib < m; ib++) {
         const int cb = ib & 1;
+        bool rejected = false;
+        if constexpr (G::kOn) rejected = *sVerdict == 0.0;   // uniform; read before this step's first barrier, replaced behind it
         // phase 1: the pivot row: Y_bj = S_ib^-1 * A(ib, bj)  (S_ib^-1 itself at bj == ib); the pivot column blocks are zeroed
 #pragma unroll
         for (int k = 0; k < M64B; k++) {
@@ -1126,7 +1184,12 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
                     double Pi[9];
 #pragma unroll
                     for (int q = 0; q < 9; q++) Pi[q] = sPinv[q];
-                    if (bj == ib) {
+                    if (rejected) {
+                        // the pivot is not eliminated (ekf_slam_gate.h): its block row becomes zero (its column below), nu_ib = 0
+#pragma unroll
+                        for (int q = 0; q < 9; q++) A[k][q] = 0.0;
+                        if (bj == ib) sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;   // its ze may be NaN
+                    } else if (bj == ib) {
 #pragma unroll
                         for (int q = 0; q < 9; q++) A[k][q] = Pi[q];
                     } else {
@@ -1151,18 +1214,20 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
             if (bij[k] >= 0) {
                 const int bi = bij[k] >> 8, bj = bij[k] & 255;
                 if (bi != ib) {
-                    double F[9], Y[9];
+                    if (!rejected) {                   // (a rejected pivot changes no other block)
+                        double F[9], Y[9];
 #pragma unroll
-                    for (int q = 0; q < 9; q++) { F[q] = sCol[cb][bi][q]; Y[q] = sY[bj][q]; }
+                        for (int q = 0; q < 9; q++) { F[q] = sCol[cb][bi][q]; Y[q] = sY[bj][q]; }
 #pragma unroll
-                    for (int i = 0; i < 3; i++)
+                        for (int i = 0; i < 3; i++)
 #pragma unroll
-                        for (int j = 0; j < 3; j++)
-                            A[k][i * 3 + j] = fma(-F[i * 3 + 2], Y[6 + j], fma(-F[i * 3 + 1], Y[3 + j], fma(-F[i * 3], Y[j], A[k][i * 3 + j])));
-                    if (bj == ib && bi > ib) {
-                        const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
+                            for (int j = 0; j < 3; j++)
+                                A[k][i * 3 + j] = fma(-F[i * 3 + 2], Y[6 + j], fma(-F[i * 3 + 1], Y[3 + j], fma(-F[i * 3], Y[j], A[k][i * 3 + j])));
+                        if (bj == ib && bi > ib) {
+                            const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
 #pragma unroll
-                        for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[k][a * 3] * z0 + A[k][a * 3 + 1] * z1 + A[k][a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                            for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[k][a * 3] * z0 + A[k][a * 3 + 1] * z1 + A[k][a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                        }
                     }
                     if (bj == ib + 1) { for (int q = 0; q < 9; q++) sCol[cb ^ 1][bi][q] = A[k][q]; }
                     if (bi == ib + 1 && bj == ib + 1) {
@@ -1170,6 +1235,7 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Src S) {
                         inv3_reg(A[k], Pn);
 #pragma unroll
                         for (int q = 0; q < 9; q++) sPinv[q] = Pn[q];
+                        if constexpr (G::kOn) *sVerdict = slam_gate_verdict(gate, Pn, sZe[3 * ib + 3], sZe[3 * ib + 4], sZe[3 * ib + 5], ib + 1);
                     }
                 }
             }
@@ -1397,15 +1463,21 @@ void launch_ekf_plan(hipStream_t st, const EkfState& E, const SlamParams& sp, do
 void launch_ekf_gather(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_gather<EkfSingle>, dim3((E.ld + 255) / 256, 32), dim3(256), 0, st, EkfSingle{E});
 }
-void launch_ekf_small(hipStream_t st, const EkfState& E) {
-    hipLaunchKernelGGL(k_ekf_small<EkfSingle>, dim3(1), dim3(SMT), 0, st, EkfSingle{E});
+static SlamGate slam_gate_of(const SlamGateArg& a) { return SlamGate{a.g.gate_d2, a.verdicts}; }
+void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
+    if (gate) hipLaunchKernelGGL((k_ekf_small<EkfSingle, SlamGate>), dim3(1), dim3(SMT), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_small<EkfSingle, NoSlamGate>), dim3(1), dim3(SMT), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
+}
+void launch_ekf_gate_finish(hipStream_t st, const EkfState& E, const SlamGateArg& gate, int slot) {
+    hipLaunchKernelGGL(k_ekf_gate_finish<EkfSingle>, dim3(1), dim3(kMarkerMax), 0, st, EkfSingle{E}, slam_gate_of(gate), gate.g, slot);
 }
 void launch_ekf_T(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_T<EkfSingle>, dim3((E.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR), dim3(256), 0, st, EkfSingle{E});
 }
-void launch_ekf_mid(hipStream_t st, const EkfState& E) {
+void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
     const int ncg = (E.ld + MIDT - 1) / MIDT;
-    hipLaunchKernelGGL(k_ekf_mid<EkfSingle>, dim3(1 + ncg * 12), dim3(MIDT), 0, st, EkfSingle{E});
+    if (gate) hipLaunchKernelGGL((k_ekf_mid<EkfSingle, SlamGate>), dim3(1 + ncg * 12), dim3(MIDT), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_mid<EkfSingle, NoSlamGate>), dim3(1 + ncg * 12), dim3(MIDT), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
 }
 void launch_ekf_apply(hipStream_t st, const EkfState& E) {
     const int t = (E.ld + 63) / 64;
@@ -1413,9 +1485,10 @@ void launch_ekf_apply(hipStream_t st, const EkfState& E) {
 }
 int ekf_fast_max_updates() { return kFastM; }
 int ekf_mid_max_updates() { return kMidM; }
-void launch_ekf_mid64(hipStream_t st, const EkfState& E) {
+void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
     const int ncg = (E.ld + M64T - 1) / M64T;
-    hipLaunchKernelGGL(k_ekf_mid64<EkfSingle>, dim3(1 + ncg * 16), dim3(M64T), 0, st, EkfSingle{E});
+    if (gate) hipLaunchKernelGGL((k_ekf_mid64<EkfSingle, SlamGate>), dim3(1 + ncg * 16), dim3(M64T), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_mid64<EkfSingle, NoSlamGate>), dim3(1 + ncg * 16), dim3(M64T), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
 }
 // the narrowest tile whose workgroups all fit on the device at once (256 CUs x 4); N_max stands in for the current N
 static bool update_tile4(const EkfState& E) {
@@ -1496,23 +1569,29 @@ void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, 
 void launch_ekf_gather(hipStream_t st, const FleetRound& R) {
     hipLaunchKernelGGL(k_ekf_gather<EkfFleet>, dim3((R.F.base.ld + 255) / 256, 32, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_small(hipStream_t st, const FleetRound& R) {
-    hipLaunchKernelGGL(k_ekf_small<EkfFleet>, dim3(1, 1, R.n), dim3(SMT), 0, st, fleet_source(R));
+void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
+    if (gate) hipLaunchKernelGGL((k_ekf_small<EkfFleet, SlamGate>), dim3(1, 1, R.n), dim3(SMT), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_small<EkfFleet, NoSlamGate>), dim3(1, 1, R.n), dim3(SMT), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
+}
+void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateArg& gate, int) {
+    hipLaunchKernelGGL(k_ekf_gate_finish<EkfFleet>, dim3(1, 1, R.n), dim3(kMarkerMax), 0, st, fleet_source(R), slam_gate_of(gate), gate.g, 0);
 }
 void launch_ekf_T(hipStream_t st, const FleetRound& R) {
     hipLaunchKernelGGL(k_ekf_T<EkfFleet>, dim3((R.F.base.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_mid(hipStream_t st, const FleetRound& R) {
+void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
     const int ncg = (R.F.base.ld + MIDT - 1) / MIDT;
-    hipLaunchKernelGGL(k_ekf_mid<EkfFleet>, dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, fleet_source(R));
+    if (gate) hipLaunchKernelGGL((k_ekf_mid<EkfFleet, SlamGate>), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_mid<EkfFleet, NoSlamGate>), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
 }
 void launch_ekf_apply(hipStream_t st, const FleetRound& R) {
     const int t = (R.F.base.ld + 63) / 64;
     hipLaunchKernelGGL(k_ekf_apply<EkfFleet>, dim3(t, t, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_mid64(hipStream_t st, const FleetRound& R) {
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
     const int ncg = (R.F.base.ld + M64T - 1) / M64T;
-    hipLaunchKernelGGL(k_ekf_mid64<EkfFleet>, dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, fleet_source(R));
+    if (gate) hipLaunchKernelGGL((k_ekf_mid64<EkfFleet, SlamGate>), dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
+    else hipLaunchKernelGGL((k_ekf_mid64<EkfFleet, NoSlamGate>), dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
 }
 void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
     const EkfState& E = R.F.base;                  // the single filter's tile choice: the same grid per robot

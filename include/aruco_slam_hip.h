@@ -132,7 +132,7 @@ int aslam_set_state(aslam_ctx* ctx, int N, const double* mu, const double* sigma
 int aslam_get_detections(aslam_ctx* ctx, int* M, int* ids, float* corners, double* rvecs, double* tvecs);
 /* the observations popped from obs_ in pop order (aruco_slam.cpp:92-95) for the last frame: id, landmark index
  * at push time (-1 new), action (0 augment, 1 update, 2 stationary no-op, 3 update rejected by the innovation gate of a localizing
- * filter), (x,y,theta), diag(R). */
+ * filter or by the SLAM gate), (x,y,theta), diag(R). */
 int aslam_get_observations(aslam_ctx* ctx, int* n, int* ids, int* idx, int* action, double* xyth, double* Rdiag);
 /* aruco_id_map inverted: ids[i] = marker id of landmark index i (aruco_slam.h:164) */
 int aslam_get_landmark_ids(aslam_ctx* ctx, int* L, int* ids);
@@ -475,8 +475,9 @@ int aslam_fleet_relocalize(aslam_ctx* ctx, int first, int count, const int* robo
  * with a consequence, and every filter keeps a record from which a caller sees that it is lost and should be relocalized.
  * The gate is off by default, and with it off every kernel, call and result is what it is without this section.  It can be set in
  * any mode and persists, but takes effect only in the localization steps of the single localizing filter (aslam_localize_begin;
- * single-camera and rig steps) and of a localization fleet (aslam_fleet_begin).  SLAM, rig SLAM and fleet SLAM ignore it: their
- * chains compose a frame's corrections into one factorisation, where a per-correction gate has no place.
+ * single-camera and rig steps) and of a localization fleet (aslam_fleet_begin).  SLAM, rig SLAM and fleet SLAM ignore it: they have
+ * a switch of their own, aslam_set_slam_gate below.  (Their per-frame chains compose a frame's corrections into one factorisation,
+ * but each pivot block of that factorisation is one correction's S, so a per-correction gate does fit that form.)
  * With a gate set those steps run a gated variant of the chain.  Everything up to the chain is unchanged: the predict, the lookup of
  * ids, the pop order, the "stationary" test against the previous step's list and every correction's H, ze and R from the
  * frame-start pose.  Then for each prepared correction (action 1), in pop order:
@@ -519,7 +520,8 @@ int aslam_get_innovation_gate(aslam_ctx* ctx, int* on, aslam_gate_params* out);
 typedef struct { int attempted, accepted, rejected, ref_flagged; double nis_sum, d2_max; int worst_id, pad; } aslam_slot_health;
 /* The getters wait for the submitted work as aslam_get_slot_ekf_stats does and refuse with ASLAM_E_STATE while no gate is set or in
    a mode the gate does not work in (the slot records: localization and fleet localization; aslam_get_track_health: localization;
-   aslam_fleet_get_health: fleet localization).
+   aslam_fleet_get_health: fleet localization).  In the SLAM modes they read the SLAM gate's records while aslam_set_slam_gate is
+   in force (the section below).
    aslam_get_slot_health: EKF slots [first, first + count) within [0, 2 max_batch) - a frame slot for single-camera and fleet calls,
    max_batch + step for a rig step (step as in aslam_get_rig_step_ekf_stats). */
 int aslam_get_slot_health(aslam_ctx* ctx, int first, int count, aslam_slot_health* out);
@@ -527,6 +529,50 @@ typedef struct { int frames, accepted_total, rejected_total, bad_streak, lost, p
 int aslam_get_track_health(aslam_ctx* ctx, aslam_track_health* out);                          /* the single localizing filter */
 /* *n_robots = robots of the fleet; the records of the first min(max, *n_robots) robots go to out */
 int aslam_fleet_get_health(aslam_ctx* ctx, int max, int* n_robots, aslam_track_health* out);  /* a localization fleet */
+
+/* ---- innovation gate for SLAM, rig SLAM and fleet SLAM ------------------------------------------------------------
+ * A filter that is building a map fuses every known-id sighting it is handed; the reference computes its outlier test in exactly this
+ * place (aruco_slam.cpp:156-175), only logs it, and leaves `// TODO: Remove map point?` with a commented-out `continue`.  One misread
+ * id or one moved marker is then written into mu and Sigma of the whole map.  This switch is the reference's sequential filter with
+ * that `continue` in force, judged by d2 instead of ||ze|| >= 1.
+ * It is a switch of its own, separate from aslam_set_innovation_gate: same struct, same defaults, same ASLAM_E_INVALID cases.  It can
+ * be set in any mode and persists; it takes effect in SLAM, rig SLAM (aslam_set_camera_rig, more than one camera) and fleet SLAM
+ * (aslam_fleet_slam_begin) and has no effect in the localization modes.  Off by default, and with it off every launch, kernel and
+ * result is what it is without this section.
+ * With the gate set a step is unchanged up to the solve: predict, id lookup, pop order, augments, the "stationary" test, and every
+ * prepared correction's ze and Jacobian at the frozen pre-frame mean.  Augments (new ids) and stationary no-ops are neither attempted
+ * nor gated.  Then per prepared correction (action 1), in pop order:
+ * 1. S = H Sigma H^T + R and S^-1 as the chain forms them (the pivot block of its block Gauss-Jordan sweep); Sigma here follows the
+ *    corrections ACCEPTED before this one in the frame.
+ * 2. d2 = ze^T S^-1 ze with the frozen-mean innovation ze, the one the reference would test.
+ * 3. The correction is rejected iff gate_d2 is finite and !(d2 <= gate_d2); a NaN d2 therefore rejects.
+ * 4. A rejected correction changes nothing in mu or Sigma: its pivot is not eliminated, which is exactly the frame without it.
+ * 5. With gate_d2 = +inf (monitor only) mu, Sigma, ids, last-observed list, pop list and EKF stats are bit for bit those of the same
+ *    context with the gate off and windows off.
+ * 6. ref_flagged counts ||ze||_2 >= 1 only.  The reference's other half, K.norm() >= 10, needs the full N x 3 gain, which these
+ *    chains never form.
+ * A rejected observation is left out of the list the step leaves as last_observed_marker_ (so the same sighting in the next frame is
+ * judged again, not "stationary"), is reported by aslam_get_observations with action 3, and is not counted in entry [2] of
+ * aslam_get_slot_ekf_stats.
+ * Records: an aslam_slot_health per EKF slot (a frame slot; max_batch + step for a rig step) and one aslam_track_health per filter
+ * (the single filter's; robot r's in fleet SLAM), with the fields and the integer streak rule of the section above, carried across
+ * slots, rounds and calls on the device.  Every seat of a SLAM filter clears its track record: aslam_set_state, aslam_load_state,
+ * aslam_localize_end and aslam_fleet_end (the single filter starts anew), aslam_fleet_slam_begin (every robot), aslam_fleet_set_state,
+ * aslam_remove_landmarks and aslam_fleet_remove_landmarks (the robots named).  `lost` only reports.
+ * aslam_get_slot_health, aslam_get_track_health and aslam_fleet_get_health are readable in the SLAM modes exactly while the SLAM gate
+ * is set (slot records: SLAM, rig SLAM, fleet SLAM; aslam_get_track_health: SLAM and rig SLAM; aslam_fleet_get_health: fleet SLAM);
+ * with only the innovation gate set they refuse there with ASLAM_E_STATE.  The record storage is the section above's, made by
+ * whichever setter runs first.
+ * Windows: while the SLAM gate is set aslam_run_staged takes the per-frame path (what ASLAM_NO_WINDOWS selects), and setting or clearing
+ * the gate first enqueues a batch still pending.  The window planner runs the "stationary" test on the host, one call behind, from
+ * a mirror of the last-observed list; a rejection on the device changes that list.  Gating inside the window chain is the follow-up
+ * this leaves open.
+ * Not covered: a misread id that is NEW to the map is an augment and enters as a landmark (aslam_remove_landmarks stays the remedy);
+ * nothing tunes gate_d2 or R.  No floating-point atomics, every sum in pop order: a robot's result does not depend on the other
+ * robots of the call. */
+int aslam_set_slam_gate(aslam_ctx* ctx, const aslam_gate_params* params /* NULL: off */);
+/* *on = 1 while the SLAM gate is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
+int aslam_get_slam_gate(aslam_ctx* ctx, int* on, aslam_gate_params* out);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);

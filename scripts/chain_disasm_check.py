@@ -51,10 +51,15 @@ def compile_ekf(csrc, out, src="ekf.hip"):
     return funcs, res
 
 
-def symbol(names, kernel, inst=None):
+GATED = "8SlamGateE"                     # mangled gate policy of a gated solve kernel; the ungated one has NoSlamGate or none
+SOLVE = ["k_ekf_mid", "k_ekf_mid64", "k_ekf_small"]
+
+
+def symbol(names, kernel, inst=None, gated=False):
     base, _, wct = kernel.partition("<")
     for n in names:
-        if re.search(r"\d" + re.escape(base) + r"(I|E)", n) and (not wct or f"Li{wct[0]}E" in n) and (inst is None or inst in n):
+        if re.search(r"\d" + re.escape(base) + r"(I|E)", n) and (not wct or f"Li{wct[0]}E" in n) and (inst is None or inst in n) \
+                and (GATED in n) == gated:
             return n
     raise KeyError(kernel)
 
@@ -74,6 +79,16 @@ def main():
         row = lambda r, n: " / ".join(r[n][x] for x in RES) + f" ({len((fa if r is ra else fb)[n])} instr.)"
         print(f"| `{k}` | {row(ra, a)} | {row(rb, s)} | {row(rb, f)} | {'yes' if same else 'NO'} |")
     print("columns: " + " / ".join(RES))
+    try:                                                 # the gated instantiations, if NEW has them
+        rows = [(f"`{k}` gated", symbol(fb, k, "EkfSingle", True), symbol(fb, k, "EkfFleet", True)) for k in SOLVE]
+        rows.append(("`k_ekf_gate_finish`", symbol(fb, "k_ekf_gate_finish", "EkfSingle", True), symbol(fb, "k_ekf_gate_finish", "EkfFleet", True)))
+    except KeyError:
+        rows = []
+    if rows:
+        print("\n| kernel | EkfSingle | EkfFleet |\n|---|---|---|")
+        for name, s_, f_ in rows:
+            cell = lambda n: " / ".join(rb[n][x] for x in RES) + f" ({len(fb[n])} instr.)"
+            print(f"| {name} | {cell(s_)} | {cell(f_)} |")
     sys.exit(0 if ok else 1)
 
 
