@@ -47,6 +47,7 @@ __device__ __forceinline__ int win_count(const unsigned long long* w, unsigned e
 __device__ __forceinline__ double aslam_wave_bcast(double v, int src) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
 }
+__device__ __forceinline__ int aslam_wave_bcast(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 #endif
 __device__ __forceinline__ double aslam_rcp_estimate(double x) { return ASLAM_RCP_ESTIMATE(x); }
 

@@ -27,8 +27,9 @@
 //             A separate "prepare" wave (lane = column) runs one step AHEAD: the workers publish the three landmark rows of step
 //             j + 2 as they stand after step j, the prepare wave applies step j + 1's correction to them and to the pose rows it
 //             carries in its own registers, forms c, S, S^-1, Kt and hands the operands to the workers: one barrier per step.  The
-//             workers log -Kt (the A operand they read) and worker wave 0 the header the prepare wave leaves in LDS (S^-1, ze, the
-//             Jacobian scalars); in the one-launch window a logger wave of its own copies both from LDS to the log;
+//             workers log -Kt (the A operand they read) and worker wave 0 the header, composed from what the prepare wave leaves in
+//             LDS (S^-1 per step; ze and the Jacobian scalars once per frame); in the one-launch window a logger wave of its own
+//             copies both from LDS to the log;
 //     replay  (SP / 8 workgroups) replays the log of piece i - 1, each on its own 8 columns of Lambda (all rows; in LDS) and its
 //             part of psi, and logs t and u;
 //     Psi     (T workgroups) adds the t^T u of piece i - 2 to Psi on the matrix cores.
@@ -170,16 +171,39 @@ template <int T, bool ONE> struct WinChainLds {
     double sA[2][4][SPP];                  // a step's A operand rows  Aop[k][row]   (P += Aop^T Bop)
     double sB[2][4][SPP];                  // ... and B operand rows   Bop[k][column]
     double sPub[2][3][SPP];                // the landmark rows of the step after next
-    double sHdr[2][kWinHdr];               // a step's log header, from the prepare wave to the wave that stores it (logger; pieces: worker wave 0)
+    double sHdr[2][kWinHdr];               // what a step newly brings to its log header (correction: S^-1; predict: its six values), from the
+                                           // prepare wave to the wave that stores the header (logger; pieces: worker wave 0)
+    double sRec[2][5][64];                 // a frame's header records (ze0, ze1, ze2, g02, g12 of correction a), by frame parity: see win_header_entry
 #ifdef ASLAM_WIN_POSE_CHECK
     double sDbg[2][3][SPP];                // the accumulators' pose rows, to compare with the prepare wave's own
 #endif
     double sMu[SPP];                       // prepare wave's scratch: mu_S by position
     int sS[SP];
     int sOff[KMAX + 1];
-    unsigned char sPos[NSMAX], sIdx[NSMAX], sFrm[NSMAX];   // per step: landmark position (255 = predict), correction index, frame
-    unsigned char sDet[NSMAX];             // ... and the correction's detection in its frame's observation list
+    // per step: landmark position (255 = predict) and correction index, for the workers and the wave that stores the header (the
+    // prepare wave counts its steps in scalar registers); the correction's detection in its frame's observation list
+    unsigned char sPos[NSMAX], sIdx[NSMAX];
+    unsigned char sDet[NSMAX];
+    // what the block gained over the size the launch's LDS claim was measured at (launch_step_kernel): sRec, less a per-step frame table
+    static constexpr int kGrown = 2 * 5 * 64 * (int)sizeof(double) - NSMAX;
 };
+// Entry `lane` (< kWinHdr) of step j's log header, composed by the wave that stores it.  A predict's header is what the prepare
+// wave left in sHdr.  A correction's is S^-1 from sHdr, type and position from the step tables, and ze, g02, g12 from the records
+// of the step's frame: the prepare wave writes them ONCE per frame, at the frame's predict, into sRec[frame parity].  Two parities
+// suffice: the prepare wave prepares step j + 1 while step j is stored, and the step in front of frame k's predict belongs to
+// frame k - 1 whatever the frames fuse (a frame without corrections is a lone predict, which reads no record).
+template <class LDS> __device__ __forceinline__ double win_header_entry(const LDS& L, int j, int cb, int fpar, int lane) {
+    double v = L.sHdr[cb][lane];
+    const int pos = L.sPos[j];
+    if (pos != 255) {
+        const int a = L.sIdx[j];
+        const int q = lane >= WH_ZE && lane < WH_ZE + 3 ? lane - WH_ZE : lane == WH_G02 ? 3 : lane == WH_G12 ? 4 : -1;
+        if (q >= 0) v = L.sRec[fpar][q][a];
+        if (lane == WH_TYPE) v = 1.0;
+        if (lane == WH_POS) v = (double)pos;
+    }
+    return v;
+}
 template <int T, int RW, bool ONE>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
@@ -187,7 +211,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
     auto& sA = L.sA; auto& sB = L.sB; auto& sPub = L.sPub; auto& sMu = L.sMu; auto& sS = L.sS; auto& sOff = L.sOff;
-    auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sFrm = L.sFrm; auto& sDet = L.sDet;
+    auto& sPos = L.sPos; auto& sIdx = L.sIdx; auto& sDet = L.sDet;
     if (threadIdx.x >= NT) return;                                  // (the launch's block is sized for its widest role)
     const int tid = threadIdx.x;
     const int nS = wd.nS, s = 3 + 3 * nS;
@@ -230,12 +254,12 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         __syncthreads();
         if (tid < wd.K) {
             const int o = sOff[tid], m = cnt - 1;
-            sPos[o] = 255; sIdx[o] = 0; sFrm[o] = (unsigned char)tid; sDet[o] = 0;
+            sPos[o] = 255; sIdx[o] = 0; sDet[o] = 0;
 #pragma unroll
             for (int a = 0; a < 63; a++)
                 if (a < m) {
                     sPos[o + 1 + a] = (unsigned char)(cp[a >> 2] >> (8 * (a & 3))); sDet[o + 1 + a] = (unsigned char)(cd[a >> 2] >> (8 * (a & 3)));
-                    sIdx[o + 1 + a] = (unsigned char)a; sFrm[o + 1 + a] = (unsigned char)tid;
+                    sIdx[o + 1 + a] = (unsigned char)a;
                 }
         }
         __syncthreads();
@@ -264,7 +288,6 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 sPos[st] = a == 0 ? 255 : fr.cpos[a - 1];
                 sIdx[st] = a == 0 ? 0 : (unsigned char)(a - 1);
                 sDet[st] = a == 0 ? 0 : fr.cdet[a - 1];
-                sFrm[st] = (unsigned char)k;
             }
         }
         __syncthreads();
@@ -303,6 +326,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
         long long stamp_acc[4] = {0, 0, 0, 0}, stamp_last = clock64();
 #endif
+        int fpar = 1;                                              // (pieces, wave 0) parity of step j's frame: the first predict makes it 0
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
             if (j >= 0) {
@@ -324,7 +348,10 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     // pieces: the step's log rows, -Kt (predict: its rows 0..2).  One launch: the logger wave stores the log
                     if (!ONE && lk < 3) log[lk * SP + 16 * (wave * RW + rr) + li] = a;
                 }
-                if (!ONE && wave == 0 && lane < kWinHdr) log[3 * SP + lane] = L.sHdr[cb][lane];
+                if (!ONE && wave == 0) {
+                    if (sPos[j] == 255) fpar ^= 1;
+                    if (lane < kWinHdr) log[3 * SP + lane] = win_header_entry(L, j, cb, fpar, lane);
+                }
                 WSTAMP(2);
                 if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
 #ifdef ASLAM_WIN_POSE_CHECK
@@ -372,6 +399,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
         long long stamp_acc[2] = {0, 0}, stamp_last = clock64();
 #endif
+        int fpar = 1;                                              // parity of step j's frame: the first predict makes it 0
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
             if (j > kWinPubLag && j % kWinPubEvery == 0 && lane == 0) win_signal(E.d_win_sync, wd.epoch, j - kWinPubLag);
@@ -382,7 +410,8 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 for (int k = 0; k < 3; k++)
 #pragma unroll
                     for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, sA[cb][k][lane + 64 * c]);
-                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, L.sHdr[cb][lane]);
+                if (sPos[j] == 255) fpar ^= 1;
+                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, win_header_entry(L, j, cb, fpar, lane));
                 // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete
                 if ((j + 1) % kWinPubEvery == 0) win_vmcnt_lag<NC>();
             }
@@ -424,6 +453,10 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     // per-frame records, lane a = correction a of the frame (aruco_slam.cpp:119-143 at the frozen mean)
     double rze0 = 0, rze1 = 0, rze2 = 0, rR0 = 0, rR1 = 0, rR2 = 0, rg02 = 0, rg12 = 0;
     double cth = 1.0, sth = 0.0;
+    // Step control in wave-uniform (scalar) registers: the frame fk, its corrections fm and the next correction fa.  A step is
+    // a predict when the frame's corrections are exhausted (every piece and every window starts with a predict), and lane a keeps
+    // the position of correction a from the predict on (vpos): no step waits for a look-up in the step tables
+    int fk = -1, fm = 0, fa = 0, vpos = 0;
     bool prev_predict = false;
     bool dirty0 = false, dirty1 = false;                           // operand buffer 0 / 1 holds a predict's fourth depth row
     // the first frame's inputs
@@ -441,9 +474,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         WSTAMP(0);
         if (n < NS) {
             const int nb = n & 1, pb = j & 1;
-            const int pos = sPos[n];
-            const bool is_predict = pos == 255;
-            const int lrow = is_predict ? 0 : 3 + 3 * pos;         // first landmark row (a predict has none: copies of the pose rows)
+            const bool is_predict = fa == fm;
+            // first landmark row (a predict has none: copies of the pose rows)
+            const int lrow = is_predict ? 0 : 3 + 3 * ASLAM_WAVE_BCAST(vpos, fa & 63);
             double r[6][NC];
 #pragma unroll
             for (int c = 0; c < NC; c++) {
@@ -491,9 +524,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
                 n_pred++;
 #endif
-                const int k = sFrm[n];
+                const int k = ++fk;
                 const int slot = wd.first_slot + k;
-                const int fm = sOff[k + 1] - sOff[k] - 1;           // corrections of the frame
+                fm = ASLAM_WAVE_BCAST(sOff[k + 1] - sOff[k] - 1, 0); fa = 0;     // corrections of the frame
                 // ---- predict (aruco_slam.cpp:35-73) with the final mean of the previous frame ----
                 const double delta_sl = kl * (e_dt * e_wl), delta_sr = kr * (e_dt * e_wr);
                 const double delta_theta = (delta_sr - delta_sl) * inv2b;
@@ -537,7 +570,8 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 if (lane == 2) mu[0] = th;
                 // ---- the frame's records at the frozen mean (pose just predicted, landmarks as the previous frame left them) ----
                 if (lane < fm) {
-                    const int q = 3 + 3 * sPos[sOff[k] + 1 + lane];
+                    vpos = sPos[sOff[k] + 1 + lane];
+                    const int q = 3 + 3 * vpos;
                     const double mx = sMu[q], my = sMu[q + 1], mth = sMu[q + 2];
                     const double gdx = mx - np0, gdy = my - np1;
                     double gdth = mth - th;
@@ -548,6 +582,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     rze0 = nObs.x - zh0; rze1 = nObs.y - zh1; rze2 = z2;
                     rg02 = -gdx * sth + gdy * cth; rg12 = -gdx * cth - gdy * sth;
                     rR0 = nObs.r[0]; rR1 = nObs.r[1]; rR2 = nObs.r[2];
+                    // what of them the log header carries, for the wave that stores it
+                    double (&rec)[5][64] = L.sRec[k & 1];
+                    rec[0][lane] = rze0; rec[1][lane] = rze1; rec[2][lane] = rze2; rec[3][lane] = rg02; rec[4][lane] = rg12;
                 }
                 __builtin_amdgcn_wave_barrier();
                 WSTAMP(10);
@@ -567,7 +604,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 WSTAMP(2);
             } else {
                 // ---- correction a of the frame: c = H P, S = c H^T + R, Kt = S^-1 c ----
-                const int a = sIdx[n];
+                const int a = fa++;
                 const double ze0 = ASLAM_WAVE_BCAST(rze0, a), ze1 = ASLAM_WAVE_BCAST(rze1, a), ze2 = ASLAM_WAVE_BCAST(rze2, a);
                 const double R0 = ASLAM_WAVE_BCAST(rR0, a), R1 = ASLAM_WAVE_BCAST(rR1, a), R2 = ASLAM_WAVE_BCAST(rR2, a);
                 const double g02 = ASLAM_WAVE_BCAST(rg02, a), g12 = ASLAM_WAVE_BCAST(rg12, a);
@@ -609,12 +646,10 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     for (int c = 0; c < NC; c++) { sA[nb][3][lane + 64 * c] = 0.0; sB[nb][3][lane + 64 * c] = 0.0; }
                     if (nb) dirty1 = false; else dirty0 = false;
                 }
-                // header of the logged step (to LDS: the logger wave, in the piece schedule worker wave 0, stores it to the log)
+                // what the step brings to its log header: S^-1 (the wave that stores the header composes the rest: win_header_entry)
                 if (lane == 0) {
-                    hdr[WH_TYPE] = 1.0; hdr[WH_POS] = (double)pos;
 #pragma unroll
                     for (int q = 0; q < 9; q++) hdr[WH_SI + q] = Si[q];
-                    hdr[WH_ZE] = ze0; hdr[WH_ZE + 1] = ze1; hdr[WH_ZE + 2] = ze2; hdr[WH_G02] = g02; hdr[WH_G12] = g12;
                 }
                 WSTAMP(5);
             }
@@ -1164,11 +1199,13 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 // competes with the prepare wave for issue slots and LDS bandwidth (ASLAM_WIN_SHARE_CU: off, for comparison).  The claim is no
 // larger than that needs: at SP = 64 the one-launch window leaves 70 388 of the CU's 163 840 bytes, which a k_ekf_win_thin workgroup
 // of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
-// waited for up to a whole window (measured: DESIGN.md).
+// waited for up to a whole window (measured: DESIGN.md).  The chain role's block has grown by kGrown bytes since (the header records);
+// the dynamic part gives them back, so that static + dynamic is what it was measured at.
 template <int T, bool ONE, class K> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const WinDesc& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
-    const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, (size_t)24 * 1024);      // static + dynamic > 80 KB of the 160 KB
+    constexpr size_t cap = (size_t)24 * 1024 + WinChainLds<T, ONE>::kGrown;
+    const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, cap);                    // static + dynamic > 80 KB of the 160 KB
     static bool attr_done = false;
     if (!attr_done && dyn > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
