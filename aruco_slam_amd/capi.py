@@ -178,6 +178,8 @@ _SIGS = {
     "aslam_get_innovation_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
     "aslam_set_slam_gate": (C.c_int, [C.c_void_p, _P(GateParams)]),
     "aslam_get_slam_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
+    "aslam_set_slam_gate_windows": (C.c_int, [C.c_void_p, C.c_int]),
+    "aslam_get_slam_gate_windows": (C.c_int, [C.c_void_p, _ip]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -698,6 +700,16 @@ class Context:
         if not on.value:
             return None
         return dict(gate_d2=p.gate_d2, min_attempted=p.min_attempted, min_accept_percent=p.min_accept_percent, lost_after=p.lost_after)
+
+    # -- the SLAM gate inside EKF windows -------------------------------------------------------------------------
+    def set_slam_gate_windows(self, on=True):
+        """keep the EKF windows of staged batches while the SLAM gate is set (off by default)"""
+        self._ck(self.lib.aslam_set_slam_gate_windows(self.h, 1 if on else 0))
+
+    def get_slam_gate_windows(self):
+        on = C.c_int()
+        self._ck(self.lib.aslam_get_slam_gate_windows(self.h, C.byref(on)))
+        return bool(on.value)
 
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""

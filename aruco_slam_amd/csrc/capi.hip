@@ -32,11 +32,11 @@ constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
-              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_COUNT };
+              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
-                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish"};
+                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -157,11 +157,15 @@ struct aslam_ctx {
     GateState gate{};                     // the parameters in force and the device records, as the gated kernels take them
     SlotHealth* h_slot_health = nullptr;  // page-locked: 2 max_batch
     // SLAM innovation gate (aslam_set_slam_gate): a switch of its own; only the per-frame chains of SLAM, rig SLAM and
-    // fleet SLAM look at it, and while it is set aslam_run_staged plans no windows.  The records are the ones above, made by whichever
+    // fleet SLAM look at it, and while it is set aslam_run_staged plans no windows (unless slam_gate_windows below keeps them).  The records are the ones above, made by whichever
     // setter runs first; the verdict buffer (2 kMarkerMax doubles per filter of a launch) is made by the first aslam_set_slam_gate.
     bool slam_gate_on = false;
     aslam_gate_params slam_gate_prm{};
     SlamGateArg slam_gate{};
+    // gated windows (aslam_set_slam_gate_windows): with the SLAM gate set, windows enabled and the one-launch form in use,
+    // a staged batch keeps its windows, run by the gated step kernels with k_ekf_win_gate_finish behind each.  The verdicts travel in
+    // the window's log header, so the switch needs no storage of its own.
+    bool slam_gate_windows = false;
     // uncertain map (aslam_localize_begin_uncertain / aslam_fleet_begin_uncertain): on exactly while the active
     // localization or localization fleet was begun with landmark covariances.  The C table (max_landmarks x 9) is made by the first
     // such begin and freed by aslam_destroy; a fleet's cross strips (R x 3 x 3n) live from its begin to aslam_fleet_end / aslam_destroy.
@@ -192,7 +196,9 @@ struct aslam_ctx {
     WinFrame* h_win_frames = nullptr;     // pinned: max_batch frame plans (uploaded to ekf.d_win_frames per batch)
     std::vector<int> m_id2idx;            // host mirror of the id -> landmark table, valid unless mirror_dirty
     int m_L = 0;
-    struct HostLast { int id; double z[3]; };
+    // unconfirmed: the entry comes from an action-1 observation of a frame planned under the SLAM gate, whose verdict the host does
+    // not know (rejected: the device's list does not hold it).  Entries read back from the device are exact.
+    struct HostLast { int id; double z[3]; bool unconfirmed = false; };
     std::vector<HostLast> m_last;         // host mirror of last_observed_marker_ (NaN z = unset)
     bool mirror_dirty = true;             // the device planned frames the host could not follow: read the tables back before planning
     int ekf_lo = 0, ekf_hi = 0;           // union of the slot ranges of EKF work enqueued since the last wait on ev_ekf
@@ -996,7 +1002,7 @@ int read_mirror(aslam_ctx* c) {
     std::vector<LastObs> h(std::max(nl, 1));
     if (nl) HIP_TRY(c, hipMemcpy(h.data(), c->ekf.d_last, sizeof(LastObs) * nl, hipMemcpyDeviceToHost));
     c->m_last.resize(nl);
-    for (int i = 0; i < nl; i++) { c->m_last[i].id = h[i].id; for (int k = 0; k < 3; k++) c->m_last[i].z[k] = h[i].z[k]; }
+    for (int i = 0; i < nl; i++) { c->m_last[i].id = h[i].id; c->m_last[i].unconfirmed = false; for (int k = 0; k < 3; k++) c->m_last[i].z[k] = h[i].z[k]; }
     c->mirror_dirty = false;
     return ASLAM_OK;
 }
@@ -1006,6 +1012,11 @@ int read_mirror(aslam_ctx* c) {
 // into windows = runs of frames whose fused landmarks fit into one set S (ekf_window.hip); every other frame, and every frame
 // the host cannot decide (a marker id it does not know: a new landmark; one id twice), takes the per-frame chain, planned on the
 // device.  A window frame may fuse any subset of S and may drop "stationary" observations; S is the union over the window.
+// Under the SLAM gate (gated windows) the host plans as if every prepared correction were accepted.  The verdicts
+// matter to the plan in one place only: a "stationary" match against an entry of the mirror whose own correction may have been
+// rejected.  Such a frame is undecidable on the host and goes to the device with the rest of its batch, like a frame with an unknown
+// id; a match that fails needs no verdict (a rejected predecessor is absent from the list, an accepted one is too far away).
+static bool gated_windows(const aslam_ctx* c) { return c->slam_gate_on && c->slam_gate_windows && c->win_enabled && !c->win_pieces; }
 int finalize_pending(aslam_ctx* c) {
     if (!c->pend.active) return ASLAM_OK;
     const aslam_ctx::Pending p = c->pend;
@@ -1065,7 +1076,7 @@ int finalize_pending(aslam_ctx* c) {
                 pop.push_back({it.idx, it.det});
             }
         }
-        if (!clean) {
+        auto to_device = [&]() {
             if (std::getenv("ASLAM_DEBUG_PLAN")) std::fprintf(stderr, "plan frame %d: nM %d left to the device\n", f, nM);
             close_window();
             device_plans = true;
@@ -1074,13 +1085,14 @@ int finalize_pending(aslam_ctx* c) {
             Op o{};
             o.frame = f; o.predict = predict; o.K = 0;
             ops.push_back(o);
-            continue;
-        }
+        };
+        if (!clean) { to_device(); continue; }
         // pop order = ascending landmark index (aruco_slam.h:85-88); "stationary" test against last frame's list (:192-198)
         FramePlan& fp = plans[f - p.first];
         fp.n_markers = nM;
         int n_stationary = 0;
         std::vector<aslam_ctx::HostLast> nlast(pop.size());
+        bool undecidable = false;
         for (size_t j = 0; j < pop.size(); j++) {
             const ObsRaw& o = ob[pop[j].second];
             bool stationary = false;
@@ -1093,15 +1105,17 @@ int finalize_pending(aslam_ctx* c) {
                 if (l.id == o.id) {                                          // std::find: first with the same id
                     const double d0 = l.z[0] - o.x, d1 = l.z[1] - o.y, d2 = l.z[2] - o.th;
                     stationary = std::sqrt(d0 * d0 + d1 * d1 + d2 * d2) < 0.01;     // NaN compares false
+                    undecidable = undecidable || (stationary && l.unconfirmed);     // the predecessor's verdict decides
                     break;
                 }
             n_stationary += stationary ? 1 : 0;
             nlast[j].id = o.id;
             if (stationary) { nlast[j].z[0] = nlast[j].z[1] = nlast[j].z[2] = std::nan(""); }
-            else { nlast[j].z[0] = o.x; nlast[j].z[1] = o.y; nlast[j].z[2] = o.th; }
+            else { nlast[j].z[0] = o.x; nlast[j].z[1] = o.y; nlast[j].z[2] = o.th; nlast[j].unconfirmed = c->slam_gate_on; }
             fp.pop_idx.push_back(pop[j].first); fp.pop_det.push_back(pop[j].second); fp.pop_act.push_back(stationary ? 2 : 1);
             if (!stationary) { fp.corr_idx.push_back(pop[j].first); fp.corr_det.push_back(pop[j].second); }
         }
+        if (undecidable) { to_device(); continue; }                            // (the mirror is read back before the next batch is planned)
         c->m_last.swap(nlast);
         const int m = (int)fp.corr_idx.size();
         const bool eligible = predict && n_new == 0 && m <= kWinCorrMax && (int)pop.size() <= 64 && m <= s_cap && m <= c->init.max_updates_per_frame;
@@ -1225,8 +1239,14 @@ int finalize_pending(aslam_ctx* c) {
             cw.nsteps = 0;
             for (int k = 0; k < o.K; k++) cw.nsteps += 1 + c->h_win_frames[o.frame + k].m;
             prof_begin(c, P_EKF_WIN_CHAIN, sa);
-            launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc);
+            const bool gated = gated_windows(c);
+            launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr);
             prof_end(c);
+            if (gated) {                                             // verdicts into records, counts, actions and the last-observed list
+                prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
+                launch_ekf_win_gate_finish(sa, c->ekf, cw, c->slam_gate, c->d_obs);
+                prof_end(c);
+            }
         } else {
             // The pieces of the window, back to back on sa: launch i carries the chain of piece i, the replay of piece i - 1 and the Psi
             // product of piece i - 2 (ekf_window.hip: k_ekf_win_step), so nothing but the stream orders them; two more launches drain
@@ -1308,7 +1328,7 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         note_ekf_range(c, first, count);
         return ASLAM_OK;
     }
-    if (!c->win_enabled || c->slam_gate_on) {  // every frame on the per-frame chain, enqueued at once
+    if (!c->win_enabled || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
         // the SLAM gate: the window planner runs the "stationary" test on the host from a mirror of the last-observed
@@ -2872,6 +2892,21 @@ int aslam_set_slam_gate(aslam_ctx* c, const aslam_gate_params* params) {
     c->slam_gate.g.min_accept_percent = p.min_accept_percent;
     c->slam_gate.g.lost_after = p.lost_after;
     c->slam_gate_on = true;
+    return ASLAM_OK;
+}
+
+// ---- the SLAM gate inside EKF windows (include/aruco_slam_hip.h) ------------------------------------------------------
+int aslam_set_slam_gate_windows(aslam_ctx* c, int on) {
+    if (!c) return ASLAM_E_INVALID;
+    // a batch still pending was submitted under the setting in force so far: its windows (or per-frame steps) are enqueued first
+    if (int r = finalize_pending(c)) return r;
+    c->slam_gate_windows = on != 0;        // (the verdicts travel in the window's log header: nothing to allocate)
+    return ASLAM_OK;
+}
+
+int aslam_get_slam_gate_windows(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->slam_gate_windows ? 1 : 0;
     return ASLAM_OK;
 }
 

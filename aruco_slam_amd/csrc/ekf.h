@@ -265,7 +265,11 @@ int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 1
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,
 // epoch set) in one launch, the three roles following each other through in-launch counters
-void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc);
+// gate != nullptr: the gated instantiation, to be followed on the same stream by launch_ekf_win_gate_finish
+void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
+                        const SlamGateArg* gate = nullptr);
+// behind a gated window: slot records and accepted counts of its K frames, the track record, the last frame's actions and last-observed list
+void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs);
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps);
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd);               // Y_0 = rows S of Sigma, position table

@@ -41,6 +41,7 @@
 #include "common.h"
 #include "ekf.h"
 #include "ekf_dev.h"
+#include "ekf_slam_gate.h"
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
@@ -78,7 +79,17 @@ template <int NC> __device__ __forceinline__ void win_vmcnt_lag() {
 __host__ __device__ inline int win_log_stride(int T) { return 3 * 16 * T + kWinHdr; }
 __host__ __device__ inline int win_tlog_stride(int T) { return 8 * 16 * T; }
 // header of a logged step (doubles after the three operand rows)
-enum { WH_TYPE = 0, WH_POS = 1, WH_SI = 2, WH_ZE = 11, WH_C = 14, WH_S = 15, WH_G02 = 16, WH_G12 = 17, WH_A = 18, WH_B = 19 };
+enum { WH_TYPE = 0, WH_POS = 1, WH_SI = 2, WH_ZE = 11, WH_C = 14, WH_S = 15, WH_G02 = 16, WH_G12 = 17, WH_A = 18, WH_B = 19, WH_D2 = 20, WH_ACC = 21 };
+// Gated window (aslam_set_slam_gate_windows): the one-launch step kernel is a template on a gate policy, as the solve
+// kernels of the per-frame chains are (ekf_slam_gate.h).  NoSlamGate is the default: every gated statement sits under `if constexpr`
+// and the policy is an empty base of the kernel's window argument, so the ungated kernels keep their arguments and their code.
+// WinGate carries the threshold.  The prepare wave judges correction j where it forms S_j^-1 from the live P: d2 = ze^T S_j^-1 ze with
+// the frame's frozen-mean ze.  A rejected step stays a step (the host planned the step count) with zero A operand rows, no mean
+// update and step type 2 in its log header, which the replay role skips: P, mu_S, Lambda, Psi and psi do not see it, whatever its ze
+// holds.  d2 and the verdict travel in the header (WH_D2; WH_ACC: 1.0 = accepted, 0.0 = rejected) to k_ekf_win_gate_finish.
+struct WinGate { static constexpr bool kOn = true; double gate_d2; };
+template <class G> struct WinArg : WinDesc, G {};
+static_assert(sizeof(WinArg<NoSlamGate>) == sizeof(WinDesc), "the ungated window argument is the window descriptor alone");
 // d_win_small: images of the window, each SPm x SPm at most (SPm = E.win_sp_max), stored with the window's own row stride SP
 __host__ __device__ inline size_t wsm_P(int SPm, int par) { return (size_t)par * SPm * SPm; }             // P image of window parity par
 __host__ __device__ inline size_t wsm_LAM(int SPm, int par) { return (size_t)(2 + par) * SPm * SPm; }      // Lambda / Psi / psi: also per parity (the flush of a
@@ -192,21 +203,23 @@ template <int T, bool ONE> struct WinChainLds {
 // of the step's frame: the prepare wave writes them ONCE per frame, at the frame's predict, into sRec[frame parity].  Two parities
 // suffice: the prepare wave prepares step j + 1 while step j is stored, and the step in front of frame k's predict belongs to
 // frame k - 1 whatever the frames fuse (a frame without corrections is a lone predict, which reads no record).
-template <class LDS> __device__ __forceinline__ double win_header_entry(const LDS& L, int j, int cb, int fpar, int lane) {
+// GATED: the prepare wave also left the step's type there (1.0, or 2.0 = rejected) with d2 and the verdict (WH_D2, WH_ACC).
+template <bool GATED, class LDS> __device__ __forceinline__ double win_header_entry(const LDS& L, int j, int cb, int fpar, int lane) {
     double v = L.sHdr[cb][lane];
     const int pos = L.sPos[j];
     if (pos != 255) {
         const int a = L.sIdx[j];
         const int q = lane >= WH_ZE && lane < WH_ZE + 3 ? lane - WH_ZE : lane == WH_G02 ? 3 : lane == WH_G12 ? 4 : -1;
         if (q >= 0) v = L.sRec[fpar][q][a];
-        if (lane == WH_TYPE) v = 1.0;
+        if (!GATED && lane == WH_TYPE) v = 1.0;
         if (lane == WH_POS) v = (double)pos;
     }
     return v;
 }
-template <int T, int RW, bool ONE>
-__device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* __restrict__ obs,
+template <int T, int RW, bool ONE, class G>
+__device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const G& gate, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
+    static_assert(ONE || !G::kOn, "only the one-launch window is gated");
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
@@ -350,7 +363,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 }
                 if (!ONE && wave == 0) {
                     if (sPos[j] == 255) fpar ^= 1;
-                    if (lane < kWinHdr) log[3 * SP + lane] = win_header_entry(L, j, cb, fpar, lane);
+                    if (lane < kWinHdr) log[3 * SP + lane] = win_header_entry<false>(L, j, cb, fpar, lane);
                 }
                 WSTAMP(2);
                 if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
@@ -411,7 +424,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #pragma unroll
                     for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, sA[cb][k][lane + 64 * c]);
                 if (sPos[j] == 255) fpar ^= 1;
-                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, win_header_entry(L, j, cb, fpar, lane));
+                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, win_header_entry<G::kOn>(L, j, cb, fpar, lane));
                 // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete
                 if ((j + 1) % kWinPubEvery == 0) win_vmcnt_lag<NC>();
             }
@@ -630,6 +643,13 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 }
                 Sm[0] += R0; Sm[4] += R1; Sm[8] += R2;
                 inv3_fast(Sm, Si);
+                // gated: the verdict on this correction, from the S^-1 just formed and the frame's frozen-mean innovation (a NaN d2 rejects)
+                double d2 = 0.0;
+                bool rejected = false;
+                if constexpr (G::kOn) {
+                    d2 = slam_gate_d2(Si, ze0, ze1, ze2);
+                    rejected = gate.gate_d2 < HUGE_VAL && !(d2 <= gate.gate_d2);
+                }
                 WSTAMP(4);
 #pragma unroll
                 for (int c = 0; c < NC; c++) {
@@ -637,8 +657,16 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     const double k0 = cc[0][c] * Si[0] + cc[1][c] * Si[3] + cc[2][c] * Si[6];
                     const double k1 = cc[0][c] * Si[1] + cc[1][c] * Si[4] + cc[2][c] * Si[7];
                     const double k2 = cc[0][c] * Si[2] + cc[1][c] * Si[5] + cc[2][c] * Si[8];
-                    mu[c] += k0 * ze0 + k1 * ze1 + k2 * ze2;                       // mu_ += K ze (aruco_slam.cpp:203)
-                    A[0][c] = -k0; A[1][c] = -k1; A[2][c] = -k2; A[3][c] = 0.0;
+                    if constexpr (G::kOn) {
+                        // a rejected step: no mean update (selected, not multiplied: its ze may be NaN) and zero A rows, so that the
+                        // workers, the pose rows carried here and the logged operands all see a zero update
+                        const double dm = k0 * ze0 + k1 * ze1 + k2 * ze2;
+                        mu[c] = rejected ? mu[c] : mu[c] + dm;
+                        A[0][c] = rejected ? 0.0 : -k0; A[1][c] = rejected ? 0.0 : -k1; A[2][c] = rejected ? 0.0 : -k2; A[3][c] = 0.0;
+                    } else {
+                        mu[c] += k0 * ze0 + k1 * ze1 + k2 * ze2;                   // mu_ += K ze (aruco_slam.cpp:203)
+                        A[0][c] = -k0; A[1][c] = -k1; A[2][c] = -k2; A[3][c] = 0.0;
+                    }
                     B[0][c] = cc[0][c]; B[1][c] = cc[1][c]; B[2][c] = cc[2][c]; B[3][c] = 0.0;
                 }
                 if (nb ? dirty1 : dirty0) {                         // the buffer last held a predict's fourth depth row
@@ -650,6 +678,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 if (lane == 0) {
 #pragma unroll
                     for (int q = 0; q < 9; q++) hdr[WH_SI + q] = Si[q];
+                    if constexpr (G::kOn) { hdr[WH_TYPE] = rejected ? 2.0 : 1.0; hdr[WH_D2] = d2; hdr[WH_ACC] = rejected ? 0.0 : 1.0; }
                 }
                 WSTAMP(5);
             }
@@ -700,7 +729,8 @@ template <int T> struct WinScanLds {
     double sRec[2][REC];
     double sT[2][4][WBW];                  // t (row 3 stays zero)
 };
-template <int T, bool ONE>
+// GATED: a step of type 2 (a correction the gate rejected) leaves Lambda and psi alone and logs t = u = 0, which adds nothing to Psi.
+template <int T, bool ONE, bool GATED>
 __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, unsigned epoch, int* sAvail, unsigned char* smem) {
     constexpr int SP = 16 * T, EPT = SP * WBW / 256, REC = 3 * SP + kWinHdr;
     constexpr int RPT = (REC + 191) / 192;                         // record doubles per loading thread
@@ -770,9 +800,11 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
         ASLAM_LDS_BARRIER();
         const double* hd = rec + 3 * SP;
         const bool is_predict = hd[WH_TYPE] == 0.0;
+        const bool skipped = GATED && hd[WH_TYPE] == 2.0;
         if (tid < WBW) {
             const int c = tid;
-            if (is_predict) {
+            if (GATED && skipped) { tt[0][c] = 0.0; tt[1][c] = 0.0; tt[2][c] = 0.0; }
+            else if (is_predict) {
                 // Lambda <- D Lambda (rows 0, 1 += (a, b) row 2); nothing for Psi / psi
                 cth = hd[WH_C]; sth = hd[WH_S];                     // the frame's cos / sin (every piece starts with a predict)
                 const double r2 = sLam[2][c];
@@ -793,7 +825,7 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
             const int row = tid / WBW, c = tid % WBW, k = row & 3;
             const double t0 = tt[0][c], t1 = tt[1][c], t2 = tt[2][c];
             double v = 0.0;
-            if (!is_predict && k < 3) {
+            if (!is_predict && !skipped && k < 3) {
                 const double* Si = hd + WH_SI + 3 * k;
                 v = row < 4 ? tt[k][c] : Si[0] * t0 + Si[1] * t1 + Si[2] * t2;     // (Z <- Z - (H Y)^T S^-1 (H Y))
                 if (row == 4) {                                     // thread (4, c): the whole of psi's entry c
@@ -806,7 +838,7 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
             if (ONE) st_wt(tlog + (size_t)n * ts + row * SP + c, v);
             else tlog[(size_t)n * ts + row * SP + c] = v;
         }
-        if (!is_predict) {
+        if (!is_predict && !skipped) {
             // Lambda[r][c] += sum_k Aop[k][r] t[k][c]      (c is the same for all of a thread's entries)
             const int c = tid % WBW;
             const double t0 = tt[0][c], t1 = tt[1][c], t2 = tt[2][c];
@@ -833,7 +865,9 @@ __device__ void win_scan_role(const EkfState& E, const WinReplay& wd, int b, uns
 
 // Psi (+)= sum over the piece's steps of t^T u on the f64 matrix cores: workgroup = tile row, wave w = tile columns w, w + 4, ...
 // The operands come straight from the t / u log (L2): four steps are fetched ahead of the four products.
-template <int T, bool ONE>
+// (GATED only names the kernel the role belongs to: where the compiler keeps a role out of line, every step kernel has its own copy,
+// and the ungated kernels' code does not depend on the gated instantiations beside them)
+template <int T, bool ONE, bool GATED>
 __device__ void win_psi_role(const EkfState& E, const WinReplay& wd, int tr, unsigned epoch, int* sAvail) {
     constexpr int SP = 16 * T, TW = (T + 3) / 4, UN = 4, NSCAN = SP / WBW;
     if (threadIdx.x >= 256) return;
@@ -932,9 +966,10 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
         old = prev;
     }
 }
-template <int T, int RW, bool ONE>
+template <int T, int RW, bool ONE, class G = NoSlamGate>
 __global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
-void k_ekf_win_step(EkfState E, SlamParams sp, WinDesc wd, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
+void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
+    const WinDesc& wd = wa;
     constexpr size_t kLds = sizeof(WinChainLds<T, ONE>) > sizeof(WinScanLds<T>) ? sizeof(WinChainLds<T, ONE>) : sizeof(WinScanLds<T>);
     __shared__ __align__(16) unsigned char smem[kLds];
     __shared__ int sTicket, sAvail;
@@ -945,9 +980,107 @@ void k_ekf_win_step(EkfState E, SlamParams sp, WinDesc wd, WinReplay rs, WinRepl
         __syncthreads();
         bx = sTicket;
     }
-    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE>(E, sp, wd, obs, enc, smem); }
-    else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
-    else if (rq.nsteps > 0) win_psi_role<T, ONE>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
+    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
+    else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE, G::kOn>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
+    else if (rq.nsteps > 0) win_psi_role<T, ONE, G::kOn>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Behind a gated window's step launch, on the same stream: the bookkeeping k_ekf_gate_finish does behind a gated per-frame solve,
+// for all K frames of the window at once.  One workgroup; wave w takes frames w, w + 16, ..., lane a = correction a of the frame
+// (the corrections are the frame's action-1 pops, in pop order).  d2, the verdict and ze of correction a are in the header of step
+// off_k + 1 + a of the window's log, which nothing overwrites before the next window's launch on this stream.  Per frame: lane 0 walks
+// the corrections once in pop order (the slot record of §19 / §24, entry [2] of the slot stats = the accepted count).  Then thread 0
+// carries the filter's track record through the K frames in order (the integer streak rule), and wave 0 turns the rejected pops of
+// the window's LAST frame into action 3 and takes them out of the last-observed list the chain left behind (win_last_frame), so
+// that a device-planned frame that follows sees the exact list.  Fixed orders throughout, no floating-point atomics.
+constexpr int kWinFinishThreads = 1024;
+__global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish(EkfState E, WinDesc wd, GateState gs, const ObsRaw* __restrict__ obs) {
+    constexpr int NW = kWinFinishThreads / 64;
+    __shared__ double sD2[NW][64];
+    __shared__ int sKind[NW][64], sFlag[NW][64], sId[NW][64];   // kind 1: accepted, 2: rejected
+    __shared__ int sOff[kWinFrames + 1], sAtt[kWinFrames], sAcc[kWinFrames];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int K = min(wd.K, kWinFrames);
+    const WinFrame* __restrict__ frames = E.d_win_frames + wd.first_slot;
+    const int ls = win_log_stride(wd.T), SP = 16 * wd.T;
+    const double* __restrict__ hdr0 = E.d_win_log + (size_t)wd.log0 * ls + 3 * SP;   // header of the window's step 0
+    if (wave == 0) {                                                // step offset of every frame: 1 predict + m corrections each
+        int inc = lane < K ? 1 + frames[lane].m : 0;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(inc, d); if (lane >= d) inc += y; }
+        sOff[lane + 1] = inc;
+        if (lane == 0) sOff[0] = 0;
+    }
+    __syncthreads();
+    for (int k = wave; k < K; k += NW) {
+        const int slot = wd.first_slot + k;
+        const WinFrame& fr = frames[k];
+        const int m = min(fr.m, kWinCorrMax);
+        if (lane < m) {
+            const double* hd = hdr0 + (size_t)(sOff[k] + 1 + lane) * ls;
+            const double z0 = hd[WH_ZE], z1 = hd[WH_ZE + 1], z2 = hd[WH_ZE + 2];
+            sD2[wave][lane] = hd[WH_D2];
+            sKind[wave][lane] = hd[WH_ACC] == 0.0 ? 2 : 1;
+            sFlag[wave][lane] = sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 ? 1 : 0;   // the ||ze|| half of aruco_slam.cpp:156 (the chains never form K)
+            sId[wave][lane] = obs[(size_t)slot * kMarkerMax + fr.cdet[lane]].id;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) {
+            int acc = 0, nrej = 0, flag = 0, worst = -1;
+            double nis = 0.0, mx = 0.0;
+            bool have = false;
+            for (int a = 0; a < m; a++) {                           // pop order
+                const double d2 = sD2[wave][a];
+                flag += sFlag[wave][a];
+                if (d2 == d2 && (!have || d2 > mx)) { have = true; mx = d2; worst = sId[wave][a]; }
+                if (sKind[wave][a] == 2) nrej++;
+                else { acc++; nis += d2; }
+            }
+            if (slot >= 0 && slot < E.max_slots) {
+                E.d_slot_stat[4 * slot + 2] = acc;                  // corrections fused: the accepted ones (the chain wrote the planned count)
+                SlotHealth* h = gs.slot + slot;
+                h->attempted = m; h->accepted = acc; h->rejected = nrej; h->ref_flagged = flag;
+                h->nis_sum = nis; h->d2_max = mx; h->worst_id = worst; h->pad = 0;
+            }
+            sAtt[k] = m; sAcc[k] = acc;
+        }
+        __builtin_amdgcn_wave_barrier();                            // (the wave's next frame rewrites the arrays)
+    }
+    __syncthreads();
+    if (tid == 0 && K > 0) {                                        // the track record, frame by frame
+        TrackHealth* t = gs.track + kTrackSingle;
+        int streak = t->bad_streak, acc_total = t->accepted_total, rej_total = t->rejected_total;
+        for (int k = 0; k < K; k++) {
+            const int att = sAtt[k], acc = sAcc[k];
+            if (att >= gs.min_attempted) streak = 100 * acc < gs.min_accept_percent * att ? streak + 1 : 0;
+            acc_total += acc; rej_total += att - acc;
+        }
+        t->frames = t->frames + K;
+        t->accepted_total = acc_total;
+        t->rejected_total = rej_total;
+        t->bad_streak = streak;
+        t->lost = streak >= gs.lost_after ? 1 : 0;
+        t->pad[0] = t->pad[1] = t->pad[2] = 0;
+    }
+    if (wave == 1 && K > 0) {                                       // the last frame's pop list and last-observed list (npop <= 64: one wave)
+        const WinFrame& fr = frames[K - 1];
+        const int np = min(fr.npop, 64);
+        const bool upd = lane < np && fr.pact[lane] == 1;
+        const unsigned long long bU = __ballot(upd);
+        bool rej = false;
+        if (upd) {
+            const int a = __popcll(bU & ((1ull << lane) - 1ull));   // the correction this pop is
+            rej = a < kWinCorrMax && hdr0[(size_t)(sOff[K - 1] + 1 + a) * ls + WH_ACC] == 0.0;
+        }
+        LastObs lo{};
+        if (lane < np) lo = E.d_last[lane];
+        const bool keep = lane < np && !rej;
+        const unsigned long long bK = __ballot(keep);               // (every lane holds its entry of d_last before any is rewritten)
+        if (rej) E.d_pop[lane].action = 3;
+        if (keep) E.d_last[__popcll(bK & ((1ull << lane) - 1ull))] = lo;
+        if (lane == 0) *E.d_nlast = __popcll(bK);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1201,8 +1334,8 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 // of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
 // waited for up to a whole window (measured: DESIGN.md).  The chain role's block has grown by kGrown bytes since (the header records);
 // the dynamic part gives them back, so that static + dynamic is what it was measured at.
-template <int T, bool ONE, class K> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
-                                                const WinDesc& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
+template <int T, bool ONE, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
+                                                const W& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
     constexpr size_t cap = (size_t)24 * 1024 + WinChainLds<T, ONE>::kGrown;
     const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, cap);                    // static + dynamic > 80 KB of the 160 KB
@@ -1217,17 +1350,29 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps) {
     const WinReplay rs{s_piece, s_log0, s_nsteps, wd.wpar}, rq{q_piece, q_log0, q_nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
-    if (wd.T == 4) launch_step_kernel<4, false>(k_ekf_win_step<4, 2, false>, st, nb, 256, sizeof(WinChainLds<4, false>), E, sp, wd, rs, rq, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8, false>(k_ekf_win_step<8, 2, false>, st, nb, 320, sizeof(WinChainLds<8, false>), E, sp, wd, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
-    else launch_step_kernel<12, false>(k_ekf_win_step<12, 2, false>, st, nb, 448, sizeof(WinChainLds<12, false>), E, sp, wd, rs, rq, obs, enc);
+    const WinArg<NoSlamGate> wa{wd, {}};
+    if (wd.T == 4) launch_step_kernel<4, false>(k_ekf_win_step<4, 2, false>, st, nb, 256, sizeof(WinChainLds<4, false>), E, sp, wa, rs, rq, obs, enc);
+    else if (wd.T == 8) launch_step_kernel<8, false>(k_ekf_win_step<8, 2, false>, st, nb, 320, sizeof(WinChainLds<8, false>), E, sp, wa, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
+    else launch_step_kernel<12, false>(k_ekf_win_step<12, 2, false>, st, nb, 448, sizeof(WinChainLds<12, false>), E, sp, wa, rs, rq, obs, enc);
 }
-void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc) {
+void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc, const SlamGateArg* gate) {
     const WinReplay r{0, 0, wd.nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
-    if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wd, r, r, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wd, r, r, obs, enc);
-    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wd, r, r, obs, enc);
+    if (gate) {                                                     // the gated instantiations: same grids, same blocks
+        const WinArg<WinGate> wa{wd, WinGate{gate->g.gate_d2}};
+        if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true, WinGate>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wa, r, r, obs, enc);
+        else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true, WinGate>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wa, r, r, obs, enc);
+        else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true, WinGate>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wa, r, r, obs, enc);
+        return;
+    }
+    const WinArg<NoSlamGate> wa{wd, {}};
+    if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wa, r, r, obs, enc);
+    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wa, r, r, obs, enc);
+    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wa, r, r, obs, enc);
+}
+void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
+    hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
 }
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd) {
     hipLaunchKernelGGL(k_ekf_win_gather, dim3((E.ld + 255) / 256, 16), dim3(256), 0, st, E, wd);       // y: rows of Y_0 in turn (one load in flight per thread otherwise)

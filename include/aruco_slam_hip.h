@@ -563,16 +563,45 @@ int aslam_fleet_get_health(aslam_ctx* ctx, int max, int* n_robots, aslam_track_h
  * is set (slot records: SLAM, rig SLAM, fleet SLAM; aslam_get_track_health: SLAM and rig SLAM; aslam_fleet_get_health: fleet SLAM);
  * with only the innovation gate set they refuse there with ASLAM_E_STATE.  The record storage is the section above's, made by
  * whichever setter runs first.
- * Windows: while the SLAM gate is set aslam_run_staged takes the per-frame path (what ASLAM_NO_WINDOWS selects), and setting or clearing
- * the gate first enqueues a batch still pending.  The window planner runs the "stationary" test on the host, one call behind, from
- * a mirror of the last-observed list; a rejection on the device changes that list.  Gating inside the window chain is the follow-up
- * this leaves open.
+ * Windows: while the SLAM gate is set aslam_run_staged takes the per-frame path (what ASLAM_NO_WINDOWS selects) unless
+ * aslam_set_slam_gate_windows (the next section) keeps the windows, and setting or clearing the gate first enqueues a batch still
+ * pending.
  * Not covered: a misread id that is NEW to the map is an augment and enters as a landmark (aslam_remove_landmarks stays the remedy);
  * nothing tunes gate_d2 or R.  No floating-point atomics, every sum in pop order: a robot's result does not depend on the other
  * robots of the call. */
 int aslam_set_slam_gate(aslam_ctx* ctx, const aslam_gate_params* params /* NULL: off */);
 /* *on = 1 while the SLAM gate is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
 int aslam_get_slam_gate(aslam_ctx* ctx, int* on, aslam_gate_params* out);
+
+/* ---- the SLAM gate inside EKF windows ------------------------------------------------------------------------------
+ * An opt-in switch, off by default, settable in any mode, persistent.  It changes which path a staged batch takes under the SLAM gate,
+ * not what the gate means.  The gated window path is taken only when all of these hold: the SLAM gate is set, windows are enabled (no
+ * ASLAM_NO_WINDOWS) and the one-launch window form is in use (no ASLAM_WIN_PIECE: the piece schedule is not gated).  Otherwise a gated
+ * context takes the per-frame path exactly as without this switch.  With the switch on but no gate set every launch, kernel and
+ * result is the ungated window's.  The setter first enqueues a batch still pending, as aslam_set_slam_gate does.  The verdicts travel
+ * in the window's step log, so the switch allocates nothing.  ASLAM_E_INVALID: a null context, or a null `on` in the getter.
+ * Inside a window the reference's corrections are sequential rank-3 steps on the window's block of Sigma.  Per correction step:
+ * 1. c = H P, S = c H^T + R and S^-1 exactly as the ungated window forms them from the live P, which follows the corrections ACCEPTED
+ *    before this one.
+ * 2. d2 = ze^T S^-1 ze with the frozen-mean ze of the frame.  The correction is rejected iff gate_d2 is finite and !(d2 <= gate_d2);
+ *    a NaN d2 rejects.
+ * 3. A rejected step changes nothing: not P, not mu, and not the accumulators from which the rest of Sigma and mu follow once per
+ *    window, whatever its ze holds (NaN and infinities included).  It stays a step, because the host planned the step count.
+ * 4. With gate_d2 = +inf nothing is rejected and every step performs the ungated step's operations in the ungated order: the results
+ *    are bit for bit the ungated window's on the same plan.
+ * Planner: the host plans one call behind and treats every prepared correction as accepted.  An entry of its last-observed mirror
+ * that came from an action-1 observation of a frame planned under the gate is unconfirmed.  A sighting that tests "stationary"
+ * against an unconfirmed entry cannot be decided on the host (the predecessor's verdict decides): the open window is closed and
+ * this frame and the rest of its batch run on the gated per-frame chain, planned on the device from the exact list (counted in entry
+ * [3] of aslam_get_plan_stats); the next batch reads the list back and forms windows again.  A test that fails needs no verdict: a
+ * rejected predecessor is absent from the list and an accepted one is too far away, both give action 1.  Everything else about
+ * windows (eligibility, cuts, widening, step counts) is unchanged, so the results are the gated per-frame path's up to rounding.
+ * Records: every window frame gets its aslam_slot_health and the accepted count in entry [2] of aslam_get_slot_ekf_stats; the
+ * window's last frame leaves the pop list with action 3 for rejected observations and the last-observed list without them; the
+ * filter's aslam_track_health advances frame by frame and is carried across windows, per-frame frames, batches and calls.  Rig steps
+ * use EKF slots max_batch + step.  Fleet SLAM has no windows and is unaffected. */
+int aslam_set_slam_gate_windows(aslam_ctx* ctx, int on);
+int aslam_get_slam_gate_windows(aslam_ctx* ctx, int* on);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
