@@ -4,11 +4,11 @@
 #include "detect.h"
 #include "pose.h"
 #include "ekf.h"
+#include "win_plan.h"
 #include "synth.h"
 #include "../../include/aruco_slam_hip.h"
 #include <string>
 #include <vector>
-#include <queue>
 #include <cfloat>
 #include <fstream>
 #include <sstream>
@@ -21,14 +21,10 @@
 #include <cmath>
 #include <algorithm>
 #include <chrono>
-#include <iterator>
 
 using namespace aslam;
 
 namespace {
-
-constexpr int kWinWidenFrames = 16;     // a window of at least this many frames is not widened to the next image size (64 -> 128 -> 192)
-constexpr int kWinChainFrames = 8;      // frames per chain kernel of a window (its log is replayed meanwhile); <= kWinPieceMax
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
@@ -194,12 +190,7 @@ struct aslam_ctx {
     ObsRaw* h_obs = nullptr;              // pinned: max_batch x kMarkerMax
     unsigned* h_nm = nullptr;             // pinned: max_batch
     WinFrame* h_win_frames = nullptr;     // pinned: max_batch frame plans (uploaded to ekf.d_win_frames per batch)
-    std::vector<int> m_id2idx;            // host mirror of the id -> landmark table, valid unless mirror_dirty
-    int m_L = 0;
-    // unconfirmed: the entry comes from an action-1 observation of a frame planned under the SLAM gate, whose verdict the host does
-    // not know (rejected: the device's list does not hold it).  Entries read back from the device are exact.
-    struct HostLast { int id; double z[3]; bool unconfirmed = false; };
-    std::vector<HostLast> m_last;         // host mirror of last_observed_marker_ (NaN z = unset)
+    PlanMirror mirror;                    // host mirror of the id -> landmark table, the landmark count and last_observed_marker_, valid unless mirror_dirty
     bool mirror_dirty = true;             // the device planned frames the host could not follow: read the tables back before planning
     int ekf_lo = 0, ekf_hi = 0;           // union of the slot ranges of EKF work enqueued since the last wait on ev_ekf
     double last_timing[6] = {0, 0, 0, 0, 0, 0};   // aslam_add_image, host clock, microseconds: upload, detection enqueue, EKF enqueue, wait, read-back / checks, total
@@ -217,9 +208,9 @@ struct aslam_ctx {
     double prof_ms[P_COUNT] = {0};
 };
 
-extern "C" int finalize_pending(aslam_ctx* c);      // defined with run_staged below (internal, not part of the C-ABI header)
-
 namespace {
+
+int finalize_pending(aslam_ctx* c);     // defined with run_staged below
 
 int fail(aslam_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -993,213 +984,125 @@ void note_ekf_range(aslam_ctx* c, int first, int count) {
 
 int read_mirror(aslam_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
-    c->m_id2idx.resize(kIdTableSize);
-    HIP_TRY(c, hipMemcpy(c->m_id2idx.data(), c->ekf.d_id2idx, sizeof(int) * kIdTableSize, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&c->m_L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
+    PlanMirror& M = c->mirror;
+    M.id2idx.resize(kIdTableSize);
+    HIP_TRY(c, hipMemcpy(M.id2idx.data(), c->ekf.d_id2idx, sizeof(int) * kIdTableSize, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&M.L, c->ekf.d_L, sizeof(int), hipMemcpyDeviceToHost));
     int nl = 0;
     HIP_TRY(c, hipMemcpy(&nl, c->ekf.d_nlast, sizeof(int), hipMemcpyDeviceToHost));
     nl = std::min(std::max(nl, 0), (int)kMarkerMax);
     std::vector<LastObs> h(std::max(nl, 1));
     if (nl) HIP_TRY(c, hipMemcpy(h.data(), c->ekf.d_last, sizeof(LastObs) * nl, hipMemcpyDeviceToHost));
-    c->m_last.resize(nl);
-    for (int i = 0; i < nl; i++) { c->m_last[i].id = h[i].id; c->m_last[i].unconfirmed = false; for (int k = 0; k < 3; k++) c->m_last[i].z[k] = h[i].z[k]; }
+    M.last.resize(nl);
+    for (int i = 0; i < nl; i++) { M.last[i].id = h[i].id; M.last[i].unconfirmed = false; for (int k = 0; k < 3; k++) M.last[i].z[k] = h[i].z[k]; }
     c->mirror_dirty = false;
     return ASLAM_OK;
 }
 
-// The EKF work of the pending batch: the host follows the reference's bookkeeping (checkLandmark, queue order, the
-// "stationary" test, aruco_slam.cpp:92-95, 192-198, 423-435) on the observations read back from the device and cuts the batch
-// into windows = runs of frames whose fused landmarks fit into one set S (ekf_window.hip); every other frame, and every frame
-// the host cannot decide (a marker id it does not know: a new landmark; one id twice), takes the per-frame chain, planned on the
-// device.  A window frame may fuse any subset of S and may drop "stationary" observations; S is the union over the window.
-// Under the SLAM gate (gated windows) the host plans as if every prepared correction were accepted.  The verdicts
-// matter to the plan in one place only: a "stationary" match against an entry of the mirror whose own correction may have been
-// rejected.  Such a frame is undecidable on the host and goes to the device with the rest of its batch, like a frame with an unknown
-// id; a match that fails needs no verdict (a rejected predecessor is absent from the list, an accepted one is too far away).
-static bool gated_windows(const aslam_ctx* c) { return c->slam_gate_on && c->slam_gate_windows && c->win_enabled && !c->win_pieces; }
-int finalize_pending(aslam_ctx* c) {
-    if (!c->pend.active) return ASLAM_OK;
-    const aslam_ctx::Pending p = c->pend;
-    c->pend.active = false;
-    HIP_TRY(c, hipEventSynchronize(c->ev_obs[p.ev]));
-    if (c->mirror_dirty) { int r = read_mirror(c); if (r) return r; }
-    if (c->ev_idx_set) HIP_TRY(c, hipEventSynchronize(c->ev_idx));          // the previous batch's upload has left the pinned rows
-    HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_obs[p.ev], 0));
-    struct FramePlan { std::vector<int> corr_idx, corr_det, pop_idx, pop_det, pop_act; int n_markers = 0; };
-    struct Op { int frame; bool predict; int K; std::vector<int> S; };      // K == 0: per-frame chain for `frame`; else a window of K frames on S
-    std::vector<Op> ops;
-    std::vector<FramePlan> plans(p.count);
-    // largest set S: contexts configured for few corrections per frame keep SP <= 128 (their chain steps stay cheap)
-    const int s_cap = c->ekf.win_sp_max >= 192 ? kWinSMax : 41;
-    int w_first = -1, w_K = 0;
-    std::vector<int> w_S;                                                   // sorted landmark indices of the open window
-    bool device_plans = false;
-    auto close_window = [&]() {
-        if (w_K == 0) return;
-        Op o{};
-        o.frame = w_first; o.predict = true;
-        if (w_K == 1) o.K = 0;                                              // a lone frame: the per-frame chain is as good
-        else { o.K = w_K; o.S = w_S; }
-        ops.push_back(o);
-        w_K = 0; w_S.clear();
-    };
-    for (int f = p.first; f < p.first + p.count; f++) {
-        const bool predict = c->is_init;            // addEncoder semantics (aruco_slam.cpp:24-29): the very first sample only arms the filter
-        c->is_init = true;
-        const ObsRaw* ob = c->h_obs + (size_t)f * kMarkerMax;
-        const int nM = (int)std::min(c->h_nm[f], (unsigned)kMarkerMax);
-        bool clean = !device_plans;
-        std::vector<std::pair<int, int>> pop;       // (landmark index, detection index) of the observations that pass the gates, pop order
-        int n_new = 0;
-        if (clean) {
-            // obs_.push(ob) in detection order into the reference's own priority queue (aruco_slam.h:85-88, aruco_slam.cpp:369-373):
-            // new markers (index -1) pop first, in libstdc++ heap order, and take the next landmark indices in that order (:256)
-            struct QItem { int idx, det; bool operator<(const QItem& o) const { return idx > o.idx; } };
-            std::priority_queue<QItem> q;
-            std::vector<int> seen;
-            for (int i = 0; i < nM && clean; i++) {
-                if (!ob[i].valid) continue;
-                const int id = ob[i].id;
-                if (id < 0 || id >= kIdTableSize || std::find(seen.begin(), seen.end(), id) != seen.end()) { clean = false; break; }   // one id twice (Q10): device
-                seen.push_back(id);
-                q.push(QItem{c->m_id2idx[id], i});
-            }
-            while (clean && !q.empty()) {
-                QItem it = q.top();
-                q.pop();
-                if (it.idx < 0) {
-                    if (c->m_L >= c->ekf.max_landmarks) { clean = false; break; }        // capacity: reported by the device
-                    it.idx = c->m_L++;
-                    c->m_id2idx[ob[it.det].id] = it.idx;
-                    n_new++;
-                }
-                pop.push_back({it.idx, it.det});
-            }
-        }
-        auto to_device = [&]() {
-            if (std::getenv("ASLAM_DEBUG_PLAN")) std::fprintf(stderr, "plan frame %d: nM %d left to the device\n", f, nM);
-            close_window();
-            device_plans = true;
-            c->plan_stats[3]++;
-            c->mirror_dirty = true;
-            Op o{};
-            o.frame = f; o.predict = predict; o.K = 0;
-            ops.push_back(o);
-        };
-        if (!clean) { to_device(); continue; }
-        // pop order = ascending landmark index (aruco_slam.h:85-88); "stationary" test against last frame's list (:192-198)
-        FramePlan& fp = plans[f - p.first];
-        fp.n_markers = nM;
-        int n_stationary = 0;
-        std::vector<aslam_ctx::HostLast> nlast(pop.size());
-        bool undecidable = false;
-        for (size_t j = 0; j < pop.size(); j++) {
-            const ObsRaw& o = ob[pop[j].second];
-            bool stationary = false;
-            if ((int)j < n_new) {                                            // augment branch: last_observation_ stays unset (Q3)
-                nlast[j].id = o.id;
-                nlast[j].z[0] = nlast[j].z[1] = nlast[j].z[2] = std::nan("");
-                continue;
-            }
-            for (const aslam_ctx::HostLast& l : c->m_last)
-                if (l.id == o.id) {                                          // std::find: first with the same id
-                    const double d0 = l.z[0] - o.x, d1 = l.z[1] - o.y, d2 = l.z[2] - o.th;
-                    stationary = std::sqrt(d0 * d0 + d1 * d1 + d2 * d2) < 0.01;     // NaN compares false
-                    undecidable = undecidable || (stationary && l.unconfirmed);     // the predecessor's verdict decides
-                    break;
-                }
-            n_stationary += stationary ? 1 : 0;
-            nlast[j].id = o.id;
-            if (stationary) { nlast[j].z[0] = nlast[j].z[1] = nlast[j].z[2] = std::nan(""); }
-            else { nlast[j].z[0] = o.x; nlast[j].z[1] = o.y; nlast[j].z[2] = o.th; nlast[j].unconfirmed = c->slam_gate_on; }
-            fp.pop_idx.push_back(pop[j].first); fp.pop_det.push_back(pop[j].second); fp.pop_act.push_back(stationary ? 2 : 1);
-            if (!stationary) { fp.corr_idx.push_back(pop[j].first); fp.corr_det.push_back(pop[j].second); }
-        }
-        if (undecidable) { to_device(); continue; }                            // (the mirror is read back before the next batch is planned)
-        c->m_last.swap(nlast);
-        const int m = (int)fp.corr_idx.size();
-        const bool eligible = predict && n_new == 0 && m <= kWinCorrMax && (int)pop.size() <= 64 && m <= s_cap && m <= c->init.max_updates_per_frame;
-        if (std::getenv("ASLAM_DEBUG_PLAN"))
-            std::fprintf(stderr, "plan frame %d: nM %d m %d new %d stationary %d predict %d eligible %d (window K %d, |S| %zu)\n", f, nM, m, n_new, n_stationary,
-                         (int)predict, (int)eligible, w_K, w_S.size());
-        if (!eligible) {
-            close_window();
-            Op o{};
-            o.frame = f; o.predict = predict; o.K = 0;
-            ops.push_back(o);
-            continue;
-        }
-        // does the frame fit into the open window?  (its landmarks are ascending, like S)
-        std::vector<int> un;
-        if (w_K > 0) std::set_union(w_S.begin(), w_S.end(), fp.corr_idx.begin(), fp.corr_idx.end(), std::back_inserter(un));
-        // a wider image makes every step of the window dearer: a window that is already long is closed rather than widened
-        const bool widens = w_K >= kWinWidenFrames && ekf_win_tiles((int)un.size()) > ekf_win_tiles((int)w_S.size());
-        if (w_K == 0 || w_K >= kWinFrames || (int)un.size() > s_cap || f != w_first + w_K || widens) {
-            close_window();
-            w_first = f; w_K = 0;
-            un = fp.corr_idx;
-        }
-        w_S.swap(un);
-        w_K++;
-    }
-    close_window();
-    // the plan of every window frame in the device's format (positions within the final S of its window), one upload per batch
-    bool any_window = false;
-    for (const Op& o : ops) {
-        if (o.K == 0) continue;
-        any_window = true;
-        for (int k = 0; k < o.K; k++) {
-            const FramePlan& fp = plans[o.frame + k - p.first];
-            WinFrame& wf = c->h_win_frames[o.frame + k];
-            wf.m = (int)fp.corr_idx.size(); wf.npop = (int)fp.pop_idx.size(); wf.n_markers = fp.n_markers; wf.pad = 0;
-            for (int a = 0; a < wf.m; a++) {
-                wf.cdet[a] = (unsigned char)fp.corr_det[a];
-                wf.cpos[a] = (unsigned char)(std::lower_bound(o.S.begin(), o.S.end(), fp.corr_idx[a]) - o.S.begin());
-            }
-            for (int i = 0; i < wf.npop; i++) {
-                wf.pdet[i] = (unsigned char)fp.pop_det[i]; wf.pact[i] = (unsigned char)fp.pop_act[i]; wf.pidx[i] = (short)fp.pop_idx[i];
-            }
-        }
-    }
-    if (any_window) {
-        HIP_TRY(c, hipMemcpyAsync(c->ekf.d_win_frames + p.first, c->h_win_frames + p.first, (size_t)p.count * sizeof(WinFrame),
-                                  hipMemcpyHostToDevice, c->stream_ekf));
-        HIP_TRY(c, hipEventRecord(c->ev_idx, c->stream_ekf));
-        c->ev_idx_set = true;
-    }
-    for (const Op& o : ops) {
-        if (o.K == 0) c->plan_stats[1]++;
-        else { c->plan_stats[0] += o.K; c->plan_stats[2]++; }
-    }
-    // Streams: sa = the EKF stream (chain pieces with their replay, per-frame chains), sb = the window's gather and its flush.  A window that is followed by another window does not wait for its own flush: the next window's P and mu_S are
-    // derived from this window's small results (launch_ekf_win_next, on sa) while the pass over Sigma runs on sb; only the next
-    // window's LAST piece (which writes mu back) and whatever is not a window wait for the flush.
+}  // extern "C": the window launcher below is internal
+
+namespace {
+bool gated_windows(const aslam_ctx* c) { return c->slam_gate_on && c->slam_gate_windows && c->win_enabled && !c->win_pieces; }
+
+hipEvent_t new_win_event(aslam_ctx* c) { return c->ev_win[c->ev_win_next++ & 63]; }
+
+// classic order: flush, then the EKF stream goes on
+int win_flush_now(aslam_ctx* c, const WinDesc& fwd) {
     hipStream_t sa = c->stream_ekf, sb = c->stream_win;
-    auto new_event = [&]() { return c->ev_win[c->ev_win_next++ & 63]; };
-    struct { bool active = false; WinDesc wd{}; hipEvent_t ev_flush = nullptr; } pf;   // the previous window's flush, not yet enqueued (and its predecessor's flush)
-    auto flush_now = [&](const WinDesc& fwd) -> int {                                    // classic order: flush, then the EKF stream goes on
-        hipEvent_t evr = new_event();
-        HIP_TRY(c, hipEventRecord(evr, sa));                         // the window's replay (Lambda, Psi, psi) is complete
-        HIP_TRY(c, hipStreamWaitEvent(sb, evr, 0));
-        prof_begin(c, P_EKF_WIN_FLUSH, sb);
-        launch_ekf_win_flush(sb, c->ekf, fwd);
+    hipEvent_t evr = new_win_event(c);
+    HIP_TRY(c, hipEventRecord(evr, sa));                             // the window's replay (Lambda, Psi, psi) is complete
+    HIP_TRY(c, hipStreamWaitEvent(sb, evr, 0));
+    prof_begin(c, P_EKF_WIN_FLUSH, sb);
+    launch_ekf_win_flush(sb, c->ekf, fwd);
+    prof_end(c);
+    hipEvent_t ev = new_win_event(c);
+    HIP_TRY(c, hipEventRecord(ev, sb));
+    HIP_TRY(c, hipStreamWaitEvent(sa, ev, 0));                       // whatever follows on the EKF stream sees the flushed Sigma
+    return ASLAM_OK;
+}
+
+int win_steps(const aslam_ctx* c, int first_slot, int K) {           // steps of K window frames: one per frame and one per correction
+    int n = 0;
+    for (int k = 0; k < K; k++) n += 1 + c->h_win_frames[first_slot + k].m;
+    return n;
+}
+
+// The whole window in one launch (ekf_window.hip: k_ekf_win_step, ONE): the chain, the replay of its log and the Psi
+// product follow each other through in-launch counters.  The chain leaves mu_S in its image only: k_ekf_win_fix puts it
+// back into the state, behind the previous window's flush, so the launch itself waits for nothing.
+void enqueue_window_one(aslam_ctx* c, const WinOp& o, const WinDesc& wd) {
+    hipStream_t sa = c->stream_ekf;
+    WinDesc cw = wd;
+    cw.first_slot = o.frame; cw.K = o.K; cw.piece = 0; cw.log0 = 0; cw.last = 1; cw.mu_out = 0;
+    if (++c->win_epoch == 0) c->win_epoch = 1;
+    cw.epoch = c->win_epoch;
+    cw.nsteps = win_steps(c, o.frame, o.K);
+    prof_begin(c, P_EKF_WIN_CHAIN, sa);
+    const bool gated = gated_windows(c);
+    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr);
+    prof_end(c);
+    if (gated) {                                                     // verdicts into records, counts, actions and the last-observed list
+        prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
+        launch_ekf_win_gate_finish(sa, c->ekf, cw, c->slam_gate, c->d_obs);
         prof_end(c);
-        hipEvent_t ev = new_event();
-        HIP_TRY(c, hipEventRecord(ev, sb));
-        HIP_TRY(c, hipStreamWaitEvent(sa, ev, 0));                   // whatever follows on the EKF stream sees the flushed Sigma
-        return ASLAM_OK;
-    };
+    }
+}
+
+// The pieces of the window (win_piece_sizes), back to back on the EKF stream: launch i carries the chain of piece i, the replay of
+// piece i - 1 and the Psi product of piece i - 2 (ekf_window.hip: k_ekf_win_step), so nothing but the stream orders them; two more
+// launches drain the replay.  What follows the window waits for that drain.
+int enqueue_window_pieces(aslam_ctx* c, const WinOp& o, const WinDesc& wd, hipEvent_t ev_prev_flush) {
+    hipStream_t sa = c->stream_ekf;
+    struct Piece { WinDesc sub; int nsteps; };
+    std::vector<Piece> pieces;
+    int log0 = 0, k0 = 0;
+    for (int kn : win_piece_sizes(o.K, c->win_piece)) {
+        Piece pc;
+        pc.sub = wd;
+        pc.sub.first_slot = o.frame + k0;
+        pc.sub.K = kn;
+        pc.sub.piece = (int)pieces.size();
+        pc.sub.log0 = log0;
+        pc.sub.last = k0 + kn == o.K ? 1 : 0;
+        pc.sub.mu_out = pc.sub.last;
+        pc.nsteps = win_steps(c, pc.sub.first_slot, kn);
+        log0 += pc.nsteps;
+        k0 += kn;
+        pieces.push_back(pc);
+    }
+    const int P = (int)pieces.size();
+    for (int i = 0; i < P + 2; i++) {
+        WinDesc cw = wd;
+        cw.K = 0;
+        if (i < P) cw = pieces[i].sub;
+        const Piece* ps = (i >= 1 && i <= P) ? &pieces[i - 1] : nullptr;
+        const Piece* pq = (i >= 2) ? &pieces[i - 2] : nullptr;
+        if (i < P && cw.last && ev_prev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, ev_prev_flush, 0));   // mu_S goes back into the state: after the previous flush's mu_R pass
+        prof_begin(c, i < P ? P_EKF_WIN_CHAIN : P_EKF_WIN_SCAN, sa);
+        launch_ekf_win_step(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, ps ? ps->sub.piece : 0, ps ? ps->sub.log0 : 0, ps ? ps->nsteps : 0,
+                            pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0);
+        prof_end(c);
+    }
+    return ASLAM_OK;
+}
+
+// Streams: sa = the EKF stream (chain pieces with their replay, per-frame chains), sb = the window's gather and its flush.  A window
+// that is followed by another window does not wait for its own flush: the next window's P and mu_S are derived from this window's
+// small results (launch_ekf_win_next, on sa) while the pass over Sigma runs on sb; only the next window's LAST piece (which writes
+// mu back) and whatever is not a window wait for the flush.
+int enqueue_plan(aslam_ctx* c, const std::vector<WinOp>& ops) {
+    hipStream_t sa = c->stream_ekf, sb = c->stream_win;
+    struct { bool active = false; WinDesc wd{}; hipEvent_t ev_flush = nullptr; } pf;   // the previous window's flush, not yet enqueued (and its predecessor's flush)
     for (size_t oi = 0; oi < ops.size(); oi++) {
-        const Op& o = ops[oi];
+        const WinOp& o = ops[oi];
         if (o.K == 0) {
-            if (pf.active) { int r = flush_now(pf.wd); if (r) return r; pf.active = false; }
+            if (pf.active) { int r = win_flush_now(c, pf.wd); if (r) return r; pf.active = false; }
             const double* e = &c->enc_host[(size_t)3 * o.frame];
             int r = run_ekf_frame(c, o.frame, e[0], e[1], e[2], o.predict);
             if (r) return r;
             continue;
         }
-        // One window = K frames on the set S.  Its chain is cut into pieces of a few frames on sa; the replay of each piece's
-        // log goes to sb, so that only the last piece's replay is not hidden behind the chain.
+        // One window = K frames on the set S: its chain on sa, its gather and its flush on sb
         WinDesc wd{};
         wd.nS = (int)o.S.size();
         wd.T = ekf_win_tiles(wd.nS);
@@ -1212,107 +1115,68 @@ int finalize_pending(aslam_ctx* c) {
             prof_begin(c, P_EKF_WIN_NEXT, sa);                       // (the previous window's Lambda, Psi, psi are complete: same stream)
             launch_ekf_win_next(sa, c->ekf, pf.wd, wd, c->win_next_split);
             prof_end(c);
-            hipEvent_t ev_next = new_event();
+            hipEvent_t ev_next = new_win_event(c);
             HIP_TRY(c, hipEventRecord(ev_next, sa));
             HIP_TRY(c, hipStreamWaitEvent(sb, ev_next, 0));          // the flush rewrites what launch_ekf_win_next reads (Sigma, mu, Y_0)
             prof_begin(c, P_EKF_WIN_FLUSH, sb);
             launch_ekf_win_flush(sb, c->ekf, pf.wd);
             prof_end(c);
-            ev_prev_flush = new_event();
+            ev_prev_flush = new_win_event(c);
             HIP_TRY(c, hipEventRecord(ev_prev_flush, sb));
             pf.active = false;
             wd.from_image = 1;
         } else {
-            hipEvent_t ev = new_event();
+            hipEvent_t ev = new_win_event(c);
             HIP_TRY(c, hipEventRecord(ev, sa));
             HIP_TRY(c, hipStreamWaitEvent(sb, ev, 0));               // Sigma as the EKF stream leaves it
         }
         launch_ekf_win_gather(sb, c->ekf, wd);                       // Y_0 of this window (behind the previous window's flush: same stream)
-        if (!c->win_pieces) {
-            // The whole window in one launch (ekf_window.hip: k_ekf_win_step, ONE): the chain, the replay of its log and the Psi
-            // product follow each other through in-launch counters.  The chain leaves mu_S in its image only: k_ekf_win_fix puts it
-            // back into the state, behind the previous window's flush, so the launch itself waits for nothing.
-            WinDesc cw = wd;
-            cw.first_slot = o.frame; cw.K = o.K; cw.piece = 0; cw.log0 = 0; cw.last = 1; cw.mu_out = 0;
-            if (++c->win_epoch == 0) c->win_epoch = 1;
-            cw.epoch = c->win_epoch;
-            cw.nsteps = 0;
-            for (int k = 0; k < o.K; k++) cw.nsteps += 1 + c->h_win_frames[o.frame + k].m;
-            prof_begin(c, P_EKF_WIN_CHAIN, sa);
-            const bool gated = gated_windows(c);
-            launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr);
-            prof_end(c);
-            if (gated) {                                             // verdicts into records, counts, actions and the last-observed list
-                prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
-                launch_ekf_win_gate_finish(sa, c->ekf, cw, c->slam_gate, c->d_obs);
-                prof_end(c);
-            }
-        } else {
-            // The pieces of the window, back to back on sa: launch i carries the chain of piece i, the replay of piece i - 1 and the Psi
-            // product of piece i - 2 (ekf_window.hip: k_ekf_win_step), so nothing but the stream orders them; two more launches drain
-            // the replay.  What follows the window waits for that drain: the pieces shrink towards the end (.., 4, 2, 1, 1 frames).
-            struct Piece { WinDesc sub; int nsteps; };
-            std::vector<Piece> pieces;
-            {
-                // piece sizes: the replay of piece i - 1 runs in the launch of piece i and takes about half as long per frame as the
-                // chain, so a piece may be at most twice as long as the one that follows it; from the window's end: 1, 1, 2, 4, 8, 8, ..
-                std::vector<int> sizes;
-                {
-                    int left = o.K, nxt = 1, count = 0;
-                    while (left > 0) {
-                        int kn = std::min(std::min(nxt, c->win_piece), left);
-                        sizes.push_back(kn);
-                        left -= kn;
-                        if (++count >= 2) nxt = std::min(2 * nxt, c->win_piece);       // 1, 1, 2, 4, ...
-                    }
-                    std::reverse(sizes.begin(), sizes.end());
-                }
-                int piece = 0, log0 = 0, k0 = 0;
-                for (int kn : sizes) {
-                    Piece pc;
-                    pc.sub = wd;
-                    pc.sub.first_slot = o.frame + k0;
-                    pc.sub.K = kn;
-                    pc.sub.piece = piece++;
-                    pc.sub.log0 = log0;
-                    pc.sub.last = k0 + kn == o.K ? 1 : 0;
-                    pc.sub.mu_out = pc.sub.last;
-                    pc.nsteps = 0;
-                    for (int k = 0; k < kn; k++) pc.nsteps += 1 + c->h_win_frames[pc.sub.first_slot + k].m;
-                    log0 += pc.nsteps;
-                    k0 += kn;
-                    pieces.push_back(pc);
-                }
-            }
-            const int P = (int)pieces.size();
-            for (int i = 0; i < P + 2; i++) {
-                WinDesc cw = wd;
-                cw.K = 0;
-                if (i < P) cw = pieces[i].sub;
-                const Piece* ps = (i >= 1 && i <= P) ? &pieces[i - 1] : nullptr;
-                const Piece* pq = (i >= 2) ? &pieces[i - 2] : nullptr;
-                if (i < P && cw.last && ev_prev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, ev_prev_flush, 0));   // mu_S goes back into the state: after the previous flush's mu_R pass
-                prof_begin(c, i < P ? P_EKF_WIN_CHAIN : P_EKF_WIN_SCAN, sa);
-                launch_ekf_win_step(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, ps ? ps->sub.piece : 0, ps ? ps->sub.log0 : 0, ps ? ps->nsteps : 0,
-                                    pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0);
-                prof_end(c);
-            }
-        }
+        if (!c->win_pieces) enqueue_window_one(c, o, wd);
+        else if (int r = enqueue_window_pieces(c, o, wd, ev_prev_flush)) return r;
         HIP_TRY(c, hipGetLastError());
         const bool next_is_window = oi + 1 < ops.size() && ops[oi + 1].K > 0 && !c->win_no_early;
         if (next_is_window) {
             pf.active = true; pf.wd = wd; pf.ev_flush = ev_prev_flush;
         } else {
-            int r = flush_now(wd);
+            int r = win_flush_now(c, wd);
             if (r) return r;
         }
     }
-    if (pf.active) { int r = flush_now(pf.wd); if (r) return r; }
+    if (pf.active) { int r = win_flush_now(c, pf.wd); if (r) return r; }
     HIP_TRY(c, hipGetLastError());
+    return ASLAM_OK;
+}
+
+// The EKF work of the pending batch: planned on the host (win_plan.h) from the observations read back from the device, then enqueued
+int finalize_pending(aslam_ctx* c) {
+    if (!c->pend.active) return ASLAM_OK;
+    const aslam_ctx::Pending p = c->pend;
+    c->pend.active = false;
+    HIP_TRY(c, hipEventSynchronize(c->ev_obs[p.ev]));
+    if (c->mirror_dirty) { int r = read_mirror(c); if (r) return r; }
+    if (c->ev_idx_set) HIP_TRY(c, hipEventSynchronize(c->ev_idx));          // the previous batch's upload has left the pinned rows
+    HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_obs[p.ev], 0));
+    const PlanLimits lim{c->ekf.max_landmarks, c->init.max_updates_per_frame, win_s_cap(c->ekf.win_sp_max), c->slam_gate_on};
+    const BatchPlan plan = plan_batch(c->mirror, c->is_init, c->mirror_dirty, lim, c->h_obs, c->h_nm, p.first, p.count, c->h_win_frames);
+    if (plan.any_window) {                                                  // the window frames' plans: one upload per batch
+        HIP_TRY(c, hipMemcpyAsync(c->ekf.d_win_frames + p.first, c->h_win_frames + p.first, (size_t)p.count * sizeof(WinFrame),
+                                  hipMemcpyHostToDevice, c->stream_ekf));
+        HIP_TRY(c, hipEventRecord(c->ev_idx, c->stream_ekf));
+        c->ev_idx_set = true;
+    }
+    c->plan_stats[3] += plan.frames_left_to_device;
+    for (const WinOp& o : plan.ops) {
+        if (o.K == 0) c->plan_stats[1]++;
+        else { c->plan_stats[0] += o.K; c->plan_stats[2]++; }
+    }
+    if (int r = enqueue_plan(c, plan.ops)) return r;
     HIP_TRY(c, hipEventRecord(c->ev_ekf, c->stream_ekf));
     note_ekf_range(c, p.first, p.count);
     return ASLAM_OK;
 }
+}  // namespace
+
+extern "C" {
 
 // the EKF steps of EKF slots [first, first + count) (frames, or rig steps' merged lists), behind the detection that produced them
 int schedule_ekf(aslam_ctx* c, int first, int count) {
@@ -1320,9 +1184,7 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
     if (c->mode == Mode::Localize) {           // frozen map: one k_loc_steps launch, not counted by aslam_get_plan_stats
         r = finalize_pending(c);
         if (r) return r;
-        const bool predict = c->is_init;       // addEncoder semantics (aruco_slam.cpp:24-29): the very first sample only arms the filter
-        c->is_init = true;
-        r = run_loc_steps(c, first, count, predict);
+        r = run_loc_steps(c, first, count, arm_filter(c->is_init));
         if (r) return r;
         HIP_TRY(c, hipEventRecord(c->ev_ekf, c->stream_ekf));
         note_ekf_range(c, first, count);
@@ -1337,9 +1199,7 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
         for (int i = 0; i < count; i++) {
             const double* e = &c->enc_host[(size_t)3 * (first + i)];
-            bool predict = c->is_init;         // addEncoder semantics (aruco_slam.cpp:24-29): the very first sample only arms the filter
-            c->is_init = true;
-            r = run_ekf_frame(c, first + i, e[0], e[1], e[2], predict);
+            r = run_ekf_frame(c, first + i, e[0], e[1], e[2], arm_filter(c->is_init));
             if (r) return r;
             c->plan_stats[1]++;
         }

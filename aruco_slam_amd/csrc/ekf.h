@@ -261,7 +261,7 @@ void reloc_free(RelocBufs& B);
 // a solved slot seats that robot's pose block in F; nullptr: the single filter's (mu_x, Sigma_xx of E, last-observed length 0)
 void launch_relocalize(hipStream_t st, const EkfState& E, const FleetState& F, const RelocParams& prm, const ObsRaw* obs,
                        const unsigned* n_markers, int first, int count, const int* robot_of_slot, int apply, RelocRecord* out);
-int ekf_win_tiles(int nS);             // T for a set of nS landmarks (4, 8 or 12)
+inline int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }   // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,
 // epoch set) in one launch, the three roles following each other through in-launch counters

@@ -98,8 +98,6 @@ __host__ __device__ inline size_t wsm_psi(int SPm, int par) { return (size_t)6 *
 __host__ __device__ inline size_t wsm_MU(int SPm, int par) { return (size_t)6 * SPm * SPm + (size_t)(2 + par) * SPm; }   // mu_S image
 __host__ __device__ inline size_t wsm_doubles(int SPm) { return (size_t)6 * SPm * SPm + (size_t)4 * SPm; }
 
-int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }
-
 __device__ __forceinline__ int win_state_index(const WinDesc& wd, int p) {      // state offset of position p of S
     return p < 3 ? p : wd.li[(p - 3) / 3] + (p - 3) % 3;
 }

@@ -9,7 +9,7 @@ other files only `window_to_window` hands over (in `two_groups` and `WIDE` a fra
 `sliding_set` widens its one window: they run here for the count 0 and the equality of everything else).  The cases below force
 what those lack:
 width changes 64 -> 128, 128 -> 64 (disjoint sets: only the pose rows in common), 192 -> 192 and 192 -> 64 (kWinWidenFrames,
-s_cap in finalize_pending: a window of 16 frames or more is closed rather than widened, and so is one whose union would pass
+s_cap in win_plan.h: a window of 16 frames or more is closed rather than widened, and so is one whose union would pass
 s_cap landmarks), a next window with one landmark (s' = 6), and next sets whose s' = 3 + 3 nS' is no multiple of 16 (all but
 `s48`, whose 15 landmarks make s' = 48 = 3 tiles exactly).
 
