@@ -173,6 +173,8 @@ _SIGS = {
     "aslam_default_relocalize_params": (None, [_P(RelocalizeParams)]),
     "aslam_relocalize": (C.c_int, [C.c_void_p, C.c_int, _P(RelocalizeParams), C.c_int, C.c_void_p]),
     "aslam_fleet_relocalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _P(RelocalizeParams), C.c_int, C.c_void_p]),
+    "aslam_slam_relocalize": (C.c_int, [C.c_void_p, C.c_int, _P(RelocalizeParams), C.c_int, C.c_void_p]),
+    "aslam_fleet_slam_relocalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _P(RelocalizeParams), C.c_int, C.c_void_p]),
     "aslam_default_gate_params": (None, [_P(GateParams)]),
     "aslam_set_innovation_gate": (C.c_int, [C.c_void_p, _P(GateParams)]),
     "aslam_get_innovation_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
@@ -649,6 +651,21 @@ class Context:
         out = np.zeros(max(rs.size, 1), RELOC_DTYPE)
         self._ck(self.lib.aslam_fleet_relocalize(self.h, int(first), int(rs.size), _ptr(rs, _ip), self._reloc_params(params), 1 if apply else 0,
                                                  out.ctypes.data_as(C.c_void_p)))
+        return out[:rs.size]
+
+    def slam_relocalize(self, slot, apply=True, **params):
+        """the SLAM (or rig SLAM) filter's pose from slot's observation list against its own map; with apply a solved
+        slot seats pose, Sigma_xx and the pose <-> landmark strip.  A RELOC_DTYPE record"""
+        out = np.zeros(1, RELOC_DTYPE)
+        self._ck(self.lib.aslam_slam_relocalize(self.h, int(slot), self._reloc_params(params), 1 if apply else 0, out.ctypes.data_as(C.c_void_p)))
+        return out[0]
+
+    def fleet_slam_relocalize(self, first, robots, apply=True, **params):
+        """fleet SLAM: slot first + i is robot robots[i]'s frame, solved against that robot's own map; one RELOC_DTYPE record per slot"""
+        rs = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(rs.size, 1), RELOC_DTYPE)
+        self._ck(self.lib.aslam_fleet_slam_relocalize(self.h, int(first), int(rs.size), _ptr(rs, _ip), self._reloc_params(params),
+                                                      1 if apply else 0, out.ctypes.data_as(C.c_void_p)))
         return out[:rs.size]
 
     # -- innovation gate and lost-track detection (DESIGN.md §19) ---------------------------------------------------------------

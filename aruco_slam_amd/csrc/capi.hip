@@ -28,11 +28,13 @@ namespace {
 
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
-              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_COUNT };
+              P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_SLAM_RELOC_SOLVE,
+              P_SLAM_RELOC_SEAT, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
-                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish"};
+                                   "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish",
+                                   "k_slam_reloc_solve", "k_slam_reloc_seat"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -144,6 +146,7 @@ struct aslam_ctx {
     FleetSlam fslam{};
     MergeBufs merge{};                    // map merge: tables allocated by the first merge, freed at aslam_fleet_end / aslam_destroy
     RelocBufs reloc{};                    // relocalization: result records, allocated by the first call, freed at the same two places
+    SlamRelocBufs slam_reloc{};           // SLAM relocalization: seat tables, allocated by the first call, freed where reloc is
     MapEditBufs map_edit{};               // landmark removal: src_of / meta tables, allocated by the first call, freed at aslam_destroy
     // innovation gate (aslam_set_innovation_gate): off unless set; only the localization and localization-fleet steps
     // look at it.  The health records (one per EKF slot, one track record per robot and one for the single filter) and their
@@ -881,6 +884,7 @@ void aslam_destroy(aslam_ctx* c) {
     ekf_fleet_free(c->fslam);
     merge_free(c->merge);
     reloc_free(c->reloc);
+    slam_reloc_free(c->slam_reloc);
     map_edit_free(c->map_edit);
     if (c->umap.cross) hipFree(c->umap.cross);
     if (c->d_map_c) hipFree(c->d_map_c);
@@ -2366,6 +2370,7 @@ int aslam_fleet_end(aslam_ctx* c) {
     { int rs = sync_streams(c); if (rs) return rs; }
     merge_free(c->merge);                               // the map merge's tables and record buffer, if a merge made them
     reloc_free(c->reloc);                               // the relocalization's result records, if a call made them
+    slam_reloc_free(c->slam_reloc);                     // the SLAM relocalization's seat tables, likewise
     return enter_mode(c, Mode::Slam);
 }
 
@@ -2659,6 +2664,78 @@ int aslam_fleet_relocalize(aslam_ctx* c, int first, int count, const int* robot_
                 if (int r = clear_cross(c, robot_of_slot[i], c->stream_ekf)) return r;
                 if (int r = clear_track_health(c, robot_of_slot[i], 1, c->stream_ekf)) return r;
             }
+    return ASLAM_OK;
+}
+
+// ---- SLAM relocalization: a lost SLAM filter against its own map (include/aruco_slam_hip.h) ----------------------
+namespace {
+// k_slam_reloc_solve and k_slam_reloc_seat on slots [first, first + count) on the EKF stream, behind the detection that produced
+// their lists and every EKF step enqueued so far (the caller has finalised a pending batch: its windows end with their flush on this
+// stream); the records back in one copy, one wait.  d_robots: the robots' indices on the device (a SLAM fleet), or nullptr
+int slam_relocalize_slots(aslam_ctx* c, const EkfState& base, size_t stride, int first, int count, const int* d_robots, const RelocParams& prm,
+                          int apply, aslam_relocalize_result* out) {
+    HIP_TRY(c, reloc_alloc(c->reloc, c->max_batch));
+    HIP_TRY(c, slam_reloc_alloc(c->slam_reloc, c->max_batch));
+    hipStream_t st = c->stream_ekf;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
+    SlamReloc A{};
+    A.base = base; A.stride = stride; A.robot_of_slot = d_robots; A.prm = prm; A.obs = c->d_obs; A.n_markers = c->d_nmarkers;
+    A.first = first; A.apply = apply; A.out = c->reloc.d; A.seat = c->slam_reloc.seat;
+    prof_begin(c, P_SLAM_RELOC_SOLVE, st);
+    launch_slam_reloc_solve(st, A, count);
+    prof_end(c);
+    prof_begin(c, P_SLAM_RELOC_SEAT, st);
+    launch_slam_reloc_seat(st, A, count);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->reloc.h, c->reloc.d, sizeof(RelocRecord) * count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int i = 0; i < count; i++) {
+        const RelocRecord& r = c->reloc.h[i];
+        aslam_relocalize_result& o = out[i];
+        o.status = r.status; o.n_candidates = r.n_candidates; o.n_inliers = r.n_inliers; o.runner_up = r.runner_up; o.best = r.best;
+        std::memcpy(o.pose, r.pose, sizeof(o.pose));
+        std::memcpy(o.sigma, r.sigma, sizeof(o.sigma));
+    }
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_slam_relocalize(aslam_ctx* c, int slot, const aslam_relocalize_params* params, int apply, aslam_relocalize_result* out) {
+    if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kSlam)) return r;
+    RelocParams prm{};
+    if (int r = reloc_params(c, params, prm)) return r;
+    if (int r = check_slot_range(c, slot, 1)) return r;
+    if (int r = finalize_pending(c)) return r;
+    if (int r = slam_relocalize_slots(c, c->ekf, 0, slot, 1, nullptr, prm, apply ? 1 : 0, out)) return r;
+    if (apply && out->status == 0) {                                            // seated: the window planner's mirror holds the old last-observed list
+        c->mirror_dirty = true;
+        return clear_track_health(c, kTrackSingle, 1, c->stream_ekf);
+    }
+    return ASLAM_OK;
+}
+
+int aslam_fleet_slam_relocalize(aslam_ctx* c, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params, int apply,
+                                aslam_relocalize_result* out) {
+    if (!c || !robot_of_slot || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (int r = allow(c, kFleetSlam)) return r;
+    RelocParams prm{};
+    if (int r = reloc_params(c, params, prm)) return r;
+    if (int r = check_slot_range(c, first, count)) return r;
+    std::vector<char> seen(c->fleet_n, 0);
+    for (int i = 0; i < count; i++) {
+        if (robot_of_slot[i] < 0 || robot_of_slot[i] >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+        if (seen[robot_of_slot[i]]) return fail(c, ASLAM_E_INVALID, "a robot named twice in one aslam_fleet_slam_relocalize");
+        seen[robot_of_slot[i]] = 1;
+    }
+    if (int r = finalize_pending(c)) return r;
+    if (int r = pinned_upload(c, c->fleet_work_up, c->d_fleet_work, robot_of_slot, count, c->stream_ekf)) return r;
+    if (int r = slam_relocalize_slots(c, c->fslam.base, c->fslam.stride, first, count, c->d_fleet_work, prm, apply ? 1 : 0, out)) return r;
+    if (apply)
+        for (int i = 0; i < count; i++)
+            if (out[i].status == 0)                                            // seated as by aslam_fleet_set_state: the arming stays
+                if (int r = clear_track_health(c, robot_of_slot[i], 1, c->stream_ekf)) return r;
     return ASLAM_OK;
 }
 

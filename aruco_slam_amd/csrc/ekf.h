@@ -261,6 +261,36 @@ void reloc_free(RelocBufs& B);
 // a solved slot seats that robot's pose block in F; nullptr: the single filter's (mu_x, Sigma_xx of E, last-observed length 0)
 void launch_relocalize(hipStream_t st, const EkfState& E, const FleetState& F, const RelocParams& prm, const ObsRaw* obs,
                        const unsigned* n_markers, int first, int count, const int* robot_of_slot, int apply, RelocRecord* out);
+// SLAM relocalization (slam_relocalize.h): a SLAM filter's pose from one slot's list against the filter's own map,
+// with Sigma_xx' and the strip Sigma_lx' that follow to first order.  Per slot of a call one seat table, written by
+// k_slam_reloc_solve and read by k_slam_reloc_seat, in a device buffer made on first use; the records are RelocBufs'.
+constexpr int kSlamRelocTile = 256;    // state indices (= lanes) of a k_slam_reloc_seat workgroup
+struct SlamRelocSeat {
+    int n_sup, N;                      // supporters fused (0: the slot is unsolved, nothing to seat); the state size 3 + 3 L the solve saw
+    double m[3];                       // the pose
+    double meas[9];                    // sum_j A_j (J_j R_j J_j^T) A_j^T: the measurement term of Sigma_xx', row-major, symmetric
+    int idx[kMarkerMax];               // per supporter, in list order: its landmark index
+    double M[kMarkerMax][9];           // ... and M_j = Lambda^-1 C_j^-1 G_j, row-major
+};
+struct SlamRelocBufs {
+    SlamRelocSeat* seat;               // one table per slot of a call (nullptr: none)
+    int cap;
+};
+struct SlamReloc {                     // kernel argument of both kernels: workgroup (slot) i works on slot first + i, record out[i], seat[i]
+    EkfState base;                     // the single filter, or robot 0's of a SLAM fleet
+    size_t stride;                     // as in FleetSlam (0 for the single filter)
+    const int* robot_of_slot;          // device, one robot per slot of the call; nullptr: the single filter
+    RelocParams prm;
+    const ObsRaw* obs;                 // the context's per-slot lists and their lengths
+    const unsigned* n_markers;
+    int first, apply;
+    RelocRecord* out;
+    SlamRelocSeat* seat;
+};
+hipError_t slam_reloc_alloc(SlamRelocBufs& B, int slots);
+void slam_reloc_free(SlamRelocBufs& B);
+void launch_slam_reloc_solve(hipStream_t st, const SlamReloc& A, int count);   // record (sigma left zero) and seat table of every slot
+void launch_slam_reloc_seat(hipStream_t st, const SlamReloc& A, int count);    // sigma of every solved record; with apply the seat itself
 inline int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }   // T for a set of nS landmarks (4, 8 or 12)
 // one launch of a window: the chain of piece wd (wd.K == 0: none), the replay (scan) of piece s_*, the Psi product of piece q_*
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,

@@ -1609,3 +1609,4 @@ void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
 #include "fleet_merge.h"      // map merge: k_fleet_export_maps, k_merge_*, and their launchers
 #include "relocalize.h"       // relocalization: k_relocalize, one workgroup per slot, and its launcher
 #include "map_edit.h"         // landmark removal: k_map_plan, k_map_cols, k_map_rows, and their launchers
+#include "slam_relocalize.h"  // SLAM relocalization: k_slam_reloc_solve, k_slam_reloc_seat, and their launchers

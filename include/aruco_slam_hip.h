@@ -469,6 +469,49 @@ int aslam_relocalize(aslam_ctx* ctx, int slot, const aslam_relocalize_params* pa
 int aslam_fleet_relocalize(aslam_ctx* ctx, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params,
                            int apply, aslam_relocalize_result* out /* count */);
 
+/* ---- SLAM relocalization: a lost SLAM filter against its own, live map (no reference counterpart) -----------------
+ * The recovery that follows `lost` in SLAM, rig SLAM and fleet SLAM (the two gate sections below), and the inverse of the reference's
+ * augment: the augment makes a landmark a function of the pose and an observation, this makes the pose a function of landmarks and
+ * observations.  A pose derived from the map's own landmarks is correlated with exactly those landmarks; a seat that wrote Sigma_xl =
+ * 0 would make the next corrections count the same information twice.  So the covariance follows to first order, on the device, in
+ * place: Sigma_xx' AND the strip Sigma_lx'.  Parameters, defaults, the result struct and the ASLAM_E_INVALID cases are those of the
+ * section above.
+ * The filter has mean mu, covariance Sigma (column-major, N = 3 + 3 L) and its id table.  For one slot, over its first nM =
+ * min(number of observations, 128) observations in list order:
+ * 1. Candidates, hypotheses, consensus, winner, runner-up and status are steps 1-4 of the section above, word for word; the "map" is
+ *    the filter's own: id -> landmark index i through its id table, (lx, ly, lt) = mu[3 + 3 i .. 5 + 3 i].  An empty map gives
+ *    status 1.
+ * 2. Fusion weights.  For supporter j of the winner b, in ascending list position, with landmark index i_j: c, s = cos, sin of
+ *    theta_j and (x, y) the observation's; J_j as in step 5 above; G_j = d hypothesis / d landmark = [[1, 0, s x + c y], [0, 1,
+ *    -(c x - s y)], [0, 0, 1]]; P_j = the 3 x 3 block Sigma(3 + 3 i_j.., 3 + 3 i_j..), taken from its upper triangle and mirrored;
+ *    C_j = J_j diag(r_j) J_j^T + G_j P_j G_j^T (upper triangle, mirrored); Lambda = sum_j C_j^-1; d_j = m_j - m0 with the heading
+ *    wrapped; m = m0 + Lambda^-1 sum_j C_j^-1 d_j with the heading wrapped; A_j = Lambda^-1 C_j^-1 and M_j = A_j G_j.
+ * 3. Covariance, first order and exact for these weights.  B is 3 x N and zero except B[:, 3 + 3 i_j .. 5 + 3 i_j] += M_j (an id
+ *    sighted twice adds twice).  Sigma_lx' = Sigma_ll B^T, read as Sigma(c, 3 + 3 i_j + k) for c = 3 .. N - 1 (the landmark's
+ *    columns), accumulated in ascending j.  Sigma_xx' = sum_j A_j (J_j diag(r_j) J_j^T) A_j^T + B Sigma B^T, upper triangle mirrored.
+ *    pose = m, sigma = Sigma_xx' (row-major).  With Sigma_ll = 0 this is the section above's Lambda^-1.
+ * 4. Seat (apply != 0 and status 0): mu[0..2] = m; Sigma(0..2, 0..2) = Sigma_xx'; rows 3 .. N - 1 of columns 0..2 receive
+ *    Sigma_lx' and columns 3 .. N - 1 of rows 0..2 its transpose, bit for bit; the last-observed list is emptied.  Nothing else is
+ *    written: not mu_l, not Sigma_ll, not the id tables, nothing at or beyond index N.  The arming is left as it is (as
+ *    aslam_set_state / aslam_fleet_set_state leave it); the filter's track record of the SLAM gate is cleared.
+ * 5. Unsolved slots, and every slot with apply = 0, write nothing but the record.
+ * 6. No floating-point atomic and a fixed order of every sum: a slot's record and seat do not depend on the other slots of the call.
+ * Dropped: the weights ignore the cross-correlation between DIFFERENT landmarks (the estimator stays unbiased and the reported
+ * covariance is exact for the weights used; it is not the generalised-least-squares optimum); no accumulation over several frames; no
+ * relinearisation; the old pose's information is discarded entirely - that is the point.  The default tolerances are the section
+ * above's, as unmeasured.
+ * Both calls are synchronous: two kernel launches behind the detection and the EKF steps submitted so far (a batch still pending is
+ * enqueued first), so they may follow aslam_run_staged / aslam_fleet_run_staged (with_ekf = 0) or an injection directly.  The seat
+ * tables live in a device buffer of max_batch entries allocated by the first call and freed by aslam_fleet_end / aslam_destroy.
+ * aslam_slam_relocalize: SLAM and rig SLAM (any camera's slot: its list is already in the base frame); ASLAM_E_STATE while
+ * localizing and in either kind of fleet.  aslam_relocalize keeps refusing outside localization. */
+int aslam_slam_relocalize(aslam_ctx* ctx, int slot, const aslam_relocalize_params* params, int apply, aslam_relocalize_result* out);
+/* slot first + i belongs to robot robot_of_slot[i], its result is out[i].  Only in fleet SLAM (ASLAM_E_STATE otherwise;
+   aslam_fleet_relocalize keeps refusing a SLAM fleet); ASLAM_E_INVALID: a slot range outside [0, max_batch), a robot index outside
+   the fleet, a robot named twice.  With apply every solved robot's filter is seated as above; unsolved robots are untouched. */
+int aslam_fleet_slam_relocalize(aslam_ctx* ctx, int first, int count, const int* robot_of_slot, const aslam_relocalize_params* params,
+                                int apply, aslam_relocalize_result* out /* count */);
+
 /* ---- innovation gate and lost-track detection for localization and localization fleets ------------------------
  * The reference tests every correction with `ze.norm() >= 1 || K.norm() >= 10` (aruco_slam.cpp:156-175) but only prints the result
  * ("Outlier test logs only"; the skip is a commented-out `continue`).  Here the test becomes a chi-square gate
@@ -504,7 +547,8 @@ int aslam_fleet_relocalize(aslam_ctx* ctx, int first, int count, const int* robo
  * fewer than min_attempted corrections leaves it; the streak is carried across the slots of a call and across calls.  Every seat
  * clears the record: aslam_localize_begin, aslam_fleet_begin, aslam_fleet_set_pose, and a solved apply != 0 of aslam_relocalize /
  * aslam_fleet_relocalize (the solved robots only).  `lost` only reports: the gate works the same way afterwards, and recovery is the
- * caller's aslam_relocalize / aslam_fleet_relocalize.
+ * caller's aslam_relocalize / aslam_fleet_relocalize (in the SLAM modes, under the SLAM gate below: aslam_slam_relocalize /
+ * aslam_fleet_slam_relocalize).
  * Defaults: gate_d2 = 16.266, the 0.999 quantile of chi-square with 3 degrees of freedom; min_attempted 2, min_accept_percent 50,
  * lost_after 3.  They are the maintainer's choice; nobody has measured them.  ASLAM_E_INVALID: gate_d2 not > 0 (NaN included; +inf
  * is allowed), min_attempted < 1, min_accept_percent outside [0, 100], lost_after < 1.
@@ -558,7 +602,9 @@ int aslam_fleet_get_health(aslam_ctx* ctx, int max, int* n_robots, aslam_track_h
  * (the single filter's; robot r's in fleet SLAM), with the fields and the integer streak rule of the section above, carried across
  * slots, rounds and calls on the device.  Every seat of a SLAM filter clears its track record: aslam_set_state, aslam_load_state,
  * aslam_localize_end and aslam_fleet_end (the single filter starts anew), aslam_fleet_slam_begin (every robot), aslam_fleet_set_state,
- * aslam_remove_landmarks and aslam_fleet_remove_landmarks (the robots named).  `lost` only reports.
+ * aslam_remove_landmarks and aslam_fleet_remove_landmarks (the robots named), and a solved apply != 0 of aslam_slam_relocalize /
+ * aslam_fleet_slam_relocalize (the solved robots only).  `lost` only reports: recovery is the caller's aslam_slam_relocalize /
+ * aslam_fleet_slam_relocalize.
  * aslam_get_slot_health, aslam_get_track_health and aslam_fleet_get_health are readable in the SLAM modes exactly while the SLAM gate
  * is set (slot records: SLAM, rig SLAM, fleet SLAM; aslam_get_track_health: SLAM and rig SLAM; aslam_fleet_get_health: fleet SLAM);
  * with only the innovation gate set they refuse there with ASLAM_E_STATE.  The record storage is the section above's, made by
