@@ -758,7 +758,13 @@ class Context:
         self._ck(self.lib.aslam_stream_open(self.h, int(rows), int(cols), int(channels), int(frames_per_submit)))
 
     def stream_push(self, img, wl, wr, dt):
-        img = np.ascontiguousarray(img, dtype=np.uint8)
+        """one frame, gray (rows, cols) or bgr8 (rows, cols, 3); rows may be padded (a view into a wider array): the array goes
+        through as it is, with its strides[0], when each row is contiguous in itself, and is copied only otherwise"""
+        img = np.asarray(img)
+        row = img.shape[1] * (img.shape[2] if img.ndim == 3 else 1) if img.ndim in (2, 3) else -1
+        if (img.dtype != np.uint8 or row < 0 or img.strides[1:] != ((1,) if img.ndim == 2 else (img.shape[2], 1))
+                or (img.shape[0] > 1 and img.strides[0] < row)):
+            img = np.ascontiguousarray(img, dtype=np.uint8)
         self._ck(self.lib.aslam_stream_push(self.h, img.ctypes.data_as(C.c_void_p), img.strides[0], float(wl), float(wr), float(dt)))
 
     def stream_slot(self, rows, cols, channels=1):

@@ -64,6 +64,8 @@ struct aslam_ctx {
     uint8_t* h_ring = nullptr;            // two half batches of page-locked frames
     std::vector<double> ring_enc;         // encoder samples of the half being filled
     int ring_H = 0, ring_half = 0, ring_fill = 0;
+    int ring_rows = 0, ring_cols = 0, ring_channels = 0;   // the frame shape the ring was opened with: its addressing never follows
+    size_t ring_fb = 0;                   // the context's live shape (bytes per frame = ring_rows * ring_cols * ring_channels)
     bool ring_acquired = false;
     hipStream_t stream_ekf = nullptr;     // EKF chain (sequential over frames); overlaps the next batch's detection
     hipEvent_t ev_detect = nullptr, ev_ekf = nullptr;
@@ -1428,10 +1430,29 @@ int aslam_get_rig_step_ekf_stats(aslam_ctx* c, int first_step, int count, int* s
 }
 
 // ---- host-fed stream: pinned ring, asynchronous upload (include/aruco_slam_hip.h) --------------------------------------
+namespace {
+bool ring_shape_is_live(const aslam_ctx* c) {
+    return c->rows == c->ring_rows && c->cols == c->ring_cols && c->channels == c->ring_channels && c->in_frame_bytes == c->ring_fb;
+}
+
+// the ring keeps the frame shape of its aslam_stream_open; a call that reconfigured the context since (aslam_stage_frames, aslam_add_image,
+// aslam_detect_batch, aslam_synth_render) leaves it unusable until it is opened again: the detector would read the slots at another shape
+int ring_usable(aslam_ctx* c) {
+    if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
+    if (!ring_shape_is_live(c)) {
+        char buf[224];
+        snprintf(buf, sizeof(buf), "the frame shape changed since aslam_stream_open (ring %d x %d x %d, context %d x %d x %d): aslam_stream_open again",
+                 c->ring_rows, c->ring_cols, c->ring_channels, c->rows, c->cols, c->channels);
+        return fail(c, ASLAM_E_STATE, buf);
+    }
+    return ASLAM_OK;
+}
+}  // namespace
+
 int ring_submit(aslam_ctx* c) {
     const int n = c->ring_fill, h = c->ring_half, H = c->ring_H;
     if (n == 0) return ASLAM_OK;
-    const size_t fb = c->in_frame_bytes;
+    const size_t fb = c->ring_fb;
     const int slot0 = h * H;
     if (c->ev_det_set[h]) HIP_TRY(c, hipStreamWaitEvent(c->stream_copy, c->ev_det[h], 0));     // the detector still reads these slots
     if (c->pend.active && slot0 < c->pend.first + c->pend.count && c->pend.first < slot0 + n) { int rp = finalize_pending(c); if (rp) return rp; }
@@ -1459,12 +1480,25 @@ int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames
     if (!c) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
     if (frames_per_submit < 1 || 2 * frames_per_submit > c->max_batch) return fail(c, ASLAM_E_INVALID, "frames_per_submit must be in [1, max_batch / 2]");
-    int r = sync_streams(c);
+    int r = ASLAM_OK;
+    if (c->h_ring && c->ring_fill > 0) {       // committed frames of the ring that goes away: into the filter first, as aslam_stream_flush does
+        if (!ring_shape_is_live(c)) {          // (at the shape they were committed with)
+            r = configure_frames(c, c->ring_rows, c->ring_cols, c->ring_channels);
+            if (r) return r;
+            c->in_frame_bytes = c->ring_fb;
+        }
+        r = ring_submit(c);
+        if (r) return r;
+        r = sync_and_check(c);
+        if (r) return r;
+    }
+    r = sync_streams(c);
     if (r) return r;
     r = configure_frames(c, rows, cols, channels);
     if (r) return r;
     c->in_frame_bytes = (size_t)rows * cols * channels;
     if (c->h_ring) { hipHostFree(c->h_ring); c->h_ring = nullptr; }
+    c->ring_fill = 0; c->ring_acquired = false;
     HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ring), (size_t)2 * frames_per_submit * c->in_frame_bytes, hipHostMallocDefault));
     if (!c->stream_copy) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
@@ -1474,7 +1508,8 @@ int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames
         }
     }
     c->ev_det_set[0] = c->ev_det_set[1] = c->ev_up_set[0] = c->ev_up_set[1] = false;
-    c->ring_H = frames_per_submit; c->ring_half = 0; c->ring_fill = 0; c->ring_acquired = false;
+    c->ring_H = frames_per_submit; c->ring_half = 0;
+    c->ring_rows = rows; c->ring_cols = cols; c->ring_channels = channels; c->ring_fb = c->in_frame_bytes;
     c->ring_enc.assign((size_t)3 * frames_per_submit, 0.0);
     return ASLAM_OK;
 }
@@ -1482,10 +1517,10 @@ int aslam_stream_open(aslam_ctx* c, int rows, int cols, int channels, int frames
 int aslam_stream_acquire(aslam_ctx* c, uint8_t** px, size_t* step) {
     if (!c || !px) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
-    if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
+    if (int r = ring_usable(c)) return r;
     if (!c->have_cam) return fail(c, ASLAM_E_STATE, "camera parameters not set (aslam_set_camera)");
-    *px = c->h_ring + ((size_t)c->ring_half * c->ring_H + c->ring_fill) * c->in_frame_bytes;
-    if (step) *step = (size_t)c->cols * c->channels;
+    *px = c->h_ring + ((size_t)c->ring_half * c->ring_H + c->ring_fill) * c->ring_fb;
+    if (step) *step = (size_t)c->ring_cols * c->ring_channels;
     c->ring_acquired = true;
     return ASLAM_OK;
 }
@@ -1494,6 +1529,7 @@ int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
     if (!c) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
     if (!c->ring_acquired) return fail(c, ASLAM_E_STATE, "aslam_stream_acquire first");
+    if (int r = ring_usable(c)) return r;
     c->ring_acquired = false;
     double* e = &c->ring_enc[(size_t)3 * c->ring_fill];
     e[0] = wl; e[1] = wr; e[2] = dt;
@@ -1504,20 +1540,21 @@ int aslam_stream_commit(aslam_ctx* c, double wl, double wr, double dt) {
 int aslam_stream_push(aslam_ctx* c, const uint8_t* px, size_t step, double wl, double wr, double dt) {
     if (!c || !px) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
+    const bool held = c->ring_acquired;        // a slot handed out by aslam_stream_acquire: a refused push leaves it as it was
     uint8_t* dst = nullptr;
     size_t dstep = 0;
     int r = aslam_stream_acquire(c, &dst, &dstep);
     if (r) return r;
-    if (step < dstep) { c->ring_acquired = false; return fail(c, ASLAM_E_INVALID, "step smaller than a row"); }
-    if (step == dstep) std::memcpy(dst, px, (size_t)c->rows * dstep);
-    else for (int y = 0; y < c->rows; y++) std::memcpy(dst + (size_t)y * dstep, px + (size_t)y * step, dstep);
+    if (step < dstep) { c->ring_acquired = held; return fail(c, ASLAM_E_INVALID, "step smaller than a row"); }
+    if (step == dstep) std::memcpy(dst, px, (size_t)c->ring_rows * dstep);
+    else for (int y = 0; y < c->ring_rows; y++) std::memcpy(dst + (size_t)y * dstep, px + (size_t)y * step, dstep);
     return aslam_stream_commit(c, wl, wr, dt);
 }
 
 int aslam_stream_flush(aslam_ctx* c) {
     if (!c) return ASLAM_E_INVALID;
     if (int r = allow(c, kSingle)) return r;
-    if (!c->h_ring) return fail(c, ASLAM_E_STATE, "aslam_stream_open first");
+    if (int r = ring_usable(c)) return r;
     int r = ring_submit(c);
     if (r) return r;
     return sync_and_check(c);

@@ -659,7 +659,18 @@ int aslam_load_state(aslam_ctx* ctx, const char* path);
  * for the call only); aslam_stream_acquire / aslam_stream_commit hand the pinned slot to the producer instead (no host
  * copy).  Every frames_per_submit frames the half is uploaded on a copy stream and its detection + EKF steps are
  * enqueued, so the upload of one half overlaps the processing of the other; the calls only block when the ring is full.
- * aslam_stream_flush submits what is pending, waits and reports device-side overflow; then the getters are valid. */
+ * aslam_stream_flush submits what is pending, waits and reports device-side overflow; then the getters are valid.
+ * A half is submitted when it holds frames_per_submit frames, or at a flush if it holds at least one; a submit moves on to the
+ * other half; a flush with nothing pending submits nothing and stays on its half.  Frame k of a half of the ring lands in
+ * slot half * frames_per_submit + k.
+ * - The ring keeps the frame shape (rows, cols, channels) of its aslam_stream_open.  A call that gives the context another
+ *   frame shape afterwards (aslam_stage_frames, aslam_add_image(s), aslam_detect_batch, aslam_synth_render with other rows,
+ *   cols or channels) leaves the stream unusable: aslam_stream_acquire, _push, _commit and _flush then return ASLAM_E_STATE
+ *   and do nothing, until aslam_stream_open is called again.  Nothing is reconfigured silently.
+ * - aslam_stream_open on an open stream first submits the frames already committed and waits for them, as aslam_stream_flush
+ *   does (at the shape they were committed with, and also when the new rows, cols or channels are then refused), so no committed
+ *   frame is lost; a slot that was acquired but not committed is dropped.  The filter carries on across the call.
+ * - A refused aslam_stream_push (step_bytes smaller than a row) consumes no slot. */
 int aslam_stream_open(aslam_ctx* ctx, int rows, int cols, int channels, int frames_per_submit);
 int aslam_stream_push(aslam_ctx* ctx, const uint8_t* px, size_t step_bytes, double wl, double wr, double dt);
 int aslam_stream_acquire(aslam_ctx* ctx, uint8_t** px, size_t* step_bytes);
