@@ -184,6 +184,8 @@ struct aslam_ctx {
     unsigned win_epoch = 0;               // one-launch windows enqueued so far: the tag of a window's hand-off counters
     bool win_no_early = false;            // ASLAM_WIN_NO_EARLY: every window waits for its own flush (test / comparison knob)
     bool win_next_split = false;          // ASLAM_WIN_NEXT_SPLIT: the early start as four launches instead of one kernel (comparison knob)
+    int win_logger_parts = 3;             // ASLAM_WIN_LOGGER_PARTS: what the chain's logger wave takes over from the prepare wave (bit 0: the header's S^-1,
+                                          // bit 1: mu_S; 0: the prepare wave does both, the comparison path)
     struct Pending { bool active = false; int first = 0, count = 0, ev = 0; } pend;
     hipEvent_t ev_obs[2] = {nullptr, nullptr}, ev_idx = nullptr;
     hipStream_t stream_win = nullptr;     // scan / flush of the windows, beside the chain on stream_ekf
@@ -784,6 +786,7 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
     c->win_enabled = std::getenv("ASLAM_NO_WINDOWS") == nullptr;
     c->win_no_early = std::getenv("ASLAM_WIN_NO_EARLY") != nullptr;
     c->win_next_split = std::getenv("ASLAM_WIN_NEXT_SPLIT") != nullptr;
+    if (const char* e = std::getenv("ASLAM_WIN_LOGGER_PARTS")) c->win_logger_parts = std::atoi(e) & 3;
     if (const char* e = std::getenv("ASLAM_WIN_PIECE")) { c->win_piece = std::min(kWinChainFrames, std::max(1, std::atoi(e))); c->win_pieces = true; }
     const int B = c->max_batch;
     const size_t px = (size_t)init->max_rows * init->max_cols;
@@ -1045,7 +1048,7 @@ void enqueue_window_one(aslam_ctx* c, const WinOp& o, const WinDesc& wd) {
     cw.nsteps = win_steps(c, o.frame, o.K);
     prof_begin(c, P_EKF_WIN_CHAIN, sa);
     const bool gated = gated_windows(c);
-    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr);
+    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts);
     prof_end(c);
     if (gated) {                                                     // verdicts into records, counts, actions and the last-observed list
         prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);

@@ -296,8 +296,10 @@ inline int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }   
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,
 // epoch set) in one launch, the three roles following each other through in-launch counters
 // gate != nullptr: the gated instantiation, to be followed on the same stream by launch_ekf_win_gate_finish
+// logger_parts: what the chain's logger wave takes over from its prepare wave (bit 0: the log header's S^-1, bit 1: mu_S; the
+// results are the same to the bit whatever it is, 0 is the comparison path)
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
-                        const SlamGateArg* gate = nullptr);
+                        const SlamGateArg* gate = nullptr, int logger_parts = 3);
 // behind a gated window: slot records and accepted counts of its K frames, the track record, the last frame's actions and last-observed list
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs);
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,

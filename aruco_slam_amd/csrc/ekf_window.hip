@@ -72,8 +72,13 @@ template <int NC> __device__ __forceinline__ void win_vmcnt_lag() {
 // development aid (make FLAGS+=-DASLAM_WIN_STAMPS): cycle stamps of the prepare wave's step phases, of the workers and of the logger wave, summed over a piece
 #ifdef ASLAM_WIN_STAMPS
 #define WSTAMP(i) do { const long long t_ = clock64(); stamp_acc[i] += t_ - stamp_last; stamp_last = t_; } while (0)
+// (a stamp orders nothing but volatile statements: a bucket of arithmetic is held between its stamps by its inputs and its result)
+#define WSTAMP_AFTER(x) asm volatile("" : "+v"(x))
+#define WSTAMP_BEFORE(x) asm volatile("" :: "v"(x))
 #else
 #define WSTAMP(i) do { } while (0)
+#define WSTAMP_AFTER(x) do { } while (0)
+#define WSTAMP_BEFORE(x) do { } while (0)
 #endif
 
 __host__ __device__ inline int win_log_stride(int T) { return 3 * 16 * T + kWinHdr; }
@@ -180,9 +185,17 @@ template <int T, bool ONE> struct WinChainLds {
     double sA[2][4][SPP];                  // a step's A operand rows  Aop[k][row]   (P += Aop^T Bop)
     double sB[2][4][SPP];                  // ... and B operand rows   Bop[k][column]
     double sPub[2][3][SPP];                // the landmark rows of the step after next
-    double sHdr[2][kWinHdr];               // what a step newly brings to its log header (correction: S^-1; predict: its six values), from the
-                                           // prepare wave to the wave that stores the header (logger; pieces: worker wave 0)
-    double sRec[2][5][64];                 // a frame's header records (ze0, ze1, ze2, g02, g12 of correction a), by frame parity: see win_header_entry
+    double sHdr[2][kWinHdr];               // what a step newly brings to its log header (correction: S^-1, unless the logger wave forms it
+                                           // itself; predict: its six values), from the prepare wave to the wave that stores the header
+                                           // (logger; pieces: worker wave 0)
+    // a frame's records (ze0, ze1, ze2, g02, g12 of correction a; one launch: also R0, R1, R2, for the logger wave's S^-1), by frame
+    // parity: see win_header_entry
+    static constexpr int kRecRows = ONE ? 8 : 5;
+    double sRec[2][kRecRows][64];
+    // one launch, the mean on the logger wave: its mu_S for the prepare wave's next predict, by the parity of the phase it is written
+    // in, and the pose that predict leaves, by frame parity (two predicts can follow each other)
+    double sMuL[2][ONE ? SPP : 1];
+    double sPose[2][4];
 #ifdef ASLAM_WIN_POSE_CHECK
     double sDbg[2][3][SPP];                // the accumulators' pose rows, to compare with the prepare wave's own
 #endif
@@ -193,8 +206,9 @@ template <int T, bool ONE> struct WinChainLds {
     // prepare wave counts its steps in scalar registers); the correction's detection in its frame's observation list
     unsigned char sPos[NSMAX], sIdx[NSMAX];
     unsigned char sDet[NSMAX];
-    // what the block gained over the size the launch's LDS claim was measured at (launch_step_kernel): sRec, less a per-step frame table
-    static constexpr int kGrown = 2 * 5 * 64 * (int)sizeof(double) - NSMAX;
+    // what the block gained over the size the launch's LDS claim was measured at (launch_step_kernel): sRec and the logger wave's
+    // mean hand-overs, less a per-step frame table
+    static constexpr int kGrown = (int)sizeof(sRec) + (int)sizeof(sMuL) + (int)sizeof(sPose) - NSMAX;
 };
 // Entry `lane` (< kWinHdr) of step j's log header, composed by the wave that stores it.  A predict's header is what the prepare
 // wave left in sHdr.  A correction's is S^-1 from sHdr, type and position from the step tables, and ze, g02, g12 from the records
@@ -214,10 +228,14 @@ template <bool GATED, class LDS> __device__ __forceinline__ double win_header_en
     }
     return v;
 }
-template <int T, int RW, bool ONE, class G>
+// LG (one launch only): what the logger wave takes over from the prepare wave.  Bit 0: it forms the log header's S^-1 itself, from
+// the step's c rows in sB and the frame's records; bit 1: it carries mu_S.  0 is the comparison path (ASLAM_WIN_LOGGER_PARTS).
+template <int T, int RW, bool ONE, class G, int LG>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const G& gate, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     static_assert(ONE || !G::kOn, "only the one-launch window is gated");
+    static_assert(ONE || LG == 0, "the piece schedule has no logger wave");
+    constexpr bool LSI = (LG & 1) != 0, LMU = (LG & 2) != 0;
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
@@ -402,37 +420,154 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         // to the log in the loop, so the publication needs this wave's store counter alone.  Steps 0 .. j - 1 - kWinPubLag are complete
         // when it has waited for them at the end of step j - 1; it then passes the barrier (as every wave that read or wrote those
         // steps' operands has) and one of its lanes publishes their count for the replay workgroups.
+        //
+        // What the prepare wave does in a correction for this wave's sake alone is done here instead, off the critical path, with
+        // the prepare wave's expressions on the prepare wave's inputs (every bit stays what it was):
+        //   LSI  S^-1 of the header.  c of step j still lies in sB[j & 1][0..2] (the prepare wave wrote it a phase earlier and now
+        //        writes the other parity only); cos / sin of the frame are kept from its predict's header, g02, g12 and R come from
+        //        the frame's records.
+        //   LMU  mu_S.  Kt is the negated A operand (exactly), ze comes from the records; a predict's pose arrives in sPose[frame
+        //        parity].  The prepare wave needs the mean at a predict only, which it prepares in phase j for step j + 1: in
+        //        phase j - 1 this wave leaves its mean (steps <= j - 1 applied) in sMuL[(j - 1) & 1] and the prepare wave adds step
+        //        j's update itself.  Two parities: with two predicts in a row this wave writes in the phase the prepare wave reads in.
+        double* const muimg = E.d_win_small + wsm_MU(E.win_sp_max, wd.wpar);
+        double lmu[NC];
         ASLAM_LDS_BARRIER();                                       // (pairs with the workers' barrier after their first publish)
+        if constexpr (LMU) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                const int col = lane + 64 * c;
+                lmu[c] = col >= s ? 0.0 : from_img ? muimg[col] : E.d_mu[sS[col]];   // (as the prepare wave loads it)
+            }
+        }
         // What the window's last frame leaves behind for whatever follows: pop list, last_observed_marker_ (aruco_slam.cpp:202,
         // 263).  Nothing of it depends on the chain, and this wave has no log to store while the first predict is prepared: it
         // does the two-level load here.  The stores need the loaded values, so no load is in flight when the loop begins.
         win_last_frame(E, frames[wd.first_slot + wd.K - 1], obs + (size_t)(wd.first_slot + wd.K - 1) * kMarkerMax, sOff[wd.K] - sOff[wd.K - 1] - 1, lane);
+        if constexpr (LMU) ASLAM_VMCNT(0);                         // (the mean's loads too: win_vmcnt_lag counts stores)
 #ifdef ASLAM_WIN_STAMPS
-        long long stamp_acc[2] = {0, 0}, stamp_last = clock64();
+        long long stamp_acc[4] = {0, 0, 0, 0}, stamp_last = clock64();
 #endif
         int fpar = 1;                                              // parity of step j's frame: the first predict makes it 0
+        double lcth = 1.0, lsth = 0.0;                             // cos / sin of step j's frame
+        // The step tables never change: position and correction index of the steps ahead are read a phase or more before they are
+        // needed, so that in a phase every LDS address is known at its start and all its reads are issued together, in front of any
+        // use: one round trip through LDS instead of one per dependent read (the wave's time goes to LDS latency, not to arithmetic).
+        // A predict takes the correction's path with harmless addresses (row 0, record 0) and its results are selected away.
+        int p_cur = 255, a_cur = 0;                                // step j
+        int p_n1 = sPos[0], a_n1 = sIdx[0];                        // step j + 1
+        int p_n2 = sPos[NS > 1 ? 1 : 0];                           // step j + 2
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
             if (j > kWinPubLag && j % kWinPubEvery == 0 && lane == 0) win_signal(E.d_win_sync, wd.epoch, j - kWinPubLag);
+            const int p_n3 = sPos[j + 3 < NS ? j + 3 : NS - 1], a_n2 = sIdx[j + 2 < NS ? j + 2 : NS - 1];
             if (j >= 0) {
                 const int cb = j & 1;
                 double* const log = logbase + (size_t)j * win_log_stride(T);
+                const int pos = p_cur, a = a_cur;
+                const bool corr = pos != 255;
+                if (!corr) fpar ^= 1;
+                const int lrow = corr ? 3 + 3 * pos : 0;
+                const auto& rec = L.sRec[fpar];
+                // ---- every read of the phase ----
+                double av[3][NC];
 #pragma unroll
                 for (int k = 0; k < 3; k++)
 #pragma unroll
-                    for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, sA[cb][k][lane + 64 * c]);
-                if (sPos[j] == 255) fpar ^= 1;
-                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, win_header_entry<G::kOn>(L, j, cb, fpar, lane));
+                    for (int c = 0; c < NC; c++) av[k][c] = sA[cb][k][lane + 64 * c];
+                // the header: what the prepare wave left, and the entry of the frame's records this lane stores (win_header_entry)
+                const int hq = lane >= WH_ZE && lane < WH_ZE + 3 ? lane - WH_ZE : lane == WH_G02 ? 3 : lane == WH_G12 ? 4 : -1;
+                const double hb = L.sHdr[cb][lane < kWinHdr ? lane : 0], hr = rec[hq >= 0 ? hq : 0][a];
+                const double hC = L.sHdr[cb][WH_C], hS = L.sHdr[cb][WH_S], hT = L.sHdr[cb][WH_TYPE];
+                const double pose = L.sPose[fpar][lane < 3 ? lane : 3];
+                double ze0 = rec[0][a], ze1 = rec[1][a], ze2 = rec[2][a];
+                const double g02 = rec[3][a], g12 = rec[4][a];
+                double R0 = 0.0, R1 = 0.0, R2 = 0.0;
+                double cB[3][6];
+                if constexpr (LSI) {
+                    R0 = rec[5][a]; R1 = rec[6][a]; R2 = rec[7][a];
+#pragma unroll
+                    for (int kk = 0; kk < 3; kk++) {
+                        cB[kk][0] = sB[cb][kk][0]; cB[kk][1] = sB[cb][kk][1]; cB[kk][2] = sB[cb][kk][2];
+                        cB[kk][3] = sB[cb][kk][lrow]; cB[kk][4] = sB[cb][kk][lrow + 1]; cB[kk][5] = sB[cb][kk][lrow + 2];
+                    }
+                }
+                // ---- the operand rows to the log ----
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+#pragma unroll
+                    for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, av[k][c]);
+                if (!corr) { lcth = hC; lsth = hS; }
+                // ---- the header entry of this lane (win_header_entry) ----
+                double hv = hb;
+                if (corr) {
+                    if (hq >= 0) hv = hr;
+                    if (!G::kOn && lane == WH_TYPE) hv = 1.0;
+                    if (lane == WH_POS) hv = (double)pos;
+                }
+                WSTAMP_BEFORE(hv);
+                WSTAMP(1);
+                if constexpr (LSI) {
+                    // ---- S = c H^T + R and its inverse, as the prepare wave forms them (below) ----
+                    double cth = lcth, sth = lsth;
+                    WSTAMP_AFTER(cth); WSTAMP_AFTER(sth);
+                    double Sm[9], Si[9];
+#pragma unroll
+                    for (int kk = 0; kk < 3; kk++) {
+                        const double p0 = cB[kk][0], p1 = cB[kk][1], p2 = cB[kk][2];
+                        const double l0 = cB[kk][3], l1 = cB[kk][4], l2 = cB[kk][5];
+                        Sm[kk * 3 + 0] = (-cth * p0 - sth * p1 + g02 * p2) + (cth * l0 + sth * l1);
+                        Sm[kk * 3 + 1] = (sth * p0 - cth * p1 + g12 * p2) + (-sth * l0 + cth * l1);
+                        Sm[kk * 3 + 2] = l2 - p2;
+                    }
+                    Sm[0] += R0; Sm[4] += R1; Sm[8] += R2;
+                    inv3_fast(Sm, Si);
+#pragma unroll
+                    for (int q = 0; q < 9; q++) hv = corr && lane == WH_SI + q ? Si[q] : hv;
+                }
+                WSTAMP_BEFORE(hv);
+                WSTAMP(2);
+                if (lane < kWinHdr) st_wt(log + 3 * SP + lane, hv);
                 // a publication follows the next barrier: this wave's stores of the steps before the last kWinPubLag are complete
                 if ((j + 1) % kWinPubEvery == 0) win_vmcnt_lag<NC>();
+                WSTAMP(1);
+                if constexpr (LMU) {
+                    WSTAMP_AFTER(ze0); WSTAMP_AFTER(ze1); WSTAMP_AFTER(ze2);
+                    // ---- mu_ += K ze (aruco_slam.cpp:203), by selection: a rejected step's ze may be NaN (type 2), a predict has none ----
+                    const bool upd = corr && !(G::kOn && hT == 2.0);
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        const double k0 = -av[0][c], k1 = -av[1][c], k2 = -av[2][c];
+                        const double dm = k0 * ze0 + k1 * ze1 + k2 * ze2;
+                        lmu[c] = upd ? lmu[c] + dm : lmu[c];
+                    }
+                    if (!corr && lane < 3) lmu[0] = pose;              // a predict: the pose it leaves
+                }
             }
-            WSTAMP(1);
+            if constexpr (LMU) {
+                // step j + 2 is a predict: the prepare wave prepares it in the next phase, from this mean (steps <= j applied)
+                if (j + 2 < NS && p_n2 == 255) {
+#pragma unroll
+                    for (int c = 0; c < NC; c++) L.sMuL[j & 1][lane + 64 * c] = lmu[c];
+                }
+            }
+            p_cur = p_n1; a_cur = a_n1; p_n1 = p_n2; a_n1 = a_n2; p_n2 = p_n3;
+            WSTAMP(3);
             ASLAM_LDS_BARRIER();
+        }
+        if constexpr (LMU) {
+            // ---- mu_S for the window's flush and the next window; back into the state where the window asks for it ----
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                const int col = lane + 64 * c;
+                if (col < s) { muimg[col] = lmu[c]; if (wd.mu_out) E.d_mu[sS[col]] = lmu[c]; }
+            }
         }
         ASLAM_VMCNT(0);                                            // the whole log: after this wave's last stores
         if (lane == 0) win_signal(E.d_win_sync, wd.epoch, NS);
 #ifdef ASLAM_WIN_STAMPS
-        if (lane == 0) printf("logger T %d steps %d: barrier-wait %lld work %lld cycles per step\n", T, NS, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1));
+        if (lane == 0) printf("logger T %d steps %d: barrier-wait %lld copy + header %lld S^-1 %lld mu %lld cycles per step\n", T, NS, stamp_acc[0] / (NS + 1),
+                              stamp_acc[1] / (NS + 1), stamp_acc[2] / (NS + 1), stamp_acc[3] / (NS + 1));
 #endif
         return;
     }
@@ -470,6 +605,15 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     int fk = -1, fm = 0, fa = 0, vpos = 0;
     bool prev_predict = false;
     bool dirty0 = false, dirty1 = false;                           // operand buffer 0 / 1 holds a predict's fourth depth row
+    // LMU (the logger wave carries the mean): what the previous step did to it, which this wave adds at a predict to the mean the
+    // logger left a phase earlier: K ze of an accepted correction (Kt is the negated A operand, which still lies in LDS: keeping
+    // it in registers would cost every correction moves), or the pose a predict left
+    double pn0 = 0.0, pn1 = 0.0, pth = 0.0;
+    bool prev_rejected = false;
+    if constexpr (LMU) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) L.sMuL[0][lane + 64 * c] = mu[c];   // the first predict reads its mean where every later one does
+    }
     // the first frame's inputs
     ObsRaw nObs{};
     if (lane < sOff[1] - 1) nObs = obs[(size_t)wd.first_slot * kMarkerMax + sDet[1 + lane]];
@@ -535,6 +679,25 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #ifdef ASLAM_WIN_STAMPS
                 n_pred++;
 #endif
+                if constexpr (LMU) {
+                    // the mean after step j: the logger's (steps <= j - 1) and step j's update, with the expression of mu_ += K ze
+#pragma unroll
+                    for (int c = 0; c < NC; c++) mu[c] = L.sMuL[nb][lane + 64 * c];
+                    if (j >= 0) {
+                        if (prev_predict) {
+                            if (lane == 0) mu[0] = pn0;
+                            if (lane == 1) mu[0] = pn1;
+                            if (lane == 2) mu[0] = pth;
+                        } else if (!prev_rejected) {                // (step j was the last correction of its frame: fm - 1)
+                            const double ze0 = ASLAM_WAVE_BCAST(rze0, fm - 1), ze1 = ASLAM_WAVE_BCAST(rze1, fm - 1), ze2 = ASLAM_WAVE_BCAST(rze2, fm - 1);
+#pragma unroll
+                            for (int c = 0; c < NC; c++) {
+                                const double k0 = -sA[pb][0][lane + 64 * c], k1 = -sA[pb][1][lane + 64 * c], k2 = -sA[pb][2][lane + 64 * c];
+                                mu[c] += k0 * ze0 + k1 * ze1 + k2 * ze2;
+                            }
+                        }
+                    }
+                }
                 const int k = ++fk;
                 const int slot = wd.first_slot + k;
                 fm = ASLAM_WAVE_BCAST(sOff[k + 1] - sOff[k] - 1, 0); fa = 0;     // corrections of the frame
@@ -576,9 +739,15 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 }
                 if (nb) dirty1 = true; else dirty0 = true;
                 const double np0 = m0 + delta_s * cm, np1 = m1 + delta_s * sm;
-                if (lane == 0) mu[0] = np0;
-                if (lane == 1) mu[0] = np1;
-                if (lane == 2) mu[0] = th;
+                if constexpr (LMU) {
+                    // the predicted pose: to the logger's mean, by frame parity, and kept for a predict that follows at once
+                    if (lane < 3) L.sPose[k & 1][lane] = lane == 0 ? np0 : lane == 1 ? np1 : th;
+                    pn0 = np0; pn1 = np1; pth = th;
+                } else {
+                    if (lane == 0) mu[0] = np0;
+                    if (lane == 1) mu[0] = np1;
+                    if (lane == 2) mu[0] = th;
+                }
                 // ---- the frame's records at the frozen mean (pose just predicted, landmarks as the previous frame left them) ----
                 if (lane < fm) {
                     vpos = sPos[sOff[k] + 1 + lane];
@@ -594,8 +763,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     rg02 = -gdx * sth + gdy * cth; rg12 = -gdx * cth - gdy * sth;
                     rR0 = nObs.r[0]; rR1 = nObs.r[1]; rR2 = nObs.r[2];
                     // what of them the log header carries, for the wave that stores it
-                    double (&rec)[5][64] = L.sRec[k & 1];
+                    auto& rec = L.sRec[k & 1];
                     rec[0][lane] = rze0; rec[1][lane] = rze1; rec[2][lane] = rze2; rec[3][lane] = rg02; rec[4][lane] = rg12;
+                    if constexpr (LSI) { rec[5][lane] = rR0; rec[6][lane] = rR1; rec[7][lane] = rR2; }
                 }
                 __builtin_amdgcn_wave_barrier();
                 WSTAMP(10);
@@ -658,11 +828,13 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     if constexpr (G::kOn) {
                         // a rejected step: no mean update (selected, not multiplied: its ze may be NaN) and zero A rows, so that the
                         // workers, the pose rows carried here and the logged operands all see a zero update
-                        const double dm = k0 * ze0 + k1 * ze1 + k2 * ze2;
-                        mu[c] = rejected ? mu[c] : mu[c] + dm;
+                        if constexpr (!LMU) {
+                            const double dm = k0 * ze0 + k1 * ze1 + k2 * ze2;
+                            mu[c] = rejected ? mu[c] : mu[c] + dm;
+                        }
                         A[0][c] = rejected ? 0.0 : -k0; A[1][c] = rejected ? 0.0 : -k1; A[2][c] = rejected ? 0.0 : -k2; A[3][c] = 0.0;
                     } else {
-                        mu[c] += k0 * ze0 + k1 * ze1 + k2 * ze2;                   // mu_ += K ze (aruco_slam.cpp:203)
+                        if constexpr (!LMU) mu[c] += k0 * ze0 + k1 * ze1 + k2 * ze2;   // mu_ += K ze (aruco_slam.cpp:203)
                         A[0][c] = -k0; A[1][c] = -k1; A[2][c] = -k2; A[3][c] = 0.0;
                     }
                     B[0][c] = cc[0][c]; B[1][c] = cc[1][c]; B[2][c] = cc[2][c]; B[3][c] = 0.0;
@@ -673,11 +845,15 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     if (nb) dirty1 = false; else dirty0 = false;
                 }
                 // what the step brings to its log header: S^-1 (the wave that stores the header composes the rest: win_header_entry)
+                // (LSI: the logger wave forms S^-1 itself; the gate's verdict needs it here all the same)
                 if (lane == 0) {
+                    if constexpr (!LSI) {
 #pragma unroll
-                    for (int q = 0; q < 9; q++) hdr[WH_SI + q] = Si[q];
+                        for (int q = 0; q < 9; q++) hdr[WH_SI + q] = Si[q];
+                    }
                     if constexpr (G::kOn) { hdr[WH_TYPE] = rejected ? 2.0 : 1.0; hdr[WH_D2] = d2; hdr[WH_ACC] = rejected ? 0.0 : 1.0; }
                 }
+                prev_rejected = rejected;
                 WSTAMP(5);
             }
             // operands to the workers and the logger wave (pieces: to the workers, who also log them), and this wave's own copy
@@ -708,10 +884,12 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
     if (lane == 0) printf("pose-check T %d piece %d steps %d: max |prepare - accumulator| pose rows %.3e over the piece, %.3e at its end\n", T, wd.piece, NS, dmax, dend);
 #endif
     // ---- mu_S for the next piece; back into the state at the window's end (one-launch window: by k_ekf_win_fix) ----
+    if constexpr (!LMU) {                                           // (LMU: the logger wave has it)
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int col = lane + 64 * c;
-        if (col < s) { muimg[col] = mu[c]; if (wd.mu_out) E.d_mu[sS[col]] = mu[c]; }
+        for (int c = 0; c < NC; c++) {
+            const int col = lane + 64 * c;
+            if (col < s) { muimg[col] = mu[c]; if (wd.mu_out) E.d_mu[sS[col]] = mu[c]; }
+        }
     }
 }
 
@@ -964,7 +1142,7 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
         old = prev;
     }
 }
-template <int T, int RW, bool ONE, class G = NoSlamGate>
+template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0>
 __global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
 void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
     const WinDesc& wd = wa;
@@ -978,7 +1156,7 @@ void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinRe
         __syncthreads();
         bx = sTicket;
     }
-    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
+    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G, LG>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
     else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE, G::kOn>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
     else if (rq.nsteps > 0) win_psi_role<T, ONE, G::kOn>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
 }
@@ -1332,12 +1510,12 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 // of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
 // waited for up to a whole window (measured: DESIGN.md).  The chain role's block has grown by kGrown bytes since (the header records);
 // the dynamic part gives them back, so that static + dynamic is what it was measured at.
-template <int T, bool ONE, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
+template <int T, bool ONE, int LG = 0, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const W& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
     constexpr size_t cap = (size_t)24 * 1024 + WinChainLds<T, ONE>::kGrown;
     const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, cap);                    // static + dynamic > 80 KB of the 160 KB
-    static bool attr_done = false;
+    static bool attr_done = false;                                 // (per instantiation: LG tells kernels of one signature apart)
     if (!attr_done && dyn > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         attr_done = true;
@@ -1353,21 +1531,31 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
     else if (wd.T == 8) launch_step_kernel<8, false>(k_ekf_win_step<8, 2, false>, st, nb, 320, sizeof(WinChainLds<8, false>), E, sp, wa, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
     else launch_step_kernel<12, false>(k_ekf_win_step<12, 2, false>, st, nb, 448, sizeof(WinChainLds<12, false>), E, sp, wa, rs, rq, obs, enc);
 }
-void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc, const SlamGateArg* gate) {
+// lg: what the logger wave takes over from the prepare wave (win_chain_role's LG; 0 = the comparison path)
+template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
+                                                                          const ObsRaw* obs, const double* enc) {
+    constexpr size_t lds = sizeof(WinChainLds<T, true>);
+    if (lg == 3) launch_step_kernel<T, true, 3>(k_ekf_win_step<T, 2, true, G, 3>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    else if (lg == 2) launch_step_kernel<T, true, 2>(k_ekf_win_step<T, 2, true, G, 2>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    else if (lg == 1) launch_step_kernel<T, true, 1>(k_ekf_win_step<T, 2, true, G, 1>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    else launch_step_kernel<T, true, 0>(k_ekf_win_step<T, 2, true, G, 0>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+}
+void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc, const SlamGateArg* gate,
+                        int logger_parts) {
     const WinReplay r{0, 0, wd.nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
     if (gate) {                                                     // the gated instantiations: same grids, same blocks
         const WinArg<WinGate> wa{wd, WinGate{gate->g.gate_d2}};
-        if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true, WinGate>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wa, r, r, obs, enc);
-        else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true, WinGate>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wa, r, r, obs, enc);
-        else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true, WinGate>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wa, r, r, obs, enc);
+        if (wd.T == 4) launch_win_one_lg<4, 256, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+        else if (wd.T == 8) launch_win_one_lg<8, 384, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+        else launch_win_one_lg<12, 512, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
         return;
     }
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_step_kernel<4, true>(k_ekf_win_step<4, 2, true>, st, nb, 256, sizeof(WinChainLds<4, true>), E, sp, wa, r, r, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8, true>(k_ekf_win_step<8, 2, true>, st, nb, 384, sizeof(WinChainLds<8, true>), E, sp, wa, r, r, obs, enc);
-    else launch_step_kernel<12, true>(k_ekf_win_step<12, 2, true>, st, nb, 512, sizeof(WinChainLds<12, true>), E, sp, wa, r, r, obs, enc);
+    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
 }
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
     hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
