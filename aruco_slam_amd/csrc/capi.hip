@@ -186,6 +186,10 @@ struct aslam_ctx {
     bool win_next_split = false;          // ASLAM_WIN_NEXT_SPLIT: the early start as four launches instead of one kernel (comparison knob)
     int win_logger_parts = 3;             // ASLAM_WIN_LOGGER_PARTS: what the chain's logger wave takes over from the prepare wave (bit 0: the header's S^-1,
                                           // bit 1: mu_S; 0: the prepare wave does both, the comparison path)
+    int win_worker_publish = -1;          // ASLAM_WIN_WORKER_PUBLISH: how the chain's workers publish (bit 0: packed rows, bit 1: the step table a
+                                          // phase ahead; 0: the comparison path; unset: the default of each window's width)
+    bool detect_wait_at_head = false;     // ASLAM_DETECT_WAIT_AT_HEAD: detection waits for EKF work on reused slots in front of its first kernel,
+                                          // not in front of its first pose stage (comparison knob)
     struct Pending { bool active = false; int first = 0, count = 0, ev = 0; } pend;
     hipEvent_t ev_obs[2] = {nullptr, nullptr}, ev_idx = nullptr;
     hipStream_t stream_win = nullptr;     // scan / flush of the windows, beside the chain on stream_ekf
@@ -572,9 +576,16 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
     g.cut_mask = cut_grid_of_call(g, count, latency) - 1;
     c->last_first = first;
     c->last_count = count;
-    if (c->ekf_count > 0 && first < c->ekf_hi && c->ekf_lo < first + count) {
-        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));   // EKF work in flight still reads observations of these slots
-        c->ekf_count = 0;
+    // EKF work in flight still reads observations of these slots.  Of all that detection writes, the EKF stream's kernels read d_obs
+    // and d_nmarkers alone ("What the EKF stream reads of a detection"), and k_pose is the one kernel that writes them:
+    // the wait stands in front of the first pose stage, so that the contour, quad and identification stages of this call run beside
+    // the EKF work of the call before last.  A fleet call waits at the head (its camera-index upload comes first), and so does every
+    // call under ASLAM_DETECT_WAIT_AT_HEAD, the comparison path.
+    bool wait_ekf = c->ekf_count > 0 && first < c->ekf_hi && c->ekf_lo < first + count;
+    if (wait_ekf) c->ekf_count = 0;
+    if (wait_ekf && (k.robots || c->detect_wait_at_head)) {
+        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));
+        wait_ekf = false;
     }
     if (k.robots) {                                         // the frames' camera indices, on the stream ahead of k_pose
         int r = pinned_upload(c, c->fleet_camidx_up, c->d_fleet_camidx + first, k.robots, count, st);
@@ -596,6 +607,10 @@ int run_detect(aslam_ctx* c, const Call& k, bool latency, bool beside_ekf = fals
                         c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_work);
         prof_end(c);
         launch_identify_stage(c, st, g, f0);
+        if (wait_ekf) {                                     // (the event's record is the one the head of this call saw: nothing was enqueued since)
+            HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));
+            wait_ekf = false;
+        }
         launch_pose_stage(c, k, st, f0, nf, refine_cfg(c, f0));
     }
     HIP_TRY(c, hipEventRecord(c->ev_detect, st));
@@ -787,6 +802,8 @@ int aslam_create(const aslam_init* init, aslam_ctx** out) {
     c->win_no_early = std::getenv("ASLAM_WIN_NO_EARLY") != nullptr;
     c->win_next_split = std::getenv("ASLAM_WIN_NEXT_SPLIT") != nullptr;
     if (const char* e = std::getenv("ASLAM_WIN_LOGGER_PARTS")) c->win_logger_parts = std::atoi(e) & 3;
+    if (const char* e = std::getenv("ASLAM_WIN_WORKER_PUBLISH")) c->win_worker_publish = std::atoi(e) & kWinWorkerPublishAll;
+    c->detect_wait_at_head = std::getenv("ASLAM_DETECT_WAIT_AT_HEAD") != nullptr;
     if (const char* e = std::getenv("ASLAM_WIN_PIECE")) { c->win_piece = std::min(kWinChainFrames, std::max(1, std::atoi(e))); c->win_pieces = true; }
     const int B = c->max_batch;
     const size_t px = (size_t)init->max_rows * init->max_cols;
@@ -1048,7 +1065,7 @@ void enqueue_window_one(aslam_ctx* c, const WinOp& o, const WinDesc& wd) {
     cw.nsteps = win_steps(c, o.frame, o.K);
     prof_begin(c, P_EKF_WIN_CHAIN, sa);
     const bool gated = gated_windows(c);
-    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts);
+    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts, c->win_worker_publish);
     prof_end(c);
     if (gated) {                                                     // verdicts into records, counts, actions and the last-observed list
         prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
@@ -1089,7 +1106,7 @@ int enqueue_window_pieces(aslam_ctx* c, const WinOp& o, const WinDesc& wd, hipEv
         if (i < P && cw.last && ev_prev_flush) HIP_TRY(c, hipStreamWaitEvent(sa, ev_prev_flush, 0));   // mu_S goes back into the state: after the previous flush's mu_R pass
         prof_begin(c, i < P ? P_EKF_WIN_CHAIN : P_EKF_WIN_SCAN, sa);
         launch_ekf_win_step(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, ps ? ps->sub.piece : 0, ps ? ps->sub.log0 : 0, ps ? ps->nsteps : 0,
-                            pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0);
+                            pq ? pq->sub.piece : 0, pq ? pq->sub.log0 : 0, pq ? pq->nsteps : 0, c->win_worker_publish);
         prof_end(c);
     }
     return ASLAM_OK;

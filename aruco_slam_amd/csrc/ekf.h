@@ -298,12 +298,19 @@ inline int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }   
 // gate != nullptr: the gated instantiation, to be followed on the same stream by launch_ekf_win_gate_finish
 // logger_parts: what the chain's logger wave takes over from its prepare wave (bit 0: the log header's S^-1, bit 1: mu_S; the
 // results are the same to the bit whatever it is, 0 is the comparison path)
+// worker_publish: how the chain's worker waves publish the landmark rows of the step after next (bit 0: packed rows written 16
+// bytes at a time, bit 1: the step table's entry read a phase ahead; the same results to the bit whatever it is, 0 is the comparison
+// path, negative: the default of the window's width).  One launch: the forms are built beside logger_parts = 3, any other
+// logger_parts runs the width's default
+constexpr int kWinWorkerPublishAll = 3;
+// the default by width (T = 4, 8, 12 tiles: 64, 128, 192 columns), from the EKF-only timings of DESIGN.md §8 "The workers' publication"
+constexpr int win_worker_publish_default(int T) { return T == 4 ? 3 : T == 8 ? 1 : 2; }
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
-                        const SlamGateArg* gate = nullptr, int logger_parts = 3);
+                        const SlamGateArg* gate = nullptr, int logger_parts = 3, int worker_publish = -1);
 // behind a gated window: slot records and accepted counts of its K frames, the track record, the last frame's actions and last-observed list
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs);
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
-                         int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps);
+                         int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps, int worker_publish = -1);
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd);               // Y_0 = rows S of Sigma, position table
 // P and mu_S of the NEXT window (set nx) from the previous window's (pv) P_K, Lambda, Psi, psi, Y_0 and the not yet flushed Sigma / mu
 void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx, bool split);   // split: the four-launch path (comparison)

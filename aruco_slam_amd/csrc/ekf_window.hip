@@ -75,6 +75,14 @@ template <int NC> __device__ __forceinline__ void win_vmcnt_lag() {
 // (a stamp orders nothing but volatile statements: a bucket of arithmetic is held between its stamps by its inputs and its result)
 #define WSTAMP_AFTER(x) asm volatile("" : "+v"(x))
 #define WSTAMP_BEFORE(x) asm volatile("" :: "v"(x))
+// a stamp behind the matrix-core result x: a real instruction reads it, so the wave stands until the MFMA that writes it has ended
+#define WSTAMP_RESULT(x) do { const int r_ = __builtin_amdgcn_readfirstlane(__double2hiint(x)); asm volatile("" :: "s"(r_)); } while (0)
+// two stamps around the drain of the LDS queue: the clock is read (in issue order) behind the last LDS instruction, then again once
+// that reading and every LDS operation in front of it have returned.  Bucket i ends at the first reading, bucket k holds the drain,
+// which is never shorter than the first reading's own way back
+#define WSTAMP_DRAIN(i, k) do { long long a_, b_; \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a_), "=&s"(b_) :: "memory"); \
+        stamp_acc[i] += a_ - stamp_last; stamp_acc[k] += b_ - a_; stamp_last = b_; } while (0)
 #else
 #define WSTAMP(i) do { } while (0)
 #define WSTAMP_AFTER(x) do { } while (0)
@@ -129,25 +137,72 @@ template <int NC> __device__ __forceinline__ double bcast_sel(const double (&v)[
 // Rows p .. p + 2 of the image leave the accumulators of the worker wave(s) that own them (row r = 16 g + lk + 4 reg of tile row
 // g): lanes with lk == r & 3 write their register reg = (r >> 2) & 3 of each of the T column tiles.  The register number must
 // be static (a select chain over the accumulators costs more than the rest of the step): one instance per p mod 16.
-template <int P16, int T, int RW>
+//
+// PK, the packed row: a publishing lane holds columns li + 16 t of its row, T values that lie 16 doubles apart, and writes them with
+// T ds_write_b64.  The packed row keeps column c = 16 t + li at element
+//     win_pub_slot(c) = 32 (t >> 1) + 2 li + (t & 1)
+// so that a lane's values of tiles 2 h and 2 h + 1 are one aligned 16-byte chunk (chunk 16 h + li of the row) and leave as T / 2
+// ds_write_b128.  It is a permutation of each 64-column chunk in itself (tiles 4 c .. 4 c + 3 go to elements 64 c .. 64 c + 63), so
+// the row needs no padding and the prepare wave reads column lane + 64 c with the same ds_read_b64 at win_pub_slot(lane) + 64 c.  Banks
+// (64 of 4 bytes; where a row starts, a multiple of 16 bytes, shifts every lane of an access alike and changes nothing below):
+//   the read  (ds_read_b64, bank = dword mod 64, the two 32-lane halves apart): lanes 0 .. 31 are li = 0 .. 15 with t & 3 = 0, 1 and
+//             read elements 64 c + 2 li + {0, 1}, 32 consecutive doubles = each of the 64 banks once; lanes 32 .. 63 (t & 3 = 2, 3)
+//             the 32 doubles behind them;
+//   the write (ds_write_b128, bank = dword mod 32, groups of 8 consecutive lanes): the 16 publishing lanes of a row are two such
+//             groups, li = 0 .. 7 and 8 .. 15, and a group writes chunks 16 h + li of 4 dwords each, 8 consecutive chunks = each of
+//             the 32 banks once.
+// (The order T li + t, a lane's T values in one piece, cannot do both: its chunks start at even chunk numbers, a half-wave read
+// touches 16 of them, and only 8 even numbers differ modulo the 16 chunks of a bank row.)  win_pub_slot_ok checks both claims.
+typedef double v2d __attribute__((vector_size(2 * sizeof(double))));
+__host__ __device__ constexpr int win_pub_slot(int c) { return (c & ~63) + 32 * ((c >> 5) & 1) + 2 * (c & 15) + ((c >> 4) & 1); }
+template <int T> constexpr bool win_pub_slot_ok() {
+    static_assert(T % 2 == 0, "tiles are packed in pairs");
+    for (int c = 0; c < T / 4 + (T % 4 != 0); c++)
+        for (int half = 0; half < 2; half++) {                     // the read: 32 lanes, 64 banks, every bank once
+            unsigned long long banks = 0;
+            for (int l = 32 * half; l < 32 * half + 32; l++) {
+                const int dw = 2 * win_pub_slot(l + 64 * c);
+                banks |= 3ull << (dw & 63);
+            }
+            if (banks != ~0ull) return false;
+        }
+    for (int h = 0; h < T / 2; h++)
+        for (int grp = 0; grp < 2; grp++) {                        // the write: 8 lanes, 32 banks, every bank once; 16-byte aligned
+            unsigned banks = 0;
+            for (int li = 8 * grp; li < 8 * grp + 8; li++) {
+                const int e = win_pub_slot(16 * (2 * h) + li);
+                if (e % 2 != 0 || win_pub_slot(16 * (2 * h + 1) + li) != e + 1) return false;
+                banks |= 15u << ((2 * e) & 31);
+            }
+            if (banks != ~0u) return false;
+        }
+    return true;
+}
+static_assert(win_pub_slot_ok<4>() && win_pub_slot_ok<8>() && win_pub_slot_ok<12>(), "the packed row's reads and writes are free of bank conflicts");
+template <int P16, int T, int RW, bool PK>
 __device__ __forceinline__ void win_publish_at(const v4d (&acc)[RW][T], int p, int wv, int lk, int li, double* rows, int spp) {
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         const int rl = (P16 + q) & 15;
         const int g = (p + q) >> 4;
-        double* d = rows + q * spp + li;
+        double* d = rows + q * spp + (PK ? 2 * li : li);
 #pragma unroll
         for (int rr = 0; rr < RW; rr++)
             if (g == wv * RW + rr && lk == (rl & 3)) {
+                if constexpr (PK) {
 #pragma unroll
-                for (int t = 0; t < T; t++) d[16 * t] = acc[rr][t][rl >> 2];
+                    for (int h = 0; h < T / 2; h++) *reinterpret_cast<v2d*>(d + 32 * h) = v2d{acc[rr][2 * h][rl >> 2], acc[rr][2 * h + 1][rl >> 2]};
+                } else {
+#pragma unroll
+                    for (int t = 0; t < T; t++) d[16 * t] = acc[rr][t][rl >> 2];
+                }
             }
     }
 }
-template <int T, int RW>
+template <int T, int RW, bool PK>
 __device__ __forceinline__ void win_publish(const v4d (&acc)[RW][T], int p, int wv, int lk, int li, double* rows, int spp) {
     switch (p & 15) {
-#define ASLAM_WP_CASE(i) case i: win_publish_at<i, T, RW>(acc, p, wv, lk, li, rows, spp); break;
+#define ASLAM_WP_CASE(i) case i: win_publish_at<i, T, RW, PK>(acc, p, wv, lk, li, rows, spp); break;
         ASLAM_WP_CASE(0) ASLAM_WP_CASE(1) ASLAM_WP_CASE(2) ASLAM_WP_CASE(3) ASLAM_WP_CASE(4) ASLAM_WP_CASE(5) ASLAM_WP_CASE(6) ASLAM_WP_CASE(7)
         ASLAM_WP_CASE(8) ASLAM_WP_CASE(9) ASLAM_WP_CASE(10) ASLAM_WP_CASE(11) ASLAM_WP_CASE(12) ASLAM_WP_CASE(13) ASLAM_WP_CASE(14) ASLAM_WP_CASE(15)
 #undef ASLAM_WP_CASE
@@ -230,12 +285,19 @@ template <bool GATED, class LDS> __device__ __forceinline__ double win_header_en
 }
 // LG (one launch only): what the logger wave takes over from the prepare wave.  Bit 0: it forms the log header's S^-1 itself, from
 // the step's c rows in sB and the frame's records; bit 1: it carries mu_S.  0 is the comparison path (ASLAM_WIN_LOGGER_PARTS).
-template <int T, int RW, bool ONE, class G, int LG>
+// WP: how the worker waves publish the landmark rows of the step after next (ASLAM_WIN_WORKER_PUBLISH; 0 is the comparison path).
+//   bit 0  packed row: T / 2 ds_write_b128 per row instead of T ds_write_b64 (win_publish_at); the prepare wave reads the same rows
+//          with the same three reads per chunk at a lane offset it forms once, in front of its loop.
+//   bit 1  the step table's entry a phase ahead: sPos[j + 3] is read with phase j's B operand and kept in a register, so that no
+//          LDS round trip stands between the MFMAs and the publication's switch (the step tables never change inside a window).
+// The prepare wave's steps and the values it reads do not depend on WP, and no floating-point operation moves.
+template <int T, int RW, bool ONE, class G, int LG, int WP>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const G& gate, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     static_assert(ONE || !G::kOn, "only the one-launch window is gated");
     static_assert(ONE || LG == 0, "the piece schedule has no logger wave");
     constexpr bool LSI = (LG & 1) != 0, LMU = (LG & 2) != 0;
+    constexpr bool PK = (WP & 1) != 0, AHEAD = (WP & 2) != 0;
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
     constexpr int NWK = (T + RW - 1) / RW, NT = (NWK + (ONE ? 2 : 1)) * 64;   // workers, prepare wave, one launch: logger wave
     WinChainLds<T, ONE>& L = *reinterpret_cast<WinChainLds<T, ONE>*>(smem);
@@ -350,14 +412,21 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
             for (int t = 0; t < T; t++) { L.sDbg[0][lk][16 * t + li] = acc[0][t][0]; L.sDbg[1][lk][16 * t + li] = acc[0][t][0]; }
         }
 #endif
-        if (NS > 1 && sPos[1] != 255) win_publish<T, RW>(acc, 3 + 3 * sPos[1], wave, lk, li, &sPub[1][0][0], SPP);
+        if (NS > 1 && sPos[1] != 255) win_publish<T, RW, PK>(acc, 3 + 3 * sPos[1], wave, lk, li, &sPub[1][0][0], SPP);
         ASLAM_LDS_BARRIER();
 #ifdef ASLAM_WIN_STAMPS
-        long long stamp_acc[4] = {0, 0, 0, 0}, stamp_last = clock64();
+        long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = clock64();
+        int st_pn = 255;                                           // (stamps only) sPos[j + 2], read a phase ahead: which accumulator the wait's stamp reads
 #endif
         int fpar = 1;                                              // (pieces, wave 0) parity of step j's frame: the first predict makes it 0
+        int pn_ahead = 255;                                        // AHEAD: sPos[j + 2], read in phase j - 1
         for (int j = -1; j < NS; j++) {
             WSTAMP(0);
+            int pn_next = 255;
+            if constexpr (AHEAD) pn_next = sPos[j + 3 < NS ? j + 3 : NS - 1];     // (issued with the B operand's reads; used a phase later)
+#ifdef ASLAM_WIN_STAMPS
+            const int st_next = sPos[j + 3 < NS ? j + 3 : NS - 1];
+#endif
             if (j >= 0) {
                 const int cb = j & 1;
                 double* const log = logbase + (size_t)j * win_log_stride(T);
@@ -382,6 +451,17 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     if (lane < kWinHdr) log[3 * SP + lane] = win_header_entry<false>(L, j, cb, fpar, lane);
                 }
                 WSTAMP(2);
+#ifdef ASLAM_WIN_STAMPS
+                // (stamps only) the wait for the products the publication reads.  The matrix core ends the MFMAs in issue order, so
+                // the last accumulator of the last-issued tile row that holds a published row stands for all of them
+                if (j + 2 < NS && st_pn != 255) {
+                    const int g0 = (3 + 3 * st_pn) >> 4, g1 = (5 + 3 * st_pn) >> 4;
+                    const int r_last = g1 - wave * RW >= 0 && g1 - wave * RW < RW ? g1 - wave * RW : g0 - wave * RW;
+                    if (r_last == 0) WSTAMP_RESULT(acc[0][T - 1][0]);
+                    else if (r_last == 1) WSTAMP_RESULT(acc[RW > 1 ? 1 : 0][T - 1][0]);
+                }
+                WSTAMP(3);
+#endif
                 if (j + 2 < NS) {                                   // landmark rows of step j + 2 as they stand after step j
 #ifdef ASLAM_WIN_POSE_CHECK
                     if (wave == 0 && lk < 3) {
@@ -389,17 +469,22 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                         for (int t = 0; t < T; t++) L.sDbg[cb][lk][16 * t + li] = acc[0][t][0];
                     }
 #endif
-                    const int pn = sPos[j + 2];
-                    if (pn != 255) win_publish<T, RW>(acc, 3 + 3 * pn, wave, lk, li, &sPub[cb][0][0], SPP);
+                    const int pn = AHEAD ? pn_ahead : sPos[j + 2];
+                    if (pn != 255) win_publish<T, RW, PK>(acc, 3 + 3 * pn, wave, lk, li, &sPub[cb][0][0], SPP);
                 }
             }
-            WSTAMP(3);
+            pn_ahead = pn_next;
+#ifdef ASLAM_WIN_STAMPS
+            st_pn = st_next;
+            WSTAMP_DRAIN(4, 5);
+#endif
             ASLAM_LDS_BARRIER();
         }
 #ifdef ASLAM_WIN_STAMPS
         if (lane == 0 && (ONE || wd.piece == 1))
-            printf("worker %d T %d steps %d: barrier-wait %lld | B reads %lld A reads + products%s %lld publish %lld cycles per step\n", wave, T, NS, stamp_acc[0] / (NS + 1),
-                   stamp_acc[1] / (NS + 1), ONE ? "" : " + log", stamp_acc[2] / (NS + 1), stamp_acc[3] / (NS + 1));
+            printf("worker %d T %d steps %d form %d: barrier-wait %lld | B reads %lld A reads + products%s %lld publish: wait for the products %lld look-up + switch + writes %lld drain %lld cycles per step\n",
+                   wave, T, NS, WP, stamp_acc[0] / (NS + 1), stamp_acc[1] / (NS + 1), ONE ? "" : " + log", stamp_acc[2] / (NS + 1), stamp_acc[3] / (NS + 1),
+                   stamp_acc[4] / (NS + 1), stamp_acc[5] / (NS + 1));
 #endif
         // P_K for the next piece / the flush
         double* Pout = E.d_win_small + wsm_P(E.win_sp_max, wd.wpar);
@@ -581,6 +666,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #endif
     const double kl = sp.kl, kr = sp.kr, inv2b = 1.0 / (2 * sp.b), invb = 1 / sp.b, Qk = sp.Q_k;
     double* const muimg = E.d_win_small + wsm_MU(E.win_sp_max, wd.wpar);
+    const int pcol = PK ? win_pub_slot(lane) : lane;               // where column `lane` of a published row's chunk lies (win_publish_at)
     double mu[NC], pB[4][NC];
     double rp[3][NC];                                              // the pose rows of P, carried here (the workers publish landmark rows only)
 #pragma unroll
@@ -636,7 +722,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 r[0][c] = rp[0][c]; r[1][c] = rp[1][c]; r[2][c] = rp[2][c];
-                r[3][c] = sPub[nb][0][lane + 64 * c]; r[4][c] = sPub[nb][1][lane + 64 * c]; r[5][c] = sPub[nb][2][lane + 64 * c];
+                r[3][c] = sPub[nb][0][pcol + 64 * c]; r[4][c] = sPub[nb][1][pcol + 64 * c]; r[5][c] = sPub[nb][2][pcol + 64 * c];
             }
 #ifdef ASLAM_WIN_POSE_CHECK
             dend = 0.0;
@@ -1142,7 +1228,7 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
         old = prev;
     }
 }
-template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0>
+template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0, int WP = 0>
 __global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
 void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
     const WinDesc& wd = wa;
@@ -1156,7 +1242,7 @@ void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinRe
         __syncthreads();
         bx = sTicket;
     }
-    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G, LG>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
+    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G, LG, WP>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
     else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE, G::kOn>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
     else if (rq.nsteps > 0) win_psi_role<T, ONE, G::kOn>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
 }
@@ -1510,52 +1596,72 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 // of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
 // waited for up to a whole window (measured: DESIGN.md).  The chain role's block has grown by kGrown bytes since (the header records);
 // the dynamic part gives them back, so that static + dynamic is what it was measured at.
-template <int T, bool ONE, int LG = 0, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
+template <int T, bool ONE, int LG = 0, int WP = 0, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const W& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
     constexpr size_t cap = (size_t)24 * 1024 + WinChainLds<T, ONE>::kGrown;
     const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, cap);                    // static + dynamic > 80 KB of the 160 KB
-    static bool attr_done = false;                                 // (per instantiation: LG tells kernels of one signature apart)
+    static bool attr_done = false;                                 // (per instantiation: LG and WP tell kernels of one signature apart)
     if (!attr_done && dyn > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         attr_done = true;
     }
     hipLaunchKernelGGL(kernel, dim3(nb), dim3(nt), dyn, st, E, sp, wd, rs, rq, obs, enc);
 }
+// wp: how the workers publish (win_chain_role's WP, bits of kWinWorkerPublishAll; 0 = the comparison path; negative: the width's default)
+#define ASLAM_WP_FORMS(F) F(0) F(1) F(2) F(3)
+template <int T, int NT> static void launch_win_pieces_wp(hipStream_t st, int nb, int wp, const EkfState& E, const SlamParams& sp, const WinArg<NoSlamGate>& wa, const WinReplay& rs,
+                                                          const WinReplay& rq, const ObsRaw* obs, const double* enc) {
+    constexpr size_t lds = sizeof(WinChainLds<T, false>);
+    switch (wp < 0 ? win_worker_publish_default(T) : wp & kWinWorkerPublishAll) {
+#define ASLAM_WP_LAUNCH(i) case i: launch_step_kernel<T, false, 0, i>(k_ekf_win_step<T, 2, false, NoSlamGate, 0, i>, st, nb, NT, lds, E, sp, wa, rs, rq, obs, enc); break;
+        ASLAM_WP_FORMS(ASLAM_WP_LAUNCH)
+#undef ASLAM_WP_LAUNCH
+    }
+}
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
-                         int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps) {
+                         int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps, int worker_publish) {
     const WinReplay rs{s_piece, s_log0, s_nsteps, wd.wpar}, rq{q_piece, q_log0, q_nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_step_kernel<4, false>(k_ekf_win_step<4, 2, false>, st, nb, 256, sizeof(WinChainLds<4, false>), E, sp, wa, rs, rq, obs, enc);
-    else if (wd.T == 8) launch_step_kernel<8, false>(k_ekf_win_step<8, 2, false>, st, nb, 320, sizeof(WinChainLds<8, false>), E, sp, wa, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
-    else launch_step_kernel<12, false>(k_ekf_win_step<12, 2, false>, st, nb, 448, sizeof(WinChainLds<12, false>), E, sp, wa, rs, rq, obs, enc);
+    if (wd.T == 4) launch_win_pieces_wp<4, 256>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);
+    else if (wd.T == 8) launch_win_pieces_wp<8, 320>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
+    else launch_win_pieces_wp<12, 448>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);
 }
-// lg: what the logger wave takes over from the prepare wave (win_chain_role's LG; 0 = the comparison path)
-template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
+// lg: what the logger wave takes over from the prepare wave (win_chain_role's LG; 0 = the comparison path).  The workers' forms are
+// built beside the default logger only: with another lg the workers publish in their default form
+template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, int wp, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
                                                                           const ObsRaw* obs, const double* enc) {
     constexpr size_t lds = sizeof(WinChainLds<T, true>);
-    if (lg == 3) launch_step_kernel<T, true, 3>(k_ekf_win_step<T, 2, true, G, 3>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
-    else if (lg == 2) launch_step_kernel<T, true, 2>(k_ekf_win_step<T, 2, true, G, 2>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
-    else if (lg == 1) launch_step_kernel<T, true, 1>(k_ekf_win_step<T, 2, true, G, 1>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
-    else launch_step_kernel<T, true, 0>(k_ekf_win_step<T, 2, true, G, 0>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    constexpr int WD = win_worker_publish_default(T);
+    if (lg == 3) {
+        switch (wp < 0 ? WD : wp & kWinWorkerPublishAll) {
+#define ASLAM_WP_LAUNCH(i) case i: launch_step_kernel<T, true, 3, i>(k_ekf_win_step<T, 2, true, G, 3, i>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc); break;
+            ASLAM_WP_FORMS(ASLAM_WP_LAUNCH)
+#undef ASLAM_WP_LAUNCH
+        }
+    }
+    else if (lg == 2) launch_step_kernel<T, true, 2, WD>(k_ekf_win_step<T, 2, true, G, 2, WD>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    else if (lg == 1) launch_step_kernel<T, true, 1, WD>(k_ekf_win_step<T, 2, true, G, 1, WD>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+    else launch_step_kernel<T, true, 0, WD>(k_ekf_win_step<T, 2, true, G, 0, WD>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
 }
+#undef ASLAM_WP_FORMS
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc, const SlamGateArg* gate,
-                        int logger_parts) {
+                        int logger_parts, int worker_publish) {
     const WinReplay r{0, 0, wd.nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
     if (gate) {                                                     // the gated instantiations: same grids, same blocks
         const WinArg<WinGate> wa{wd, WinGate{gate->g.gate_d2}};
-        if (wd.T == 4) launch_win_one_lg<4, 256, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
-        else if (wd.T == 8) launch_win_one_lg<8, 384, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
-        else launch_win_one_lg<12, 512, WinGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+        if (wd.T == 4) launch_win_one_lg<4, 256, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+        else if (wd.T == 8) launch_win_one_lg<8, 384, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+        else launch_win_one_lg<12, 512, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
         return;
     }
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
-    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
-    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, E, sp, wa, r, obs, enc);
+    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
 }
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
     hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
