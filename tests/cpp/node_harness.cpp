@@ -58,6 +58,9 @@ int main(int argc, char** argv) {
     double* dst[] = {&d.kl, &d.kr, &d.b, &d.Q_k, &d.R_x, &d.R_y, &d.R_theta, &d.marker_length};
     for (int i = 0; i < 8; i++) nh.getParam(std::string("/aruco_slam_node/") + keys[i], *dst[i]);
     nh.getParam("/aruco_slam_node/aruco/markers_dictionary", d.markers_dictionary);
+    // the reference's node asks for this key with a trailing underscore (aruco_slam_node.cpp:161), so the key of its parameters.yaml,
+    // which has none, never takes effect and the struct's default of 3 stands
+    nh.getParam("/aruco_slam_node/const/USEFUL_DISTANCE_THRESHOLD_", d.USEFUL_DISTANCE_THRESHOLD);
     std::string base, cam;
     nh.getParam("/aruco_slam_node/frame/robot_frame_base", base);
     nh.getParam("/aruco_slam_node/frame/camera_frame_optical", cam);

@@ -47,22 +47,24 @@ def _inv3(A):
     return C / (a * C[0, 0] + b * C[1, 0] + c * C[2, 0])
 
 
-def reference_step(mu, S, wl, wr, dt, obs, kl=0.05, kr=0.05, b=0.09, Qk=0.01, dtype=LD):
-    """predict, then the corrections obs = [(index, z(3), Rdiag(3))] in pop order; returns (mu, Sigma) in `dtype`"""
+def reference_step(mu, S, wl, wr, dt, obs, kl=0.05, kr=0.05, b=0.09, Qk=0.01, dtype=LD, predict=True):
+    """predict, then the corrections obs = [(index, z(3), Rdiag(3))] in pop order; returns (mu, Sigma) in `dtype`.  predict = False:
+    the corrections alone, on a state that a predict of the caller's has left"""
     mu = np.array(mu, dtype=dtype); S = np.array(S, dtype=dtype)
-    wl, wr, dt = dtype(wl), dtype(wr), dtype(dt)
-    dsl, dsr = dtype(kl) * (dt * wl), dtype(kr) * (dt * wr)
-    dth = (dsr - dsl) / (2 * dtype(b)); ds = (dsr + dsl) / 2
-    th = mu[2] + dth / 2
-    c, s = np.cos(th), np.sin(th)
-    mu[0] += ds * c; mu[1] += ds * s; mu[2] = wrap_once(mu[2] + dth)
-    H = np.array([[1, 0, -ds * s], [0, 1, ds * c], [0, 0, 1]], dtype=dtype)
-    f = dtype(kl) * dt / 2
-    wkh = np.array([[f * c, f * c], [f * s, f * s], [f / dtype(b), -f / dtype(b)]], dtype=dtype)
-    Q = wkh @ np.diag(np.array([dtype(Qk) * abs(wl), dtype(Qk) * abs(wr)], dtype=dtype)) @ wkh.T
-    S[:3, :] = H @ S[:3, :]
-    S[:, :3] = S[:, :3] @ H.T
-    S[:3, :3] += Q
+    if predict:
+        wl, wr, dt = dtype(wl), dtype(wr), dtype(dt)
+        dsl, dsr = dtype(kl) * (dt * wl), dtype(kr) * (dt * wr)
+        dth = (dsr - dsl) / (2 * dtype(b)); ds = (dsr + dsl) / 2
+        th = mu[2] + dth / 2
+        c, s = np.cos(th), np.sin(th)
+        mu[0] += ds * c; mu[1] += ds * s; mu[2] = wrap_once(mu[2] + dth)
+        H = np.array([[1, 0, -ds * s], [0, 1, ds * c], [0, 0, 1]], dtype=dtype)
+        f = dtype(kl) * dt / 2
+        wkh = np.array([[f * c, f * c], [f * s, f * s], [f / dtype(b), -f / dtype(b)]], dtype=dtype)
+        Q = wkh @ np.diag(np.array([dtype(Qk) * abs(wl), dtype(Qk) * abs(wr)], dtype=dtype)) @ wkh.T
+        S[:3, :] = H @ S[:3, :]
+        S[:, :3] = S[:, :3] @ H.T
+        S[:3, :3] += Q
     mu0 = mu.copy()                                           # every correction is linearised at the pre-frame mean (Q1)
     st, ct = np.sin(mu0[2]), np.cos(mu0[2])
     for idx, z, Rd in obs:

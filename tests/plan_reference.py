@@ -131,13 +131,13 @@ def new_z(rng):
     return np.array([rng.uniform(0.5, 2), rng.uniform(-1, 1), rng.uniform(-3, 3)])
 
 
-def make_frame(rng, ref, spec, prev_obs, shift=0.0):
+def make_frame(rng, ref, spec, prev_obs, shift=0.0, kl=0.05, kr=0.05, b=0.09):
     """one frame from spec = [(kind, what)] in detection order, observed from the reference's current state:
     ("new", id): an observation of an id (mapped or not) at a random place; ("known", index): a noisy observation of that landmark
     under its id; ("repeat", id or (id, detection position there)): the previous frame's observation of the id again;
     ("gated", id): an observation that did not pass the gates (valid = 0).  shift moves the x of the "known" observations (frames that alternate it are never "stationary").  Asserts the margins that keep the reference's own decisions away from rounding."""
     mu = ref.lit.mu
-    pose = predicted_pose(mu, WL, WR, DT)
+    pose = predicted_pose(mu, WL, WR, DT, kl=kl, kr=kr, b=b)
     obs = []
     for kind, what in spec:
         if kind == "known":
@@ -155,7 +155,7 @@ def make_frame(rng, ref, spec, prev_obs, shift=0.0):
         else:
             assert kind == "gated"
             obs.append((int(what), 0, new_z(rng), rng.uniform(0.02, 0.2, 3)))
-    dth = (0.05 * DT * WR - 0.05 * DT * WL) / (2 * 0.09)
+    dth = (kr * DT * WR - kl * DT * WL) / (2 * b)
     assert abs(abs(float(mu[2]) + dth) - math.pi) > 1e-6, "the predicted heading is within 1e-6 of +-pi before its wrap"
     check_margins(ref, obs, prev_obs, pose)
     return obs

@@ -18,12 +18,14 @@ K = np.array([[450.0, 0, 319.5], [0, 450.0, 239.5], [0, 0, 1]])
 D = np.zeros(5)
 
 
-def make_case(seed, groups, n_land):
+def make_case(seed, groups, n_land, params=None, motions=None):
     """groups: list of (n_frames, landmark subset); frames of a group all see the same landmarks (windows), the pose of every
-    marker changes from frame to frame (no "stationary" branch) unless a subset entry is negative = 'repeat last pose'."""
+    marker changes from frame to frame (no "stationary" branch) unless a subset entry is negative = 'repeat last pose'.
+    params: filter parameters (Q_k, kl, kr, b) of the transcription, default the reference's; motions: (wl, wr, dt) that the frames
+    cycle through in place of the drawn wheel speeds and the 0.05 s step (the draws are made all the same)."""
     rng = np.random.RandomState(seed)
     ids_all = rng.permutation(np.arange(1, 400))[:n_land]
-    s = LiteralSlam(r2c=(0.1, -0.05))
+    s = LiteralSlam(r2c=(0.1, -0.05), **(params or {}))
     s.K, s.D = K, D
     hl = 0.135
     obj = [(-hl, hl, 0), (hl, hl, 0), (hl, -hl, 0), (-hl, -hl, 0)]
@@ -32,8 +34,12 @@ def make_case(seed, groups, n_land):
     f = 0
     for n_frames, subset, repeat in groups:
         for k in range(n_frames):
-            t += 0.05
             wl, wr = rng.uniform(1, 4), rng.uniform(1, 4)
+            if motions is None:
+                t += 0.05
+            else:
+                wl, wr, dt = motions[f % len(motions)]
+                t += dt
             ids, corners, rvs, tvs = [], [], [], []
             for li in subset:
                 rs = np.random.RandomState(1000 * seed + 31 * int(li) + (f - 1 if (repeat and k > 0) else f))
@@ -55,13 +61,14 @@ def make_case(seed, groups, n_land):
     return frames, exp
 
 
-def run_device(frames, exp, batch, windows=True, check=True, max_landmarks=40, max_updates=24):
+def run_device(frames, exp, batch, windows=True, check=True, max_landmarks=40, max_updates=24, params=None):
+    """params: filter parameters (Q_k, kl, kr, b) of the context, default aslam_init's"""
     if not windows:
         os.environ["ASLAM_NO_WINDOWS"] = "1"
     try:
         nfr = len(frames)
         ctx = capi.Context(max_rows=64, max_cols=64, max_batch=nfr, persistent_waves=4, max_landmarks=max_landmarks, r2c_t=(0.1, -0.05, 0.0),
-                           max_updates_per_frame=max_updates)
+                           max_updates_per_frame=max_updates, **(params or {}))
     finally:
         os.environ.pop("ASLAM_NO_WINDOWS", None)
     ctx.set_camera(K, D)

@@ -79,6 +79,48 @@ def test_detected_markers(ran):
         assert np.allclose(quat_matrix(m["orientation"]), Rr @ orc.rodrigues(r)[0], atol=1e-12)
 
 
+def test_markers_at_other_parameters():
+    """marker_length 0.41 and a 4.5 m range gate (every other case here runs at 0.27 and 3 m): the scale of both marker lists and the
+    range filter of the detected ones (capi.hip: aslam_get_map_markers, aslam_get_detected_markers).  Injected quads, no detector:
+    markers at 2 m, at 3.5 m (past the default gate, inside the configured one), at 4.4, 4.6 and 6 m"""
+    import pose_reference as pr
+    from test_pose_kernel import D_DEFAULT, K900, corners_of
+    length, threshold = 0.41, 4.5
+    q_r2c = np.array([0.5, -0.5, 0.5, -0.5])
+    ctx = capi.Context(max_rows=64, max_cols=64, max_batch=1, persistent_waves=4, max_landmarks=4, marker_length=length,
+                       useful_distance_threshold=threshold, r2c_t=(0.18, -0.1, 0.05), r2c_q=tuple(q_r2c))
+    ctx.set_camera(K900, D_DEFAULT)
+    norms = [2.0, 3.5, 4.4, 4.6, 6.0]
+    quads = []
+    for k, n in enumerate(norms):
+        d = np.array([0.1 * (k - 2), 0.05 * (2 - k), 1.0])
+        t = np.array(d / np.linalg.norm(d) * n, np.longdouble)
+        quads.append(corners_of(pr.rot_y(0.2 * (k - 2)) @ pr.facing(), t, K900, D_DEFAULT, marker_length=length))
+    want_ids = [11, 3, 40, 7, 25]
+    ctx.inject_candidates(0, want_ids, [0] * 5, np.array(quads, np.float32).reshape(-1, 8))
+    ctx.run_pose(0, 1)
+    ids, _, rv, tv = ctx.get_detections()
+    assert ids.tolist() == want_ids
+    assert np.allclose(np.linalg.norm(tv, axis=1), norms, rtol=1e-4), "the pose was not solved at the configured marker_length"
+    inside = [bool(np.float32(np.linalg.norm(t)) <= np.float32(threshold)) for t in tv]
+    assert inside == [True, True, True, False, False]
+    mk = ctx.detected_markers()
+    assert [m["id"] for m in mk] == [i for i, k in zip(want_ids, inside) if k]
+    Rr = quat_matrix(q_r2c)
+    kept = [j for j, k in enumerate(inside) if k]
+    for m, j in zip(mk, kept):
+        assert m["scale"] == (length, length, 0.01) and m["color"] == (1.0, 0.0, 0.0, 1.0) and m["lifetime"] == 0.1
+        assert np.allclose(m["position"], Rr @ tv[j] + np.array([0.18, -0.1, 0.05]), atol=1e-13)
+        assert np.allclose(quat_matrix(m["orientation"]), Rr @ orc.rodrigues(rv[j])[0], atol=1e-12)
+    mu = np.array([0.1, 0.2, 0.3, 1.0, -2.0, 0.5, -1.5, 0.7, -2.8])
+    ctx.set_state(mu, np.eye(9) * 0.01, [5, 9])
+    mk = ctx.map_markers()
+    assert len(mk) == 2
+    for i, m in enumerate(mk):
+        assert m["id"] == i and m["scale"] == (length, length, 0.01)
+        assert np.array_equal(m["position"], [mu[3 + 3 * i], mu[4 + 3 * i], 0.3])
+
+
 def test_state_round_trip_through_a_file(ran, tmp_path):
     ctx, _ = ran
     f = tmp_path / "state.bin"

@@ -99,15 +99,23 @@ class Slot:
         return [i for i, k in zip(idx, keep) if k]
 
 
-def observe_oracle(K, D, rv, tv, corners, mount, threshold=3.0):
-    """getObservations' body in the oracle (camera frame), one marker, then the mount: (valid, xyth, diag R)"""
-    o = orc.Slam(useful_distance_threshold=threshold)
+R_XYT = (100.0, 100.0, 10.0)
+
+
+def observe_oracle(K, D, rv, tv, corners, mount, threshold=3.0, marker_length=L, R_xyt=R_XYT, r2c=False):
+    """getObservations' body in the oracle (camera frame), one marker, then the mount: (valid, xyth, diag R).  r2c: the mount is the
+    single camera's r2c_t, which the oracle applies itself"""
+    o = orc.Slam(useful_distance_threshold=threshold, marker_length=marker_length, R_x=R_xyt[0], R_y=R_xyt[1], R_theta=R_xyt[2],
+                 r2c_tx=mount[0] if r2c else 0.0, r2c_ty=mount[1] if r2c else 0.0)
     o.set_camera(K, D)
     o.add_encoder(0, 0, 0)
     o.add_poses([0], corners[None], rv[None], tv[None])
     _, _, _, xyth, R = o.log_observations()
     if len(xyth) == 0:
         return False, None, None
+    if r2c:
+        assert mount[2] == 0.0
+        return True, xyth[0], np.diag(R[0])
     x0, y0, th0 = xyth[0]
     mx, my, psi = mount
     c, s = math.cos(psi), math.sin(psi)
@@ -127,17 +135,19 @@ def angle_diff(a, b):
     return np.where(at_wrap, np.abs((a - b + pr.PI) % (2 * pr.PI) - pr.PI), d)
 
 
-def run_slots(ctx, slots, tol, first=0, robots=None, threshold=3.0, check_cost=True):
+def run_slots(ctx, slots, tol, first=0, robots=None, threshold=3.0, check_cost=True, **par):
+    """par: marker_length, R_xyt and r2c where the context's are not the defaults (observe_oracle)"""
     for s, sl in enumerate(slots):
         ctx.inject_candidates(first + s, sl.ids, sl.rots, np.array(sl.corners, np.float32).reshape(-1, 8) if sl.ids else np.zeros((0, 8)))
     ctx.run_pose(first, len(slots), robots)
     out = []
     for s, sl in enumerate(slots):
-        out.append(check_slot(ctx, first + s, sl, tol, threshold, check_cost))
+        out.append(check_slot(ctx, first + s, sl, tol, threshold, check_cost, **par))
     return out
 
 
-def check_slot(ctx, slot, sl, tol, threshold, check_cost):
+def check_slot(ctx, slot, sl, tol, threshold, check_cost, marker_length=L, R_xyt=R_XYT, r2c=False):
+    L = marker_length
     K, D, mount = sl.cam
     exp = sl.expected()
     ids, corners, rv, tv = ctx.get_slot_detections(slot)
@@ -177,7 +187,7 @@ def check_slot(ctx, slot, sl, tol, threshold, check_cost):
         assert g.max() <= tol["step"], f"slot {slot}: not a stationary point of the cost (Gauss-Newton step {g.max():.3g} relative)"
     # observation against the oracle's tail fed the kernel's own pose, and against the reference formulas
     for j in range(len(ids)):
-        ok, z, r = observe_oracle(K, D, rv[j], tv[j], corners[j], mount, threshold)
+        ok, z, r = observe_oracle(K, D, rv[j], tv[j], corners[j], mount, threshold, L, R_xyt, r2c)
         assert bool(valid[j]) == ok, f"slot {slot} marker {j}: valid {valid[j]}, oracle {ok}"
         if ok:
             e = max(rel(xyth[j, :2], z[:2]), float(angle_diff(xyth[j, 2], z[2])), rel(Rd[j], r))
@@ -188,7 +198,7 @@ def check_slot(ctx, slot, sl, tol, threshold, check_cost):
     e = max(rel(xyth[:, :2], z_ref[:, :2]), float(angle_diff(xyth[:, 2], z_ref[:, 2]).max()))
     note("observation vs reference", e)
     assert e <= tol["obs_ref"], f"slot {slot}: observation differs from the reference by {e:.3g}"
-    R_ref, slack = pr.covariance(rv, tv, corners, K, D, L)
+    R_ref, slack = pr.covariance(rv, tv, corners, K, D, L, R_xyt)
     dR = np.abs(Rd - np.asarray(R_ref, np.float64))
     assert (dR <= tol["obs_ref"] * np.asarray(R_ref, np.float64) + np.asarray(slack, np.float64)).all(), f"slot {slot}: diag R differs from the reference"
     pass_d, m_d = pr.range_gate(tv, threshold)
@@ -314,6 +324,56 @@ def test_range_gate_near_three_metres(tol):
         sl.add(k, corners_of(R, t, K900, D_DEFAULT), truth=(R, t))
     run_slots(ctx, [sl], tol)
     _, valid, _, _ = ctx.get_slot_raw_observations(0)
+    assert valid[0] == 1 and valid[1] == 0
+
+
+# ---- parameters away from the defaults ---------------------------------------------------------------------------------------
+# Every other case runs at marker_length 0.27, R = (100, 100, 10), a 3 m range gate and r2c_t = 0.  Here: a marker_length that must
+# reach solve_marker_pose, the covariance's half-length and |t| / marker_length alike; R_x != R_y; a range gate that is not 3 m; and
+# the single camera's r2c_t (capi.hip: single_camera).
+
+R_OTHER = (40.0, 250.0, 3.0)
+R2C = (0.12, -0.07, 0.0)
+
+
+@pytest.mark.parametrize("threshold", [1.5, 6.0])
+@pytest.mark.parametrize("length", [0.10, 0.50])
+def test_non_default_parameters(length, threshold, tol):
+    """marker_length 0.10 / 0.50, R = (40, 250, 3), r2c_t = (0.12, -0.07, 0), |t| at the threshold -+ 0.1 m and within a few float ulps
+    of it; poses against the oracle's solvePnP at that length, observations against the oracle's Slam built with the same values
+    and against the reference formulas"""
+    ctx = context(2, marker_length=length, R_x=R_OTHER[0], R_y=R_OTHER[1], R_theta=R_OTHER[2], useful_distance_threshold=threshold,
+                  r2c_t=R2C)
+    ctx.set_camera(K900, D_DEFAULT)
+    cam = (K900, D_DEFAULT, R2C)
+    rng = np.random.RandomState(int(1000 * length + 10 * threshold))
+    spread = Slot(cam)                                           # poses of every heading, well inside the gate; every other one with
+                                                                 # corner noise, so that object_error and with it R_x, R_y, R_theta show
+    k = 0
+    while k < 12:
+        R = pr.rot_x(rng.uniform(-0.5, 0.5)) @ pr.rot_y(rng.uniform(-0.9, 0.9)) @ pr.rot_z(rng.uniform(-math.pi, math.pi)) @ pr.facing()
+        t = np.array([rng.uniform(-0.25, 0.25), rng.uniform(-0.15, 0.15), 1.0], np.longdouble) * rng.uniform(0.4, 0.9) * min(threshold, 3.0)
+        c = corners_of(R, t, K900, D_DEFAULT, marker_length=length)
+        if (c[:, 0] > 2).all() and (c[:, 0] < COLS - 2).all() and (c[:, 1] > 2).all() and (c[:, 1] < ROWS - 2).all():
+            noisy = k % 2 == 1
+            spread.add(k, (c + rng.uniform(-0.5, 0.5, c.shape)).astype(np.float32) if noisy else c, rot=k % 4, truth=(R, t), clean=not noisy)
+            k += 1
+    gate = Slot(cam)
+    u = np.spacing(np.float32(threshold))
+    norms = [threshold - 0.1, threshold + 0.1] + [threshold + j * float(u) for j in (-3, -1, 0, 1, 3)]
+    for k, n in enumerate(norms):
+        d = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.2, 0.2), 1.0])
+        t = np.array(d / np.linalg.norm(d) * n, np.longdouble)
+        R = pr.rot_y(0.3) @ pr.facing()
+        gate.add(k, corners_of(R, t, K900, D_DEFAULT, marker_length=length), truth=(R, t))
+    run_slots(ctx, [spread, gate], tol, threshold=threshold, marker_length=length, R_xyt=R_OTHER, r2c=True)
+    _, valid, xyth, Rd = ctx.get_slot_raw_observations(0)
+    assert valid[0::2].all(), "a noise-free marker well inside the range was gated"
+    # R_x != R_y: the entries of diag R are object_error (R_x, R_y, R_theta) + (1e-2, 1e-2, 1e-3), and the noisy corners make it show
+    oe = (Rd[1::2, 0] - 1e-2) / R_OTHER[0]
+    assert (oe > 1e-6).all(), oe                                 # (the constants of diag R are 1e-2 and 1e-3, compared at 5e-15)
+    assert np.allclose(Rd[1::2, 1] - 1e-2, oe * R_OTHER[1], rtol=1e-9, atol=1e-15) and np.allclose(Rd[1::2, 2] - 1e-3, oe * R_OTHER[2], rtol=1e-9, atol=1e-15)
+    _, valid, _, _ = ctx.get_slot_raw_observations(1)
     assert valid[0] == 1 and valid[1] == 0
 
 

@@ -32,15 +32,17 @@ CAM = (synth.camera_matrix(64, 64, 60.0), np.zeros(5), (0.0, 0.0, 0.0))
 
 # ---- sequences and their reference ------------------------------------------------------------------------------------------------
 
-def make_frames(rng, mu, ids, plan, nan=()):
+def make_frames(rng, mu, ids, plan, nan=(), motions=None, params=None):
     """plan = per frame the landmark indices it sees, ascending (frame 0 arms the filter and sees nothing), outliers = set of (frame,
-    position): frames = [[(id, z, Rdiag)]] in a random detection order; nan: (frame, position) whose z[0] is NaN"""
+    position): frames = [[(id, z, Rdiag)]] in a random detection order; nan: (frame, position) whose z[0] is NaN.  motions: frame f's
+    (wl, wr, dt) in place of (WL, WR, DT), params: the filter's Q_k, kl, kr, b in place of the defaults"""
     pose = mu[:3].copy()
     frames, marks = [], []
     prev = {}
     for f, (seen, out) in enumerate(plan):
         if f:
-            pose = predicted_pose(np.concatenate([pose, mu[3:]]), WL, WR, DT)
+            pose = predicted_pose(np.concatenate([pose, mu[3:]]), *((WL, WR, DT) if motions is None else motions[f]),
+                                  **{k: v for k, v in (params or {}).items() if k != "Q_k"})
         obs = []
         for k, i in enumerate(seen):
             while True:                                            # drawn again while it lies within 0.03 of the frame before's sighting
@@ -68,14 +70,15 @@ def assert_repeats_decidable(frames):
                 assert d == 0.0 or math.isnan(d) or d > 0.02, f"a repeated sighting {d} from its predecessor"
 
 
-def reference(mu, S, ids, frames, gate=None, marks=None):
-    """GatedLiteralSlam over the frames (frame 0 arms): per frame its pop log, stats, slot record and the track record behind it"""
-    lit = GatedLiteralSlam(gate=dict(gate_d2=GATE, **(gate or {})))
+def reference(mu, S, ids, frames, gate=None, marks=None, motions=None, params=None, cls=GatedLiteralSlam):
+    """GatedLiteralSlam over the frames (frame 0 arms): per frame its pop log, stats, slot record and the track record behind it.
+    motions: frame f's (wl, wr, dt) in place of (WL, WR, DT); params: the transcription's Q_k, kl, kr, b"""
+    lit = cls(gate=dict(gate_d2=GATE, **(gate or {})), **(params or {}))
     lit.seat(mu, S, ids)
     per = []
     for f, obs in enumerate(frames):
         lit.last_time = 0.0                                        # (every sample's dt is DT exactly)
-        lit.add_encoder(WL if f else 0.0, WR if f else 0.0, DT if f else 0.0)
+        lit.add_encoder(*((0.0, 0.0, 0.0) if not f else (WL, WR, DT) if motions is None else motions[f]))
         lit.add_frame(obs)
         per.append(dict(log=list(lit.log), stats=list(lit.stats), health=dict(lit.health), track=dict(lit.track)))
         if marks is not None:                                      # the reference alone separates outliers from true sightings
@@ -99,9 +102,11 @@ def plan_list(ctx):
 class Run:
     """a context on a sequence: state seated, every frame injected, run in the given batches"""
 
-    def __init__(self, mu, S, ids, frames, batches=None, gate=GATE, switch=True, windows=True, cap=24, ML=None, gate_kw=None, rig=0):
+    def __init__(self, mu, S, ids, frames, batches=None, gate=GATE, switch=True, windows=True, cap=24, ML=None, gate_kw=None, rig=0,
+                 motions=None, params=None):
         n = len(frames)
-        kw = dict(max_rows=64, max_cols=64, max_batch=n * max(rig, 1), persistent_waves=4, max_landmarks=ML or len(ids), max_updates_per_frame=cap)
+        kw = dict(max_rows=64, max_cols=64, max_batch=n * max(rig, 1), persistent_waves=4, max_landmarks=ML or len(ids), max_updates_per_frame=cap,
+                  **(params or {}))
         ctx = capi.Context(**kw) if windows else no_windows_context(**kw)
         if gate is not None:
             ctx.set_slam_gate(gate_d2=gate, **(gate_kw or {}))
@@ -111,7 +116,8 @@ class Run:
             ctx.set_camera_rig([CAM] * rig)
         ctx.set_state(mu, S, ids)
         slots = n * max(rig, 1)
-        enc = np.repeat(np.array([[0.0, 0.0, 0.0]] + [[WL, WR, DT]] * (n - 1)), max(rig, 1), axis=0)
+        enc = np.repeat(np.array([[0.0, 0.0, 0.0]] + ([[WL, WR, DT]] * (n - 1) if motions is None else [list(m) for m in motions[1:n]])),
+                        max(rig, 1), axis=0)
         ctx.stage_encoders(enc[:, 0], enc[:, 1], enc[:, 2])
         for s, obs in enumerate(frames):
             cams = [obs] if not rig else [obs[c::rig] for c in range(rig)]

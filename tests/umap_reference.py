@@ -32,9 +32,10 @@ def sym_blocks(map_sigmas):
 
 
 class UncertainMapLocalizer(GatedLocalizer):
-    """mu_x (3) and the dense Sigma of [pose, map] with fixed block-diagonal Sigma_ll, in long double"""
+    """mu_x (3) and the dense Sigma of [pose, map] with fixed block-diagonal Sigma_ll, in long double (or in `dtype`)"""
 
-    def __init__(self, ids, xyth, map_sigmas, pose, pose_sigma, gate=None, cross=True, **kw):
+    def __init__(self, ids, xyth, map_sigmas, pose, pose_sigma, gate=None, cross=True, dtype=LD, **kw):
+        self.dtype = LD = dtype                         # np.float64: the double form, to show that a case is well conditioned
         super().__init__(ids, xyth, pose, pose_sigma, gate if gate is not None else dict(gate_d2=math.inf), **kw)
         L = self.xyth.shape[0]
         self.L, self.N = L, 3 + 3 * L
@@ -56,6 +57,7 @@ class UncertainMapLocalizer(GatedLocalizer):
 
     def seat(self, pose, pose_sigma):
         """a seat of the pose drops its correlation with the map"""
+        LD = self.dtype
         self.x = np.asarray(pose, LD).copy()
         self.S[:3, :3] = np.asarray(pose_sigma, LD).reshape(3, 3)
         self.S[:3, 3:] = 0
@@ -65,6 +67,7 @@ class UncertainMapLocalizer(GatedLocalizer):
         self.track = dict(TRACK_ZERO)
 
     def predict(self, wl, wr, dt):
+        LD = self.dtype
         wl, wr, dt = LD(wl), LD(wr), LD(dt)
         kl, kr, b, Qk = LD(self.kl), LD(self.kr), LD(self.b), LD(self.Q_k)
         delta_sl, delta_sr = kl * (dt * wl), kr * (dt * wr)
@@ -86,6 +89,7 @@ class UncertainMapLocalizer(GatedLocalizer):
         S[:3, :3] += Q
 
     def add_observations(self, obs):
+        LD = self.dtype
         g = self.gate
         q = _Heap()
         for k, (lid, valid, z, r) in enumerate(obs):
