@@ -121,6 +121,16 @@ TRACK_HEALTH_DTYPE = np.dtype([("frames", "<i4"), ("accepted_total", "<i4"), ("r
                                ("lost", "<i4"), ("pad", "<i4", (3,))], align=True)
 
 
+class ConfirmParams(C.Structure):
+    """mirror of aslam_confirm_params"""
+    _fields_ = [("min_sightings", C.c_int), ("max_gap", C.c_int)]
+
+
+# mirror of aslam_slot_confirm: what Context.get_slot_confirm returns
+SLOT_CONFIRM_DTYPE = np.dtype([("judged", "<i4"), ("tentative", "<i4"), ("withheld", "<i4"), ("promoted", "<i4"),
+                               ("withheld_mask", "<u4", (4,))], align=True)
+
+
 class AslamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aslam error {code} ({E_NAMES.get(code, '?')}): {msg}")
@@ -182,6 +192,12 @@ _SIGS = {
     "aslam_get_slam_gate": (C.c_int, [C.c_void_p, _ip, _P(GateParams)]),
     "aslam_set_slam_gate_windows": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_get_slam_gate_windows": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_default_confirm_params": (None, [_P(ConfirmParams)]),
+    "aslam_set_landmark_confirmation": (C.c_int, [C.c_void_p, _P(ConfirmParams)]),
+    "aslam_get_landmark_confirmation": (C.c_int, [C.c_void_p, _ip, _P(ConfirmParams)]),
+    "aslam_get_slot_confirm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "aslam_get_tentative": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip]),
+    "aslam_fleet_get_tentative": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -727,6 +743,51 @@ class Context:
         on = C.c_int()
         self._ck(self.lib.aslam_get_slam_gate_windows(self.h, C.byref(on)))
         return bool(on.value)
+
+    # -- landmark confirmation -------------------------------------------------------------------------------------
+    def set_landmark_confirmation(self, params=True, **kw):
+        """set_landmark_confirmation(min_sightings=..., max_gap=...): the library's defaults with the given fields replaced;
+        set_landmark_confirmation(None): off"""
+        if params is None:
+            if kw:
+                raise ValueError("set_landmark_confirmation(None) takes no parameters")
+            self._ck(self.lib.aslam_set_landmark_confirmation(self.h, None))
+            return
+        p = ConfirmParams()
+        self.lib.aslam_default_confirm_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in ("min_sightings", "max_gap"):
+                raise KeyError(k)
+            setattr(p, k, int(v))
+        self._ck(self.lib.aslam_set_landmark_confirmation(self.h, C.byref(p)))
+
+    def get_landmark_confirmation(self):
+        """None while landmark confirmation is off, else its parameters as a dict"""
+        on, p = C.c_int(), ConfirmParams()
+        self._ck(self.lib.aslam_get_landmark_confirmation(self.h, C.byref(on), C.byref(p)))
+        if not on.value:
+            return None
+        return dict(min_sightings=p.min_sightings, max_gap=p.max_gap)
+
+    def get_slot_confirm(self, first, count):
+        """one SLOT_CONFIRM_DTYPE record per EKF slot first .. first + count - 1"""
+        out = np.zeros(max(int(count), 1), SLOT_CONFIRM_DTYPE)
+        self._ck(self.lib.aslam_get_slot_confirm(self.h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:max(int(count), 0)]
+
+    def _tentative(self, call):
+        ids, counts, ages = (np.zeros(1024, np.int32) for _ in range(3))
+        n = C.c_int()
+        self._ck(call(1024, C.byref(n), _ptr(ids, _ip), _ptr(counts, _ip), _ptr(ages, _ip)))
+        return ids[:n.value].copy(), counts[:n.value].copy(), ages[:n.value].copy()
+
+    def get_tentative(self):
+        """(ids, counts, ages) of the single SLAM filter's tentative ids, ascending by id"""
+        return self._tentative(lambda *a: self.lib.aslam_get_tentative(self.h, *a))
+
+    def fleet_get_tentative(self, robot):
+        """(ids, counts, ages) of robot's tentative ids in a SLAM fleet, ascending by id"""
+        return self._tentative(lambda *a: self.lib.aslam_fleet_get_tentative(self.h, int(robot), *a))
 
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""

@@ -29,12 +29,12 @@ namespace {
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
               P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_SLAM_RELOC_SOLVE,
-              P_SLAM_RELOC_SEAT, P_COUNT };
+              P_SLAM_RELOC_SEAT, P_CONFIRM, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
                                    "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish",
-                                   "k_slam_reloc_solve", "k_slam_reloc_seat"};
+                                   "k_slam_reloc_solve", "k_slam_reloc_seat", "confirm"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -174,6 +174,17 @@ struct aslam_ctx {
     MapCov umap{};                        // the C table, the fleet's strips (nullptr: the single filter's strip is in Sigma), landmarks
     double* d_map_c = nullptr;
     TrackHealth* h_track_health = nullptr;   // page-locked: ASLAM_MAX_ROBOTS + 1
+    // landmark confirmation (aslam_set_landmark_confirmation): off unless set; only EKF steps of SLAM filters look at it.
+    // The tables (one per robot a fleet can have, then the single filter's), the per-slot records and the page-locked buffer the getters
+    // read through are made by the first setter call with parameters and freed by aslam_destroy.  k_confirm runs on whichever stream
+    // carries the list it judges; ev_confirm orders a launch behind the previous one when the stream changes (they share the tables).
+    bool confirm_on = false;
+    aslam_confirm_params confirm_prm{};
+    ConfirmTable* d_confirm = nullptr;    // kConfirmSingle + 1 tables
+    SlotConfirm* d_confirm_rec = nullptr; // 2 max_batch records
+    char* h_confirm = nullptr;            // page-locked: one table, or 2 max_batch records
+    hipEvent_t ev_confirm = nullptr;
+    hipStream_t confirm_stream = nullptr; // stream of the most recent k_confirm (nullptr: none since the last full synchronisation)
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -691,6 +702,63 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     return ASLAM_OK;
 }
 
+// Landmark confirmation of a launch's filters on stream st, in front of whatever reads their slots' lists there: the
+// launch follows the previous k_confirm (the filters' tables) and, on another stream than the EKF's, EKF work still reading these slots.
+int launch_confirm_on(aslam_ctx* c, hipStream_t st, ConfirmArg& A, int filters, int first, int count) {
+    if (c->confirm_stream && c->confirm_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_confirm, 0));
+    if (st != c->stream_ekf && c->ekf_count > 0 && first < c->ekf_hi && c->ekf_lo < first + count) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_ekf, 0));
+    A.tables = c->d_confirm;
+    A.min_sightings = c->confirm_prm.min_sightings; A.max_gap = c->confirm_prm.max_gap;
+    A.obs = c->d_obs; A.n_markers = c->d_nmarkers; A.rec = c->d_confirm_rec;
+    prof_begin(c, P_CONFIRM, st);
+    launch_confirm(st, A, filters);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_confirm, st));
+    c->confirm_stream = st;
+    return ASLAM_OK;
+}
+
+// the single SLAM filter's EKF slots [first, first + count) judged on st (nothing while the switch is off or the map is frozen)
+int confirm_slots(aslam_ctx* c, hipStream_t st, int first, int count) {
+    if (!c->confirm_on || c->mode != Mode::Slam) return ASLAM_OK;
+    ConfirmArg A{};
+    A.first = first; A.count = count;
+    return launch_confirm_on(c, st, A, 1, first, count);
+}
+
+// one round of a fleet SLAM call judged on st: n robots, one slot each, rows {robot, slot, predict, 0} at d_work
+int confirm_round(aslam_ctx* c, hipStream_t st, const int* d_work, int n) {
+    if (!c->confirm_on) return ASLAM_OK;
+    ConfirmArg A{};
+    A.work = d_work;
+    return launch_confirm_on(c, st, A, n, 0, 0);
+}
+
+// Reseed of n SLAM filters: the single one (robots == nullptr) or the listed robots of the SLAM fleet.  Streams
+// synchronised by the caller; the tables are in place when this returns.  Nothing while the switch is off: switching it on reseeds.
+int confirm_reseed(aslam_ctx* c, int n, const int* robots) {
+    if (!c->confirm_on || n <= 0) return ASLAM_OK;
+    ConfirmReseed A{};
+    A.tables = c->d_confirm;
+    A.n = n;
+    if (robots) {
+        A.base = c->fslam.base; A.stride = c->fslam.stride;
+        for (int k = 0; k < n; k++) A.robot[k] = (unsigned char)robots[k];
+    } else {
+        A.base = c->ekf; A.stride = 0; A.single = 1;
+    }
+    launch_confirm_reseed(c->stream_ekf, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
+    return ASLAM_OK;
+}
+int confirm_reseed_fleet(aslam_ctx* c) {
+    std::vector<int> all(c->fleet_n);
+    for (int r = 0; r < c->fleet_n; r++) all[r] = r;
+    return confirm_reseed(c, c->fleet_n, all.data());
+}
+
 int sync_streams(aslam_ctx* c) {
     { int r = finalize_pending(c); if (r) return r; }
     if (c->stream_copy) HIP_TRY(c, hipStreamSynchronize(c->stream_copy));
@@ -699,6 +767,7 @@ int sync_streams(aslam_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
     if (c->stream_win) HIP_TRY(c, hipStreamSynchronize(c->stream_win));
     c->ekf_count = 0;
+    c->confirm_stream = nullptr;
     return ASLAM_OK;
 }
 
@@ -908,6 +977,9 @@ void aslam_destroy(aslam_ctx* c) {
     reloc_free(c->reloc);
     slam_reloc_free(c->slam_reloc);
     map_edit_free(c->map_edit);
+    hipFree(c->d_confirm); hipFree(c->d_confirm_rec);
+    if (c->h_confirm) hipHostFree(c->h_confirm);
+    if (c->ev_confirm) hipEventDestroy(c->ev_confirm);
     if (c->umap.cross) hipFree(c->umap.cross);
     if (c->d_map_c) hipFree(c->d_map_c);
     hipFree(c->gate.slot); hipFree(c->gate.track); hipFree(c->slam_gate.verdicts);
@@ -1223,6 +1295,8 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         // list, which a rejection on the device changes; the mirror is stale from here on
         if (c->slam_gate_on) c->mirror_dirty = true;
         HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+        r = confirm_slots(c, c->stream_ekf, first, count);
+        if (r) return r;
         for (int i = 0; i < count; i++) {
             const double* e = &c->enc_host[(size_t)3 * (first + i)];
             r = run_ekf_frame(c, first + i, e[0], e[1], e[2], arm_filter(c->is_init));
@@ -1237,6 +1311,8 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
     hipStream_t st = c->last_detect;
     const int e = c->ev_obs_next;
     c->ev_obs_next ^= 1;
+    r = confirm_slots(c, st, first, count);    // the host planner and its mirror only ever see the judged lists
+    if (r) return r;
     HIP_TRY(c, hipMemcpyAsync(c->h_obs + (size_t)first * kMarkerMax, c->d_obs + (size_t)first * kMarkerMax, (size_t)count * kMarkerMax * sizeof(ObsRaw),
                               hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(c->h_nm + first, c->d_nmarkers + first, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1330,6 +1406,8 @@ int add_frames(aslam_ctx* c, const Call& k, const uint8_t* const* px, int rows, 
         r = run_loc_steps(c, k.ekf_first, 1, false);
     } else {
         HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
+        r = confirm_slots(c, c->stream_ekf, k.ekf_first, 1);
+        if (r) return r;
         r = run_ekf_frame(c, k.ekf_first, 0, 0, 0, false);
     }
     if (r) return r;
@@ -1765,6 +1843,7 @@ int aslam_set_state(aslam_ctx* c, int N, const double* mu, const double* sigma, 
     int r = write_state(c, c->ekf, N, mu, sigma, landmark_ids);
     if (r) return r;
     c->mirror_dirty = true;
+    if (int rc = confirm_reseed(c, 1, nullptr)) return rc;
     return clear_track_health(c, kTrackSingle, 1);
 }
 
@@ -2125,8 +2204,15 @@ int enter_mode(aslam_ctx* c, Mode m, const std::vector<RigCam>& cams = {}) {
     c->fleet_n = fleet ? R : 0;
     c->fleet_armed.assign(c->fleet_n, 0);
     // a seat of every SLAM filter the mode starts with (the localization modes' begins clear their own records)
-    if (m == Mode::Slam) return clear_track_health(c, kTrackSingle, 1);
-    if (m == Mode::FleetSlam) return clear_track_health(c, 0, R);
+    // ... and a reseed of their landmark confirmation
+    if (m == Mode::Slam) {
+        if (int r = confirm_reseed(c, 1, nullptr)) return r;
+        return clear_track_health(c, kTrackSingle, 1);
+    }
+    if (m == Mode::FleetSlam) {
+        if (int r = confirm_reseed_fleet(c)) return r;
+        return clear_track_health(c, 0, R);
+    }
     return ASLAM_OK;
 }
 }  // namespace
@@ -2263,6 +2349,7 @@ int run_fleet_slam(aslam_ctx* c, int first, int count, const int* robots) {
     int row = 0;
     for (const std::vector<int>& rd : rounds) {
         const FleetRound R{c->fslam, c->d_fleet_work + 4 * row, c->d_enc, (int)rd.size()};
+        if (int rj = confirm_round(c, st, R.work, R.n)) return rj;
         prof_begin(c, P_EKF_PLAN, st);
         launch_ekf_plan(st, R, c->sp, c->d_obs, c->d_nmarkers, c->d_ctr, c->init.max_updates_per_frame);
         prof_end(c);
@@ -2472,6 +2559,7 @@ int aslam_fleet_set_state(aslam_ctx* c, int robot, int N, const double* mu, cons
     if (L > 0 && !landmark_ids) return fail(c, ASLAM_E_INVALID, "landmark ids required");
     { int rs = sync_streams(c); if (rs) return rs; }
     if (int r = write_state(c, ekf_fleet_robot(c->fslam, robot), N, mu, sigma, landmark_ids)) return r;
+    if (int r = confirm_reseed(c, 1, &robot)) return r;
     return clear_track_health(c, robot, 1);
 }
 
@@ -2535,6 +2623,7 @@ int aslam_remove_landmarks(aslam_ctx* c, int n, const int* ids, int* removed) {
     int r = run_map_edit(c, J, removed);
     if (r) return r;
     c->mirror_dirty = true;
+    if (int rc = confirm_reseed(c, 1, nullptr)) return rc;   // a removed id earns its place again
     return clear_track_health(c, kTrackSingle, 1);
 }
 
@@ -2562,6 +2651,11 @@ int aslam_fleet_remove_landmarks(aslam_ctx* c, int n, const int* ids, int n_robo
     J.stride = c->fslam.stride;
     J.n = n_robots;
     if (int r = run_map_edit(c, J, removed)) return r;
+    {
+        std::vector<int> named(n_robots);
+        for (int k = 0; k < n_robots; k++) named[k] = J.robot[k];
+        if (int r = confirm_reseed(c, n_robots, named.data())) return r;
+    }
     for (int k = 0; k < n_robots; k++)
         if (int r = clear_track_health(c, J.robot[k], 1)) return r;
     return ASLAM_OK;
@@ -2914,6 +3008,104 @@ int aslam_get_slam_gate(aslam_ctx* c, int* on, aslam_gate_params* out) {
     return ASLAM_OK;
 }
 
+// ---- landmark confirmation (include/aruco_slam_hip.h) ------------------------------------------------------------------
+static_assert(kConfirmSingle == ASLAM_MAX_ROBOTS, "the single filter's table follows the robots'");
+static_assert(sizeof(SlotConfirm) == sizeof(aslam_slot_confirm), "records are copied as they are");
+
+void aslam_default_confirm_params(aslam_confirm_params* p) {
+    if (!p) return;
+    p->min_sightings = 3;
+    p->max_gap = 10;
+}
+
+int aslam_set_landmark_confirmation(aslam_ctx* c, const aslam_confirm_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (params) {
+        if (params->min_sightings < 2 || params->min_sightings > 127) return fail(c, ASLAM_E_INVALID, "min_sightings 2..127");
+        if (params->max_gap < 1 || params->max_gap > 1000000) return fail(c, ASLAM_E_INVALID, "max_gap 1..1000000 frames");
+    }
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    if (!params) { c->confirm_on = false; return ASLAM_OK; }
+    if (!c->ev_confirm) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_confirm, hipEventDisableTiming));
+    if (!c->d_confirm_rec) {
+        const size_t ns = (size_t)c->ekf.max_slots;
+        HIP_TRY(c, dalloc(&c->d_confirm_rec, ns));
+        HIP_TRY(c, hipMemset(c->d_confirm_rec, 0, ns * sizeof(SlotConfirm)));
+    }
+    if (!c->h_confirm)
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_confirm), std::max(sizeof(ConfirmTable), (size_t)c->ekf.max_slots * sizeof(SlotConfirm)),
+                                 hipHostMallocDefault));
+    if (!c->d_confirm) {
+        ConfirmTable* d = nullptr;
+        HIP_TRY(c, dalloc(&d, (size_t)kConfirmSingle + 1));
+        HIP_TRY(c, hipMemset(d, 0, ((size_t)kConfirmSingle + 1) * sizeof(ConfirmTable)));
+        c->d_confirm = d;
+    }
+    c->confirm_prm = *params;
+    c->confirm_on = true;
+    // every SLAM filter present starts from its map as it stands (a frozen map's filter is reseeded by aslam_localize_end)
+    if (c->mode == Mode::Slam) return confirm_reseed(c, 1, nullptr);
+    if (c->mode == Mode::FleetSlam) return confirm_reseed_fleet(c);
+    return ASLAM_OK;
+}
+
+int aslam_get_landmark_confirmation(aslam_ctx* c, int* on, aslam_confirm_params* out) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->confirm_on ? 1 : 0;
+    if (out) {
+        if (c->confirm_on) *out = c->confirm_prm;
+        else aslam_default_confirm_params(out);
+    }
+    return ASLAM_OK;
+}
+
+int aslam_get_slot_confirm(aslam_ctx* c, int first, int count, aslam_slot_confirm* out) {
+    if (!c || !out) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->confirm_on) return fail(c, ASLAM_E_STATE, "landmark confirmation is off (aslam_set_landmark_confirmation first)");
+    if (first < 0 || count < 1 || count > c->ekf.max_slots || first > c->ekf.max_slots - count)
+        return fail(c, ASLAM_E_INVALID, "EKF slot range outside [0, 2 max_batch)");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    HIP_TRY(c, hipMemcpyAsync(c->h_confirm, c->d_confirm_rec + first, sizeof(SlotConfirm) * count, hipMemcpyDeviceToHost, c->stream_ekf));
+    HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
+    std::memcpy(out, c->h_confirm, sizeof(SlotConfirm) * count);
+    return ASLAM_OK;
+}
+
+namespace {
+// the tentative ids of table `table`, ascending: count > 0 and last sighted at most max_gap frames ago
+int read_tentative(aslam_ctx* c, int table, int max, int* n, int* ids, int* counts, int* ages) {
+    if (max < 0 || (max > 0 && (!ids || !counts || !ages))) return fail(c, ASLAM_E_INVALID, "max entries need output arrays");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    HIP_TRY(c, hipMemcpyAsync(c->h_confirm, c->d_confirm + table, sizeof(ConfirmTable), hipMemcpyDeviceToHost, c->stream_ekf));
+    HIP_TRY(c, hipStreamSynchronize(c->stream_ekf));
+    const ConfirmTable& T = *reinterpret_cast<const ConfirmTable*>(c->h_confirm);
+    int k = 0;
+    for (int id = 0; id < kIdTableSize; id++) {
+        if (T.cnt[id] <= 0 || T.t - T.last[id] > c->confirm_prm.max_gap) continue;
+        if (k < max) { ids[k] = id; counts[k] = T.cnt[id]; ages[k] = T.t - T.last[id]; }
+        k++;
+    }
+    *n = k;
+    return ASLAM_OK;
+}
+}  // namespace
+
+int aslam_get_tentative(aslam_ctx* c, int max, int* n, int* ids, int* counts, int* ages) {
+    if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->confirm_on) return fail(c, ASLAM_E_STATE, "landmark confirmation is off (aslam_set_landmark_confirmation first)");
+    if (int r = allow(c, kSlam)) return r;
+    return read_tentative(c, kConfirmSingle, max, n, ids, counts, ages);
+}
+
+int aslam_fleet_get_tentative(aslam_ctx* c, int robot, int max, int* n, int* ids, int* counts, int* ages) {
+    if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->confirm_on) return fail(c, ASLAM_E_STATE, "landmark confirmation is off (aslam_set_landmark_confirmation first)");
+    if (int r = allow(c, kFleetSlam)) return r;
+    if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
+    return read_tentative(c, robot, max, n, ids, counts, ages);
+}
+
 namespace {
 // what every health getter checks first.  In a SLAM mode (SLAM, fleet SLAM) the records are the SLAM gate's: readable while it is set
 // and the getter serves that mode (slam_modes).  In the localization modes they are the innovation gate's, as before (loc_modes).
@@ -3065,6 +3257,7 @@ int aslam_get_slot_raw_observations(aslam_ctx* c, int slot, int* n_out, int* ids
     int r = check_slot_range(c, slot, 1);
     if (r) return r;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->confirm_stream) HIP_TRY(c, hipStreamSynchronize(c->confirm_stream));   // landmark confirmation rewrites valid flags on the stream that carries the list
     unsigned n = 0;
     HIP_TRY(c, hipMemcpy(&n, c->d_nmarkers + slot, sizeof(unsigned), hipMemcpyDeviceToHost));
     n = std::min(n, (unsigned)kMarkerMax);

@@ -239,6 +239,37 @@ void map_edit_free(MapEditBufs& B);
 void launch_map_plan(hipStream_t st, const MapEdit& J);
 void launch_map_cols(hipStream_t st, const MapEdit& J);
 void launch_map_rows(hipStream_t st, const MapEdit& J);
+// landmark confirmation (landmark_confirm.h): a filter on the observation lists of EKF slots, in front of everything
+// that reads them.  One table per SLAM filter (robot r's at tables[r], the single filter's at tables[kConfirmSingle]) and one record
+// per EKF slot, in device buffers made by the first aslam_set_landmark_confirmation.  SlotConfirm has the layout of aslam_slot_confirm.
+constexpr int kConfirmSingle = 256;    // the single filter's table follows the robots' (< ASLAM_MAX_ROBOTS = 256)
+struct ConfirmTable {
+    int cnt[kIdTableSize];             // per marker id: sightings of the running tentative count, or -1 = confirmed
+    int last[kIdTableSize];            // ... the filter's frame counter at its last counted sighting
+    int t, pad[3];                     // the filter's frame counter
+};
+struct SlotConfirm {
+    int judged, tentative, withheld, promoted;
+    unsigned withheld_mask[4];
+};
+struct ConfirmArg {                    // kernel argument of k_confirm: workgroup blockIdx.z is one filter of the launch
+    ConfirmTable* tables;
+    const int* work;                   // a fleet round's rows {robot, slot, predict, 0}: filter k = robot work[4 k] on slot work[4 k + 1];
+    int first, count;                  // nullptr: the single filter on EKF slots [first, first + count), ascending
+    int min_sightings, max_gap;
+    ObsRaw* obs;                       // the context's per-slot lists and their lengths
+    const unsigned* n_markers;
+    SlotConfirm* rec;                  // per EKF slot
+};
+struct ConfirmReseed {                 // kernel argument of k_confirm_reseed: filter k = robot[k] of a SLAM fleet, or the single filter
+    EkfState base;                     // robot 0's filter, or the single filter
+    size_t stride;                     // as in FleetSlam (0 for the single filter)
+    ConfirmTable* tables;
+    int n, single;                     // filters of the call = gridDim.z; single: filter 0 is the single filter (table kConfirmSingle)
+    unsigned char robot[256];
+};
+void launch_confirm(hipStream_t st, const ConfirmArg& A, int filters);
+void launch_confirm_reseed(hipStream_t st, const ConfirmReseed& A);
 // relocalization (relocalize.h): per slot of a call one 128-byte result record (16 doubles: the five counts as int32
 // in the first four, then pose and covariance), in a device buffer made on first use together with its page-locked copy
 struct RelocParams {

@@ -1610,3 +1610,4 @@ void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
 #include "relocalize.h"       // relocalization: k_relocalize, one workgroup per slot, and its launcher
 #include "map_edit.h"         // landmark removal: k_map_plan, k_map_cols, k_map_rows, and their launchers
 #include "slam_relocalize.h"  // SLAM relocalization: k_slam_reloc_solve, k_slam_reloc_seat, and their launchers
+#include "landmark_confirm.h" // landmark confirmation: k_confirm, k_confirm_reseed, and their launchers

@@ -612,8 +612,9 @@ int aslam_fleet_get_health(aslam_ctx* ctx, int max, int* n_robots, aslam_track_h
  * Windows: while the SLAM gate is set aslam_run_staged takes the per-frame path (what ASLAM_NO_WINDOWS selects) unless
  * aslam_set_slam_gate_windows (the next section) keeps the windows, and setting or clearing the gate first enqueues a batch still
  * pending.
- * Not covered: a misread id that is NEW to the map is an augment and enters as a landmark (aslam_remove_landmarks stays the remedy);
- * nothing tunes gate_d2 or R.  No floating-point atomics, every sum in pop order: a robot's result does not depend on the other
+ * Not covered: a misread id that is NEW to the map is an augment and enters as a landmark; aslam_set_landmark_confirmation (the
+ * section on landmark confirmation below) is the switch that keeps it out, and aslam_remove_landmarks removes one that got in.
+ * Nothing tunes gate_d2 or R.  No floating-point atomics, every sum in pop order: a robot's result does not depend on the other
  * robots of the call. */
 int aslam_set_slam_gate(aslam_ctx* ctx, const aslam_gate_params* params /* NULL: off */);
 /* *on = 1 while the SLAM gate is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
@@ -648,6 +649,78 @@ int aslam_get_slam_gate(aslam_ctx* ctx, int* on, aslam_gate_params* out);
  * use EKF slots max_batch + step.  Fleet SLAM has no windows and is unaffected. */
 int aslam_set_slam_gate_windows(aslam_ctx* ctx, int on);
 int aslam_get_slam_gate_windows(aslam_ctx* ctx, int* on);
+
+/* ---- landmark confirmation: new landmarks confirmed by repeated sightings (no reference counterpart) ------------------
+ * A SLAM filter appends a landmark the first time any unknown marker id shows up with valid != 0, so one misread id becomes three rows
+ * of mu and Sigma for good.  With this switch a new id enters the map only after min_sightings judged frames have seen it.
+ * Switch.  aslam_set_landmark_confirmation(ctx, params).  It is off by default, settable in any mode, and persists.
+ * Where it takes effect.  Only in EKF steps of SLAM filters, through every entry point that runs such a step:
+ * - SLAM, rig SLAM and fleet SLAM;
+ * - aslam_add_image, aslam_add_images, aslam_run_staged, aslam_run_staged_rig, the host-fed stream, aslam_fleet_add_images,
+ *   aslam_fleet_run_staged;
+ * - with_ekf 1 and 2; windows on or off; SLAM gate on or off.
+ * Localization and localization fleets never judge anything, because unknown ids are dropped there already.  With the switch off, no
+ * launch, kernel or result differs from today.
+ * Parameters and per-filter state.
+ * - min_sightings K is in [2, 127].
+ * - max_gap G is in [1, 1 000 000] frames.
+ * - Each SLAM filter keeps, for every id in [0, 1024): confirmed, count and last.
+ * - Each SLAM filter keeps a frame counter t.
+ * Judging one EKF slot.  An EKF slot is a frame slot, or max_batch + step for a rig step's merged list.  A slot is judged once per EKF
+ * call that covers it, before that call's EKF work, over its first min(n, 128) observations.
+ * 1. t += 1.  A slot with no observations still advances t.
+ * 2. Step A.  U is the set of distinct ids that have at least one sighting with valid != 0 and 0 <= id < 1024, and that are not
+ *    confirmed.  For each id in U:
+ *    - if count > 0 && t - last > G, set count = 0 (the run went stale);
+ *    - count += 1; last = t;
+ *    - if count >= K, set confirmed = 1, count = 0 (promoted).
+ *    - An id sighted twice in one slot counts once.
+ * 3. Step B.  Every sighting with valid != 0, id in range and id still not confirmed gets valid = 0 in the slot's list, in place, and
+ *    its bit is set in the slot's mask.
+ * 4. Everything else stays untouched and keeps its order:
+ *    - confirmed ids;
+ *    - ids outside [0, 1024), which only injection can deliver;
+ *    - sightings that already have valid == 0;
+ *    - x, y, theta, R.
+ * 5. The EKF step then runs on the list as it stands.
+ *    - In the slot where an id is promoted, all its sightings pass.
+ *    - The first is the reference's augment; a second one in the same slot is whatever it is today for an id that is twice in the
+ *      list of the frame that first sees it (a second augment: the id is looked up before the frame's augments).
+ * The result is a pure function of the filter's table and the list.  It does not depend on lane order, on the other robots of a call,
+ * or on how a batch was cut.  Withheld sightings look exactly like sightings dropped by the range or covariance gates (valid = 0), to
+ * every chain, to the window planner and to aslam_get_slot_raw_observations.
+ * Seeding.  "Reseed" means: confirmed := the ids in the filter's landmark id table, all counts 0, t = 0.  These calls reseed:
+ * - the setter when called with parameters, for every SLAM filter present; it first enqueues a pending batch and synchronises, as
+ *   aslam_set_slam_gate does;
+ * - aslam_set_state, aslam_load_state, aslam_localize_end, aslam_fleet_end (the single filter);
+ * - aslam_fleet_slam_begin, for every robot;
+ * - aslam_fleet_set_state, for that robot;
+ * - aslam_remove_landmarks and aslam_fleet_remove_landmarks, for the filters named (a call that names no id returns before it touches
+ *   anything and reseeds nothing).  A removed id must therefore earn its place again, and the tentative counts restart.
+ * aslam_slam_relocalize does not reseed, because the map is untouched.  Calling the setter with NULL switches confirmation off; calling
+ * it again later reseeds.
+ * Records.  An aslam_slot_confirm per EKF slot in [0, 2 max_batch): judged = sightings with valid != 0 and id in range; tentative = the
+ * size of U; withheld = sightings invalidated; promoted = ids confirmed in this slot; bit i % 32 of withheld_mask[i / 32] marks list
+ * position i.  aslam_get_tentative / aslam_fleet_get_tentative list, in ascending id order, the ids with count > 0 && t - last <= G,
+ * with age = t - last; *n receives how many there are, of which the first `max` are written.  They wait for the enqueued work, as the
+ * health getters do.
+ * Errors.  ASLAM_E_INVALID: a null context, parameters out of range, a bad slot range, or a robot outside the fleet.  ASLAM_E_STATE:
+ * the record and tentative getters while the switch is off; aslam_get_tentative in any fleet mode or while localizing;
+ * aslam_fleet_get_tentative outside fleet SLAM.  A refused call changes nothing.
+ * Lifetime.  The tables (one per robot a fleet can hold and the single filter's, 8 KB each) and records are allocated by the first
+ * setter call with parameters and freed by aslam_destroy.  Robots' tables are reseeded with the fleet: they mean nothing outside it.
+ * Dropped.  There is no spatial test on tentative sightings, because their world position needs the live pose, which this stage never
+ * reads.  Tentative sightings carry no information into the filter until promotion.  The tables are not saved by aslam_save_state.
+ * The defaults K = 3, G = 10 are the maintainer's choice.  Nobody has measured them. */
+typedef struct { int min_sightings, max_gap; } aslam_confirm_params;
+typedef struct { int judged, tentative, withheld, promoted; uint32_t withheld_mask[4]; } aslam_slot_confirm;
+void aslam_default_confirm_params(aslam_confirm_params* p);
+int aslam_set_landmark_confirmation(aslam_ctx* ctx, const aslam_confirm_params* params /* NULL: off */);
+/* *on = 1 while confirmation is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
+int aslam_get_landmark_confirmation(aslam_ctx* ctx, int* on, aslam_confirm_params* out);
+int aslam_get_slot_confirm(aslam_ctx* ctx, int first, int count, aslam_slot_confirm* out);   /* EKF slots in [0, 2 max_batch) */
+int aslam_get_tentative(aslam_ctx* ctx, int max, int* n, int* ids, int* counts, int* ages);
+int aslam_fleet_get_tentative(aslam_ctx* ctx, int robot, int max, int* n, int* ids, int* counts, int* ages);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
