@@ -131,6 +131,17 @@ SLOT_CONFIRM_DTYPE = np.dtype([("judged", "<i4"), ("tentative", "<i4"), ("withhe
                                ("withheld_mask", "<u4", (4,))], align=True)
 
 
+class PoseAmbiguityParams(C.Structure):
+    """mirror of aslam_pose_ambiguity_params"""
+    _fields_ = [("ratio", C.c_double), ("floor_px", C.c_double), ("min_dtheta", C.c_double), ("reject", C.c_int), ("pad", C.c_int)]
+
+
+# mirrors of aslam_pose_ambiguity / aslam_slot_pose_ambiguity: what Context.get_slot_pose_ambiguity returns
+POSE_AMBIGUITY_DTYPE = np.dtype([("rvec_alt", "<f8", (3,)), ("tvec_alt", "<f8", (3,)), ("xyth_alt", "<f8", (3,)), ("rms", "<f8"),
+                                 ("rms_alt", "<f8"), ("dtheta", "<f8"), ("flags", "<i4"), ("iters", "<i4")], align=True)
+SLOT_POSE_AMBIGUITY_DTYPE = np.dtype([("checked", "<i4"), ("ambiguous", "<i4"), ("rejected", "<i4"), ("pad", "<i4")], align=True)
+
+
 class AslamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aslam error {code} ({E_NAMES.get(code, '?')}): {msg}")
@@ -198,6 +209,10 @@ _SIGS = {
     "aslam_get_slot_confirm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_tentative": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip]),
     "aslam_fleet_get_tentative": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
+    "aslam_default_pose_ambiguity_params": (None, [_P(PoseAmbiguityParams)]),
+    "aslam_set_pose_ambiguity": (C.c_int, [C.c_void_p, _P(PoseAmbiguityParams)]),
+    "aslam_get_pose_ambiguity": (C.c_int, [C.c_void_p, _ip, _P(PoseAmbiguityParams)]),
+    "aslam_get_slot_pose_ambiguity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -788,6 +803,41 @@ class Context:
     def fleet_get_tentative(self, robot):
         """(ids, counts, ages) of robot's tentative ids in a SLAM fleet, ascending by id"""
         return self._tentative(lambda *a: self.lib.aslam_fleet_get_tentative(self.h, int(robot), *a))
+
+    # -- pose ambiguity check (DESIGN.md §30) ---------------------------------------------------------------------------------------
+    def set_pose_ambiguity(self, params=True, **kw):
+        """set_pose_ambiguity(ratio=..., floor_px=..., min_dtheta=..., reject=...): the library's defaults with the given fields
+        replaced; set_pose_ambiguity(None): off"""
+        if params is None:
+            if kw:
+                raise ValueError("set_pose_ambiguity(None) takes no parameters")
+            self._ck(self.lib.aslam_set_pose_ambiguity(self.h, None))
+            return
+        p = PoseAmbiguityParams()
+        self.lib.aslam_default_pose_ambiguity_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in ("ratio", "floor_px", "min_dtheta", "reject"):
+                raise KeyError(k)
+            setattr(p, k, int(v) if k == "reject" else float(v))
+        self._ck(self.lib.aslam_set_pose_ambiguity(self.h, C.byref(p)))
+
+    def get_pose_ambiguity(self):
+        """None while the pose ambiguity check is off, else its parameters as a dict"""
+        on, p = C.c_int(), PoseAmbiguityParams()
+        self._ck(self.lib.aslam_get_pose_ambiguity(self.h, C.byref(on), C.byref(p)))
+        if not on.value:
+            return None
+        return dict(ratio=p.ratio, floor_px=p.floor_px, min_dtheta=p.min_dtheta, reject=p.reject)
+
+    def get_slot_pose_ambiguity(self, slot):
+        """(records, sum) of a frame slot's last checked pose stage: one POSE_AMBIGUITY_DTYPE record per marker of its list and the
+        slot's SLOT_POSE_AMBIGUITY_DTYPE sum"""
+        out = np.zeros(MARKER_MAX, POSE_AMBIGUITY_DTYPE)
+        s = np.zeros(1, SLOT_POSE_AMBIGUITY_DTYPE)
+        n = C.c_int()
+        self._ck(self.lib.aslam_get_slot_pose_ambiguity(self.h, int(slot), MARKER_MAX, C.byref(n), out.ctypes.data_as(C.c_void_p),
+                                                        s.ctypes.data_as(C.c_void_p)))
+        return out[:n.value].copy(), s[0].copy()
 
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""

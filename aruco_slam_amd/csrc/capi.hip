@@ -29,12 +29,12 @@ namespace {
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
               P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_SLAM_RELOC_SOLVE,
-              P_SLAM_RELOC_SEAT, P_CONFIRM, P_COUNT };
+              P_SLAM_RELOC_SEAT, P_CONFIRM, P_POSE_ALT, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
                                    "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish",
-                                   "k_slam_reloc_solve", "k_slam_reloc_seat", "confirm"};
+                                   "k_slam_reloc_solve", "k_slam_reloc_seat", "confirm", "k_pose_alt"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -185,6 +185,13 @@ struct aslam_ctx {
     char* h_confirm = nullptr;            // page-locked: one table, or 2 max_batch records
     hipEvent_t ev_confirm = nullptr;
     hipStream_t confirm_stream = nullptr; // stream of the most recent k_confirm (nullptr: none since the last full synchronisation)
+    // pose ambiguity check (aslam_set_pose_ambiguity): off unless set; k_pose_alt then follows every k_pose on its
+    // stream.  The records (kMarkerMax per frame slot) and slot sums are made by the first setter call with parameters and freed by
+    // aslam_destroy.
+    bool pose_amb_on = false;
+    aslam_pose_ambiguity_params pose_amb_prm{};
+    PoseAmbiguity* d_pose_amb = nullptr;        // max_batch x kMarkerMax
+    SlotPoseAmbiguity* d_pose_amb_sum = nullptr;   // max_batch
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -493,7 +500,8 @@ int detect_chunk() {
     return chunk_env > 0 ? std::min(chunk_env, max_frames_per_call()) : max_frames_per_call();
 }
 
-// k_pose over frames [f0, f0 + nf) of call k, on stream st (a fleet's camera indices are already on the stream)
+// k_pose over frames [f0, f0 + nf) of call k, on stream st (a fleet's camera indices are already on the stream), and behind it
+// k_pose_alt while the pose ambiguity check is set
 void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int nf, const RefineCfg& rf) {
     prof_begin(c, P_POSE, st);
     if (k.robots) {
@@ -504,6 +512,20 @@ void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int 
         cams.cam0 = (f0 - k.first) % cams.n;
         launch_pose(st, nf, c->d_finals + (size_t)f0 * kCandMax, c->d_nfinal + f0, c->d_markers + (size_t)f0 * kMarkerMax,
                     c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr, rf);
+    }
+    prof_end(c);
+    if (!c->pose_amb_on) return;
+    // the ambiguity check of the same frames, with the same camera source
+    const aslam_pose_ambiguity_params& p = c->pose_amb_prm;
+    const PoseAmbArg arg{p.ratio, p.floor_px, p.min_dtheta, p.reject, 0, c->d_pose_amb + (size_t)f0 * kMarkerMax, c->d_pose_amb_sum + f0};
+    prof_begin(c, P_POSE_ALT, st);
+    if (k.robots) {
+        launch_pose_alt_table(st, nf, c->d_markers + (size_t)f0 * kMarkerMax, c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax,
+                              c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, arg);
+    } else {
+        PoseCams cams = k.rig ? *k.rig : single_camera(c);
+        cams.cam0 = (f0 - k.first) % cams.n;
+        launch_pose_alt(st, nf, c->d_markers + (size_t)f0 * kMarkerMax, c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, arg);
     }
     prof_end(c);
 }
@@ -980,6 +1002,7 @@ void aslam_destroy(aslam_ctx* c) {
     hipFree(c->d_confirm); hipFree(c->d_confirm_rec);
     if (c->h_confirm) hipHostFree(c->h_confirm);
     if (c->ev_confirm) hipEventDestroy(c->ev_confirm);
+    hipFree(c->d_pose_amb); hipFree(c->d_pose_amb_sum);
     if (c->umap.cross) hipFree(c->umap.cross);
     if (c->d_map_c) hipFree(c->d_map_c);
     hipFree(c->gate.slot); hipFree(c->gate.track); hipFree(c->slam_gate.verdicts);
@@ -3104,6 +3127,71 @@ int aslam_fleet_get_tentative(aslam_ctx* c, int robot, int max, int* n, int* ids
     if (int r = allow(c, kFleetSlam)) return r;
     if (robot < 0 || robot >= c->fleet_n) return fail(c, ASLAM_E_INVALID, "robot index outside the fleet");
     return read_tentative(c, robot, max, n, ids, counts, ages);
+}
+
+// ---- pose ambiguity check (include/aruco_slam_hip.h) --------------------------------------------------------------------
+static_assert(sizeof(PoseAmbiguity) == sizeof(aslam_pose_ambiguity), "records are copied as they are");
+static_assert(sizeof(SlotPoseAmbiguity) == sizeof(aslam_slot_pose_ambiguity), "records are copied as they are");
+
+void aslam_default_pose_ambiguity_params(aslam_pose_ambiguity_params* p) {
+    if (!p) return;
+    p->ratio = 1.5;
+    p->floor_px = 0.5;
+    p->min_dtheta = 0.05;
+    p->reject = 1;
+    p->pad = 0;
+}
+
+int aslam_set_pose_ambiguity(aslam_ctx* c, const aslam_pose_ambiguity_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (params) {
+        if (!(std::isfinite(params->ratio) && params->ratio >= 1.0)) return fail(c, ASLAM_E_INVALID, "ratio >= 1, finite");
+        if (!(std::isfinite(params->floor_px) && params->floor_px >= 0.0)) return fail(c, ASLAM_E_INVALID, "floor_px >= 0, finite");
+        if (!(params->min_dtheta >= 0.0 && params->min_dtheta < 3.14159265358979323846)) return fail(c, ASLAM_E_INVALID, "min_dtheta in [0, pi)");
+        if (params->reject != 0 && params->reject != 1) return fail(c, ASLAM_E_INVALID, "reject 0 or 1");
+    }
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    if (!params) { c->pose_amb_on = false; return ASLAM_OK; }
+    if (!c->d_pose_amb) {
+        const size_t n = (size_t)c->max_batch * kMarkerMax;
+        HIP_TRY(c, dalloc(&c->d_pose_amb, n));
+        HIP_TRY(c, hipMemset(c->d_pose_amb, 0, n * sizeof(PoseAmbiguity)));
+    }
+    if (!c->d_pose_amb_sum) {
+        HIP_TRY(c, dalloc(&c->d_pose_amb_sum, (size_t)c->max_batch));
+        HIP_TRY(c, hipMemset(c->d_pose_amb_sum, 0, (size_t)c->max_batch * sizeof(SlotPoseAmbiguity)));
+    }
+    c->pose_amb_prm = *params;
+    c->pose_amb_prm.pad = 0;
+    c->pose_amb_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_get_pose_ambiguity(aslam_ctx* c, int* on, aslam_pose_ambiguity_params* out) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->pose_amb_on ? 1 : 0;
+    if (out) {
+        if (c->pose_amb_on) *out = c->pose_amb_prm;
+        else aslam_default_pose_ambiguity_params(out);
+    }
+    return ASLAM_OK;
+}
+
+int aslam_get_slot_pose_ambiguity(aslam_ctx* c, int slot, int max, int* n, aslam_pose_ambiguity* out, aslam_slot_pose_ambiguity* sum) {
+    if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->pose_amb_on) return fail(c, ASLAM_E_STATE, "the pose ambiguity check is off (aslam_set_pose_ambiguity first)");
+    if (int r = check_slot_range(c, slot, 1)) return r;
+    if (max < 0 || (max > 0 && !out)) return fail(c, ASLAM_E_INVALID, "max records need an output array");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    SlotPoseAmbiguity s{};
+    HIP_TRY(c, hipMemcpy(&s, c->d_pose_amb_sum + slot, sizeof(s), hipMemcpyDeviceToHost));
+    const int m = std::min(std::max(s.checked, 0), kMarkerMax);
+    *n = m;
+    const int w = std::min(m, max);
+    if (w > 0) HIP_TRY(c, hipMemcpy(out, c->d_pose_amb + (size_t)slot * kMarkerMax, (size_t)w * sizeof(PoseAmbiguity), hipMemcpyDeviceToHost));
+    if (sum) std::memcpy(sum, &s, sizeof(s));
+    return ASLAM_OK;
 }
 
 namespace {

@@ -17,6 +17,26 @@ void launch_pose(hipStream_t st, int nframes, const FinalCand* finals, const uns
 // launch_pose with frame f's camera read from a device table: tab[cam_of_frame[f]] (a fleet, one camera per robot)
 void launch_pose_table(hipStream_t st, int nframes, const FinalCand* finals, const unsigned* n_final, Marker* markers, unsigned* n_markers,
                        ObsRaw* obs, const RigCam* tab, const int* cam_of_frame, const SlamParams& sp, Counters* ctr, const RefineCfg& rf);
+// Pose ambiguity check: what k_pose_alt leaves per marker and per frame slot.  The layouts are those of
+// aslam_pose_ambiguity / aslam_slot_pose_ambiguity (include/aruco_slam_hip.h): the getter copies them as they are.
+struct PoseAmbiguity {
+    double rvec_alt[3], tvec_alt[3], xyth_alt[3];
+    double rms, rms_alt, dtheta;
+    int flags, iters;                 // flags: 1 ambiguous, 2 rejected (valid := 0), 4 the refinement ended non-finite
+};
+struct SlotPoseAmbiguity { int checked, ambiguous, rejected, pad; };
+struct PoseAmbArg {
+    double ratio, floor_px, min_dtheta;
+    int reject, pad;
+    PoseAmbiguity* rec;               // kMarkerMax records per frame, frame 0 of the launch first
+    SlotPoseAmbiguity* sum;           // one per frame
+};
+// k_pose_alt behind k_pose on the same frames, marker lists and camera source: the mirrored second pose of every marker of the
+// lists, the records, and valid := 0 in obs for rejected sightings
+void launch_pose_alt(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const PoseCams& cams,
+                     const SlamParams& sp, const PoseAmbArg& arg);
+void launch_pose_alt_table(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const RigCam* tab,
+                           const int* cam_of_frame, const SlamParams& sp, const PoseAmbArg& arg);
 // concatenates the observation lists of n_steps rig steps (C = n_cams frames each, from slot frame0) into step lists at slots step0..
 void launch_rig_merge(hipStream_t st, int n_steps, ObsRaw* obs, unsigned* n_markers, double* enc, int frame0, int n_cams, int step0, Counters* ctr);
 

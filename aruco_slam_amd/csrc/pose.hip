@@ -5,6 +5,7 @@
 //   (x, y, theta) observation, CalculateCovariance (aruco_slam.cpp:437-471) and the covariance gate.
 // One workgroup per frame; the pose solve is one lane per marker (6-parameter Levenberg-Marquardt on 8
 // residuals in fp64 — a latency-bound scalar chain; frames of the batch supply the parallelism).
+// k_pose_alt (the pose ambiguity check, off by default) follows it with the mirrored second solve of every marker, 8 lanes per marker.
 #include "common.h"
 #include "pose.h"
 #include <cfloat>
@@ -552,6 +553,237 @@ void launch_pose_table(hipStream_t st, int nframes, const FinalCand* finals, con
                        ObsRaw* obs, const RigCam* tab, const int* cam_of_frame, const SlamParams& sp, Counters* ctr, const RefineCfg& rf) {
     hipLaunchKernelGGL(k_pose<CamTable>, dim3(nframes), dim3(128), 0, st, finals, n_final, markers, n_markers, obs, CamTable{tab, cam_of_frame},
                        sp, ctr, rf);
+}
+
+// ---- pose ambiguity check: the mirrored second pose of every marker k_pose solved -----------------------------------
+// A group of 8 lanes per marker, one lane per residual row; kPoseAltGroups markers per pass of the workgroup.  No oracle fixes the
+// operation order of this solve, so it is wave-cooperative where solve_marker_pose may not be: a lane forms its own row of the
+// projection and of the Jacobian, J^T J, J^T e and |e|^2 are summed over the group by a fixed butterfly, and every lane of the group
+// then holds the same bits and solves the same 6 x 6 system.
+
+// The value of lane l ^ 1, l ^ 2 and l ^ 7 of the group.  On the device a DPP move (quad_perm [1,0,3,2], quad_perm [2,3,0,1],
+// row_half_mirror): registers only.  The tests' CPU emulation has no DPP: there the same lanes are named to its __shfl_xor.
+#if defined(__HIP__)
+template <int CTRL> __device__ __forceinline__ double group8_from(double v) {
+    int w[2];
+    __builtin_memcpy(w, &v, sizeof(double));
+    w[0] = __builtin_amdgcn_update_dpp(w[0], w[0], CTRL, 0xF, 0xF, false);
+    w[1] = __builtin_amdgcn_update_dpp(w[1], w[1], CTRL, 0xF, 0xF, false);
+    __builtin_memcpy(&v, w, sizeof(double));
+    return v;
+}
+#define ASLAM_GROUP8_XOR1(v) group8_from<0xB1>(v)
+#define ASLAM_GROUP8_XOR2(v) group8_from<0x4E>(v)
+#define ASLAM_GROUP8_XOR7(v) group8_from<0x141>(v)
+#else
+#define ASLAM_GROUP8_XOR1(v) __shfl_xor(v, 1)
+#define ASLAM_GROUP8_XOR2(v) __shfl_xor(v, 2)
+#define ASLAM_GROUP8_XOR7(v) __shfl_xor(v, 7)
+#endif
+// Sum over the 8 lanes of a group, the same bits in every lane: pairs, then quads, then the two quads (after the second step a quad
+// is uniform, so the mirrored lane of the other quad holds that quad's sum).  a + b = b + a to the bit, so both sides of every
+// exchange form the same sum.  Called by all 64 lanes of the wave together.
+__device__ __forceinline__ double group8_sum(double v) {
+    v += ASLAM_GROUP8_XOR1(v);
+    v += ASLAM_GROUP8_XOR2(v);
+    v += ASLAM_GROUP8_XOR7(v);
+    return v;
+}
+
+// row `row` (= 2 corner + coordinate) of project4 and of its Jacobian, with project4's expressions
+__device__ __forceinline__ void project_row(const double* p /*r,t*/, double hl, const CamParams& cam, int row, double& out, double* Jr /*6*/) {
+    double R[9], dR[27];
+    rodrigues_fwd(p, R, dR);
+    const double* k = cam.k;
+    const int i = row >> 1;
+    const bool second = (row & 1) != 0;
+    const double X = (i == 0 || i == 3) ? -hl : hl, Y = (i < 2) ? hl : -hl;     // Z = 0
+    double x = R[0] * X + R[1] * Y + p[3];
+    double y = R[3] * X + R[4] * Y + p[4];
+    double z = R[6] * X + R[7] * Y + p[5];
+    z = z ? 1. / z : 1;
+    x *= z; y *= z;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    const double cd = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+    const double ox = (x * cd + k[2] * a1 + k[3] * a2) * cam.fx + cam.cx;
+    const double oy = (y * cd + k[2] * a3 + k[3] * a1) * cam.fy + cam.cy;
+    out = second ? oy : ox;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dxd, dyd;
+        if (j < 3) {
+            const double dx0 = X * dR[j * 9] + Y * dR[j * 9 + 1];
+            const double dy0 = X * dR[j * 9 + 3] + Y * dR[j * 9 + 4];
+            const double dz0 = X * dR[j * 9 + 6] + Y * dR[j * 9 + 7];
+            dxd = z * (dx0 - x * dz0);
+            dyd = z * (dy0 - y * dz0);
+        } else {
+            dxd = j == 3 ? z : (j == 4 ? 0. : -x * z);
+            dyd = j == 3 ? 0. : (j == 4 ? z : -y * z);
+        }
+        const double dr2 = 2 * x * dxd + 2 * y * dyd;
+        const double dcd = (k[0] + 2 * k[1] * r2 + 3 * k[4] * r4) * dr2;
+        const double da1 = 2 * (x * dyd + y * dxd);
+        const double dmx = dxd * cd + x * dcd + k[2] * da1 + k[3] * (dr2 + 4 * x * dxd);
+        const double dmy = dyd * cd + y * dcd + k[2] * (dr2 + 4 * y * dyd) + k[3] * da1;
+        Jr[j] = second ? cam.fy * dmy : cam.fx * dmx;
+    }
+}
+
+// the group's normal equations at p: S[0..20] = upper triangle of J^T J by rows, S[21..26] = J^T e, S[27] = |e|^2
+__device__ __forceinline__ void normal_equations(const double* p, double hl, const CamParams& cam, int row, double m_row, double* S) {
+    double out, Jr[6];
+    project_row(p, hl, cam, row, out, Jr);
+    const double e = out - m_row;
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++) S[q++] = Jr[i] * Jr[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++) S[21 + i] = Jr[i] * e;
+    S[27] = e * e;
+#pragma unroll
+    for (int i = 0; i < 28; i++) S[i] = group8_sum(S[i]);
+}
+
+// 32 groups: the 20 markers of a headline frame take one pass (16 groups took two, the second for 4 markers, at the same cost), and
+// four waves of this register count are one per SIMD of a CU
+constexpr int kPoseAltGroups = 32, kPoseAltThreads = 8 * kPoseAltGroups;
+
+template <class Cams>
+__global__ __launch_bounds__(kPoseAltThreads) void k_pose_alt(const Marker* __restrict__ markers, const unsigned* __restrict__ n_markers,
+                                                  ObsRaw* __restrict__ obs, Cams cams, SlamParams sp, PoseAmbArg A) {
+    __shared__ int sCnt[kPoseAltThreads / 64][2];
+    const int tid = threadIdx.x, f = blockIdx.x;
+    const int g = tid >> 3, row = tid & 7;
+    const RigCam& rc = frame_cam(cams, f);
+    const CamParams& cam = rc.cam;
+    const int M = (int)min(n_markers[f], (unsigned)kMarkerMax);
+    const double hl = (double)((float)sp.marker_length / 2.f);
+    const double LOG10 = log(10.);
+    int nAmb = 0, nRej = 0;
+    for (int k0 = 0; k0 < M; k0 += kPoseAltGroups) {               // uniform
+        const int k = k0 + g;
+        const bool have = k < M;
+        const size_t at = (size_t)f * kMarkerMax + (have ? k : 0);  // a group past the list's end repeats marker 0 and writes nothing
+        double m[8], p1[6];
+        for (int i = 0; i < 8; i++) m[i] = markers[at].c[i];
+        for (int i = 0; i < 3; i++) { p1[i] = markers[at].rvec[i]; p1[3 + i] = markers[at].tvec[i]; }
+        const double obs_th = obs[at].th;
+        const int obs_valid = obs[at].valid;
+        // the primary pose's cost
+        double e1 = 0;
+        {
+            double proj[8];
+            project4(p1, hl, cam, proj, nullptr);
+            for (int i = 0; i < 8; i++) { const double d = proj[i] - m[i]; e1 += d * d; }
+        }
+        // the mirrored start: R' = (I - 2 v v^T) R1 diag(1, 1, -1), v the line of sight
+        double prev[6];
+        {
+            double R1[9], H[9], Rm[9];
+            rodrigues_fwd(p1, R1, nullptr);
+            const double nt = sqrt(p1[3] * p1[3] + p1[4] * p1[4] + p1[5] * p1[5]);
+            const double v[3] = {p1[3] / nt, p1[4] / nt, p1[5] / nt};
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) H[i * 3 + j] = (i == j ? 1. : 0.) - 2 * v[i] * v[j];
+            mul33(H, R1, Rm);
+            Rm[2] = -Rm[2]; Rm[5] = -Rm[5]; Rm[8] = -Rm[8];
+            rodrigues_inv(Rm, prev);
+            prev[3] = p1[3]; prev[4] = p1[4]; prev[5] = p1[5];
+        }
+        // solve_marker_pose's damped iteration from there.  One trip = one damped solve and one evaluation of the trial point, with its
+        // normal equations: an accepted trial has them ready, a refused one (rare) wasted them.  Every lane of the wave makes every
+        // trip - the group sums are wave collectives - and a group that is done keeps its result.
+        double cur[28], T[28];
+        normal_equations(prev, hl, cam, row, m[row], cur);
+        double prevErrNorm = sqrt(cur[27]);
+        int lambdaLg10 = -3, iters = 0;
+        bool done = false;
+        for (int trip = 0; trip < 64; trip++) {                    // (at most 20 accepted and 39 refused trips)
+            if (__ballot(!done) == 0ull) break;
+            double Am[36], b[6], x[6], trial[6];
+            {
+                const double lambda = exp(lambdaLg10 * LOG10);
+                int q = 0;
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+#pragma unroll
+                    for (int j = i; j < 6; j++) { Am[i * 6 + j] = cur[q]; Am[j * 6 + i] = cur[q]; q++; }
+#pragma unroll
+                for (int i = 0; i < 6; i++) { Am[i * 6 + i] *= 1. + lambda; b[i] = cur[21 + i]; }
+                solve_pp<6>(Am, b, x);
+#pragma unroll
+                for (int i = 0; i < 6; i++) trial[i] = prev[i] - x[i];
+            }
+            normal_equations(trial, hl, cam, row, m[row], T);
+            const double errNorm = sqrt(T[27]);
+            if (done) continue;
+            if (errNorm > prevErrNorm && ++lambdaLg10 <= 16) continue;
+            lambdaLg10 = max(lambdaLg10 - 1, -16);
+            double dn = 0, pn = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++) { const double d = trial[i] - prev[i]; dn += d * d; pn += prev[i] * prev[i]; }
+            if (++iters >= 20 || sqrt(dn) / sqrt(pn) < (double)FLT_EPSILON) done = true;
+#pragma unroll
+            for (int i = 0; i < 6; i++) prev[i] = trial[i];
+#pragma unroll
+            for (int i = 0; i < 28; i++) cur[i] = T[i];
+            prevErrNorm = errNorm;
+        }
+        // the alternate observation: k_pose's formula on (r2, t2) with the frame's mount
+        double R2[9];
+        rodrigues_fwd(prev, R2, nullptr);
+        const double x0 = prev[5], y0 = -prev[3];
+        double th0 = atan2(-R2[2], R2[8]);
+        wrap_once(th0);
+        const double ax = (rc.cpsi * x0 - rc.spsi * y0) + rc.mx;
+        const double ay = (rc.spsi * x0 + rc.cpsi * y0) + rc.my;
+        double ath = th0 + rc.psi;
+        wrap_once(ath);
+        double dth = ath - obs_th;
+        wrap_once(dth);
+        dth = fabs(dth);
+        bool fin = isfinite(cur[27]) && isfinite(ax) && isfinite(ay) && isfinite(ath) && isfinite(dth);
+        for (int i = 0; i < 6; i++) fin = fin && isfinite(prev[i]);
+        PoseAmbiguity r;
+        for (int i = 0; i < 3; i++) { r.rvec_alt[i] = fin ? prev[i] : 0.; r.tvec_alt[i] = fin ? prev[3 + i] : 0.; }
+        r.xyth_alt[0] = fin ? ax : 0.; r.xyth_alt[1] = fin ? ay : 0.; r.xyth_alt[2] = fin ? ath : 0.;
+        r.rms = sqrt(e1 / 4.0);
+        r.rms_alt = fin ? sqrt(cur[27] / 4.0) : 0.;
+        r.dtheta = fin ? dth : 0.;
+        r.iters = iters;
+        const bool amb = fin && r.rms_alt <= fmax(A.ratio * r.rms, A.floor_px) && r.dtheta > A.min_dtheta;
+        const bool rej = amb && A.reject != 0 && obs_valid != 0;
+        r.flags = (fin ? 0 : 4) | (amb ? 1 : 0) | (rej ? 2 : 0);
+        const bool writer = row == 0 && have;
+        if (writer) {
+            A.rec[at] = r;
+            if (rej) obs[at].valid = 0;                            // downstream: a sighting the range gate dropped
+        }
+        nAmb += __popcll(__ballot(writer && amb));
+        nRej += __popcll(__ballot(writer && rej));
+    }
+    if ((tid & 63) == 0) { sCnt[tid >> 6][0] = nAmb; sCnt[tid >> 6][1] = nRej; }
+    __syncthreads();
+    if (tid == 0) {
+        SlotPoseAmbiguity s;
+        s.checked = M; s.ambiguous = 0; s.rejected = 0; s.pad = 0;
+        for (int w = 0; w < kPoseAltThreads / 64; w++) { s.ambiguous += sCnt[w][0]; s.rejected += sCnt[w][1]; }
+        A.sum[f] = s;
+    }
+}
+
+void launch_pose_alt(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const PoseCams& cams,
+                     const SlamParams& sp, const PoseAmbArg& arg) {
+    hipLaunchKernelGGL(k_pose_alt<PoseCams>, dim3(nframes), dim3(kPoseAltThreads), 0, st, markers, n_markers, obs, cams, sp, arg);
+}
+
+void launch_pose_alt_table(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const RigCam* tab,
+                           const int* cam_of_frame, const SlamParams& sp, const PoseAmbArg& arg) {
+    hipLaunchKernelGGL(k_pose_alt<CamTable>, dim3(nframes), dim3(kPoseAltThreads), 0, st, markers, n_markers, obs, CamTable{tab, cam_of_frame}, sp, arg);
 }
 
 // One rig step = the observation lists of its C frames (slots frame0 + s C + c) concatenated in camera order into one list at

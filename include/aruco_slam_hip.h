@@ -722,6 +722,56 @@ int aslam_get_slot_confirm(aslam_ctx* ctx, int first, int count, aslam_slot_conf
 int aslam_get_tentative(aslam_ctx* ctx, int max, int* n, int* ids, int* counts, int* ages);
 int aslam_fleet_get_tentative(aslam_ctx* ctx, int robot, int max, int* n, int* ids, int* counts, int* ages);
 
+/* ---- pose ambiguity check: markers with a second plausible pose flagged and dropped (no reference counterpart) ---------
+ * The pose stage returns one pose per marker: the minimum the homography start leads the Levenberg-Marquardt solve to.  A square seen
+ * from a distance has a second, mirrored pose - its normal reflected about the line of sight - that fits the four corners almost as
+ * well.  The two differ in exactly what the filter consumes: theta = atan2(-R02, R22) comes out tens of degrees apart while (x, y)
+ * barely moves.  The SLAM gate sees such a flip only on a known id and landmark confirmation counts sightings without judging them.
+ * Switch.  aslam_set_pose_ambiguity(ctx, params).  It is off by default, settable in any mode, and persists.  With the switch off, no
+ * launch, kernel or result differs from today.
+ * Where it runs.  One kernel, k_pose_alt, directly behind the pose kernel on the same stream with the same camera source, in every
+ * entry point that runs detection: the single camera, rigs (ahead of the merge of a step's lists, so a rejection survives it), both
+ * fleet kinds, localization, the host-fed stream, aslam_detect_batch, aslam_debug_run_pose and aslam_debug_run_pose_refined.
+ * aslam_run_staged(..., with_ekf = 2) runs no pose stage and so no check.
+ * Parameters.  ratio >= 1, finite; floor_px >= 0, finite; min_dtheta in [0, pi); reject 0 or 1.
+ * Per marker k of a frame's marker list, all M <= 128 of them, whatever their valid flag:
+ * 1. Primary pose.  (r1, t1) is what the pose stage stored, m the marker's 8 float corners as doubles, e1 the sum of squared
+ *    reprojection residuals in double, rms = sqrt(e1 / 4).
+ * 2. Mirrored start.  With R1 = rodrigues(r1) and v = t1 / |t1|: R' = (I - 2 v v^T) R1 diag(1, 1, -1) - the normal reflected about
+ *    the line of sight, the in-plane axes kept, determinant +1.  The start is (rodrigues_inv(R'), t1).
+ * 3. Refinement.  The damped iteration of the primary solve from there: Levenberg-Marquardt on the 8 residuals, lambda = 10^k from
+ *    k = -3, at most 20 accepted steps, stop when |dp| / |p| < FLT_EPSILON.  Result: (r2, t2) = rvec_alt, tvec_alt, e2,
+ *    rms_alt = sqrt(e2 / 4), iters = accepted steps.  The arithmetic order is the kernel's own and fixed, without floating-point
+ *    atomics: the same marker gives the same bits whatever else the call carries.  A non-finite result sets flag 4, zeroes the alt
+ *    fields (rvec_alt, tvec_alt, xyth_alt, rms_alt, dtheta) and is never ambiguous.
+ * 4. Alternate observation.  xyth_alt is (r2, t2) put through the pose stage's observation formula with the frame's mount;
+ *    dtheta = |wrap(xyth_alt.theta - observation.theta)|.
+ * 5. Flag 1 (ambiguous): rms_alt <= max(ratio * rms, floor_px) && dtheta > min_dtheta, on the doubles stored in the record.  Where the
+ *    second minimum does not exist (roughly below 1 m for the reference's marker) the descent returns to the primary pose, dtheta ~ 0
+ *    and the marker passes; a second pose that differs in pitch only is harmless to an SE(2) filter and passes too.
+ * 6. Flag 2 (rejected): flag 1, reject set and the sighting's valid nonzero.  Then valid = 0 in the slot's raw observation list, in
+ *    place: downstream - every chain, the window planner, landmark confirmation, aslam_get_slot_raw_observations - it looks exactly
+ *    like a sighting the range gate dropped.  The marker list and aslam_get_slot_detections are not touched.
+ * 7. Slot sum: checked = M, ambiguous = markers with flag 1, rejected = markers with flag 2.
+ * Records.  aslam_get_slot_pose_ambiguity(ctx, slot, max, n, out, sum) waits for the enqueued work, as the health getters do.  *n = the
+ * markers of the slot's last checked pose stage, of which the first `max` records are written to out (may be NULL with max = 0); sum
+ * (may be NULL) receives the slot sum.  A slot never checked reads as empty.
+ * Errors.  ASLAM_E_INVALID: a null context, parameters out of range, a slot outside [0, max_batch), max < 0 or records without an
+ * array.  ASLAM_E_STATE: the slot getter while the switch is off.  A refused call changes nothing.  The setter first enqueues a pending
+ * batch and synchronises, as aslam_set_slam_gate does.
+ * Lifetime.  max_batch x 128 records and max_batch sums, allocated by the first setter call with parameters, freed by aslam_destroy.
+ * Dropped.  No swap to the better-fitting pose: that would change what the pose stage reports.  No use of the filter's prediction to
+ * pick a side: the gate does that.  No accumulation over frames.
+ * The defaults ratio = 1.5, floor_px = 0.5, min_dtheta = 0.05, reject = 1 are the maintainer's choice.  Nobody has measured them. */
+typedef struct { double ratio, floor_px, min_dtheta; int reject, pad; } aslam_pose_ambiguity_params;
+typedef struct { double rvec_alt[3], tvec_alt[3], xyth_alt[3]; double rms, rms_alt, dtheta; int flags, iters; } aslam_pose_ambiguity;
+typedef struct { int checked, ambiguous, rejected, pad; } aslam_slot_pose_ambiguity;
+void aslam_default_pose_ambiguity_params(aslam_pose_ambiguity_params* p);
+int aslam_set_pose_ambiguity(aslam_ctx* ctx, const aslam_pose_ambiguity_params* params /* NULL: off */);
+/* *on = 1 while the check is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
+int aslam_get_pose_ambiguity(aslam_ctx* ctx, int* on, aslam_pose_ambiguity_params* out);
+int aslam_get_slot_pose_ambiguity(aslam_ctx* ctx, int slot, int max, int* n, aslam_pose_ambiguity* out, aslam_slot_pose_ambiguity* sum);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
