@@ -142,6 +142,18 @@ POSE_AMBIGUITY_DTYPE = np.dtype([("rvec_alt", "<f8", (3,)), ("tvec_alt", "<f8", 
 SLOT_POSE_AMBIGUITY_DTYPE = np.dtype([("checked", "<i4"), ("ambiguous", "<i4"), ("rejected", "<i4"), ("pad", "<i4")], align=True)
 
 
+class ObsCovarianceParams(C.Structure):
+    """mirror of aslam_obs_covariance_params"""
+    _fields_ = [("sigma_px", C.c_double), ("scale", C.c_double), ("floor_xy", C.c_double), ("floor_th", C.c_double),
+                ("gate_norm", C.c_double), ("use_residual", C.c_int), ("pad", C.c_int)]
+
+
+# mirrors of aslam_obs_covariance / aslam_slot_obs_covariance: what Context.get_slot_obs_covariance returns
+OBS_COVARIANCE_DTYPE = np.dtype([("cov", "<f8", (3, 3)), ("sigma2", "<f8"), ("e2", "<f8"), ("r_ref", "<f8", (3,)), ("flags", "<i4"),
+                                 ("pad", "<i4")], align=True)
+SLOT_OBS_COVARIANCE_DTYPE = np.dtype([("checked", "<i4"), ("degenerate", "<i4"), ("gated", "<i4"), ("pad", "<i4")], align=True)
+
+
 class AslamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aslam error {code} ({E_NAMES.get(code, '?')}): {msg}")
@@ -213,6 +225,10 @@ _SIGS = {
     "aslam_set_pose_ambiguity": (C.c_int, [C.c_void_p, _P(PoseAmbiguityParams)]),
     "aslam_get_pose_ambiguity": (C.c_int, [C.c_void_p, _ip, _P(PoseAmbiguityParams)]),
     "aslam_get_slot_pose_ambiguity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p]),
+    "aslam_default_obs_covariance_params": (None, [_P(ObsCovarianceParams)]),
+    "aslam_set_observation_covariance": (C.c_int, [C.c_void_p, _P(ObsCovarianceParams)]),
+    "aslam_get_observation_covariance": (C.c_int, [C.c_void_p, _ip, _P(ObsCovarianceParams)]),
+    "aslam_get_slot_obs_covariance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -839,6 +855,43 @@ class Context:
                                                         s.ctypes.data_as(C.c_void_p)))
         return out[:n.value].copy(), s[0].copy()
 
+    # -- observation covariance -------------------------------------------------------------------------------------
+    _OBS_COV_FIELDS = ("sigma_px", "scale", "floor_xy", "floor_th", "gate_norm", "use_residual")
+
+    def set_observation_covariance(self, params=True, **kw):
+        """set_observation_covariance(sigma_px=..., scale=..., floor_xy=..., floor_th=..., gate_norm=..., use_residual=...): the
+        library's defaults with the given fields replaced; set_observation_covariance(None): off"""
+        if params is None:
+            if kw:
+                raise ValueError("set_observation_covariance(None) takes no parameters")
+            self._ck(self.lib.aslam_set_observation_covariance(self.h, None))
+            return
+        p = ObsCovarianceParams()
+        self.lib.aslam_default_obs_covariance_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in self._OBS_COV_FIELDS:
+                raise KeyError(k)
+            setattr(p, k, int(v) if k == "use_residual" else float(v))
+        self._ck(self.lib.aslam_set_observation_covariance(self.h, C.byref(p)))
+
+    def get_observation_covariance(self):
+        """None while the observation covariance is off, else its parameters as a dict"""
+        on, p = C.c_int(), ObsCovarianceParams()
+        self._ck(self.lib.aslam_get_observation_covariance(self.h, C.byref(on), C.byref(p)))
+        if not on.value:
+            return None
+        return {k: getattr(p, k) for k in self._OBS_COV_FIELDS}
+
+    def get_slot_obs_covariance(self, slot):
+        """(records, sum) of a frame slot's last pose stage under the switch: one OBS_COVARIANCE_DTYPE record per marker of its list
+        and the slot's SLOT_OBS_COVARIANCE_DTYPE sum"""
+        out = np.zeros(MARKER_MAX, OBS_COVARIANCE_DTYPE)
+        s = np.zeros(1, SLOT_OBS_COVARIANCE_DTYPE)
+        n = C.c_int()
+        self._ck(self.lib.aslam_get_slot_obs_covariance(self.h, int(slot), MARKER_MAX, C.byref(n), out.ctypes.data_as(C.c_void_p),
+                                                        s.ctypes.data_as(C.c_void_p)))
+        return out[:n.value].copy(), s[0].copy()
+
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""
         out = np.zeros(max(int(count), 1), SLOT_HEALTH_DTYPE)
@@ -1226,8 +1279,8 @@ class Context:
         return dict(frames_in_windows=int(out[0]), frames_per_frame_chain=int(out[1]), windows=int(out[2]), frames_device_planned=int(out[3]))
 
     def profile_get(self):
-        names = (C.c_char_p * 32)(); calls = np.zeros(32, np.int32); ms = np.zeros(32)
-        n = self.lib.aslam_profile_get(self.h, 32, names, _ptr(calls, _ip), _ptr(ms, _dp))
+        names = (C.c_char_p * 64)(); calls = np.zeros(64, np.int32); ms = np.zeros(64)
+        n = self.lib.aslam_profile_get(self.h, 64, names, _ptr(calls, _ip), _ptr(ms, _dp))
         return {names[i].decode(): (int(calls[i]), float(ms[i])) for i in range(n)}
 
     def synth_render(self, slot, rows, cols, K, ids, poses, marker_length=0.27, background=128, noise_amp=0, seed=0,

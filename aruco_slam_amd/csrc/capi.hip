@@ -29,12 +29,12 @@ namespace {
 enum ProfId { P_THRESH, P_SEG, P_LINK, P_WRITE, P_QUADS, P_ASSEMBLE, P_IDENTIFY, P_POSE, P_EKF_PLAN, P_EKF_GATHER, P_EKF_SMALL,
               P_EKF_T, P_EKF_UPDATE, P_EKF_MID, P_EKF_APPLY, P_EKF_MID64, P_EKF_WIN_CHAIN, P_EKF_WIN_SCAN, P_EKF_WIN_FLUSH, P_EKF_WIN_NEXT, P_LOC_STEPS, P_FLEET_STEPS,
               P_MAP_PLAN, P_MAP_COLS, P_MAP_ROWS, P_EKF_GATE_FINISH, P_EKF_WIN_GATE_FINISH, P_SLAM_RELOC_SOLVE,
-              P_SLAM_RELOC_SEAT, P_CONFIRM, P_POSE_ALT, P_COUNT };
+              P_SLAM_RELOC_SEAT, P_CONFIRM, P_POSE_ALT, P_POSE_COV, P_COUNT };
 const char* kProfNames[P_COUNT] = {"k_threshold", "k_seg", "k_link", "k_trace_write", "k_quads", "k_assemble", "k_identify", "k_pose",
                                    "k_ekf_plan", "k_ekf_gather", "k_ekf_small", "k_ekf_T", "k_ekf_update_mfma", "k_ekf_mid", "k_ekf_apply",
                                    "k_ekf_mid64", "k_ekf_win_step", "k_ekf_win_drain", "k_ekf_win_flush", "k_ekf_win_next", "k_loc_steps",
                                    "k_fleet_steps", "k_map_plan", "k_map_cols", "k_map_rows", "k_ekf_gate_finish", "k_ekf_win_gate_finish",
-                                   "k_slam_reloc_solve", "k_slam_reloc_seat", "confirm", "k_pose_alt"};
+                                   "k_slam_reloc_solve", "k_slam_reloc_seat", "confirm", "k_pose_alt", "k_pose_cov"};
 
 struct ProfSpan { int id; hipEvent_t a, b; hipStream_t st; };
 
@@ -192,6 +192,12 @@ struct aslam_ctx {
     aslam_pose_ambiguity_params pose_amb_prm{};
     PoseAmbiguity* d_pose_amb = nullptr;        // max_batch x kMarkerMax
     SlotPoseAmbiguity* d_pose_amb_sum = nullptr;   // max_batch
+    // observation covariance (aslam_set_observation_covariance): off unless set; k_pose_cov then follows every k_pose
+    // on its stream, ahead of k_pose_alt.  Records and slot sums as for the ambiguity check.
+    bool obs_cov_on = false;
+    aslam_obs_covariance_params obs_cov_prm{};
+    ObsCovariance* d_obs_cov = nullptr;         // max_batch x kMarkerMax
+    SlotObsCovariance* d_obs_cov_sum = nullptr; // max_batch
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -501,7 +507,7 @@ int detect_chunk() {
 }
 
 // k_pose over frames [f0, f0 + nf) of call k, on stream st (a fleet's camera indices are already on the stream), and behind it
-// k_pose_alt while the pose ambiguity check is set
+// k_pose_cov while the observation covariance is set and k_pose_alt while the pose ambiguity check is set
 void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int nf, const RefineCfg& rf) {
     prof_begin(c, P_POSE, st);
     if (k.robots) {
@@ -514,6 +520,22 @@ void launch_pose_stage(aslam_ctx* c, const Call& k, hipStream_t st, int f0, int 
                     c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, c->d_ctr, rf);
     }
     prof_end(c);
+    if (c->obs_cov_on) {
+        // R and valid of the same frames from the pose solve's Jacobian: ahead of the ambiguity check, which reads valid
+        const aslam_obs_covariance_params& p = c->obs_cov_prm;
+        const ObsCovArg arg{p.sigma_px, p.scale, p.floor_xy, p.floor_th, p.gate_norm, p.use_residual, 0,
+                            c->d_obs_cov + (size_t)f0 * kMarkerMax, c->d_obs_cov_sum + f0};
+        prof_begin(c, P_POSE_COV, st);
+        if (k.robots) {
+            launch_pose_cov_table(st, nf, c->d_markers + (size_t)f0 * kMarkerMax, c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax,
+                                  c->d_fleet_cams, c->d_fleet_camidx + f0, c->sp, arg);
+        } else {
+            PoseCams cams = k.rig ? *k.rig : single_camera(c);
+            cams.cam0 = (f0 - k.first) % cams.n;
+            launch_pose_cov(st, nf, c->d_markers + (size_t)f0 * kMarkerMax, c->d_nmarkers + f0, c->d_obs + (size_t)f0 * kMarkerMax, cams, c->sp, arg);
+        }
+        prof_end(c);
+    }
     if (!c->pose_amb_on) return;
     // the ambiguity check of the same frames, with the same camera source
     const aslam_pose_ambiguity_params& p = c->pose_amb_prm;
@@ -1003,6 +1025,7 @@ void aslam_destroy(aslam_ctx* c) {
     if (c->h_confirm) hipHostFree(c->h_confirm);
     if (c->ev_confirm) hipEventDestroy(c->ev_confirm);
     hipFree(c->d_pose_amb); hipFree(c->d_pose_amb_sum);
+    hipFree(c->d_obs_cov); hipFree(c->d_obs_cov_sum);
     if (c->umap.cross) hipFree(c->umap.cross);
     if (c->d_map_c) hipFree(c->d_map_c);
     hipFree(c->gate.slot); hipFree(c->gate.track); hipFree(c->slam_gate.verdicts);
@@ -3190,6 +3213,75 @@ int aslam_get_slot_pose_ambiguity(aslam_ctx* c, int slot, int max, int* n, aslam
     *n = m;
     const int w = std::min(m, max);
     if (w > 0) HIP_TRY(c, hipMemcpy(out, c->d_pose_amb + (size_t)slot * kMarkerMax, (size_t)w * sizeof(PoseAmbiguity), hipMemcpyDeviceToHost));
+    if (sum) std::memcpy(sum, &s, sizeof(s));
+    return ASLAM_OK;
+}
+
+// ---- observation covariance (include/aruco_slam_hip.h) ------------------------------------------------------------------
+static_assert(sizeof(ObsCovariance) == sizeof(aslam_obs_covariance), "records are copied as they are");
+static_assert(sizeof(SlotObsCovariance) == sizeof(aslam_slot_obs_covariance), "records are copied as they are");
+
+void aslam_default_obs_covariance_params(aslam_obs_covariance_params* p) {
+    if (!p) return;
+    p->sigma_px = 0.5;
+    p->scale = 1.0;
+    p->floor_xy = 1e-6;
+    p->floor_th = 1e-6;
+    p->gate_norm = 1.0;
+    p->use_residual = 1;
+    p->pad = 0;
+}
+
+int aslam_set_observation_covariance(aslam_ctx* c, const aslam_obs_covariance_params* params) {
+    if (!c) return ASLAM_E_INVALID;
+    if (params) {
+        if (!(std::isfinite(params->sigma_px) && params->sigma_px > 0.0)) return fail(c, ASLAM_E_INVALID, "sigma_px > 0, finite");
+        if (!(std::isfinite(params->scale) && params->scale > 0.0)) return fail(c, ASLAM_E_INVALID, "scale > 0, finite");
+        if (!(std::isfinite(params->floor_xy) && params->floor_xy >= 0.0)) return fail(c, ASLAM_E_INVALID, "floor_xy >= 0, finite");
+        if (!(std::isfinite(params->floor_th) && params->floor_th >= 0.0)) return fail(c, ASLAM_E_INVALID, "floor_th >= 0, finite");
+        if (!(params->gate_norm > 0.0)) return fail(c, ASLAM_E_INVALID, "gate_norm > 0 (+inf allowed)");
+        if (params->use_residual != 0 && params->use_residual != 1) return fail(c, ASLAM_E_INVALID, "use_residual 0 or 1");
+    }
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    if (!params) { c->obs_cov_on = false; return ASLAM_OK; }
+    if (!c->d_obs_cov) {
+        const size_t n = (size_t)c->max_batch * kMarkerMax;
+        HIP_TRY(c, dalloc(&c->d_obs_cov, n));
+        HIP_TRY(c, hipMemset(c->d_obs_cov, 0, n * sizeof(ObsCovariance)));
+    }
+    if (!c->d_obs_cov_sum) {
+        HIP_TRY(c, dalloc(&c->d_obs_cov_sum, (size_t)c->max_batch));
+        HIP_TRY(c, hipMemset(c->d_obs_cov_sum, 0, (size_t)c->max_batch * sizeof(SlotObsCovariance)));
+    }
+    c->obs_cov_prm = *params;
+    c->obs_cov_prm.pad = 0;
+    c->obs_cov_on = true;
+    return ASLAM_OK;
+}
+
+int aslam_get_observation_covariance(aslam_ctx* c, int* on, aslam_obs_covariance_params* out) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->obs_cov_on ? 1 : 0;
+    if (out) {
+        if (c->obs_cov_on) *out = c->obs_cov_prm;
+        else aslam_default_obs_covariance_params(out);
+    }
+    return ASLAM_OK;
+}
+
+int aslam_get_slot_obs_covariance(aslam_ctx* c, int slot, int max, int* n, aslam_obs_covariance* out, aslam_slot_obs_covariance* sum) {
+    if (!c || !n) return fail(c, ASLAM_E_INVALID, "null argument");
+    if (!c->obs_cov_on) return fail(c, ASLAM_E_STATE, "the observation covariance is off (aslam_set_observation_covariance first)");
+    if (int r = check_slot_range(c, slot, 1)) return r;
+    if (max < 0 || (max > 0 && !out)) return fail(c, ASLAM_E_INVALID, "max records need an output array");
+    { int rs = sync_streams(c); if (rs) return rs; }
+    SlotObsCovariance s{};
+    HIP_TRY(c, hipMemcpy(&s, c->d_obs_cov_sum + slot, sizeof(s), hipMemcpyDeviceToHost));
+    const int m = std::min(std::max(s.checked, 0), kMarkerMax);
+    *n = m;
+    const int w = std::min(m, max);
+    if (w > 0) HIP_TRY(c, hipMemcpy(out, c->d_obs_cov + (size_t)slot * kMarkerMax, (size_t)w * sizeof(ObsCovariance), hipMemcpyDeviceToHost));
     if (sum) std::memcpy(sum, &s, sizeof(s));
     return ASLAM_OK;
 }

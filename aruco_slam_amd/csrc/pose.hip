@@ -6,6 +6,7 @@
 // One workgroup per frame; the pose solve is one lane per marker (6-parameter Levenberg-Marquardt on 8
 // residuals in fp64 — a latency-bound scalar chain; frames of the batch supply the parallelism).
 // k_pose_alt (the pose ambiguity check, off by default) follows it with the mirrored second solve of every marker, 8 lanes per marker.
+// k_pose_cov (the observation covariance, off by default) goes between the two: R of every sighting from the solve's own Jacobian.
 #include "common.h"
 #include "pose.h"
 #include <cfloat>
@@ -784,6 +785,165 @@ void launch_pose_alt(hipStream_t st, int nframes, const Marker* markers, const u
 void launch_pose_alt_table(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const RigCam* tab,
                            const int* cam_of_frame, const SlamParams& sp, const PoseAmbArg& arg) {
     hipLaunchKernelGGL(k_pose_alt<CamTable>, dim3(nframes), dim3(kPoseAltThreads), 0, st, markers, n_markers, obs, CamTable{tab, cam_of_frame}, sp, arg);
+}
+
+// ---- observation covariance: the first-order covariance of every pose k_pose solved ---------------------------------
+// k_pose_alt's layout - a group of 8 lanes per marker, one residual row per lane, kPoseCovGroups markers per pass - for one
+// evaluation at the stored pose p: N = J^T J (upper triangle) and |e|^2 summed over the group by the fixed butterfly, then every lane
+// of the group factors the same N = L L^T and forms Y = L^-1 G^T; G N^-1 G^T = Y^T Y comes out symmetric by construction.  A matrix
+// that is not positive definite ends in a NaN (the root of a negative pivot) or an infinity, which is flag 1.
+constexpr int kPoseCovGroups = 32, kPoseCovThreads = 8 * kPoseCovGroups;
+
+// y = L^-1 b for a right-hand side whose entries above FIRST are zero (inv = 1 / diag L); compile-time indices throughout
+template <int FIRST> __device__ __forceinline__ void chol6_forward(const double* Lm, const double* inv, const double* b, double* y) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        if (i < FIRST) { y[i] = 0.; continue; }
+        double s = b[i];
+#pragma unroll
+        for (int k = FIRST; k < i; k++) s -= Lm[i * 6 + k] * y[k];
+        y[i] = s * inv[i];
+    }
+}
+template <int FIRST> __device__ __forceinline__ double dot6_from(const double* a, const double* b) {
+    double s = a[FIRST] * b[FIRST];
+#pragma unroll
+    for (int k = FIRST + 1; k < 6; k++) s += a[k] * b[k];
+    return s;
+}
+
+template <class Cams>
+__global__ __launch_bounds__(kPoseCovThreads) void k_pose_cov(const Marker* __restrict__ markers, const unsigned* __restrict__ n_markers,
+                                                  ObsRaw* __restrict__ obs, Cams cams, SlamParams sp, ObsCovArg A) {
+    __shared__ int sCnt[kPoseCovThreads / 64][2];
+    const int tid = threadIdx.x, f = blockIdx.x;
+    const int g = tid >> 3, row = tid & 7;
+    const RigCam& rc = frame_cam(cams, f);
+    const CamParams& cam = rc.cam;
+    const int M = (int)min(n_markers[f], (unsigned)kMarkerMax);
+    const double hl = (double)((float)sp.marker_length / 2.f);
+    const double var_px = A.sigma_px * A.sigma_px;
+    int nDeg = 0, nGated = 0;
+    for (int k0 = 0; k0 < M; k0 += kPoseCovGroups) {               // uniform
+        const int k = k0 + g;
+        const bool have = k < M;
+        const size_t at = (size_t)f * kMarkerMax + (have ? k : 0);  // a group past the list's end repeats marker 0 and writes nothing
+        double p[6];
+        for (int i = 0; i < 3; i++) { p[i] = markers[at].rvec[i]; p[3 + i] = markers[at].tvec[i]; }
+        const double m_row = markers[at].c[row];
+        const double r_ref[3] = {obs[at].r[0], obs[at].r[1], obs[at].r[2]};
+        // N (upper triangle by rows) and |e|^2 at p, the same bits in every lane of the group
+        double S[22];
+        {
+            double out, Jr[6];
+            project_row(p, hl, cam, row, out, Jr);
+            const double e = out - m_row;
+            int q = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = i; j < 6; j++) S[q++] = Jr[i] * Jr[j];
+            S[21] = e * e;
+#pragma unroll
+            for (int i = 0; i < 22; i++) S[i] = group8_sum(S[i]);
+        }
+        const double e2 = S[21];
+        const double sigma2 = A.use_residual ? var_px + e2 / 8.0 : var_px;
+        // N = L L^T
+        double Lm[36], inv[6];
+        {
+            int q = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = i; j < 6; j++) Lm[j * 6 + i] = S[q++];     // the lower triangle, column i
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                double d = Lm[j * 6 + j];
+#pragma unroll
+                for (int c = 0; c < j; c++) d -= Lm[j * 6 + c] * Lm[j * 6 + c];
+                d = sqrt(d);
+                Lm[j * 6 + j] = d;
+                inv[j] = 1. / d;
+#pragma unroll
+                for (int i = j + 1; i < 6; i++) {
+                    double s = Lm[i * 6 + j];
+#pragma unroll
+                    for (int c = 0; c < j; c++) s -= Lm[i * 6 + c] * Lm[j * 6 + c];
+                    Lm[i * 6 + j] = s * inv[j];
+                }
+            }
+        }
+        // G^T, one column per observation component: x0 = t_z, y0 = -t_x, th0 = atan2(-R02, R22)
+        double gth[6] = {0., 0., 0., 0., 0., 0.};
+        {
+            double R[9], dR[27];
+            rodrigues_fwd(p, R, dR);
+            const double den = R[2] * R[2] + R[8] * R[8];
+#pragma unroll
+            for (int j = 0; j < 3; j++) gth[j] = (R[2] * dR[j * 9 + 8] - R[8] * dR[j * 9 + 2]) / den;
+        }
+        const double gx[6] = {0., 0., 0., 0., 0., 1.}, gy[6] = {0., 0., 0., -1., 0., 0.};
+        double Yx[6], Yy[6], Yt[6];
+        chol6_forward<5>(Lm, inv, gx, Yx);
+        chol6_forward<3>(Lm, inv, gy, Yy);
+        chol6_forward<0>(Lm, inv, gth, Yt);
+        // C = G N^-1 G^T = Y^T Y in the camera's frame, then the mount: M C M^T, M = blkdiag(Rot(psi), 1)
+        const double cxx = dot6_from<5>(Yx, Yx), cxy = dot6_from<5>(Yx, Yy), cxt = dot6_from<5>(Yx, Yt);
+        const double cyy = dot6_from<3>(Yy, Yy), cyt = dot6_from<3>(Yy, Yt), ctt = dot6_from<0>(Yt, Yt);
+        const double c = rc.cpsi, s = rc.spsi;
+        const double t00 = c * cxx - s * cxy, t01 = c * cxy - s * cyy, t10 = s * cxx + c * cxy, t11 = s * cxy + c * cyy;
+        double cov[9];
+        cov[0] = sigma2 * (c * t00 - s * t01);
+        cov[1] = sigma2 * (s * t00 + c * t01);
+        cov[2] = sigma2 * (c * cxt - s * cyt);
+        cov[4] = sigma2 * (s * t10 + c * t11);
+        cov[5] = sigma2 * (s * cxt + c * cyt);
+        cov[8] = sigma2 * ctt;
+        cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
+        bool ok = cov[0] > 0. && cov[4] > 0. && cov[8] > 0.;
+#pragma unroll
+        for (int i = 0; i < 9; i++) ok = ok && isfinite(cov[i]);
+        // the gates: k_pose's range gate in its own expression, and the reference's bound on |r| applied to the new r
+        const double nt = sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5]);
+        const bool far = (float)nt > sp.useful_distance_threshold;
+        const double r0 = A.scale * cov[0] + A.floor_xy, r1 = A.scale * cov[4] + A.floor_xy, r2 = A.scale * cov[8] + A.floor_th;
+        const bool gated = ok && sqrt(r0 * r0 + r1 * r1 + r2 * r2) > A.gate_norm;
+        ObsCovariance rec;
+#pragma unroll
+        for (int i = 0; i < 9; i++) rec.cov[i] = ok ? cov[i] : 0.;
+        rec.sigma2 = sigma2;
+        rec.e2 = e2;
+        for (int i = 0; i < 3; i++) rec.r_ref[i] = r_ref[i];
+        rec.flags = (ok ? 0 : 1) | (gated ? 2 : 0) | (far ? 4 : 0);
+        rec.pad = 0;
+        const bool writer = row == 0 && have;
+        if (writer) {
+            A.rec[at] = rec;
+            if (ok) { obs[at].r[0] = r0; obs[at].r[1] = r1; obs[at].r[2] = r2; }
+            obs[at].valid = rec.flags == 0 ? 1 : 0;
+        }
+        nDeg += __popcll(__ballot(writer && !ok));
+        nGated += __popcll(__ballot(writer && gated));
+    }
+    if ((tid & 63) == 0) { sCnt[tid >> 6][0] = nDeg; sCnt[tid >> 6][1] = nGated; }
+    __syncthreads();
+    if (tid == 0) {
+        SlotObsCovariance sm;
+        sm.checked = M; sm.degenerate = 0; sm.gated = 0; sm.pad = 0;
+        for (int w = 0; w < kPoseCovThreads / 64; w++) { sm.degenerate += sCnt[w][0]; sm.gated += sCnt[w][1]; }
+        A.sum[f] = sm;
+    }
+}
+
+void launch_pose_cov(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const PoseCams& cams,
+                     const SlamParams& sp, const ObsCovArg& arg) {
+    hipLaunchKernelGGL(k_pose_cov<PoseCams>, dim3(nframes), dim3(kPoseCovThreads), 0, st, markers, n_markers, obs, cams, sp, arg);
+}
+
+void launch_pose_cov_table(hipStream_t st, int nframes, const Marker* markers, const unsigned* n_markers, ObsRaw* obs, const RigCam* tab,
+                           const int* cam_of_frame, const SlamParams& sp, const ObsCovArg& arg) {
+    hipLaunchKernelGGL(k_pose_cov<CamTable>, dim3(nframes), dim3(kPoseCovThreads), 0, st, markers, n_markers, obs, CamTable{tab, cam_of_frame}, sp, arg);
 }
 
 // One rig step = the observation lists of its C frames (slots frame0 + s C + c) concatenated in camera order into one list at

@@ -772,6 +772,67 @@ int aslam_set_pose_ambiguity(aslam_ctx* ctx, const aslam_pose_ambiguity_params* 
 int aslam_get_pose_ambiguity(aslam_ctx* ctx, int* on, aslam_pose_ambiguity_params* out);
 int aslam_get_slot_pose_ambiguity(aslam_ctx* ctx, int slot, int max, int* n, aslam_pose_ambiguity* out, aslam_slot_pose_ambiguity* sum);
 
+/* ---- observation covariance: R of every sighting from the pose solve's own Jacobian (no reference counterpart) ---------
+ * Every gate and every filter step of the library takes a sighting's R from the reference's CalculateCovariance: one scalar
+ * reprojection error times (R_x, R_y, R_theta) plus (1e-2, 1e-2, 1e-3).  That is not a covariance of anything: against
+ * the first-order covariance of the pose solve it is off by a factor of hundreds in (x, y), and too small in theta for a distant
+ * frontal marker.  With this switch set, R is the diagonal of that first-order covariance instead.
+ * Switch.  aslam_set_observation_covariance(ctx, params).  It is off by default, settable in any mode, and persists.  With the switch
+ * off, no launch, kernel or result differs from today.
+ * Where it runs.  One kernel, k_pose_cov, directly behind the pose kernel and ahead of the pose ambiguity check (which reads valid), on
+ * the same stream with the same camera source, in every entry point that runs detection: the single camera, rigs (ahead of the merge
+ * of a step's lists), both fleet kinds, localization and uncertain-map localization, the host-fed stream, aslam_detect_batch,
+ * aslam_debug_run_pose and aslam_debug_run_pose_refined.  aslam_run_staged(..., with_ekf = 2) runs no pose stage and so none of this.
+ * Every consumer of a slot's raw observation list sees the new R and valid without a change of its own: every chain, the window
+ * planner, landmark confirmation, the gates, aslam_get_observations and aslam_get_slot_raw_observations.
+ * Parameters.  sigma_px > 0, finite; scale > 0, finite; floor_xy >= 0 and floor_th >= 0, finite; gate_norm > 0, +inf allowed;
+ * use_residual 0 or 1.
+ * Per marker k of a frame's marker list, all M <= 128 of them, with p = (r, t) the pose the pose stage stored and m the marker's 8 float
+ * corners as doubles:
+ * 1. Jacobian.  J is the 8 x 6 Jacobian of the projection of the 4 corners (pinhole + plumb-bob) at p, N = J^T J, and
+ *    e2 = |project(p) - m|^2, the sum of the 8 squared residuals, in double.
+ * 2. Pixel variance.  sigma2 = sigma_px^2, plus e2 / 8 when use_residual is set: a marker that fits badly (blur, occlusion) gets a
+ *    larger covariance, the one thing the reference's object_error did.
+ * 3. Observation Jacobian.  G is the 3 x 6 Jacobian of the camera-frame observation (t_z, -t_x, atan2(-R02, R22)) with respect to
+ *    (r, t): the translation rows are the constants e_6 and -e_4, the heading row is
+ *    (R02 dR22/dr_j - R22 dR02/dr_j) / (R02^2 + R22^2) for j < 3 and zero for t.  M = blkdiag(Rot(psi), 1) is the frame's mount.
+ * 4. Covariance.  cov = sigma2 M G N^-1 G^T M^T, row-major over (x, y, theta) in the base frame, stored symmetric to the bit.  It is
+ *    neither scaled nor floored.  N is factored by Cholesky; the arithmetic order is the kernel's own and fixed, without
+ *    floating-point atomics: the same marker gives the same bits whatever else the call carries.
+ * 5. Flag 1 (degenerate): an entry of cov is non-finite or a diagonal entry is <= 0.  cov is then zeroed, the sighting gets valid = 0,
+ *    R keeps the pose stage's values and flag 2 is not evaluated.
+ * 6. Otherwise R is replaced: R[0] = scale cov[0] + floor_xy, R[1] = scale cov[4] + floor_xy, R[2] = scale cov[8] + floor_th.
+ *    r_ref keeps what the pose stage had written.  The chains stay diagonal: cov's off-diagonal entries are reported, not consumed.
+ * 7. valid is recomputed, not inherited - the pose stage's flag mixes the range gate with the reference's bound on its own R, which
+ *    no longer applies.  Flag 4: the range gate in the pose stage's expression, (float)|t| > useful_distance_threshold.  Flag 2:
+ *    sqrt(R0^2 + R1^2 + R2^2) > gate_norm on the new R (gate_norm = 1 is the reference's bound, aruco_slam.cpp:367).
+ *    valid = !(flags & 7).  A sighting the reference's covariance gate had dropped can therefore come back.
+ * 8. Slot sum: checked = M, degenerate = markers with flag 1, gated = markers with flag 2.
+ * Records.  aslam_get_slot_obs_covariance(ctx, slot, max, n, out, sum) waits for the enqueued work, as the health getters do.  *n = the
+ * markers of the slot's last pose stage under the switch, of which the first `max` records are written to out (may be NULL with
+ * max = 0); sum (may be NULL) receives the slot sum.  A slot never processed reads as empty.
+ * Errors.  ASLAM_E_INVALID: a null context, parameters out of range, a slot outside [0, max_batch), max < 0 or records without an
+ * array.  ASLAM_E_STATE: the slot getter while the switch is off.  A refused call changes nothing.  The setter first enqueues a pending
+ * batch and synchronises, as aslam_set_pose_ambiguity does.
+ * Lifetime.  max_batch x 128 records and max_batch sums, allocated by the first setter call with parameters, freed by aslam_destroy.
+ * Dropped.  The full 3 x 3 R inside the EKF chains: they stay diagonal, and the record carries the full matrix so that a caller can
+ * see what the diagonal leaves out.  No estimation of sigma_px from data.  No fusion of k_pose_cov into k_pose_alt when both are on.
+ * No change of any gate default.
+ * The defaults sigma_px = 0.5, use_residual = 1, scale = 1, floor_xy = 1e-6, floor_th = 1e-6 and gate_norm = 1 (the reference's own
+ * bound) are the maintainer's choice.  sigma_px and the two floors are untuned: nobody has measured them. */
+typedef struct { double sigma_px, scale, floor_xy, floor_th, gate_norm; int use_residual, pad; } aslam_obs_covariance_params;
+typedef struct { double cov[9];      /* row-major 3x3 of (x, y, theta) in the base frame: sigma2 * M G N^-1 G^T M^T, unscaled, no floors */
+                 double sigma2;      /* the pixel variance used for this marker */
+                 double e2;          /* sum of the 8 squared reprojection residuals at the primary pose, double */
+                 double r_ref[3];    /* the CalculateCovariance diagonal k_pose had written and this replaced */
+                 int flags, pad; } aslam_obs_covariance;
+typedef struct { int checked, degenerate, gated, pad; } aslam_slot_obs_covariance;
+void aslam_default_obs_covariance_params(aslam_obs_covariance_params* p);
+int aslam_set_observation_covariance(aslam_ctx* ctx, const aslam_obs_covariance_params* params /* NULL: off */);
+/* *on = 1 while the switch is set; out (may be NULL) receives the parameters in force, the defaults while it is off */
+int aslam_get_observation_covariance(aslam_ctx* ctx, int* on, aslam_obs_covariance_params* out);
+int aslam_get_slot_obs_covariance(aslam_ctx* ctx, int slot, int max, int* n, aslam_obs_covariance* out, aslam_slot_obs_covariance* sum);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
