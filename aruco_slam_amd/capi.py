@@ -229,6 +229,8 @@ _SIGS = {
     "aslam_set_observation_covariance": (C.c_int, [C.c_void_p, _P(ObsCovarianceParams)]),
     "aslam_get_observation_covariance": (C.c_int, [C.c_void_p, _ip, _P(ObsCovarianceParams)]),
     "aslam_get_slot_obs_covariance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p]),
+    "aslam_set_consistent_innovations": (C.c_int, [C.c_void_p, C.c_int]),
+    "aslam_get_consistent_innovations": (C.c_int, [C.c_void_p, _ip]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -891,6 +893,17 @@ class Context:
         self._ck(self.lib.aslam_get_slot_obs_covariance(self.h, int(slot), MARKER_MAX, C.byref(n), out.ctypes.data_as(C.c_void_p),
                                                         s.ctypes.data_as(C.c_void_p)))
         return out[:n.value].copy(), s[0].copy()
+
+    # -- consistent innovations ---------------------------------------------------------------------------------------
+    def set_consistent_innovations(self, on=True):
+        """every correction of a frame is formed at the mean the previous one left (e_i = ze_i - H_i (mu_{i-1} - mu_0)); off: the
+        reference's frozen-mean innovations.  While it is on no EKF window is planned."""
+        self._ck(self.lib.aslam_set_consistent_innovations(self.h, int(bool(on))))
+
+    def get_consistent_innovations(self):
+        on = C.c_int()
+        self._ck(self.lib.aslam_get_consistent_innovations(self.h, C.byref(on)))
+        return bool(on.value)
 
     def get_slot_health(self, first, count):
         """one SLOT_HEALTH_DTYPE record per EKF slot first .. first + count - 1"""

@@ -198,6 +198,9 @@ struct aslam_ctx {
     aslam_obs_covariance_params obs_cov_prm{};
     ObsCovariance* d_obs_cov = nullptr;         // max_batch x kMarkerMax
     SlotObsCovariance* d_obs_cov_sum = nullptr; // max_batch
+    // consistent innovations (aslam_set_consistent_innovations): off unless set, kept across mode changes.  Every
+    // per-frame solve and every localization step then runs in its RunningMean instantiation, and aslam_run_staged plans no windows.
+    bool consistent_on = false;
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -688,7 +691,7 @@ template <class S> int run_chain(aslam_ctx* c, const S& s, int slot = 0) {
     };
     if (fast) {
         prof_begin(c, P_EKF_MID, st);
-        launch_ekf_mid(st, s, gate);
+        launch_ekf_mid(st, s, gate, c->consistent_on);
         prof_end(c);
         finish();
         prof_begin(c, P_EKF_APPLY, st);
@@ -696,7 +699,7 @@ template <class S> int run_chain(aslam_ctx* c, const S& s, int slot = 0) {
         prof_end(c);
     } else if (c->init.max_updates_per_frame <= ekf_mid_max_updates()) {
         prof_begin(c, P_EKF_MID64, st);
-        launch_ekf_mid64(st, s, gate);
+        launch_ekf_mid64(st, s, gate, c->consistent_on);
         prof_end(c);
         finish();
         prof_begin(c, P_EKF_T, st);
@@ -710,7 +713,7 @@ template <class S> int run_chain(aslam_ctx* c, const S& s, int slot = 0) {
         launch_ekf_gather(st, s);
         prof_end(c);
         prof_begin(c, P_EKF_SMALL, st);
-        launch_ekf_small(st, s, gate);
+        launch_ekf_small(st, s, gate, c->consistent_on);
         prof_end(c);
         finish();
         prof_begin(c, P_EKF_T, st);
@@ -740,7 +743,7 @@ int run_loc_steps(aslam_ctx* c, int first, int count, bool predict_first) {
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_LOC_STEPS, st);
     launch_loc_steps(st, c->ekf, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, first, count, predict_first ? 1 : 0, c->gate_on ? &c->gate : nullptr,
-                     c->umap_on ? &c->umap : nullptr);
+                     c->umap_on ? &c->umap : nullptr, c->consistent_on);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return ASLAM_OK;
@@ -1334,12 +1337,14 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         note_ekf_range(c, first, count);
         return ASLAM_OK;
     }
-    if (!c->win_enabled || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
+    // consistent innovations: the window chain forms the reference's frozen-mean corrections only, so no window is planned
+    if (!c->win_enabled || c->consistent_on || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
         // the SLAM gate: the window planner runs the "stationary" test on the host from a mirror of the last-observed
-        // list, which a rejection on the device changes; the mirror is stale from here on
-        if (c->slam_gate_on) c->mirror_dirty = true;
+        // list, which a rejection on the device changes; the mirror is stale from here on.  Frames the device planned while the
+        // consistent switch kept a window-enabled context on this path are frames the host did not follow either.
+        if (c->slam_gate_on || c->consistent_on) c->mirror_dirty = true;
         HIP_TRY(c, hipStreamWaitEvent(c->stream_ekf, c->ev_detect, 0));
         r = confirm_slots(c, c->stream_ekf, first, count);
         if (r) return r;
@@ -2362,7 +2367,7 @@ int run_fleet_steps(aslam_ctx* c, int first, int count, const int* robots) {
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_detect, 0));
     prof_begin(c, P_FLEET_STEPS, st);
     launch_fleet_steps(st, c->ekf, c->fleet, c->sp, c->d_obs, c->d_nmarkers, c->d_enc, c->d_fleet_work, ng, c->gate_on ? &c->gate : nullptr,
-                       c->umap_on ? &c->umap : nullptr);
+                       c->umap_on ? &c->umap : nullptr, c->consistent_on);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_ekf, st));
@@ -3283,6 +3288,22 @@ int aslam_get_slot_obs_covariance(aslam_ctx* c, int slot, int max, int* n, aslam
     const int w = std::min(m, max);
     if (w > 0) HIP_TRY(c, hipMemcpy(out, c->d_obs_cov + (size_t)slot * kMarkerMax, (size_t)w * sizeof(ObsCovariance), hipMemcpyDeviceToHost));
     if (sum) std::memcpy(sum, &s, sizeof(s));
+    return ASLAM_OK;
+}
+
+// Consistent innovations: one switch per context, in any mode, kept across mode changes
+int aslam_set_consistent_innovations(aslam_ctx* c, int on) {
+    if (!c) return ASLAM_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, ASLAM_E_INVALID, "on: 0 or 1");
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    c->consistent_on = on == 1;
+    return ASLAM_OK;
+}
+
+int aslam_get_consistent_innovations(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->consistent_on ? 1 : 0;
     return ASLAM_OK;
 }
 

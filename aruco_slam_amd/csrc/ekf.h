@@ -96,15 +96,15 @@ void ekf_free(EkfState& E);
 void launch_ekf_predict_only(hipStream_t st, const EkfState& E, const SlamParams& sp, double wl, double wr, double dt);
 void launch_ekf_plan(hipStream_t st, const EkfState& E, const SlamParams& sp, double wl, double wr, double dt, int do_predict,
                      const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m, int slot);
-struct SlamGateArg;                    // below: the SLAM gate of a launch; nullptr = the ungated kernel
-void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
+struct SlamGateArg;                    // below: the SLAM gate of a launch; nullptr = the ungated kernel.  consistent: the RunningMean solve
+void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_apply(hipStream_t st, const EkfState& E);
 int ekf_fast_max_updates();
 int ekf_mid_max_updates();
-void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
+void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_update_mfma(hipStream_t st, const EkfState& E, int depth = -1);   // depth >= 0: rows of d_T / d_Wt to contract instead of 3 * *d_m
 void launch_ekf_gather(hipStream_t st, const EkfState& E);
-void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr);
+void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_T(hipStream_t st, const EkfState& E);
 void launch_ekf_export_map(hipStream_t st, const EkfState& E);
 // innovation gate of the localization steps (ekf_localize.h): the parameters in force and where the gated kernels
@@ -144,7 +144,8 @@ struct MapCov {
 // gate != nullptr: the gated kernel (k_loc_steps_gated, k_fleet_steps_gated) with those parameters; umap != nullptr: the
 // Schmidt-Kalman kernels (k_loc_steps_umap[_gated], k_fleet_steps_umap[_gated]) on that map
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr, const MapCov* umap = nullptr);
+                      const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr, const MapCov* umap = nullptr,
+                      bool consistent = false);   // consistent: the RunningMean kernels (k_*_ci*)
 void launch_umap_clear_cross(hipStream_t st, const EkfState& E, int L);   // the single filter's Sigma_xl := 0 (a seat of its pose)
 // fleet localization (ekf_fleet.h): one workgroup per robot of the work list (n_groups robots), each on its own filter in F
 constexpr int kFleetState = 12;        // doubles per robot: mu_x (3), then Sigma_xx row-major (9)
@@ -155,7 +156,7 @@ struct FleetState {
 };
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
                         const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate = nullptr,
-                        const MapCov* umap = nullptr);
+                        const MapCov* umap = nullptr, bool consistent = false);
 // fleet SLAM (ekf_fleet_slam.h): R complete filters with the single filter's chain layouts in one allocation; robot r's buffers lie
 // r * stride bytes past robot 0's.  No window buffers; d_slot_stat and max_slots are the context's.
 struct FleetSlam {
@@ -177,12 +178,12 @@ struct FleetRound {
     int n;
 };
 void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers, Counters* ctr, int max_m);
-void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
+void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_apply(hipStream_t st, const FleetRound& R);
-void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R);
 void launch_ekf_gather(hipStream_t st, const FleetRound& R);
-void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr);
+void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate = nullptr, bool consistent = false);
 void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateArg& gate, int slot = 0);   // every robot of the round; slot: unused (the work list's)
 void launch_ekf_T(hipStream_t st, const FleetRound& R);
 // map merge (fleet_merge.h): n_maps <= kMergeMaxMaps maps of per_map MapRecord records each, aligned

@@ -455,13 +455,16 @@ static __global__ __launch_bounds__(256) void k_ekf_gather(Src S) {
 // treated it differently and k_ekf_small<EkfSingle> no longer compiled to the instructions of the former k_ekf_small
 // Gated (G = SlamGate, ekf_slam_gate.h): thread 0 judges correction i where it forms S_i^-1; a rejected one keeps gamma column block i = 0
 // (as initialised) and is left out of g, which is the sweep without it.
-template <class Src, class G>
-static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 3*9*kMarkerMax + 16 + kMarkerMax doubles of LDS */, const G& gate) {
+// RunningMean (C): thread 0 forms the running innovation e_i = ze_i - sum_{j<i} D_ij e_j beside S_i, from the D blocks of
+// step (b) (rejected j: D_ij = 0); the gate judges e_i and g = sum_i gamma_.i e_i.
+template <class Src, class G, class C>
+static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >= 3*9*kMarkerMax + 16 + 4*kMarkerMax doubles of LDS */, const G& gate) {
     double* sC = scratch;
     double* sD = scratch + kMarkerMax * 9;
     double* sBeta = scratch + 2 * kMarkerMax * 9;
     double* sSinv = scratch + 3 * kMarkerMax * 9;
     double* sRejected = scratch + 3 * kMarkerMax * 9 + 16;   // gated: per correction, 1.0 = rejected
+    double* sE = sRejected + kMarkerMax;                     // RunningMean: the running innovations, 3 per correction
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = *E.d_m;
     const int n3 = 3 * m;
@@ -529,7 +532,19 @@ static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >
                     S[a * 3 + b] = s + (a == b ? u.r[a] : 0.0);
                 }
             inv3_pp(S, sSinv);
-            if constexpr (G::kOn) sRejected[i] = 1.0 - slam_gate_verdict(gate, sSinv, u.ze[0], u.ze[1], u.ze[2], i);
+            if constexpr (C::kOn) {
+                // e_i = ze_i - sum_{j<i} D_ij e_j with D_ij = H_i K_j as step (b) left it in LDS (zero for a rejected j, whose e may be NaN)
+                double e[3] = {u.ze[0], u.ze[1], u.ze[2]};
+                for (int j = 0; j < i; j++) {
+                    if constexpr (G::kOn) { if (sRejected[j] != 0.0) continue; }
+                    const double e0 = sE[3 * j], e1 = sE[3 * j + 1], e2 = sE[3 * j + 2];
+                    for (int a = 0; a < 3; a++) e[a] -= sD[j * 9 + a * 3] * e0 + sD[j * 9 + a * 3 + 1] * e1 + sD[j * 9 + a * 3 + 2] * e2;
+                }
+                for (int a = 0; a < 3; a++) sE[3 * i + a] = e[a];
+                if constexpr (G::kOn) sRejected[i] = 1.0 - slam_gate_verdict(gate, sSinv, e[0], e[1], e[2], i);
+            } else {
+                if constexpr (G::kOn) sRejected[i] = 1.0 - slam_gate_verdict(gate, sSinv, u.ze[0], u.ze[1], u.ze[2], i);
+            }
         }
         __syncthreads();
         bool rejected = false;
@@ -553,7 +568,8 @@ static __device__ void ekf_small_general(const EkfState& E, double* scratch /* >
         double s = 0;
         for (int q = r / 3 * 3; q < n3; q++) {
             if constexpr (G::kOn) { if (sRejected[q / 3] != 0.0) continue; }       // its gamma is zero, its ze may be NaN
-            s += ga[(size_t)r * n3 + q] * E.d_upd[q / 3].ze[q % 3];
+            if constexpr (C::kOn) s += ga[(size_t)r * n3 + q] * sE[q];
+            else s += ga[(size_t)r * n3 + q] * E.d_upd[q / 3].ze[q % 3];
         }
         E.d_g[r] = s;
     }
@@ -580,8 +596,11 @@ __device__ __forceinline__ void inv3_cof(const double* P, int n3, double* o) {  
     o[6] = C * id; o[7] = (b * g - a * h) * id; o[8] = (a * e - b * d) * id;
 }
 
-template <class Src, class G = NoSlamGate>
-static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
+// RunningMean (C): the pseudo-innovation exists only to reproduce Q1, so ungated g = G ze and sNu is not accumulated;
+// gated, sNu carries the running innovation instead, e_r -= (H_r K_i) e_i, pivot i is judged by e_i (complete behind the barrier of
+// step i - 1) and g = G ze with the rejected entries of ze zeroed.
+template <class Src, class G = NoSlamGate, class C = FrozenMean>
+static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G, C> arg) {
     const Src& S = arg;
     const G& gate = arg;
     const EkfState E = S.state();
@@ -594,7 +613,7 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
     const int ld = E.ld;
     const int tc = tid % kSmallMax, tr = tid / kSmallMax;     // column, row group (0..7); rows r = tr + 8*i
     if (n3 > kSmallMax) {                              // uniform branch
-        ekf_small_general<Src, G>(E, sA0, gate);
+        ekf_small_general<Src, G, C>(E, sA0, gate);
     } else if (m > 0) {
         // A[(3i+a)][(3j+b)] = (V_i H_j^T)[a][b] + delta_ij R_i[a][b]   (aruco_slam.cpp:146: (Gx*sigma_)*Gx^T + Rk)
         if (tc < n3) {
@@ -632,8 +651,9 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
                 // every thread forms S_i^-1 here, so every thread reaches the same verdict from the same LDS words; thread 0 leaves it
                 double Pg[9];
                 inv3_cof(cur + k0 * n3 + k0, n3, Pg);
-                if (tid == 0) rejected = slam_gate_verdict(gate, Pg, sZe[k0], sZe[k0 + 1], sZe[k0 + 2], ib) == 0.0;
-                else rejected = slam_gate_rejects(gate, slam_gate_d2(Pg, sZe[k0], sZe[k0 + 1], sZe[k0 + 2]));
+                const double* zj = C::kOn ? sNu : sZe;                       // what the pivot is judged by: e_i or ze_i
+                if (tid == 0) rejected = slam_gate_verdict(gate, Pg, zj[k0], zj[k0 + 1], zj[k0 + 2], ib) == 0.0;
+                else rejected = slam_gate_rejects(gate, slam_gate_d2(Pg, zj[k0], zj[k0 + 1], zj[k0 + 2]));
             }
             if (rejected) {
                 // the pivot is not eliminated: its rows and columns become zero, the rest is copied; nu_i = 0 (its ze may be NaN)
@@ -645,7 +665,8 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
                         if (r < n3) nxt[r * n3 + tc] = (cin || (r >= k0 && r < k0 + 3)) ? 0.0 : cur[r * n3 + tc];
                     }
                 }
-                if (tid < 3) sNu[k0 + tid] = 0.0;
+                if constexpr (C::kOn) { if (tid < 3) sZe[k0 + tid] = 0.0; }      // nothing reads sZe before the final product
+                else { if (tid < 3) sNu[k0 + tid] = 0.0; }
             } else if (tc < n3) {
                 double Pi[9];
                 inv3_cof(cur + k0 * n3 + k0, n3, Pi);                         // S_i^-1 (every thread, from LDS broadcast reads)
@@ -657,7 +678,8 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
                 const double y0 = Pi[0] * p0 + Pi[1] * p1 + Pi[2] * p2;       // (S_i^-1 * pivot rows)[., tc]
                 const double y1 = Pi[3] * p0 + Pi[4] * p1 + Pi[5] * p2;
                 const double y2 = Pi[6] * p0 + Pi[7] * p1 + Pi[8] * p2;
-                const double z0 = sZe[k0], z1 = sZe[k0 + 1], z2 = sZe[k0 + 2];
+                const double* zs = C::kOn ? sNu : sZe;                       // rows k0 .. k0 + 2 of sNu are final: only rows below the pivot change
+                const double z0 = zs[k0], z1 = zs[k0 + 1], z2 = zs[k0 + 2];
 #pragma unroll
                 for (int i = 0; i < SMR; i++) {
                     const int r = tr + 8 * i;
@@ -668,12 +690,13 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
                             const double f0 = cur[r * n3 + k0], f1 = cur[r * n3 + k0 + 1], f2 = cur[r * n3 + k0 + 2];
                             const double old = cin ? 0.0 : cur[r * n3 + tc];
                             nxt[r * n3 + tc] = old - (f0 * y0 + f1 * y1 + f2 * y2);
-                            if (tc == k0 && r > k0 + 2) {
+                            if ((!C::kOn || G::kOn) && tc == k0 && r > k0 + 2) {
                                 // block multiplier H_r K_i = F_r S_i^-1 : nu_r += (H_r K_i) ze_i
                                 const double m0 = f0 * Pi[0] + f1 * Pi[3] + f2 * Pi[6];
                                 const double m1 = f0 * Pi[1] + f1 * Pi[4] + f2 * Pi[7];
                                 const double m2 = f0 * Pi[2] + f1 * Pi[5] + f2 * Pi[8];
-                                sNu[r] += m0 * z0 + m1 * z1 + m2 * z2;
+                                if constexpr (C::kOn) sNu[r] -= m0 * z0 + m1 * z1 + m2 * z2;      // e_r -= (H_r K_i) e_i
+                                else sNu[r] += m0 * z0 + m1 * z1 + m2 * z2;
                             }
                         }
                     }
@@ -685,7 +708,8 @@ static __global__ __launch_bounds__(768) void k_ekf_small(Solve<Src, G> arg) {
         for (int p = tid; p < n3 * n3; p += SMT) E.d_G[p] = cur[p];
         if (tid < n3) {
             double s = 0;
-            for (int c = 0; c < n3; c++) s += cur[tid * n3 + c] * sNu[c];
+            const double* zg = C::kOn ? sZe : sNu;
+            for (int c = 0; c < n3; c++) s += cur[tid * n3 + c] * zg[c];
             E.d_g[tid] = s;
         }
     }
@@ -766,8 +790,13 @@ constexpr int kFastN3 = 3 * kFastM;      // 72
 constexpr int MIDT = 576;                // kFastM x kFastM: one thread per 3x3 block of the innovation matrix
 
 // <= 128 VGPRs (4 waves per SIMD) so that the workgroup always finds room beside the persistent detection waves of the other stream
-template <class Src, class G = NoSlamGate>
-static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G> arg) {
+// RunningMean (C): ungated, g = G ze and sNu is not accumulated.  Gated, sNu carries the running innovation: thread
+// (bi, ib) applies pivot ib to e_bi for bi > ib + 1 with the multiplier it has just formed, and the owner of the NEXT pivot block
+// (ib + 1, ib + 1), which judges it in this same step, applies pivot ib to its own e_{ib+1} first, from the published column block
+// and S_ib^-1 (one 3 x 3 product more on that thread, no barrier more).  A rejected pivot zeroes its entries of sZe, which nothing
+// reads before g = G ze.
+template <class Src, class G = NoSlamGate, class C = FrozenMean>
+static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G, C> arg) {
     const Src& S = arg;
     const G& gate = arg;
     const EkfState E = S.state();
@@ -872,7 +901,16 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G> arg) {
 #pragma unroll
                 for (int k = 0; k < 9; k++) A[k] = 0.0;
             }
-            if (bi == ib && bj == ib) sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;
+            if (bi == ib && bj == ib) {
+                if constexpr (C::kOn) sZe[3 * ib] = sZe[3 * ib + 1] = sZe[3 * ib + 2] = 0.0;
+                else sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;
+            }
+        }
+        double en[3] = {0.0, 0.0, 0.0};                                     // RunningMean, gated, owner of block (ib + 1, ib + 1): e_{ib+1}
+        if constexpr (C::kOn && G::kOn) {
+            if (act && bi == ib + 1 && bj == ib + 1) {
+                en[0] = sNu[3 * ib + 3]; en[1] = sNu[3 * ib + 4]; en[2] = sNu[3 * ib + 5];
+            }
         }
         if (act && !rejected) {
             double Pi[9], Y[9];
@@ -903,10 +941,25 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G> arg) {
 #pragma unroll
                     for (int j = 0; j < 3; j++)
                         A[i * 3 + j] = fma(-F[i * 3 + 2], Y[6 + j], fma(-F[i * 3 + 1], Y[3 + j], fma(-F[i * 3], Y[j], A[i * 3 + j])));
-                if (bj == ib && bi > ib) {
-                    const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
+                if constexpr (!C::kOn) {
+                    if (bj == ib && bi > ib) {
+                        const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
 #pragma unroll
-                    for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[a * 3] * z0 + A[a * 3 + 1] * z1 + A[a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                        for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[a * 3] * z0 + A[a * 3 + 1] * z1 + A[a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                    }
+                } else if constexpr (G::kOn) {
+                    // e_bi -= (H_bi K_ib) e_ib; e_ib is final since step ib - 1.  Row ib + 1 is its diagonal owner's (below)
+                    const double z0 = sNu[3 * ib], z1 = sNu[3 * ib + 1], z2 = sNu[3 * ib + 2];
+                    if (bj == ib && bi > ib + 1) {
+#pragma unroll
+                        for (int a = 0; a < 3; a++) sNu[3 * bi + a] += A[a * 3] * z0 + A[a * 3 + 1] * z1 + A[a * 3 + 2] * z2;   // H K = -A
+                    }
+                    if (bi == ib + 1 && bj == ib + 1) {
+                        double HK[9];
+                        mul3(F, Pi, HK);                                         // F = A(ib + 1, ib) as published, H K = F S_ib^-1
+#pragma unroll
+                        for (int a = 0; a < 3; a++) en[a] -= HK[a * 3] * z0 + HK[a * 3 + 1] * z1 + HK[a * 3 + 2] * z2;
+                    }
                 }
             }
         }
@@ -919,18 +972,24 @@ static __global__ __launch_bounds__(576, 4) void k_ekf_mid(Solve<Src, G> arg) {
                 inv3_reg(A, Pn);
 #pragma unroll
                 for (int k = 0; k < 9; k++) sPinv[cb ^ 1][k] = Pn[k];
-                if constexpr (G::kOn) sPinv[cb ^ 1][9] = slam_gate_verdict(gate, Pn, sZe[3 * ib + 3], sZe[3 * ib + 4], sZe[3 * ib + 5], ib + 1);
+                if constexpr (G::kOn && C::kOn) {
+                    sNu[3 * ib + 3] = en[0]; sNu[3 * ib + 4] = en[1]; sNu[3 * ib + 5] = en[2];
+                    sPinv[cb ^ 1][9] = slam_gate_verdict(gate, Pn, en[0], en[1], en[2], ib + 1);
+                } else if constexpr (G::kOn) {
+                    sPinv[cb ^ 1][9] = slam_gate_verdict(gate, Pn, sZe[3 * ib + 3], sZe[3 * ib + 4], sZe[3 * ib + 5], ib + 1);
+                }
             }
         }
         __syncthreads();
     }
-    // G = A^-1 (block (bi, bj) from its owner), g = G nu
+    // G = A^-1 (block (bi, bj) from its owner), g = G nu (RunningMean: G ze)
     if (act) {
 #pragma unroll
         for (int a = 0; a < 3; a++)
 #pragma unroll
             for (int b = 0; b < 3; b++) E.d_G[(size_t)(3 * bi + a) * kFastN3 + 3 * bj + b] = A[a * 3 + b];   // fixed row stride (k_ekf_apply loads before it knows m)
-        const double n0 = sNu[3 * bj], n1 = sNu[3 * bj + 1], n2 = sNu[3 * bj + 2];
+        const double* zg = C::kOn ? sZe : sNu;
+        const double n0 = zg[3 * bj], n1 = zg[3 * bj + 1], n2 = zg[3 * bj + 2];
 #pragma unroll
         for (int a = 0; a < 3; a++) sPart[bi][bj][a] = A[a * 3] * n0 + A[a * 3 + 1] * n1 + A[a * 3 + 2] * n2;
     }
@@ -1086,8 +1145,10 @@ constexpr int M64T = 512;                // threads of k_ekf_mid64: 8 wavefronts
 constexpr int M64B = (kMidM * kMidM + M64T - 1) / M64T;   // 3x3 blocks per thread (8)
 
 // The fast chain's Gauss-Jordan with up to M64B blocks per thread, dense block index e = tid + M64T k -> (e / m, e % m).
-template <class Src, class G = NoSlamGate>
-static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
+// RunningMean (C) as in k_ekf_mid: gated, the owner of block (ib + 1, ib + 1) applies pivot ib to its own e_{ib+1} in
+// phase 2, from the column block it has loaded and S_ib^-1 = sY[ib] (sPinv is being replaced in that phase), and judges behind it.
+template <class Src, class G = NoSlamGate, class C = FrozenMean>
+static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G, C> arg) {
     const Src& S = arg;
     const G& gate = arg;
     const EkfState E = S.state();
@@ -1188,7 +1249,10 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
                         // the pivot is not eliminated (ekf_slam_gate.h): its block row becomes zero (its column below), nu_ib = 0
 #pragma unroll
                         for (int q = 0; q < 9; q++) A[k][q] = 0.0;
-                        if (bj == ib) sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;   // its ze may be NaN
+                        if (bj == ib) {                                                        // its ze may be NaN
+                            if constexpr (C::kOn) sZe[3 * ib] = sZe[3 * ib + 1] = sZe[3 * ib + 2] = 0.0;
+                            else sNu[3 * ib] = sNu[3 * ib + 1] = sNu[3 * ib + 2] = 0.0;
+                        }
                     } else if (bj == ib) {
 #pragma unroll
                         for (int q = 0; q < 9; q++) A[k][q] = Pi[q];
@@ -1223,10 +1287,27 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
 #pragma unroll
                             for (int j = 0; j < 3; j++)
                                 A[k][i * 3 + j] = fma(-F[i * 3 + 2], Y[6 + j], fma(-F[i * 3 + 1], Y[3 + j], fma(-F[i * 3], Y[j], A[k][i * 3 + j])));
-                        if (bj == ib && bi > ib) {
-                            const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
+                        if constexpr (!C::kOn) {
+                            if (bj == ib && bi > ib) {
+                                const double z0 = sZe[3 * ib], z1 = sZe[3 * ib + 1], z2 = sZe[3 * ib + 2];
 #pragma unroll
-                            for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[k][a * 3] * z0 + A[k][a * 3 + 1] * z1 + A[k][a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                                for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= A[k][a * 3] * z0 + A[k][a * 3 + 1] * z1 + A[k][a * 3 + 2] * z2;   // nu += (H K) ze, H K = -A
+                            }
+                        } else if constexpr (G::kOn) {
+                            // e_bi -= (H_bi K_ib) e_ib; e_ib is final since step ib - 1.  Row ib + 1 is its diagonal owner's
+                            const double z0 = sNu[3 * ib], z1 = sNu[3 * ib + 1], z2 = sNu[3 * ib + 2];
+                            if (bj == ib && bi > ib + 1) {
+#pragma unroll
+                                for (int a = 0; a < 3; a++) sNu[3 * bi + a] += A[k][a * 3] * z0 + A[k][a * 3 + 1] * z1 + A[k][a * 3 + 2] * z2;   // H K = -A
+                            }
+                            if (bi == ib + 1 && bj == ib + 1) {
+                                double Pi[9], HK[9];
+#pragma unroll
+                                for (int q = 0; q < 9; q++) Pi[q] = sY[ib][q];
+                                mul3(F, Pi, HK);                                 // F = A(ib + 1, ib) as published, H K = F S_ib^-1
+#pragma unroll
+                                for (int a = 0; a < 3; a++) sNu[3 * bi + a] -= HK[a * 3] * z0 + HK[a * 3 + 1] * z1 + HK[a * 3 + 2] * z2;
+                            }
                         }
                     }
                     if (bj == ib + 1) { for (int q = 0; q < 9; q++) sCol[cb ^ 1][bi][q] = A[k][q]; }
@@ -1235,7 +1316,10 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
                         inv3_reg(A[k], Pn);
 #pragma unroll
                         for (int q = 0; q < 9; q++) sPinv[q] = Pn[q];
-                        if constexpr (G::kOn) *sVerdict = slam_gate_verdict(gate, Pn, sZe[3 * ib + 3], sZe[3 * ib + 4], sZe[3 * ib + 5], ib + 1);
+                        if constexpr (G::kOn) {
+                            const double* zj = C::kOn ? sNu : sZe;            // RunningMean: e_{ib+1}, completed by this thread just above
+                            *sVerdict = slam_gate_verdict(gate, Pn, zj[3 * ib + 3], zj[3 * ib + 4], zj[3 * ib + 5], ib + 1);
+                        }
                     }
                 }
             }
@@ -1250,7 +1334,8 @@ static __global__ __launch_bounds__(M64T) void k_ekf_mid64(Solve<Src, G> arg) {
             for (int a = 0; a < 3; a++)
 #pragma unroll
                 for (int c = 0; c < 3; c++) E.d_G[(size_t)(3 * bi + a) * n3 + 3 * bj + c] = A[k][a * 3 + c];
-            const double n0 = sNu[3 * bj], n1 = sNu[3 * bj + 1], n2 = sNu[3 * bj + 2];
+            const double* zg = C::kOn ? sZe : sNu;
+            const double n0 = zg[3 * bj], n1 = zg[3 * bj + 1], n2 = zg[3 * bj + 2];
 #pragma unroll
             for (int a = 0; a < 3; a++) sPart[bi][bj][a] = A[k][a * 3] * n0 + A[k][a * 3 + 1] * n1 + A[k][a * 3 + 2] * n2;
         }
@@ -1464,9 +1549,19 @@ void launch_ekf_gather(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_gather<EkfSingle>, dim3((E.ld + 255) / 256, 32), dim3(256), 0, st, EkfSingle{E});
 }
 static SlamGate slam_gate_of(const SlamGateArg& a) { return SlamGate{a.g.gate_d2, a.verdicts}; }
-void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
-    if (gate) hipLaunchKernelGGL((k_ekf_small<EkfSingle, SlamGate>), dim3(1), dim3(SMT), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_small<EkfSingle, NoSlamGate>), dim3(1), dim3(SMT), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
+// a solve kernel's four instantiations on one state source: gate x innovation policy (consistent: RunningMean)
+#define ASLAM_LAUNCH_SOLVE(kernel, SrcT, src, grid, block)                                                                                          \
+    do {                                                                                                                                           \
+        if (consistent) {                                                                                                                          \
+            if (gate) hipLaunchKernelGGL((kernel<SrcT, SlamGate, RunningMean>), grid, block, 0, st, Solve<SrcT, SlamGate, RunningMean>{src, slam_gate_of(*gate), {}});   \
+            else hipLaunchKernelGGL((kernel<SrcT, NoSlamGate, RunningMean>), grid, block, 0, st, Solve<SrcT, NoSlamGate, RunningMean>{src, NoSlamGate{}, {}});           \
+        } else {                                                                                                                                   \
+            if (gate) hipLaunchKernelGGL((kernel<SrcT, SlamGate>), grid, block, 0, st, Solve<SrcT, SlamGate>{src, slam_gate_of(*gate)});             \
+            else hipLaunchKernelGGL((kernel<SrcT, NoSlamGate>), grid, block, 0, st, Solve<SrcT, NoSlamGate>{src, NoSlamGate{}});                     \
+        }                                                                                                                                          \
+    } while (0)
+void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
+    ASLAM_LAUNCH_SOLVE(k_ekf_small, EkfSingle, EkfSingle{E}, dim3(1), dim3(SMT));
 }
 void launch_ekf_gate_finish(hipStream_t st, const EkfState& E, const SlamGateArg& gate, int slot) {
     hipLaunchKernelGGL(k_ekf_gate_finish<EkfSingle>, dim3(1), dim3(kMarkerMax), 0, st, EkfSingle{E}, slam_gate_of(gate), gate.g, slot);
@@ -1474,10 +1569,9 @@ void launch_ekf_gate_finish(hipStream_t st, const EkfState& E, const SlamGateArg
 void launch_ekf_T(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_T<EkfSingle>, dim3((E.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR), dim3(256), 0, st, EkfSingle{E});
 }
-void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
+void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
     const int ncg = (E.ld + MIDT - 1) / MIDT;
-    if (gate) hipLaunchKernelGGL((k_ekf_mid<EkfSingle, SlamGate>), dim3(1 + ncg * 12), dim3(MIDT), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_mid<EkfSingle, NoSlamGate>), dim3(1 + ncg * 12), dim3(MIDT), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
+    ASLAM_LAUNCH_SOLVE(k_ekf_mid, EkfSingle, EkfSingle{E}, dim3(1 + ncg * 12), dim3(MIDT));
 }
 void launch_ekf_apply(hipStream_t st, const EkfState& E) {
     const int t = (E.ld + 63) / 64;
@@ -1485,10 +1579,9 @@ void launch_ekf_apply(hipStream_t st, const EkfState& E) {
 }
 int ekf_fast_max_updates() { return kFastM; }
 int ekf_mid_max_updates() { return kMidM; }
-void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate) {
+void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
     const int ncg = (E.ld + M64T - 1) / M64T;
-    if (gate) hipLaunchKernelGGL((k_ekf_mid64<EkfSingle, SlamGate>), dim3(1 + ncg * 16), dim3(M64T), 0, st, Solve<EkfSingle, SlamGate>{EkfSingle{E}, slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_mid64<EkfSingle, NoSlamGate>), dim3(1 + ncg * 16), dim3(M64T), 0, st, Solve<EkfSingle, NoSlamGate>{EkfSingle{E}, NoSlamGate{}});
+    ASLAM_LAUNCH_SOLVE(k_ekf_mid64, EkfSingle, EkfSingle{E}, dim3(1 + ncg * 16), dim3(M64T));
 }
 // the narrowest tile whose workgroups all fit on the device at once (256 CUs x 4); N_max stands in for the current N
 static bool update_tile4(const EkfState& E) {
@@ -1569,9 +1662,8 @@ void launch_ekf_plan(hipStream_t st, const FleetRound& R, const SlamParams& sp, 
 void launch_ekf_gather(hipStream_t st, const FleetRound& R) {
     hipLaunchKernelGGL(k_ekf_gather<EkfFleet>, dim3((R.F.base.ld + 255) / 256, 32, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
-    if (gate) hipLaunchKernelGGL((k_ekf_small<EkfFleet, SlamGate>), dim3(1, 1, R.n), dim3(SMT), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_small<EkfFleet, NoSlamGate>), dim3(1, 1, R.n), dim3(SMT), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
+void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
+    ASLAM_LAUNCH_SOLVE(k_ekf_small, EkfFleet, fleet_source(R), dim3(1, 1, R.n), dim3(SMT));
 }
 void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateArg& gate, int) {
     hipLaunchKernelGGL(k_ekf_gate_finish<EkfFleet>, dim3(1, 1, R.n), dim3(kMarkerMax), 0, st, fleet_source(R), slam_gate_of(gate), gate.g, 0);
@@ -1579,19 +1671,17 @@ void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateA
 void launch_ekf_T(hipStream_t st, const FleetRound& R) {
     hipLaunchKernelGGL(k_ekf_T<EkfFleet>, dim3((R.F.base.ld + TC - 1) / TC, (3 * kMarkerMax + TR - 1) / TR, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
+void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
     const int ncg = (R.F.base.ld + MIDT - 1) / MIDT;
-    if (gate) hipLaunchKernelGGL((k_ekf_mid<EkfFleet, SlamGate>), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_mid<EkfFleet, NoSlamGate>), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
+    ASLAM_LAUNCH_SOLVE(k_ekf_mid, EkfFleet, fleet_source(R), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT));
 }
 void launch_ekf_apply(hipStream_t st, const FleetRound& R) {
     const int t = (R.F.base.ld + 63) / 64;
     hipLaunchKernelGGL(k_ekf_apply<EkfFleet>, dim3(t, t, R.n), dim3(256), 0, st, fleet_source(R));
 }
-void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate) {
+void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
     const int ncg = (R.F.base.ld + M64T - 1) / M64T;
-    if (gate) hipLaunchKernelGGL((k_ekf_mid64<EkfFleet, SlamGate>), dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, Solve<EkfFleet, SlamGate>{fleet_source(R), slam_gate_of(*gate)});
-    else hipLaunchKernelGGL((k_ekf_mid64<EkfFleet, NoSlamGate>), dim3(1 + ncg * 16, 1, R.n), dim3(M64T), 0, st, Solve<EkfFleet, NoSlamGate>{fleet_source(R), NoSlamGate{}});
+    ASLAM_LAUNCH_SOLVE(k_ekf_mid64, EkfFleet, fleet_source(R), dim3(1 + ncg * 16, 1, R.n), dim3(M64T));
 }
 void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
     const EkfState& E = R.F.base;                  // the single filter's tile choice: the same grid per robot

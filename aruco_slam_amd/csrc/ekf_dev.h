@@ -53,6 +53,12 @@ __device__ __forceinline__ double aslam_rcp_estimate(double x) { return ASLAM_RC
 
 typedef double v4d __attribute__((vector_size(4 * sizeof(double))));   // accumulator of v_mfma_f64_16x16x4_f64
 
+// Innovation policy of the per-frame chains and the localization steps (include/aruco_slam_hip.h).  FrozenMean, the
+// default, is the reference (quirk Q1): every correction of a frame adds K ze with ze formed at the frame's predicted mean.  RunningMean
+// corrects from the mean the previous correction left, e_i = ze_i - H_i (mu_{i-1} - mu_0): the exact linear sequential update.
+struct FrozenMean { static constexpr bool kOn = false; };
+struct RunningMean { static constexpr bool kOn = true; };
+
 __device__ __forceinline__ void wrap1(double& a) {      // ArucoSlam::normAngle (aruco_slam.cpp:412-421): wraps once
     const double PI = 3.14159265358979323846;
     if (a >= PI) a -= 2.0 * PI;

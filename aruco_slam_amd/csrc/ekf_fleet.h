@@ -83,8 +83,59 @@ __global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_gated(EkfState 
     loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
 }
 
+// the same four with consistent innovations: a robot's workgroup is the single filter's RunningMean body
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_ci(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                              const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                              const int* __restrict__ work, int n_groups) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps<LocFleet, NoGate, FixedMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc);
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_ci_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                    const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                    const int* __restrict__ work, int n_groups, GateState g) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps<LocFleet, Gated, FixedMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_ci(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                   const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                   const int* __restrict__ work, int n_groups, MapCov mc) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps<LocFleet, NoGate, UncertainMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, NoGate{},
+                                                           UncertainMap{mc});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_ci_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                         const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                         const int* __restrict__ work, int n_groups, GateState g, MapCov mc) {
+    const int* h = work + 4 * blockIdx.x;
+    loc_steps<LocFleet, Gated, UncertainMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g},
+                                                          UncertainMap{mc});
+}
+
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
-                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate, const MapCov* umap) {
+                        const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate, const MapCov* umap,
+                        bool consistent) {
+    if (consistent) {                // the RunningMean kernels, the same launches otherwise
+        if (umap) {
+            static bool allowed[2] = {false, false};
+            const size_t dyn = umap_lds_bytes(umap->L);
+            if (gate) {
+                umap_allow_lds(k_fleet_steps_umap_ci_gated, allowed[1]);
+                hipLaunchKernelGGL(k_fleet_steps_umap_ci_gated, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate, *umap);
+            } else {
+                umap_allow_lds(k_fleet_steps_umap_ci, allowed[0]);
+                hipLaunchKernelGGL(k_fleet_steps_umap_ci, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *umap);
+            }
+            return;
+        }
+        if (gate)
+            hipLaunchKernelGGL(k_fleet_steps_ci_gated, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate);
+        else
+            hipLaunchKernelGGL(k_fleet_steps_ci, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups);
+        return;
+    }
     if (umap) {
         static bool allowed[2] = {false, false};
         const size_t dyn = umap_lds_bytes(umap->L);

@@ -27,6 +27,13 @@
 // S, K and the decision from the six columns it needs (pose block and block i), updates those six itself and publishes K and the
 // fuse flag; behind one barrier every lane subtracts K (Hx X[:, j]) from its own columns, behind a second one the chain goes on.  A
 // rejected correction costs the first barrier only.
+//
+// loc_steps<Src, G, M, C> takes a compile-time innovation policy C (include/aruco_slam_hip.h).  FrozenMean, the
+// default, is the reference's chain (quirk Q1): every correction adds K ze with ze formed at the frame's predicted mean.
+// RunningMean (k_loc_steps_ci[_gated], k_loc_steps_umap_ci[_gated], k_fleet_steps_*_ci*) corrects from the mean the previous
+// correction left: lane 0 forms e = ze - H (mu_x - sPose), a plain difference with no angle wrap, where H is the pose part of the
+// Jacobian (on an uncertain map the landmarks are not estimated), judges the correction by e and adds K e.  S, K, the covariance
+// update and ref_flagged (the reference's logged test on ze) are untouched.  Every new statement sits under `if constexpr (C::kOn)`.
 #pragma once
 #include "common.h"
 #include "ekf.h"
@@ -96,7 +103,7 @@ struct UncertainMap {
     MapCov m;
 };
 
-template <class Src, class G = NoGate, class M = FixedMap>
+template <class Src, class G = NoGate, class M = FixedMap, class C = FrozenMean>
 __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
                                           const double* enc, const G& gate = G{}, const M& umap = M{}) {
     __shared__ LastObs sLast[kMarkerMax];       // last_observed_marker_ of the previous step
@@ -384,15 +391,26 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
                     }
                     inv3_reg(S, Si);
                     mul3(PHt, Si, K);                                        // K_x = P H^T S^-1
+                    // the innovation the correction is judged by and applied with: ze, or e = ze - H (mu_x - mu_0) at the running mean
+                    [[maybe_unused]] double e0, e1, e2;
+                    if constexpr (C::kOn) {
+                        const double dx = mx - sPose[0], dy = my - sPose[1], dth = mt - sPose[2];
+                        e0 = cr.ze[0] - (H[0] * dx + H[1] * dy + H[2] * dth);
+                        e1 = cr.ze[1] - (H[3] * dx + H[4] * dy + H[5] * dth);
+                        e2 = cr.ze[2] - (H[6] * dx + H[7] * dy + H[8] * dth);
+                    }
                     bool fuse = true;
                     if constexpr (G::kOn) {
-                        const double z0 = cr.ze[0], z1 = cr.ze[1], z2 = cr.ze[2];
+                        const double z0 = C::kOn ? e0 : cr.ze[0], z1 = C::kOn ? e1 : cr.ze[1], z2 = C::kOn ? e2 : cr.ze[2];
                         const double d2 = z0 * (Si[0] * z0 + Si[1] * z1 + Si[2] * z2) + z1 * (Si[3] * z0 + Si[4] * z1 + Si[5] * z2) +
                                           z2 * (Si[6] * z0 + Si[7] * z1 + Si[8] * z2);            // ze^T S^-1 ze
                         double kk = 0.0;
 #pragma unroll
                         for (int i = 0; i < 9; i++) kk += K[i] * K[i];
-                        hFlag += (sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;   // aruco_slam.cpp:156
+                        if constexpr (C::kOn)                                    // the reference's logged test stays on ze
+                            hFlag += (sqrt(cr.ze[0] * cr.ze[0] + cr.ze[1] * cr.ze[1] + cr.ze[2] * cr.ze[2]) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;
+                        else
+                            hFlag += (sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 || sqrt(kk) >= 10.0) ? 1 : 0;   // aruco_slam.cpp:156
                         const int pop = sCorrPop[q];
                         if (d2 == d2 && (!hHave || d2 > hMax)) { hHave = true; hMax = d2; hWorst = sLast[pop].id; }
                         if (gate.g.gate_d2 < HUGE_VAL && !(d2 <= gate.g.gate_d2)) {       // a NaN d2 rejects
@@ -405,9 +423,15 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
                         }
                     }
                     if (fuse) {
-                        mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
-                        my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
-                        mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
+                        if constexpr (C::kOn) {
+                            mx += K[0] * e0 + K[1] * e1 + K[2] * e2;
+                            my += K[3] * e0 + K[4] * e1 + K[5] * e2;
+                            mt += K[6] * e0 + K[7] * e1 + K[8] * e2;
+                        } else {
+                            mx += K[0] * cr.ze[0] + K[1] * cr.ze[1] + K[2] * cr.ze[2];
+                            my += K[3] * cr.ze[0] + K[4] * cr.ze[1] + K[5] * cr.ze[2];
+                            mt += K[6] * cr.ze[0] + K[7] * cr.ze[1] + K[8] * cr.ze[2];
+                        }
                         if constexpr (M::kOn) {
                             // X <- X - K cst on the six columns lane 0 holds: Sigma_xx in registers, block i in place (no other
                             // lane reads or writes block i's columns during this correction)
@@ -538,6 +562,31 @@ __global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_gated(EkfState E,
     loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
 }
 
+// the same four with consistent innovations: every correction is formed at the mean the previous one left
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_ci(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                            const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                            int first, int count, int predict_first) {
+    loc_steps<LocSingle, NoGate, FixedMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc);
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_ci_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                  const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                  int first, int count, int predict_first, GateState g) {
+    loc_steps<LocSingle, Gated, FixedMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_ci(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                 const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                 int first, int count, int predict_first, MapCov mc) {
+    loc_steps<LocSingle, NoGate, UncertainMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
+}
+
+__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_ci_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
+                                                                       const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
+                                                                       int first, int count, int predict_first, GateState g, MapCov mc) {
+    loc_steps<LocSingle, Gated, UncertainMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
+}
+
 // Sigma_xl := 0 of the single filter (rows 0..2 and their mirror in columns 0..2): what a seat of its pose does on an uncertain map
 __global__ void k_umap_clear_cross(EkfState E, int L) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -562,7 +611,26 @@ template <class Kern> void umap_allow_lds(Kern kernel, bool& done) {
 }
 
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
-                      const double* enc, int first, int count, int predict_first, const GateState* gate, const MapCov* umap) {
+                      const double* enc, int first, int count, int predict_first, const GateState* gate, const MapCov* umap, bool consistent) {
+    if (consistent) {                // the RunningMean kernels, the same launches otherwise
+        if (umap) {
+            static bool allowed[2] = {false, false};
+            const size_t dyn = umap_lds_bytes(umap->L);
+            if (gate) {
+                umap_allow_lds(k_loc_steps_umap_ci_gated, allowed[1]);
+                hipLaunchKernelGGL(k_loc_steps_umap_ci_gated, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate, *umap);
+            } else {
+                umap_allow_lds(k_loc_steps_umap_ci, allowed[0]);
+                hipLaunchKernelGGL(k_loc_steps_umap_ci, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *umap);
+            }
+            return;
+        }
+        if (gate)
+            hipLaunchKernelGGL(k_loc_steps_ci_gated, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate);
+        else
+            hipLaunchKernelGGL(k_loc_steps_ci, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
+        return;
+    }
     if (umap) {
         static bool allowed[2] = {false, false};
         const size_t dyn = umap_lds_bytes(umap->L);

@@ -13,6 +13,7 @@
 //               them into the pop list's actions, the compacted last-observed list, the slot record and the track record.
 #pragma once
 #include "ekf.h"
+#include "ekf_dev.h"
 #include "ekf_fleet_slam.h"
 #include <cmath>
 
@@ -29,7 +30,11 @@ struct SlamGate {
 // What a solve kernel takes: its state source and its gate policy as the two bases of one struct.  NoSlamGate is an empty base, so an
 // ungated kernel's argument has the bytes of Src alone (an empty struct passed beside Src would take a slot of its own and move the
 // hidden arguments behind it: the kernels would no longer be instruction for instruction the ungated ones).
-template <class Src, class G> struct Solve : Src, G {};
+// The innovation policy C (FrozenMean / RunningMean, ekf_dev.h) is a third base, empty in both its forms: the argument
+// bytes of every instantiation are those of Src and G.  With RunningMean the solve carries the running innovation e_r -= (H_r K_i) e_i
+// through the sweep where the gate needs it (the multiplier is the block the sweep already forms), judges pivot i by e_i and emits
+// g = G ze (rejected entries masked), which is sum_i gamma_i e_i: G, and with it Sigma, keep their bits.
+template <class Src, class G, class C = FrozenMean> struct Solve : Src, G, C {};
 
 __device__ __forceinline__ bool slam_gate_rejects(const SlamGate& g, double d2) {
     return g.gate_d2 < HUGE_VAL && !(d2 <= g.gate_d2);                         // a NaN d2 rejects

@@ -833,6 +833,31 @@ int aslam_set_observation_covariance(aslam_ctx* ctx, const aslam_obs_covariance_
 int aslam_get_observation_covariance(aslam_ctx* ctx, int* on, aslam_obs_covariance_params* out);
 int aslam_get_slot_obs_covariance(aslam_ctx* ctx, int slot, int max, int* n, aslam_obs_covariance* out, aslam_slot_obs_covariance* sum);
 
+/* ---- consistent innovations: correct from the mean the previous correction left (no reference counterpart) -----------
+ * The reference forms all innovations of a frame at the frame's predicted mean mu_0 (quirk Q1) and then applies the m corrections one
+ * after the other, each adding K_i ze_i.  With an honest R (aslam_set_observation_covariance) a frame of m sightings then moves the
+ * mean by about H_m = 1 + 1/2 + ... + 1/m innovations instead of one, and every d2 the gates compute is inflated with it.
+ * Switch.  aslam_set_consistent_innovations(ctx, on), on = 0 or 1.  Off by default, settable in any mode, kept across
+ * aslam_localize_begin / _end and the fleet begins and ends.  With the switch off, no launch, kernel or result differs from today.
+ * Semantics.  In pop order, correction i with the reference's ze_i and H_i, both formed at mu_0 exactly as today:
+ *     e_i = ze_i - H_i (mu_{i-1} - mu_0)        mu_i = mu_{i-1} + K_i e_i
+ * The difference is plain (no angle wrap, and e_i's third component is not wrapped again).  S_i, K_i and the covariance update do not
+ * depend on the innovation and keep their bits.  A rejected correction contributes nothing to mu.  This is the exact linear sequential
+ * update: the mean equals the joint update mu_0 + Sigma_0 H^T (H Sigma_0 H^T + blockdiag R)^-1 ze over the accepted corrections.
+ * On an uncertain map the landmarks are not estimated, so only the pose columns of H_i enter.
+ * Gates.  Everything that judges a correction uses e_i: d2, the verdict, nis_sum, d2_max and worst_id, in the innovation gate of
+ * localization and fleets and in the SLAM gate.  ref_flagged stays the reference's logged test on ze_i (and on K where the chain forms
+ * it): the record of what the reference would have logged.
+ * Where it runs.  The localization steps (single and fleet, fixed and uncertain map, gated or not) and the per-frame SLAM chains
+ * (single, rig and fleet SLAM, every chain size, gated or not), each in an instantiation of its own beside the existing kernels.
+ * Dropped.  Relinearisation: H_i stays the Jacobian at mu_0, one meaning for every chain.  EKF windows: while the switch is on,
+ * aslam_run_staged and the host-fed stream plan no windows, gated windows included, and every frame takes the per-frame chain
+ * (aslam_get_plan_stats shows it); the window chain keeps the reference's frozen-mean corrections.
+ * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
+ * pending batch and synchronises, as the other setters do. */
+int aslam_set_consistent_innovations(aslam_ctx* ctx, int on);
+int aslam_get_consistent_innovations(aslam_ctx* ctx, int* on);
+
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);
 int aslam_load_state(aslam_ctx* ctx, const char* path);
