@@ -231,6 +231,8 @@ _SIGS = {
     "aslam_get_slot_obs_covariance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p]),
     "aslam_set_consistent_innovations": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_get_consistent_innovations": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_set_consistent_windows": (C.c_int, [C.c_void_p, C.c_int]),
+    "aslam_get_consistent_windows": (C.c_int, [C.c_void_p, _ip]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -897,12 +899,23 @@ class Context:
     # -- consistent innovations ---------------------------------------------------------------------------------------
     def set_consistent_innovations(self, on=True):
         """every correction of a frame is formed at the mean the previous one left (e_i = ze_i - H_i (mu_{i-1} - mu_0)); off: the
-        reference's frozen-mean innovations.  While it is on no EKF window is planned."""
+        reference's frozen-mean innovations.  While it is on no EKF window is planned unless set_consistent_windows is on too."""
         self._ck(self.lib.aslam_set_consistent_innovations(self.h, int(bool(on))))
 
     def get_consistent_innovations(self):
         on = C.c_int()
         self._ck(self.lib.aslam_get_consistent_innovations(self.h, C.byref(on)))
+        return bool(on.value)
+
+    # -- consistent innovations inside EKF windows (DESIGN.md §33) ------------------------------------------------------------------
+    def set_consistent_windows(self, on=True):
+        """while consistent innovations are on, plan EKF windows again: the window chain corrects its mean with the running
+        innovation.  Off by default; changes nothing while consistent innovations are off."""
+        self._ck(self.lib.aslam_set_consistent_windows(self.h, int(bool(on))))
+
+    def get_consistent_windows(self):
+        on = C.c_int()
+        self._ck(self.lib.aslam_get_consistent_windows(self.h, C.byref(on)))
         return bool(on.value)
 
     def get_slot_health(self, first, count):

@@ -201,6 +201,9 @@ struct aslam_ctx {
     // consistent innovations (aslam_set_consistent_innovations): off unless set, kept across mode changes.  Every
     // per-frame solve and every localization step then runs in its RunningMean instantiation, and aslam_run_staged plans no windows.
     bool consistent_on = false;
+    // consistent windows (aslam_set_consistent_windows): off unless set, kept across mode changes.  With it and
+    // consistent_on both set, windows are planned again and their chain runs in its RunningMean instantiation (consistent_windows below)
+    bool consistent_windows = false;
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -1150,6 +1153,11 @@ int read_mirror(aslam_ctx* c) {
 
 namespace {
 bool gated_windows(const aslam_ctx* c) { return c->slam_gate_on && c->slam_gate_windows && c->win_enabled && !c->win_pieces; }
+// consistent innovations inside windows: the one-launch window with the mean on the logger wave, ungated.  A gated
+// context keeps the per-frame path while consistent innovations are on (the gated consistent window is not built)
+bool consistent_windows(const aslam_ctx* c) {
+    return c->consistent_on && c->consistent_windows && c->win_enabled && !c->win_pieces && c->win_logger_parts == 3 && !c->slam_gate_on;
+}
 
 hipEvent_t new_win_event(aslam_ctx* c) { return c->ev_win[c->ev_win_next++ & 63]; }
 
@@ -1186,7 +1194,8 @@ void enqueue_window_one(aslam_ctx* c, const WinOp& o, const WinDesc& wd) {
     cw.nsteps = win_steps(c, o.frame, o.K);
     prof_begin(c, P_EKF_WIN_CHAIN, sa);
     const bool gated = gated_windows(c);
-    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts, c->win_worker_publish);
+    launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts, c->win_worker_publish,
+                       consistent_windows(c));
     prof_end(c);
     if (gated) {                                                     // verdicts into records, counts, actions and the last-observed list
         prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
@@ -1337,8 +1346,9 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         note_ekf_range(c, first, count);
         return ASLAM_OK;
     }
-    // consistent innovations: the window chain forms the reference's frozen-mean corrections only, so no window is planned
-    if (!c->win_enabled || c->consistent_on || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
+    // consistent innovations: the window chain's default form makes the reference's frozen-mean corrections, so no window
+    // is planned unless the consistent window is switched on and can run
+    if (!c->win_enabled || (c->consistent_on && !consistent_windows(c)) || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
         // the SLAM gate: the window planner runs the "stationary" test on the host from a mirror of the last-observed
@@ -3304,6 +3314,22 @@ int aslam_set_consistent_innovations(aslam_ctx* c, int on) {
 int aslam_get_consistent_innovations(aslam_ctx* c, int* on) {
     if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
     *on = c->consistent_on ? 1 : 0;
+    return ASLAM_OK;
+}
+
+// Consistent innovations inside EKF windows: one switch per context, in any mode, kept across mode changes
+int aslam_set_consistent_windows(aslam_ctx* c, int on) {
+    if (!c) return ASLAM_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, ASLAM_E_INVALID, "on: 0 or 1");
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    c->consistent_windows = on == 1;
+    return ASLAM_OK;
+}
+
+int aslam_get_consistent_windows(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->consistent_windows ? 1 : 0;
     return ASLAM_OK;
 }
 

@@ -103,6 +103,18 @@ enum { WH_TYPE = 0, WH_POS = 1, WH_SI = 2, WH_ZE = 11, WH_C = 14, WH_S = 15, WH_
 struct WinGate { static constexpr bool kOn = true; double gate_d2; };
 template <class G> struct WinArg : WinDesc, G {};
 static_assert(sizeof(WinArg<NoSlamGate>) == sizeof(WinDesc), "the ungated window argument is the window descriptor alone");
+// Consistent window (aslam_set_consistent_windows): the one-launch step kernel is also a template on the innovation
+// policy of ekf_dev.h.  FrozenMean is the default; every RunningMean statement sits under `if constexpr`.  RunningMean corrects the
+// mean with e = ze - H (mu_{j-1} - mu_0), mu_0 the frame's predicted mean, H as the chain writes it (Gxm below), no angle wrap.  The
+// two waves that carry a copy of the mean (logger: every step; prepare: a frame's last correction, at the next predict) form e with
+// this one function from the same six differences, so that both copies keep the same bits.  d: mu_{j-1} - mu_0 at columns 0, 1, 2 and
+// lrow .. lrow + 2; ze comes in and e goes out in e0, e1, e2.
+__device__ __forceinline__ void win_running_innovation(double cth, double sth, double g02, double g12, const double (&d)[6], double& e0, double& e1,
+                                                       double& e2) {
+    e0 = e0 - ((-cth * d[0] - sth * d[1] + g02 * d[2]) + (cth * d[3] + sth * d[4]));
+    e1 = e1 - ((sth * d[0] - cth * d[1] + g12 * d[2]) + (-sth * d[3] + cth * d[4]));
+    e2 = e2 - (d[5] - d[2]);
+}
 // d_win_small: images of the window, each SPm x SPm at most (SPm = E.win_sp_max), stored with the window's own row stride SP
 __host__ __device__ inline size_t wsm_P(int SPm, int par) { return (size_t)par * SPm * SPm; }             // P image of window parity par
 __host__ __device__ inline size_t wsm_LAM(int SPm, int par) { return (size_t)(2 + par) * SPm * SPm; }      // Lambda / Psi / psi: also per parity (the flush of a
@@ -291,11 +303,13 @@ template <bool GATED, class LDS> __device__ __forceinline__ double win_header_en
 //   bit 1  the step table's entry a phase ahead: sPos[j + 3] is read with phase j's B operand and kept in a register, so that no
 //          LDS round trip stands between the MFMAs and the publication's switch (the step tables never change inside a window).
 // The prepare wave's steps and the values it reads do not depend on WP, and no floating-point operation moves.
-template <int T, int RW, bool ONE, class G, int LG, int WP>
+// IN: the innovation policy (FrozenMean, or RunningMean: the consistent window of DESIGN.md §33, beside LG = 3 and the ungated form only).
+template <int T, int RW, bool ONE, class G, int LG, int WP, class IN = FrozenMean>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const G& gate, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     static_assert(ONE || !G::kOn, "only the one-launch window is gated");
     static_assert(ONE || LG == 0, "the piece schedule has no logger wave");
+    static_assert(!IN::kOn || (ONE && LG == 3 && !G::kOn), "the consistent window: one launch, the mean on the logger wave, ungated");
     constexpr bool LSI = (LG & 1) != 0, LMU = (LG & 2) != 0;
     constexpr bool PK = (WP & 1) != 0, AHEAD = (WP & 2) != 0;
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
@@ -517,6 +531,11 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
         //        j's update itself.  Two parities: with two predicts in a row this wave writes in the phase the prepare wave reads in.
         double* const muimg = E.d_win_small + wsm_MU(E.win_sp_max, wd.wpar);
         double lmu[NC];
+        double lmu0[IN::kOn ? NC : 1];                             // RunningMean: the frame's predicted mean mu_0, snapshot at its predict
+        if constexpr (IN::kOn) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) lmu0[c] = 0.0;
+        }
         ASLAM_LDS_BARRIER();                                       // (pairs with the workers' barrier after their first publish)
         if constexpr (LMU) {
 #pragma unroll
@@ -583,10 +602,20 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #pragma unroll
                     for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, av[k][c]);
                 if (!corr) { lcth = hC; lsth = hS; }
+                if constexpr (IN::kOn) {
+                    // ---- e = ze - H (mu_{j-1} - mu_0): six columns of this wave's own mean, by wave-uniform cross-lane reads ----
+                    double dl[NC], d[6];
+#pragma unroll
+                    for (int c = 0; c < NC; c++) dl[c] = lmu[c] - lmu0[c];
+#pragma unroll
+                    for (int q = 0; q < 3; q++) { d[q] = bcast_sel<NC>(dl, q); d[3 + q] = bcast_sel<NC>(dl, lrow + q); }
+                    win_running_innovation(lcth, lsth, g02, g12, d, ze0, ze1, ze2);
+                }
                 // ---- the header entry of this lane (win_header_entry) ----
                 double hv = hb;
                 if (corr) {
                     if (hq >= 0) hv = hr;
+                    if constexpr (IN::kOn) hv = hq == 0 ? ze0 : hq == 1 ? ze1 : hq == 2 ? ze2 : hv;   // WH_ZE carries e: the replay's psi follows
                     if (!G::kOn && lane == WH_TYPE) hv = 1.0;
                     if (lane == WH_POS) hv = (double)pos;
                 }
@@ -627,6 +656,12 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                         lmu[c] = upd ? lmu[c] + dm : lmu[c];
                     }
                     if (!corr && lane < 3) lmu[0] = pose;              // a predict: the pose it leaves
+                    if constexpr (IN::kOn) {
+                        if (!corr) {
+#pragma unroll
+                            for (int c = 0; c < NC; c++) lmu0[c] = lmu[c];
+                        }
+                    }
                 }
             }
             if constexpr (LMU) {
@@ -775,7 +810,15 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                             if (lane == 1) mu[0] = pn1;
                             if (lane == 2) mu[0] = pth;
                         } else if (!prev_rejected) {                // (step j was the last correction of its frame: fm - 1)
-                            const double ze0 = ASLAM_WAVE_BCAST(rze0, fm - 1), ze1 = ASLAM_WAVE_BCAST(rze1, fm - 1), ze2 = ASLAM_WAVE_BCAST(rze2, fm - 1);
+                            double ze0 = ASLAM_WAVE_BCAST(rze0, fm - 1), ze1 = ASLAM_WAVE_BCAST(rze1, fm - 1), ze2 = ASLAM_WAVE_BCAST(rze2, fm - 1);
+                            if constexpr (IN::kOn) {
+                                // e of that correction, as the logger wave forms it: mu_{j-1} is the row the logger left (loaded above),
+                                // mu_0 the pose this wave predicted for the frame and the landmark means it left in sMu at that predict
+                                const int lr = 3 + 3 * ASLAM_WAVE_BCAST(vpos, (fm - 1) & 63);
+                                const double* ml = L.sMuL[nb];
+                                const double d[6] = {ml[0] - pn0, ml[1] - pn1, ml[2] - pth, ml[lr] - sMu[lr], ml[lr + 1] - sMu[lr + 1], ml[lr + 2] - sMu[lr + 2]};
+                                win_running_innovation(cth, sth, ASLAM_WAVE_BCAST(rg02, fm - 1), ASLAM_WAVE_BCAST(rg12, fm - 1), d, ze0, ze1, ze2);
+                            }
 #pragma unroll
                             for (int c = 0; c < NC; c++) {
                                 const double k0 = -sA[pb][0][lane + 64 * c], k1 = -sA[pb][1][lane + 64 * c], k2 = -sA[pb][2][lane + 64 * c];
@@ -1228,7 +1271,7 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
         old = prev;
     }
 }
-template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0, int WP = 0>
+template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0, int WP = 0, class IN = FrozenMean>
 __global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
 void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
     const WinDesc& wd = wa;
@@ -1242,7 +1285,7 @@ void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinRe
         __syncthreads();
         bx = sTicket;
     }
-    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G, LG, WP>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
+    if (bx == 0) { if (wd.K > 0) win_chain_role<T, RW, ONE, G, LG, WP, IN>(E, sp, wd, static_cast<const G&>(wa), obs, enc, smem); }
     else if (bx <= NSCAN) { if (rs.nsteps > 0) win_scan_role<T, ONE, G::kOn>(E, rs, bx - 1, wd.epoch, &sAvail, smem); }
     else if (rq.nsteps > 0) win_psi_role<T, ONE, G::kOn>(E, rq, bx - 1 - NSCAN, wd.epoch, &sAvail);
 }
@@ -1596,12 +1639,12 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 // of the previous window's flush (67 584 bytes) still finds when detection fills every other CU; with 4 KB less room the flush
 // waited for up to a whole window (measured: DESIGN.md).  The chain role's block has grown by kGrown bytes since (the header records);
 // the dynamic part gives them back, so that static + dynamic is what it was measured at.
-template <int T, bool ONE, int LG = 0, int WP = 0, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
+template <int T, bool ONE, int LG = 0, int WP = 0, class IN = FrozenMean, class K, class W> static void launch_step_kernel(K kernel, hipStream_t st, int nb, int nt, size_t static_lds, const EkfState& E, const SlamParams& sp,
                                                 const W& wd, const WinReplay& rs, const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     static const bool share = std::getenv("ASLAM_WIN_SHARE_CU") != nullptr;
     constexpr size_t cap = (size_t)24 * 1024 + WinChainLds<T, ONE>::kGrown;
     const size_t dyn = share ? 0 : (size_t)84 * 1024 - std::min(static_lds, cap);                    // static + dynamic > 80 KB of the 160 KB
-    static bool attr_done = false;                                 // (per instantiation: LG and WP tell kernels of one signature apart)
+    static bool attr_done = false;                                 // (per instantiation: LG, WP and IN tell kernels of one signature apart)
     if (!attr_done && dyn > 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         attr_done = true;
@@ -1631,9 +1674,16 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
 // lg: what the logger wave takes over from the prepare wave (win_chain_role's LG; 0 = the comparison path).  The workers' forms are
 // built beside the default logger only: with another lg the workers publish in their default form
 template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, int wp, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
-                                                                          const ObsRaw* obs, const double* enc) {
+                                                                          const ObsRaw* obs, const double* enc, bool consistent = false) {
     constexpr size_t lds = sizeof(WinChainLds<T, true>);
     constexpr int WD = win_worker_publish_default(T);
+    if constexpr (!G::kOn) {
+        // the consistent window: built beside logger_parts = 3 and the width's default publication only
+        if (consistent) {
+            launch_step_kernel<T, true, 3, WD, RunningMean>(k_ekf_win_step<T, 2, true, G, 3, WD, RunningMean>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+            return;
+        }
+    }
     if (lg == 3) {
         switch (wp < 0 ? WD : wp & kWinWorkerPublishAll) {
 #define ASLAM_WP_LAUNCH(i) case i: launch_step_kernel<T, true, 3, i>(k_ekf_win_step<T, 2, true, G, 3, i>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc); break;
@@ -1647,7 +1697,7 @@ template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStre
 }
 #undef ASLAM_WP_FORMS
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc, const SlamGateArg* gate,
-                        int logger_parts, int worker_publish) {
+                        int logger_parts, int worker_publish, bool consistent) {
     const WinReplay r{0, 0, wd.nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
@@ -1659,9 +1709,9 @@ void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp,
         return;
     }
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
-    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
-    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
+    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
+    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
 }
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
     hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);

@@ -852,11 +852,29 @@ int aslam_get_slot_obs_covariance(aslam_ctx* ctx, int slot, int max, int* n, asl
  * (single, rig and fleet SLAM, every chain size, gated or not), each in an instantiation of its own beside the existing kernels.
  * Dropped.  Relinearisation: H_i stays the Jacobian at mu_0, one meaning for every chain.  EKF windows: while the switch is on,
  * aslam_run_staged and the host-fed stream plan no windows, gated windows included, and every frame takes the per-frame chain
- * (aslam_get_plan_stats shows it); the window chain keeps the reference's frozen-mean corrections.
+ * (aslam_get_plan_stats shows it); the window chain keeps the reference's frozen-mean corrections, unless
+ * aslam_set_consistent_windows (the next section) is on as well.
  * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
  * pending batch and synchronises, as the other setters do. */
 int aslam_set_consistent_innovations(aslam_ctx* ctx, int on);
 int aslam_get_consistent_innovations(aslam_ctx* ctx, int* on);
+
+/* ---- consistent innovations inside EKF windows (no reference counterpart) ------------------------------------------------
+ * While consistent innovations are on, every frame takes the per-frame chain (above).  aslam_set_consistent_windows(ctx, on), on = 0
+ * or 1, lets aslam_run_staged and the host-fed stream plan EKF windows again: the window chain then corrects its mean with the same
+ * e_i = ze_i - H_i (mu_{i-1} - mu_0), the log header carries e_i, so that the means outside the window's set follow, and the
+ * covariance keeps the bits of a frozen-mean window.  aslam_get_plan_stats reports the windows.
+ * Switch.  Off by default, settable in any mode, kept across aslam_localize_begin / _end and the fleet begins and ends.  With
+ * consistent innovations off it changes nothing: the same kernels, the same bits.  With consistent innovations on and this switch off
+ * everything is as described above.
+ * Where it runs.  SLAM and rig SLAM without a SLAM gate, in the one-launch window with the mean on the chain's logger wave (the
+ * defaults; ASLAM_WIN_PIECE or ASLAM_WIN_LOGGER_PARTS other than 3 keep the per-frame chain).  A context with a SLAM gate keeps the
+ * per-frame chain while consistent innovations are on, whatever aslam_set_slam_gate_windows says: the gated consistent window is
+ * not built.  Localization, fleets and fleet SLAM have no windows and do not look at the switch.
+ * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
+ * pending batch and synchronises, as the other setters do. */
+int aslam_set_consistent_windows(aslam_ctx* ctx, int on);
+int aslam_get_consistent_windows(aslam_ctx* ctx, int* on);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);

@@ -1,5 +1,6 @@
 """development aid: the EKF alone (observations injected, no detector) on three scenes - cfg2 panels, cfg2 sliding ring, cfg3 panels -
-per-kernel HIP-event times per frame and the planner's window statistics.  usage: python scripts/ekf_window_timing.py [cfg2 cfg2_sliding cfg3]"""
+per-kernel HIP-event times per frame and the planner's window statistics.  usage: python scripts/ekf_window_timing.py [--consistent]
+[cfg2 cfg2_sliding cfg3]; --consistent: consistent innovations on, inside the windows too"""
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,6 +25,9 @@ def run(name, laps=2):
     lap = w.lap_length()
     ctx = capi.Context(max_rows=64, max_cols=64, max_batch=lap, max_landmarks=w.L + 8, max_updates_per_frame=24 if w.M <= 24 else 64)
     ctx.set_camera(synth.camera_matrix(64, 64, 50.0), np.zeros(5))
+    if CONSISTENT:
+        ctx.set_consistent_innovations(True)
+        ctx.set_consistent_windows(True)
     rng = np.random.RandomState(3)
     frames = [w.frame(i) for i in range(lap)]
     turn = w.frame(lap)
@@ -55,5 +59,6 @@ def run(name, laps=2):
     ctx.close()
 
 
-for nm in (sys.argv[1:] or ["cfg2", "cfg2_sliding", "cfg3"]):
+CONSISTENT = "--consistent" in sys.argv[1:]
+for nm in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["cfg2", "cfg2_sliding", "cfg3"]):
     run(nm)
