@@ -9,14 +9,18 @@ a plain difference with no angle wrap.  d2, the verdict, nis_sum, d2_max and wor
 reference's logged test on ze_i.  joint_mean is the other formulation of the same mean, mu_0 + Sigma_0 H^T (H Sigma_0 H^T +
 blockdiag R)^-1 ze in one solve.  ConsistentLocalizer and ConsistentUmapLocalizer are gate_reference.GatedLocalizer and
 umap_reference.UncertainMapLocalizer with the same change (on an uncertain map only the pose columns of H enter: the landmarks are not
-estimated).  Everything compared with a threshold is kept, so that a test can assert that no decision hangs on rounding."""
+estimated).  ConsistentLiteral is the literal transcription on ready observations (slam_gate_reference.GatedLiteralSlam: double, dense
+literal products, augments, the "stationary" test, the gate, the records) with e_i in place of ze_i, the one literal that builds a map
+with the switch on; ConsistentPlanReference is plan_reference.PlanReference (landmark cap, cap on fused corrections, pop order) on it.
+Everything compared with a threshold is kept, so that a test can assert that no decision hangs on rounding."""
 import math
 
 import numpy as np
 
 from ekf_reference import LD, _inv3, wrap_once
 from oracle.ekf_literal import _Heap, norm_angle
-from slam_gate_reference import new_health, note_correction, rejects
+from plan_reference import PlanReference
+from slam_gate_reference import GatedLiteralSlam, new_health, note_correction, rejects
 from tests.gate_reference import GatedLocalizer
 from tests.umap_reference import UncertainMapLocalizer, inv3
 
@@ -261,3 +265,68 @@ class ConsistentUmapLocalizer(UncertainMapLocalizer):
         self.stats = [len(obs), 0, h["accepted"], nstat]
         self.health = h
         _advance(self.track, h, g)
+
+
+class ConsistentLiteral(GatedLiteralSlam):
+    """GatedLiteralSlam with every correction formed at the running mean: e = ze - Gx (mu - mu_0), mu_0 = the mean at the start of the
+    frame (the `mu` both drivers hand to correct).  d2, the verdict, nis_sum, d2_max and worst_id are formed from e; ref_flagged stays
+    the reference's logged test on ||ze||; a rejected sighting leaves the last-observed list and moves nothing.  No gate (or +inf) is
+    the ungated filter with records; consistent = False is GatedLiteralSlam itself"""
+
+    def __init__(self, gate=None, consistent=True, **kw):
+        super().__init__(gate=gate if gate is not None else dict(gate_d2=math.inf), **kw)
+        self.consistent = consistent
+
+    def add_frame(self, obs):
+        """obs = [(id, z, Rdiag)] or [(id, valid, z, Rdiag)] in detection order"""
+        super().add_frame([(o[0], o[2], o[3]) for o in obs if o[1]] if obs and len(obs[0]) == 4 else obs)
+
+    def correct(self, ob, mu):
+        if not self.consistent:
+            return super().correct(ob, mu)
+        N = self.mu.size
+        i3 = 3 + 3 * ob["index"]
+        F = np.zeros((6, N)); F[:3, :3] = np.eye(3); F[3:, i3:i3 + 3] = np.eye(3)
+        x, y, th = mu[0], mu[1], mu[2]
+        s, c = math.sin(th), math.cos(th)
+        gdx, gdy = mu[i3] - x, mu[i3 + 1] - y
+        gdth = norm_angle(mu[i3 + 2] - th)
+        z = ob["z"].copy()
+        ze = z - np.array([gdx * c + gdy * s, -gdx * s + gdy * c, gdth])
+        ze[2] = norm_angle(ze[2])
+        Gx = np.array([[-c, -s, -gdx * s + gdy * c, c, s, 0], [s, -c, -gdx * c - gdy * s, -s, c, 0], [0, 0, -1, 0, 0, 1]], float) @ F
+        last = next((o for o in self.last_observed if o["id"] == ob["id"]), None)
+        if last is not None and np.linalg.norm(last["last"] - z) < 0.01:
+            return 2                                              # a no-op: neither attempted nor gated
+        n0 = mu.size                                              # landmarks appended in this frame were not in mu_0: they have not moved
+        d = self.mu.copy(); d[:n0] -= mu; d[n0:] = 0.0
+        e = ze - Gx @ d                                           # plain difference, no wrap
+        with np.errstate(all="ignore"):
+            Si = np.linalg.inv(Gx @ self.sigma @ Gx.T + ob["R"])
+            d2 = float(e @ Si @ e)
+            n_ze = float(np.sqrt((ze * ze).sum()))
+        rej = rejects(self.gate["gate_d2"], d2)
+        self.d2_seen.append(d2); self.norms_seen.append(n_ze)
+        note_correction(self.health, d2, n_ze, rej, ob["id"])
+        if rej:
+            return 3
+        ob["last"] = z
+        Kg = self.sigma @ Gx.T @ Si
+        self.mu = self.mu + Kg @ e
+        self.sigma = (np.eye(N) - Kg @ Gx) @ self.sigma
+        return 1
+
+
+class ConsistentPlanReference(PlanReference):
+    """PlanReference with ConsistentLiteral's correct behind its plan: frame() hands every correction the mean at the start of the
+    frame, which is mu_0.  No gate: the records are kept and not read"""
+
+    def __init__(self, mu, S, ids, max_landmarks, cap, last=(), consistent=True):
+        super().__init__(mu, S, ids, max_landmarks, cap, last)
+        plain, self.lit = self.lit, ConsistentLiteral(consistent=consistent)
+        self.lit.mu, self.lit.sigma = plain.mu, plain.sigma
+        self.lit.is_init, self.lit.last_time = plain.is_init, plain.last_time
+
+    def frame(self, obs, *a, **kw):
+        self.lit.health = new_health()
+        return super().frame(obs, *a, **kw)

@@ -9,12 +9,18 @@ about it, so that streams of different phase meet the landmarks in another order
 reference_run drives tests/plan_reference.PlanReference (LiteralSlam's own augment / correct: double, dense literal products) from
 the empty map; gated_reference_run does the same with tests/slam_gate_reference.GatedLiteralSlam.  long_double_tail restates the
 corrections behind the map build with ekf_reference.reference_step in long double: the distance between the two is the floor that
-any bound on the device's error is judged against.  Results are cached on their arguments: the cases of one stream share them."""
+any bound on the device's error is judged against.  Results are cached on their arguments: the cases of one stream share them.
+
+consistent_reference_run, consistent_gated_reference_run and consistent_long_double_tail are the same three with consistent
+innovations (tests/consistent_reference.py: ConsistentPlanReference, ConsistentLiteral, consistent_step), for
+tests/test_long_runs_consistent.py; with consistent = False the two runs are reference_run and gated_reference_run bit for bit.
+HONEST_R is the variance of the noise the sightings carry (NOISE squared): with it the gains are of order one."""
 import functools
 import math
 
 import numpy as np
 
+from consistent_reference import ConsistentLiteral, ConsistentPlanReference, consistent_step
 from ekf_reference import LD, predicted_pose, reference_step, rel_err, wrap_once
 from plan_reference import PlanReference
 from slam_gate_reference import GatedLiteralSlam, gated_reference_step
@@ -23,6 +29,7 @@ WL, WR, DT = -2.0, 2.3, 1 / 30.0
 RADIUS = 3.0
 NOISE = (2e-3, 2e-3, 1e-3)
 RDIAG = (0.05, 0.05, 0.01)
+HONEST_R = tuple(n * n for n in NOISE)               # (4e-6, 4e-6, 1e-6)
 SCHEDULE = (1, 7, 64, 33, 2, 50)                     # batch lengths of the calls, cycled; max_batch = 64
 MAX_BATCH = 64
 LAP = 160                                            # frames: 2 pi / 0.0398 = 157.8 rounded up
@@ -34,9 +41,11 @@ REPEAT_MARGIN = 0.05                                 # 5 x the "stationary" rule
 class Stream(tuple):
     """frames = ((wl, wr, dt), [(id, valid, z, Rdiag)] in detection order); hashed by the arguments that made it"""
 
-    def __new__(cls, frames, key, outliers):
+    def __new__(cls, frames, key, outliers, wraps=(), ids=None, world=None):
         self = super().__new__(cls, frames)
         self.key, self.outliers = key, outliers      # outliers: {frame: id of the displaced sighting}
+        self.wraps = tuple(wraps)                    # the frames whose predict takes the true heading across +-pi
+        self.ids, self.world = ids, world            # the true map: marker ids and (x, y, theta), in landmark order
         return self
 
     def __hash__(self):
@@ -60,15 +69,17 @@ def batches_of(frames, schedule=SCHEDULE):
 
 
 @functools.lru_cache(maxsize=None)
-def ring_stream(L, m, frames, seed, phase=0.0, outlier_every=0):
+def ring_stream(L, m, frames, seed, phase=0.0, outlier_every=0, R=RDIAG, start=0.0):
     """the stream of `frames` frames.  outlier_every = k > 0: from frame OUTLIER_FROM on, every k-th frame's first sighting (detection
-    order) has z[0] moved by OUTLIER_SHIFT; the random draws do not depend on it, so the stream is otherwise the one without outliers"""
+    order) has z[0] moved by OUTLIER_SHIFT; the random draws do not depend on it, so the stream is otherwise the one without outliers.
+    R: the Rdiag every sighting carries (the draws do not depend on it either).  start: the true heading before frame 0 (robots that
+    share one world, and so one map, start at different headings; a filter on such a stream starts at (0, 0, start))"""
     rng = np.random.RandomState(seed)
     ang = np.linspace(0, 2 * math.pi, L, endpoint=False) + phase
     world = np.stack([RADIUS * np.cos(ang), RADIUS * np.sin(ang), rng.uniform(-3, 3, L)], 1)
     ids = (37 * np.arange(L) + 5) % 1024
     assert len(set(ids.tolist())) == L
-    pose = np.zeros(3)
+    pose = np.array([0.0, 0.0, start])
     out, outliers, wraps, prev = [], {}, [], {}
     for f in range(frames):
         new = predicted_pose(pose, WL, WR, DT)
@@ -91,12 +102,12 @@ def ring_stream(L, m, frames, seed, phase=0.0, outlier_every=0):
                 d = float(np.linalg.norm(prev[lid] - z))
                 assert d > REPEAT_MARGIN, f"frame {f}: id {lid} is sighted {d} from its previous sighting (the stationary rule's 0.01)"
             now[lid] = z
-            obs.append((lid, 1, z, np.array(RDIAG)))
+            obs.append((lid, 1, z, np.array(R)))
         prev = now
         out.append(((WL, WR, DT), obs))
     for f0 in range(0, frames - LAP + 1, LAP):
         assert any(f0 <= w < f0 + LAP for w in wraps), f"the heading does not cross +-pi in frames {f0} .. {f0 + LAP - 1}"
-    return Stream(out, (L, m, frames, seed, phase, outlier_every), outliers)
+    return Stream(out, (L, m, frames, seed, phase, outlier_every, tuple(R), start), outliers, wraps, ids.astype(np.int32), world)
 
 
 def _exact_dt(lit):
@@ -108,7 +119,10 @@ def reference_run(stream, max_landmarks, cap, batches):
     """PlanReference from mu = 0(3), Sigma = 0(3 x 3), no ids.  Returns dict(states = [(mu, Sigma)], ids = [[id]], mask = [int],
     pops = [[(id, index, action)]] at the end of every batch (pops: of its last frame), stats = [[4 ints]] of every frame,
     complete = the frame after which the map holds every landmark)"""
-    ref = PlanReference(np.zeros(3), np.zeros((3, 3)), [], max_landmarks, cap)
+    return _plan_run(PlanReference(np.zeros(3), np.zeros((3, 3)), [], max_landmarks, cap), stream, batches)
+
+
+def _plan_run(ref, stream, batches):
     res = dict(states=[], ids=[], mask=[], pops=[], stats=[], complete=None)
     L = len({o[0] for _, obs in stream for o in obs})
     for first, count in batches:
@@ -132,6 +146,12 @@ def gated_reference_run(stream, batches, gate_d2):
     """GatedLiteralSlam from the empty map under the SLAM gate: reference_run's results (mask: none, the literal filter has no caps)
     plus health = the slot record of every frame, track = the track record at the end of every batch, rejected = {frame: [id]}"""
     lit = GatedLiteralSlam(gate=dict(gate_d2=gate_d2))
+    res = _gated_run(lit, stream, batches)
+    lit.assert_margins()
+    return res
+
+
+def _gated_run(lit, stream, batches):
     lit.add_encoder(0.0, 0.0, 0.0)                   # the arming sample
     lit.add_frame([])
     res = dict(states=[], ids=[], mask=[], pops=[], stats=[], health=[], track=[], rejected={}, complete=None)
@@ -151,7 +171,25 @@ def gated_reference_run(stream, batches, gate_d2):
         res["states"].append((lit.mu.copy(), lit.sigma.copy()))
         res["ids"].append(sorted(lit.id_map, key=lit.id_map.get)); res["mask"].append(0)
         res["pops"].append(list(lit.log)); res["track"].append(dict(lit.track))
-    lit.assert_margins()
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def consistent_reference_run(stream, max_landmarks, cap, batches, consistent=True):
+    """reference_run with consistent innovations (ConsistentPlanReference); consistent = False is reference_run bit for bit"""
+    return _plan_run(ConsistentPlanReference(np.zeros(3), np.zeros((3, 3)), [], max_landmarks, cap, consistent=consistent), stream, batches)
+
+
+@functools.lru_cache(maxsize=None)
+def consistent_gated_reference_run(stream, batches, gate_d2, consistent=True):
+    """gated_reference_run with consistent innovations (ConsistentLiteral; gate_d2 = +inf: the ungated filter with records), plus
+    d2 = every d2 it compared with the gate; consistent = False is gated_reference_run bit for bit (its margins are then not asserted:
+    that run is only what the consistent one is told apart from)"""
+    lit = ConsistentLiteral(gate=dict(gate_d2=gate_d2), consistent=consistent)
+    res = _gated_run(lit, stream, batches)
+    if consistent:
+        lit.assert_margins()
+    res["d2"] = list(lit.d2_seen)
     return res
 
 
@@ -179,6 +217,27 @@ def long_double_tail(stream, max_landmarks, cap, batches, gate_d2=None):
                 mu, S = reference_step(mu, S, wl, wr, dt, pops, dtype=LD)
             else:
                 mu, S, _ = gated_reference_step(mu, S, wl, wr, dt, pops, gate_d2, dtype=LD)
+        mu_r, S_r = ref["states"][k]
+        out[k] = (float(np.abs(mu_r - mu).max()), rel_err(S_r, S))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def consistent_long_double_tail(stream, max_landmarks, cap, batches, gate_d2=None):
+    """long_double_tail with consistent innovations: consistent_reference.consistent_step in long double, started from the consistent
+    literal state at the end of the first batch that holds the whole map.  Returns {batch: (max |dmu|, Sigma relative)}"""
+    ref = (consistent_reference_run(stream, max_landmarks, cap, batches) if gate_d2 is None else
+           consistent_gated_reference_run(stream, batches, gate_d2))
+    k0 = first_complete_batch(ref, batches)
+    index = {lid: k for k, lid in enumerate(ref["ids"][k0])}
+    mu, S = (a.astype(LD) for a in ref["states"][k0])
+    out = {}
+    for k in range(k0 + 1, len(batches)):
+        first, count = batches[k]
+        for f in range(first, first + count):
+            (wl, wr, dt), obs = stream[f]
+            pops = sorted((index[o[0]], o[2], o[3]) for o in obs)          # distinct mapped ids pop in ascending index
+            mu, S, _ = consistent_step(mu, S, wl, wr, dt, pops, math.inf if gate_d2 is None else gate_d2, dtype=LD)
         mu_r, S_r = ref["states"][k]
         out[k] = (float(np.abs(mu_r - mu).max()), rel_err(S_r, S))
     return out

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from aruco_slam_amd import capi, synth
-from consistent_reference import ConsistentLocalizer, ConsistentUmapLocalizer, consistent_step, joint_mean
+from consistent_reference import ConsistentLiteral, ConsistentLocalizer, ConsistentUmapLocalizer, consistent_step, joint_mean
 from ekf_reference import CHAIN_CAP, CHAIN_KERNELS, LD, ekf_kernels_run, observe, predicted_pose, random_state, rel_err
 from slam_gate_reference import DEFAULTS, OUTLIER, TRACK_ZERO, advance_track, assert_margins, check_slot_health, check_track
 from test_ekf_sizes import DT, ID_TABLE, WL, WR, landmark_ids, pick
@@ -740,42 +740,3 @@ def test_gpu_rendered_ring_slam_equals_the_reference_sequence():
     print(f"rendered ring: |dmu| {np.abs(mu_g - lit.mu).max():.3g}, Sigma {e_S:.3g}, {ids_g.size} landmarks")
     assert np.allclose(mu_g, lit.mu, rtol=1e-9, atol=1e-11) and e_S <= 1e-9
 
-
-def ConsistentLiteral():
-    """the literal transcription on ready observations (slam_gate_reference.GatedLiteralSlam at +inf) with e_i in place of ze_i"""
-    from oracle.ekf_literal import norm_angle
-    from slam_gate_reference import GatedLiteralSlam
-
-    class Lit(GatedLiteralSlam):
-        def add_frame(self, obs):
-            self.mu0 = self.mu.copy()
-            obs = [(o[0], o[2], o[3]) for o in obs if o[1]] if obs and len(obs[0]) == 4 else obs
-            super().add_frame(obs)
-
-        def correct(self, ob, mu):
-            N = self.mu.size
-            i3 = 3 + 3 * ob["index"]
-            F = np.zeros((6, N)); F[:3, :3] = np.eye(3); F[3:, i3:i3 + 3] = np.eye(3)
-            x, y, th = mu[0], mu[1], mu[2]
-            s, c = math.sin(th), math.cos(th)
-            gdx, gdy = mu[i3] - x, mu[i3 + 1] - y
-            gdth = norm_angle(mu[i3 + 2] - th)
-            z = ob["z"].copy()
-            ze = z - np.array([gdx * c + gdy * s, -gdx * s + gdy * c, gdth])
-            ze[2] = norm_angle(ze[2])
-            Gx = np.array([[-c, -s, -gdx * s + gdy * c, c, s, 0], [s, -c, -gdx * c - gdy * s, -s, c, 0], [0, 0, -1, 0, 0, 1]], float) @ F
-            last = next((o for o in self.last_observed if o["id"] == ob["id"]), None)
-            if last is not None and np.linalg.norm(last["last"] - z) < 0.01:
-                return 2
-            n0 = self.mu0.size                                       # landmarks appended in this frame were not in mu_0: they have not moved
-            d = self.mu.copy(); d[:n0] -= self.mu0; d[n0:] = 0.0
-            e = ze - Gx @ d
-            Si = np.linalg.inv(Gx @ self.sigma @ Gx.T + ob["R"])
-            ob["last"] = z
-            Kg = self.sigma @ Gx.T @ Si
-            self.mu = self.mu + Kg @ e
-            self.sigma = (np.eye(N) - Kg @ Gx) @ self.sigma
-            self.health["accepted"] += 1
-            return 1
-
-    return Lit(gate=dict(gate_d2=INF))
