@@ -1433,7 +1433,7 @@ constexpr int kWarpUnroll = 25;        // pixels of the warped marker image per 
 // k_identify is the production kernel.  k_identify_record is the same body that also writes every candidate's IdentRecord (test
 // instrumentation: aslam_debug_run_identify).  The switch is the preprocessor's, not a template parameter: as k_identify<false>
 // the unchanged body compiled to different gfx950 code (other register allocation), and the production kernel must stay what it
-// is (scripts/identify_disasm_check.py compares it with a parent tree's).
+// is (scripts/disasm_check.py BASE_CSRC NEW_CSRC detect.hip compares it with a parent tree's).
 #define ASLAM_IDENT_KERNEL k_identify
 #define ASLAM_IDENT_RECORD 0
 #include "detect_identify.h"

@@ -141,11 +141,11 @@ struct MapCov {
 };
 // localization steps of EKF slots [first, first + count) in one launch (ekf_localize.h): the map stays frozen, only the pose block
 // is corrected; predict_first = 0: the first slot's encoder sample only arms the filter (or came with aslam_add_encoder).
-// gate != nullptr: the gated kernel (k_loc_steps_gated, k_fleet_steps_gated) with those parameters; umap != nullptr: the
-// Schmidt-Kalman kernels (k_loc_steps_umap[_gated], k_fleet_steps_umap[_gated]) on that map
+// gate, umap and consistent choose the instantiation of k_loc_steps<G, M, C> / k_fleet_steps<G, M, C>.  gate != nullptr: the Gated
+// kernels with those parameters; umap != nullptr: the Schmidt-Kalman kernels (UncertainMap) on that map
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
                       const double* enc, int first, int count, int predict_first, const GateState* gate = nullptr, const MapCov* umap = nullptr,
-                      bool consistent = false);   // consistent: the RunningMean kernels (k_*_ci*)
+                      bool consistent = false);   // consistent: the RunningMean kernels
 void launch_umap_clear_cross(hipStream_t st, const EkfState& E, int L);   // the single filter's Sigma_xl := 0 (a seat of its pose)
 // fleet localization (ekf_fleet.h): one workgroup per robot of the work list (n_groups robots), each on its own filter in F
 constexpr int kFleetState = 12;        // doubles per robot: mu_x (3), then Sigma_xx row-major (9)

@@ -1549,19 +1549,20 @@ void launch_ekf_gather(hipStream_t st, const EkfState& E) {
     hipLaunchKernelGGL(k_ekf_gather<EkfSingle>, dim3((E.ld + 255) / 256, 32), dim3(256), 0, st, EkfSingle{E});
 }
 static SlamGate slam_gate_of(const SlamGateArg& a) { return SlamGate{a.g.gate_d2, a.verdicts}; }
-// a solve kernel's four instantiations on one state source: gate x innovation policy (consistent: RunningMean)
-#define ASLAM_LAUNCH_SOLVE(kernel, SrcT, src, grid, block)                                                                                          \
-    do {                                                                                                                                           \
-        if (consistent) {                                                                                                                          \
-            if (gate) hipLaunchKernelGGL((kernel<SrcT, SlamGate, RunningMean>), grid, block, 0, st, Solve<SrcT, SlamGate, RunningMean>{src, slam_gate_of(*gate), {}});   \
-            else hipLaunchKernelGGL((kernel<SrcT, NoSlamGate, RunningMean>), grid, block, 0, st, Solve<SrcT, NoSlamGate, RunningMean>{src, NoSlamGate{}, {}});           \
-        } else {                                                                                                                                   \
-            if (gate) hipLaunchKernelGGL((kernel<SrcT, SlamGate>), grid, block, 0, st, Solve<SrcT, SlamGate>{src, slam_gate_of(*gate)});             \
-            else hipLaunchKernelGGL((kernel<SrcT, NoSlamGate>), grid, block, 0, st, Solve<SrcT, NoSlamGate>{src, NoSlamGate{}});                     \
-        }                                                                                                                                          \
-    } while (0)
+// a solve kernel's four instantiations on one state source, gate x innovation policy (consistent: RunningMean), in the
+// style of with_loc_policies (ekf_localize.h): what a launch asks for -> f(G, C) with the two policy objects, filled in
+template <class F> static void with_solve_policies(const SlamGateArg* gate, bool consistent, F&& f) {
+    auto innovation = [&](auto g) { consistent ? f(g, RunningMean{}) : f(g, FrozenMean{}); };
+    gate ? innovation(slam_gate_of(*gate)) : innovation(NoSlamGate{});
+}
+template <class Src, class G, class C>
+static void launch_solve(void (*kernel)(Solve<Src, G, C>), hipStream_t st, dim3 grid, dim3 block, const Src& src, const G& g, const C& c) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, Solve<Src, G, C>{src, g, c});
+}
 void launch_ekf_small(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
-    ASLAM_LAUNCH_SOLVE(k_ekf_small, EkfSingle, EkfSingle{E}, dim3(1), dim3(SMT));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_small<EkfSingle, decltype(g), decltype(c)>, st, dim3(1), dim3(SMT), EkfSingle{E}, g, c);
+    });
 }
 void launch_ekf_gate_finish(hipStream_t st, const EkfState& E, const SlamGateArg& gate, int slot) {
     hipLaunchKernelGGL(k_ekf_gate_finish<EkfSingle>, dim3(1), dim3(kMarkerMax), 0, st, EkfSingle{E}, slam_gate_of(gate), gate.g, slot);
@@ -1571,7 +1572,9 @@ void launch_ekf_T(hipStream_t st, const EkfState& E) {
 }
 void launch_ekf_mid(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
     const int ncg = (E.ld + MIDT - 1) / MIDT;
-    ASLAM_LAUNCH_SOLVE(k_ekf_mid, EkfSingle, EkfSingle{E}, dim3(1 + ncg * 12), dim3(MIDT));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_mid<EkfSingle, decltype(g), decltype(c)>, st, dim3(1 + ncg * 12), dim3(MIDT), EkfSingle{E}, g, c);
+    });
 }
 void launch_ekf_apply(hipStream_t st, const EkfState& E) {
     const int t = (E.ld + 63) / 64;
@@ -1581,7 +1584,9 @@ int ekf_fast_max_updates() { return kFastM; }
 int ekf_mid_max_updates() { return kMidM; }
 void launch_ekf_mid64(hipStream_t st, const EkfState& E, const SlamGateArg* gate, bool consistent) {
     const int ncg = (E.ld + M64T - 1) / M64T;
-    ASLAM_LAUNCH_SOLVE(k_ekf_mid64, EkfSingle, EkfSingle{E}, dim3(1 + ncg * 16), dim3(M64T));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_mid64<EkfSingle, decltype(g), decltype(c)>, st, dim3(1 + ncg * 16), dim3(M64T), EkfSingle{E}, g, c);
+    });
 }
 // the narrowest tile whose workgroups all fit on the device at once (256 CUs x 4); N_max stands in for the current N
 static bool update_tile4(const EkfState& E) {
@@ -1663,7 +1668,9 @@ void launch_ekf_gather(hipStream_t st, const FleetRound& R) {
     hipLaunchKernelGGL(k_ekf_gather<EkfFleet>, dim3((R.F.base.ld + 255) / 256, 32, R.n), dim3(256), 0, st, fleet_source(R));
 }
 void launch_ekf_small(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
-    ASLAM_LAUNCH_SOLVE(k_ekf_small, EkfFleet, fleet_source(R), dim3(1, 1, R.n), dim3(SMT));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_small<EkfFleet, decltype(g), decltype(c)>, st, dim3(1, 1, R.n), dim3(SMT), fleet_source(R), g, c);
+    });
 }
 void launch_ekf_gate_finish(hipStream_t st, const FleetRound& R, const SlamGateArg& gate, int) {
     hipLaunchKernelGGL(k_ekf_gate_finish<EkfFleet>, dim3(1, 1, R.n), dim3(kMarkerMax), 0, st, fleet_source(R), slam_gate_of(gate), gate.g, 0);
@@ -1673,7 +1680,9 @@ void launch_ekf_T(hipStream_t st, const FleetRound& R) {
 }
 void launch_ekf_mid(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
     const int ncg = (R.F.base.ld + MIDT - 1) / MIDT;
-    ASLAM_LAUNCH_SOLVE(k_ekf_mid, EkfFleet, fleet_source(R), dim3(1 + ncg * 12, 1, R.n), dim3(MIDT));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_mid<EkfFleet, decltype(g), decltype(c)>, st, dim3(1 + ncg * 12, 1, R.n), dim3(MIDT), fleet_source(R), g, c);
+    });
 }
 void launch_ekf_apply(hipStream_t st, const FleetRound& R) {
     const int t = (R.F.base.ld + 63) / 64;
@@ -1681,7 +1690,9 @@ void launch_ekf_apply(hipStream_t st, const FleetRound& R) {
 }
 void launch_ekf_mid64(hipStream_t st, const FleetRound& R, const SlamGateArg* gate, bool consistent) {
     const int ncg = (R.F.base.ld + M64T - 1) / M64T;
-    ASLAM_LAUNCH_SOLVE(k_ekf_mid64, EkfFleet, fleet_source(R), dim3(1 + ncg * 16, 1, R.n), dim3(M64T));
+    with_solve_policies(gate, consistent, [&](auto g, auto c) {
+        launch_solve(k_ekf_mid64<EkfFleet, decltype(g), decltype(c)>, st, dim3(1 + ncg * 16, 1, R.n), dim3(M64T), fleet_source(R), g, c);
+    });
 }
 void launch_ekf_update_mfma(hipStream_t st, const FleetRound& R) {
     const EkfState& E = R.F.base;                  // the single filter's tile choice: the same grid per robot

@@ -2,9 +2,9 @@
 // one shared frozen map (the id table and the landmark rows of mu, as in localization, ekf_localize.h).  Included by ekf.hip
 // (both the gfx950 build and the CPU emulation see it).
 //
-// k_fleet_steps runs one 128-lane workgroup per robot present in a call: §11's per-slot body (loc_steps) over that robot's slots in
-// ascending order, on the robot's own filter.  Robots never interact, so the workgroups are independent.  The host builds the work
-// list below and keeps the armed flags.
+// k_fleet_steps<G, M, C> (the policies of ekf_localize.h) runs one 128-lane workgroup per robot present in a call: §11's per-slot
+// body (loc_steps) over that robot's slots in ascending order, on the robot's own filter.  Robots never interact, so the workgroups
+// are independent.  The host builds the work list below and keeps the armed flags.
 #pragma once
 #include "ekf_localize.h"
 
@@ -53,105 +53,22 @@ struct LocFleet {
     }
 };
 
+// one instantiation per combination of policies, as k_loc_steps (ekf_localize.h): every robot's workgroup gates its own corrections
+// and keeps its own records, carries its own Sigma_xl in dynamic LDS (§23), corrects from its own running mean (§32)
+template <class G, class M, class C>
 __global__ __launch_bounds__(kMarkerMax) void k_fleet_steps(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
                                                            const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                           const int* __restrict__ work, int n_groups) {
+                                                           const int* __restrict__ work, int n_groups, LocPolicy<G, M, C> p) {
     const int* h = work + 4 * blockIdx.x;            // wave-uniform: scalar loads
-    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc);
-}
-
-// the same with the innovation gate: every robot's workgroup gates its own corrections and keeps its own records
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                 const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                 const int* __restrict__ work, int n_groups, GateState g) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g});
-}
-
-// the same two on an uncertain map: every robot's workgroup carries its own Sigma_xl in dynamic LDS
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                const int* __restrict__ work, int n_groups, MapCov mc) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                      const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                      const int* __restrict__ work, int n_groups, GateState g, MapCov mc) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
-}
-
-// the same four with consistent innovations: a robot's workgroup is the single filter's RunningMean body
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_ci(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                              const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                              const int* __restrict__ work, int n_groups) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps<LocFleet, NoGate, FixedMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc);
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_ci_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                    const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                    const int* __restrict__ work, int n_groups, GateState g) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps<LocFleet, Gated, FixedMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_ci(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                   const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                   const int* __restrict__ work, int n_groups, MapCov mc) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps<LocFleet, NoGate, UncertainMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, NoGate{},
-                                                           UncertainMap{mc});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_fleet_steps_umap_ci_gated(EkfState E, FleetState F, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                         const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                         const int* __restrict__ work, int n_groups, GateState g, MapCov mc) {
-    const int* h = work + 4 * blockIdx.x;
-    loc_steps<LocFleet, Gated, UncertainMap, RunningMean>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, Gated{g},
-                                                          UncertainMap{mc});
+    loc_steps<LocFleet, G, M, C>(LocFleet{F, h[0], work + 4 * n_groups + h[2], h[3], h[1]}, E, sp, obs, n_markers, enc, G(p), M(p));
 }
 
 void launch_fleet_steps(hipStream_t st, const EkfState& E, const FleetState& F, const SlamParams& sp, const ObsRaw* obs,
                         const unsigned* n_markers, const double* enc, const int* work, int n_groups, const GateState* gate, const MapCov* umap,
                         bool consistent) {
-    if (consistent) {                // the RunningMean kernels, the same launches otherwise
-        if (umap) {
-            static bool allowed[2] = {false, false};
-            const size_t dyn = umap_lds_bytes(umap->L);
-            if (gate) {
-                umap_allow_lds(k_fleet_steps_umap_ci_gated, allowed[1]);
-                hipLaunchKernelGGL(k_fleet_steps_umap_ci_gated, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate, *umap);
-            } else {
-                umap_allow_lds(k_fleet_steps_umap_ci, allowed[0]);
-                hipLaunchKernelGGL(k_fleet_steps_umap_ci, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *umap);
-            }
-            return;
-        }
-        if (gate)
-            hipLaunchKernelGGL(k_fleet_steps_ci_gated, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate);
-        else
-            hipLaunchKernelGGL(k_fleet_steps_ci, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups);
-        return;
-    }
-    if (umap) {
-        static bool allowed[2] = {false, false};
-        const size_t dyn = umap_lds_bytes(umap->L);
-        if (gate) {
-            umap_allow_lds(k_fleet_steps_umap_gated, allowed[1]);
-            hipLaunchKernelGGL(k_fleet_steps_umap_gated, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate, *umap);
-        } else {
-            umap_allow_lds(k_fleet_steps_umap, allowed[0]);
-            hipLaunchKernelGGL(k_fleet_steps_umap, dim3(n_groups), dim3(kMarkerMax), dyn, st, E, F, sp, obs, n_markers, enc, work, n_groups, *umap);
-        }
-        return;
-    }
-    if (gate)
-        hipLaunchKernelGGL(k_fleet_steps_gated, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups, *gate);
-    else
-        hipLaunchKernelGGL(k_fleet_steps, dim3(n_groups), dim3(kMarkerMax), 0, st, E, F, sp, obs, n_markers, enc, work, n_groups);
+    with_loc_policies(gate, umap, consistent, [&](auto g, auto m, auto c) {
+        launch_steps_kernel<k_fleet_steps<decltype(g), decltype(m), decltype(c)>>(st, n_groups, g, m, c, E, F, sp, obs, n_markers, enc, work, n_groups);
+    });
 }
 
 } // namespace aslam

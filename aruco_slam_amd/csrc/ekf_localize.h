@@ -11,17 +11,19 @@
 //
 // The body is loc_steps<Src>: Src says which slots the workgroup steps through and where the filter it corrects lives.  LocSingle
 // is the context's one filter (k_loc_steps); a fleet's workgroup uses LocFleet, its robot's own filter (ekf_fleet.h).
+// k_loc_steps<G, M, C> and k_fleet_steps<G, M, C> are kernel templates on the three policies below, one instantiation per combination a
+// launch can ask for; with_loc_policies picks it and launch_steps_kernel launches it, for both.
 //
 // loc_steps<Src, G> takes a compile-time gate policy G (include/aruco_slam_hip.h).  NoGate, the default, is the
-// chain above and nothing else: every gated statement sits under `if constexpr (G::kOn)`.  Gated (k_loc_steps_gated,
-// k_fleet_steps_gated) adds on lane 0, per correction, d2 = ze^T S^-1 ze, the reference's logged test (aruco_slam.cpp:156), the
+// chain above and nothing else: every gated statement sits under `if constexpr (G::kOn)`.  Gated (k_loc_steps<Gated, ..>,
+// k_fleet_steps<Gated, ..>) adds on lane 0, per correction, d2 = ze^T S^-1 ze, the reference's logged test (aruco_slam.cpp:156), the
 // skip of a correction whose d2 exceeds a finite gate, the slot's health sums in pop order and the filter's track record, which
 // stays in registers across the slots of a launch; a rejected flag per popped observation lives in LDS, and after the chain all
 // lanes compact the last-observed list with two ballots so that it holds the accepted updates and the no-ops only.
 //
 // loc_steps<Src, G, M> takes a compile-time map policy M (include/aruco_slam_hip.h).  FixedMap, the default, is the
-// filter above: every new statement sits under `if constexpr (M::kOn)`.  UncertainMap (k_loc_steps_umap[_gated],
-// k_fleet_steps_umap[_gated]) is the Schmidt-Kalman filter on a map whose landmarks carry fixed covariance blocks C_i: the strip
+// filter above: every new statement sits under `if constexpr (M::kOn)`.  UncertainMap (k_loc_steps<.., UncertainMap, ..>,
+// k_fleet_steps<.., UncertainMap, ..>) is the Schmidt-Kalman filter on a map whose landmarks carry fixed covariance blocks C_i: the strip
 // X = [Sigma_xx | Sigma_xl] replaces P.  Sigma_xl (3 x 3L) lives in dynamic LDS for the whole launch (Src says where it is loaded
 // from and stored to), Sigma_xx stays in lane 0's registers.  The front half of the slot body is shared; per correction lane 0 forms
 // S, K and the decision from the six columns it needs (pose block and block i), updates those six itself and publishes K and the
@@ -30,7 +32,7 @@
 //
 // loc_steps<Src, G, M, C> takes a compile-time innovation policy C (include/aruco_slam_hip.h).  FrozenMean, the
 // default, is the reference's chain (quirk Q1): every correction adds K ze with ze formed at the frame's predicted mean.
-// RunningMean (k_loc_steps_ci[_gated], k_loc_steps_umap_ci[_gated], k_fleet_steps_*_ci*) corrects from the mean the previous
+// RunningMean (k_loc_steps<.., RunningMean>, k_fleet_steps<.., RunningMean>) corrects from the mean the previous
 // correction left: lane 0 forms e = ze - H (mu_x - sPose), a plain difference with no angle wrap, where H is the pose part of the
 // Jacobian (on an uncertain map the landmarks are not estimated), judges the correction by e and adds K e.  S, K, the covariance
 // update and ref_flagged (the reference's logged test on ze) are untouched.  Every new statement sits under `if constexpr (C::kOn)`.
@@ -537,54 +539,19 @@ __device__ __forceinline__ void loc_steps(const Src& src, const EkfState& E, con
     }
 }
 
+// What a step kernel takes behind its own arguments: its three policies as the bases of one struct, as Solve<Src, G, C> does for the
+// SLAM solves (ekf_slam_gate.h).  Empty bases take no room, so GateState and MapCov lie where two arguments of their own would.
+// The kernels hand loc_steps copies of the bases, G(p) and M(p): the payloads are then read at the kernel's top, as arguments of their
+// own are (with references into p the compiler orders the first scalar loads of the fleet's uncertain-map kernels differently).
+template <class G, class M, class C> struct LocPolicy : G, M, C {};
+
+// the single filter's kernel, one instantiation per combination of policies (DESIGN.md §35 lists them); on an uncertain map Sigma_xl
+// is in dynamic LDS, 24 * 3 L bytes
+template <class G, class M, class C>
 __global__ __launch_bounds__(kMarkerMax) void k_loc_steps(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
                                                          const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                         int first, int count, int predict_first) {
-    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc);
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                               const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                               int first, int count, int predict_first, GateState g) {
-    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g});
-}
-
-// the same two on an uncertain map: Sigma_xl in dynamic LDS, 24 * 3 L bytes
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                              const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                              int first, int count, int predict_first, MapCov mc) {
-    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                    const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                    int first, int count, int predict_first, GateState g, MapCov mc) {
-    loc_steps(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
-}
-
-// the same four with consistent innovations: every correction is formed at the mean the previous one left
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_ci(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                            const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                            int first, int count, int predict_first) {
-    loc_steps<LocSingle, NoGate, FixedMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc);
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_ci_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                  const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                  int first, int count, int predict_first, GateState g) {
-    loc_steps<LocSingle, Gated, FixedMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_ci(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                 const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                 int first, int count, int predict_first, MapCov mc) {
-    loc_steps<LocSingle, NoGate, UncertainMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, NoGate{}, UncertainMap{mc});
-}
-
-__global__ __launch_bounds__(kMarkerMax) void k_loc_steps_umap_ci_gated(EkfState E, SlamParams sp, const ObsRaw* __restrict__ obs,
-                                                                       const unsigned* __restrict__ n_markers, const double* __restrict__ enc,
-                                                                       int first, int count, int predict_first, GateState g, MapCov mc) {
-    loc_steps<LocSingle, Gated, UncertainMap, RunningMean>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, Gated{g}, UncertainMap{mc});
+                                                         int first, int count, int predict_first, LocPolicy<G, M, C> p) {
+    loc_steps<LocSingle, G, M, C>(LocSingle{E, first, count, predict_first}, E, sp, obs, n_markers, enc, G(p), M(p));
 }
 
 // Sigma_xl := 0 of the single filter (rows 0..2 and their mirror in columns 0..2): what a seat of its pose does on an uncertain map
@@ -602,51 +569,36 @@ void launch_umap_clear_cross(hipStream_t st, const EkfState& E, int L) {
     hipLaunchKernelGGL(k_umap_clear_cross, dim3((3 * L + 255) / 256), dim3(256), 0, st, E, L);
 }
 
-// dynamic LDS of an uncertain-map kernel: the strip's landmark columns; above 64 KB a kernel has to be told once
+// what a launch asks for -> the policies of its kernel instantiation: f(G, M, C) gets the three policy objects, filled in
+template <class F> void with_loc_policies(const GateState* gate, const MapCov* umap, bool consistent, F&& f) {
+    auto innovation = [&](auto g, auto m) { consistent ? f(g, m, RunningMean{}) : f(g, m, FrozenMean{}); };
+    auto map = [&](auto g) { umap ? innovation(g, UncertainMap{*umap}) : innovation(g, FixedMap{}); };
+    gate ? map(Gated{*gate}) : map(NoGate{});
+}
+
+// one launch of the step kernel Kernel (k_loc_steps<G, M, C> or k_fleet_steps<G, M, C>) with n_groups workgroups: a... are the kernel's
+// own arguments, the policies follow them.  Dynamic LDS of an uncertain-map kernel: the strip's landmark columns; above 64 KB a kernel
+// has to be told once, and Kernel being a template argument makes `allowed` one flag per kernel, not one per signature.
 inline size_t umap_lds_bytes(int L) { return sizeof(double) * 9 * (size_t)L; }
-template <class Kern> void umap_allow_lds(Kern kernel, bool& done) {
-    if (done) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)umap_lds_bytes(kIdTableSize));
-    done = true;
+template <auto Kernel, class G, class M, class C, class... A>
+void launch_steps_kernel(hipStream_t st, int n_groups, const G& g, const M& m, const C& c, const A&... a) {
+    size_t dyn = 0;
+    if constexpr (M::kOn) {
+        static bool allowed = false;
+        if (!allowed) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)umap_lds_bytes(kIdTableSize));
+            allowed = true;
+        }
+        dyn = umap_lds_bytes(m.m.L);
+    }
+    hipLaunchKernelGGL(Kernel, dim3(n_groups), dim3(kMarkerMax), dyn, st, a..., LocPolicy<G, M, C>{g, m, c});
 }
 
 void launch_loc_steps(hipStream_t st, const EkfState& E, const SlamParams& sp, const ObsRaw* obs, const unsigned* n_markers,
                       const double* enc, int first, int count, int predict_first, const GateState* gate, const MapCov* umap, bool consistent) {
-    if (consistent) {                // the RunningMean kernels, the same launches otherwise
-        if (umap) {
-            static bool allowed[2] = {false, false};
-            const size_t dyn = umap_lds_bytes(umap->L);
-            if (gate) {
-                umap_allow_lds(k_loc_steps_umap_ci_gated, allowed[1]);
-                hipLaunchKernelGGL(k_loc_steps_umap_ci_gated, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate, *umap);
-            } else {
-                umap_allow_lds(k_loc_steps_umap_ci, allowed[0]);
-                hipLaunchKernelGGL(k_loc_steps_umap_ci, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *umap);
-            }
-            return;
-        }
-        if (gate)
-            hipLaunchKernelGGL(k_loc_steps_ci_gated, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate);
-        else
-            hipLaunchKernelGGL(k_loc_steps_ci, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
-        return;
-    }
-    if (umap) {
-        static bool allowed[2] = {false, false};
-        const size_t dyn = umap_lds_bytes(umap->L);
-        if (gate) {
-            umap_allow_lds(k_loc_steps_umap_gated, allowed[1]);
-            hipLaunchKernelGGL(k_loc_steps_umap_gated, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate, *umap);
-        } else {
-            umap_allow_lds(k_loc_steps_umap, allowed[0]);
-            hipLaunchKernelGGL(k_loc_steps_umap, dim3(1), dim3(kMarkerMax), dyn, st, E, sp, obs, n_markers, enc, first, count, predict_first, *umap);
-        }
-        return;
-    }
-    if (gate)
-        hipLaunchKernelGGL(k_loc_steps_gated, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first, *gate);
-    else
-        hipLaunchKernelGGL(k_loc_steps, dim3(1), dim3(kMarkerMax), 0, st, E, sp, obs, n_markers, enc, first, count, predict_first);
+    with_loc_policies(gate, umap, consistent, [&](auto g, auto m, auto c) {
+        launch_steps_kernel<k_loc_steps<decltype(g), decltype(m), decltype(c)>>(st, 1, g, m, c, E, sp, obs, n_markers, enc, first, count, predict_first);
+    });
 }
 
 } // namespace aslam

@@ -45,6 +45,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 
 namespace aslam {
 
@@ -1277,8 +1278,14 @@ __device__ __forceinline__ int win_ticket(unsigned long long* w, unsigned epoch)
         old = prev;
     }
 }
+// the step kernel's block: the chain role's waves (ceil(T / RW) workers, the prepare wave, in a one-launch window the logger wave), and
+// no fewer than the 256 threads the replay roles use
+constexpr int win_step_threads(int T, int RW, bool ONE) {
+    const int chain = ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64;
+    return chain > 256 ? chain : 256;
+}
 template <int T, int RW, bool ONE, class G = NoSlamGate, int LG = 0, int WP = 0, class IN = FrozenMean>
-__global__ __launch_bounds__(((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 > 256 ? ((T + RW - 1) / RW + (ONE ? 2 : 1)) * 64 : 256)
+__global__ __launch_bounds__(win_step_threads(T, RW, ONE))
 void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinReplay rq, const ObsRaw* __restrict__ obs, const double* __restrict__ enc) {
     const WinDesc& wd = wa;
     constexpr size_t kLds = sizeof(WinChainLds<T, ONE>) > sizeof(WinScanLds<T>) ? sizeof(WinChainLds<T, ONE>) : sizeof(WinScanLds<T>);
@@ -1638,6 +1645,12 @@ __global__ __launch_bounds__(256) void k_ekf_win_next(EkfState E, WinDesc pv, Wi
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
+// a window's run-time width (4, 8 or 12 blocks of 16 columns) as a compile-time one: f(std::integral_constant<int, T>{})
+template <class F> static void with_win_width(int T, F&& f) {
+    if (T == 4) f(std::integral_constant<int, 4>{});
+    else if (T == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 12>{});
+}
 // Every workgroup of a step launch asks for more than half of a CU's LDS (an unused dynamic allocation on top of the static one), so
 // that no second workgroup - a replay workgroup of the same launch, or anything else - is placed on the chain workgroup's CU and
 // competes with the prepare wave for issue slots and LDS bandwidth (ASLAM_WIN_SHARE_CU: off, for comparison).  The claim is no
@@ -1659,11 +1672,11 @@ template <int T, bool ONE, int LG = 0, int WP = 0, class IN = FrozenMean, class 
 }
 // wp: how the workers publish (win_chain_role's WP, bits of kWinWorkerPublishAll; 0 = the comparison path; negative: the width's default)
 #define ASLAM_WP_FORMS(F) F(0) F(1) F(2) F(3)
-template <int T, int NT> static void launch_win_pieces_wp(hipStream_t st, int nb, int wp, const EkfState& E, const SlamParams& sp, const WinArg<NoSlamGate>& wa, const WinReplay& rs,
+template <int T> static void launch_win_pieces_wp(hipStream_t st, int nb, int wp, const EkfState& E, const SlamParams& sp, const WinArg<NoSlamGate>& wa, const WinReplay& rs,
                                                           const WinReplay& rq, const ObsRaw* obs, const double* enc) {
     constexpr size_t lds = sizeof(WinChainLds<T, false>);
     switch (wp < 0 ? win_worker_publish_default(T) : wp & kWinWorkerPublishAll) {
-#define ASLAM_WP_LAUNCH(i) case i: launch_step_kernel<T, false, 0, i>(k_ekf_win_step<T, 2, false, NoSlamGate, 0, i>, st, nb, NT, lds, E, sp, wa, rs, rq, obs, enc); break;
+#define ASLAM_WP_LAUNCH(i) case i: launch_step_kernel<T, false, 0, i>(k_ekf_win_step<T, 2, false, NoSlamGate, 0, i>, st, nb, win_step_threads(T, 2, false), lds, E, sp, wa, rs, rq, obs, enc); break;
         ASLAM_WP_FORMS(ASLAM_WP_LAUNCH)
 #undef ASLAM_WP_LAUNCH
     }
@@ -1673,16 +1686,15 @@ void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp
     const WinReplay rs{s_piece, s_log0, s_nsteps, wd.wpar}, rq{q_piece, q_log0, q_nsteps, wd.wpar};
     const int nb = 1 + 16 * wd.T / WBW + wd.T;
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_win_pieces_wp<4, 256>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);
-    else if (wd.T == 8) launch_win_pieces_wp<8, 320>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);   // (3 + 3 + 2 rows on three workers: measured slower)
-    else launch_win_pieces_wp<12, 448>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc);
+    // (T = 8: 3 + 3 + 2 rows on three workers measured slower than RW = 2)
+    with_win_width(wd.T, [&](auto T) { launch_win_pieces_wp<T()>(st, nb, worker_publish, E, sp, wa, rs, rq, obs, enc); });
 }
 // lg: what the logger wave takes over from the prepare wave (win_chain_role's LG; 0 = the comparison path).  The workers' forms are
 // built beside the default logger only: with another lg the workers publish in their default form
-template <int T, int NT, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, int wp, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
+template <int T, class G, class W> static void launch_win_one_lg(hipStream_t st, int nb, int lg, int wp, const EkfState& E, const SlamParams& sp, const W& wa, const WinReplay& r,
                                                                           const ObsRaw* obs, const double* enc, bool consistent = false) {
     constexpr size_t lds = sizeof(WinChainLds<T, true>);
-    constexpr int WD = win_worker_publish_default(T);
+    constexpr int WD = win_worker_publish_default(T), NT = win_step_threads(T, 2, true);
     if constexpr (!G::kOn) {
         // the consistent window: built beside logger_parts = 3 and the width's default publication only
         if (consistent) {
@@ -1709,15 +1721,11 @@ void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp,
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
     if (gate) {                                                     // the gated instantiations: same grids, same blocks
         const WinArg<WinGate> wa{wd, WinGate{gate->g.gate_d2}};
-        if (wd.T == 4) launch_win_one_lg<4, 256, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
-        else if (wd.T == 8) launch_win_one_lg<8, 384, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
-        else launch_win_one_lg<12, 512, WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc);
+        with_win_width(wd.T, [&](auto T) { launch_win_one_lg<T(), WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc); });
         return;
     }
     const WinArg<NoSlamGate> wa{wd, {}};
-    if (wd.T == 4) launch_win_one_lg<4, 256, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
-    else if (wd.T == 8) launch_win_one_lg<8, 384, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
-    else launch_win_one_lg<12, 512, NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent);
+    with_win_width(wd.T, [&](auto T) { launch_win_one_lg<T(), NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent); });
 }
 void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
     hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
@@ -1727,9 +1735,7 @@ void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd)
 }
 static void launch_thin(hipStream_t st, const EkfState& E, const WinDesc& wd, int ncols) {
     const int SP = 16 * wd.T, nb = (ncols + 63) / 64;
-    if (wd.T == 4) hipLaunchKernelGGL(k_ekf_win_thin<4>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd);
-    else if (wd.T == 8) hipLaunchKernelGGL(k_ekf_win_thin<8>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd);
-    else hipLaunchKernelGGL(k_ekf_win_thin<12>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd);
+    with_win_width(wd.T, [&](auto T) { hipLaunchKernelGGL(k_ekf_win_thin<T()>, dim3(nb, 2 * SP / 64), dim3(256), 0, st, E, wd); });
 }
 void launch_ekf_win_next(hipStream_t st, const EkfState& E, const WinDesc& pv, const WinDesc& nx, bool split) {
     if (!split) {
