@@ -23,6 +23,9 @@
 #include <ucontext.h>
 #include <atomic>
 #include <mutex>
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/common_interface_defs.h>
+#endif
 
 #define __global__
 #define __device__
@@ -60,12 +63,23 @@ asm(".text\n"
 #endif
 
 namespace hipemu {
-#ifdef HIPEMU_FAST_SWITCH
+#if defined(HIPEMU_FAST_SWITCH) && defined(__SANITIZE_ADDRESS__)
+// AddressSanitizer keeps the bounds of the running stack per OS thread; a lane switch moves to another stack, so it is told
+// (without this its first no-return call on a lane stack prints "ASan is ignoring requested __asan_handle_no_return ... False
+// positive error reports may follow").  A lane's bounds are known when it is made; the scheduler's are learnt by the first lane it enters.
+struct LaneCtx { void* sp = nullptr; const void* bottom = nullptr; size_t size = 0; void* fake = nullptr; };
+inline void switch_ctx(LaneCtx* from, LaneCtx* to, bool from_ends = false) {
+    __sanitizer_start_switch_fiber(from_ends ? nullptr : &from->fake, to->bottom, to->size);
+    hipemu_switch(&from->sp, to->sp);
+    __sanitizer_finish_switch_fiber(from->fake, nullptr, nullptr);
+}
+#define HIPEMU_ASAN_FIBERS 1
+#elif defined(HIPEMU_FAST_SWITCH)
 struct LaneCtx { void* sp = nullptr; };
-inline void switch_ctx(LaneCtx* from, LaneCtx* to) { hipemu_switch(&from->sp, to->sp); }
+inline void switch_ctx(LaneCtx* from, LaneCtx* to, bool = false) { hipemu_switch(&from->sp, to->sp); }
 #else
 typedef ucontext_t LaneCtx;
-inline void switch_ctx(LaneCtx* from, LaneCtx* to) { swapcontext(from, to); }
+inline void switch_ctx(LaneCtx* from, LaneCtx* to, bool = false) { swapcontext(from, to); }
 #endif
 struct Lane {
     LaneCtx ctx;
@@ -96,6 +110,9 @@ struct BlockCtx {
 inline thread_local uint3_emu t_threadIdx, t_blockIdx;
 inline thread_local int t_lane, t_wave;
 inline thread_local BlockCtx* t_block;
+#ifdef HIPEMU_GUARD_DYN_LDS
+inline thread_local unsigned char* t_dyn_lds;  // the running workgroup's dynamic LDS: a heap block of exactly the launch's byte count
+#endif
 inline dim3 g_blockDim, g_gridDim;
 inline void yield_lane() {                     // back to the block scheduler, which resumes the next live lane
     BlockCtx* b = t_block;
@@ -271,7 +288,12 @@ namespace hipemu {
 constexpr size_t kStackBytes = 96 * 1024;
 template <class F> struct Tramp {
     static void entry(unsigned lo, unsigned hi) { run(reinterpret_cast<F*>(((unsigned long long)hi << 32) | lo)); }
-    static void entry_fast() { run(static_cast<F*>(t_block->body)); }
+    static void entry_fast() {
+#ifdef HIPEMU_ASAN_FIBERS
+        __sanitizer_finish_switch_fiber(nullptr, &t_block->sched.bottom, &t_block->sched.size);   // first time on this lane's stack
+#endif
+        run(static_cast<F*>(t_block->body));
+    }
     static void run(F* f) {
         (*f)();
         BlockCtx* b = t_block;
@@ -283,7 +305,7 @@ template <class F> struct Tramp {
         // a lane that returns may complete a pending barrier / collective of the others
         if (b->live > 0 && b->arrived >= b->live) { b->arrived = 0; b->gen++; }
         if (w.live > 0 && w.arrived >= w.live) { w.arrived = 0; w.gen++; }
-        switch_ctx(&me.ctx, &b->sched);
+        switch_ctx(&me.ctx, &b->sched, true);
         __builtin_unreachable();
     }
 };
@@ -298,8 +320,17 @@ struct StackPool {
         return p;
     }
 };
-template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by, unsigned bz, StackPool& stacks) {
+template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by, unsigned bz, StackPool& stacks, size_t shmem) {
     const int T = (int)(block.x * block.y * block.z);
+#ifdef HIPEMU_GUARD_DYN_LDS
+    // sanitized build: the dynamic LDS of a workgroup is a heap block of exactly the bytes the launch asked for, so that
+    // AddressSanitizer's redzones stand where the device's allocation ends (none requested: a null pointer)
+    void* dyn = nullptr;
+    if (shmem > 0) { if (posix_memalign(&dyn, 16, shmem) != 0) std::abort(); std::memset(dyn, 0xCD, shmem); }
+    t_dyn_lds = static_cast<unsigned char*>(dyn);
+#else
+    (void)shmem;
+#endif
     const int nw = (T + 63) / 64;
     BlockCtx ctx;
     ctx.lanes.resize(T);
@@ -326,6 +357,10 @@ template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by,
         top[-2] = reinterpret_cast<void*>(entry);
         for (int r = 3; r <= 8; r++) top[-r] = nullptr;
         l.ctx.sp = top - 8;
+#ifdef HIPEMU_ASAN_FIBERS
+        l.ctx.bottom = stack_base + (size_t)t * kStackBytes;
+        l.ctx.size = kStackBytes;
+#endif
 #else
         getcontext(&l.ctx);
         l.ctx.uc_stack.ss_sp = stack_base + (size_t)t * kStackBytes;
@@ -346,8 +381,12 @@ template <class F> void run_block(F& body, dim3 block, unsigned bx, unsigned by,
         }
     }
     t_block = nullptr;
+#ifdef HIPEMU_GUARD_DYN_LDS
+    t_dyn_lds = nullptr;
+    std::free(dyn);
+#endif
 }
-template <class F> void run_grid(const char*, dim3 grid, dim3 block, F&& body) {
+template <class F> void run_grid(const char*, dim3 grid, dim3 block, size_t shmem, F&& body) {
     g_blockDim = block;
     g_gridDim = grid;
     const unsigned long long nblocks = (unsigned long long)grid.x * grid.y * grid.z;
@@ -374,7 +413,7 @@ template <class F> void run_grid(const char*, dim3 grid, dim3 block, F&& body) {
             else if (order_mode == 2) i = perm[i];
             unsigned bx = (unsigned)(i % grid.x), by = (unsigned)((i / grid.x) % grid.y), bz = (unsigned)(i / ((unsigned long long)grid.x * grid.y));
             F local = body;                      // per-OS-thread copy of the launch closure
-            run_block(local, block, bx, by, bz, stacks);
+            run_block(local, block, bx, by, bz, stacks, shmem);
         }
     };
     unsigned nthreads = std::min<unsigned long long>(nblocks, std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
@@ -386,10 +425,14 @@ template <class F> void run_grid(const char*, dim3 grid, dim3 block, F&& body) {
 }
 
 #define ASLAM_LDS_BARRIER() __syncthreads()
+#ifdef HIPEMU_GUARD_DYN_LDS
+#define ASLAM_DYN_LDS(name) unsigned char* const name = hipemu::t_dyn_lds
+#else
 #define ASLAM_DYN_LDS(name) alignas(16) static thread_local unsigned char name[160 * 1024]
+#endif
 #define ASLAM_RCP_ESTIMATE(x) (1.0 / (x))
 #define ASLAM_WAVE_BCAST(v, src) __shfl(v, src)
 #define ASLAM_SPIN_UNTIL(cond) do { while (!(cond)) hipemu::yield_lane(); } while (0)
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    hipemu::run_grid(#kernel, dim3(grid), dim3(block), [&]() { kernel(__VA_ARGS__); })
+    hipemu::run_grid(#kernel, dim3(grid), dim3(block), (size_t)(shmem), [&]() { kernel(__VA_ARGS__); })
