@@ -233,6 +233,8 @@ _SIGS = {
     "aslam_get_consistent_innovations": (C.c_int, [C.c_void_p, _ip]),
     "aslam_set_consistent_windows": (C.c_int, [C.c_void_p, C.c_int]),
     "aslam_get_consistent_windows": (C.c_int, [C.c_void_p, _ip]),
+    "aslam_set_gated_consistent_windows": (C.c_int, [C.c_void_p, C.c_int]),
+    "aslam_get_gated_consistent_windows": (C.c_int, [C.c_void_p, _ip]),
     "aslam_get_slot_health": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aslam_get_track_health": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aslam_fleet_get_health": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p]),
@@ -916,6 +918,18 @@ class Context:
     def get_consistent_windows(self):
         on = C.c_int()
         self._ck(self.lib.aslam_get_consistent_windows(self.h, C.byref(on)))
+        return bool(on.value)
+
+    # -- the SLAM gate on the running innovation inside EKF windows ---------------------------------------------------
+    def set_gated_consistent_windows(self, on=True):
+        """with a SLAM gate, consistent innovations, set_slam_gate_windows and set_consistent_windows all on, plan EKF windows again:
+        the gated window chain judges and applies the running innovation.  Off by default; changes nothing in any other combination.
+        `on` goes to the library as it is: anything but 0 / 1 (False / True) is refused."""
+        self._ck(self.lib.aslam_set_gated_consistent_windows(self.h, int(on)))
+
+    def get_gated_consistent_windows(self):
+        on = C.c_int()
+        self._ck(self.lib.aslam_get_gated_consistent_windows(self.h, C.byref(on)))
         return bool(on.value)
 
     def get_slot_health(self, first, count):

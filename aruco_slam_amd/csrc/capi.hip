@@ -204,6 +204,10 @@ struct aslam_ctx {
     // consistent windows (aslam_set_consistent_windows): off unless set, kept across mode changes.  With it and
     // consistent_on both set, windows are planned again and their chain runs in its RunningMean instantiation (consistent_windows below)
     bool consistent_windows = false;
+    // gated consistent windows (aslam_set_gated_consistent_windows): off unless set, kept across mode changes.  With the SLAM
+    // gate, slam_gate_windows, consistent_on and consistent_windows all set, a staged batch keeps its windows and their chain runs gated in
+    // its RunningMean instantiation (gated_consistent_windows below).  Nothing to allocate: e and ||ze|| travel in the window's log header
+    bool gated_consistent_windows = false;
 
     // windowed EKF (ekf_window.hip): the observations of a batch come back to the host, which cuts the batch into runs of
     // frames that fuse the same landmarks; the batch's EKF work is enqueued one call later (or at the next synchronisation),
@@ -1154,9 +1158,14 @@ int read_mirror(aslam_ctx* c) {
 namespace {
 bool gated_windows(const aslam_ctx* c) { return c->slam_gate_on && c->slam_gate_windows && c->win_enabled && !c->win_pieces; }
 // consistent innovations inside windows: the one-launch window with the mean on the logger wave, ungated.  A gated
-// context keeps the per-frame path while consistent innovations are on (the gated consistent window is not built)
+// context keeps the per-frame path while consistent innovations are on, unless the gated consistent window is switched on too
 bool consistent_windows(const aslam_ctx* c) {
     return c->consistent_on && c->consistent_windows && c->win_enabled && !c->win_pieces && c->win_logger_parts == 3 && !c->slam_gate_on;
+}
+// the gate on the running innovation inside windows: the gated one-launch window in its RunningMean instantiation, one form
+// per width whatever the logger-parts and worker-publish knobs say.  Its own switch on top of the gate's and the consistent window's
+bool gated_consistent_windows(const aslam_ctx* c) {
+    return gated_windows(c) && c->consistent_on && c->consistent_windows && c->gated_consistent_windows;
 }
 
 hipEvent_t new_win_event(aslam_ctx* c) { return c->ev_win[c->ev_win_next++ & 63]; }
@@ -1193,13 +1202,13 @@ void enqueue_window_one(aslam_ctx* c, const WinOp& o, const WinDesc& wd) {
     cw.epoch = c->win_epoch;
     cw.nsteps = win_steps(c, o.frame, o.K);
     prof_begin(c, P_EKF_WIN_CHAIN, sa);
-    const bool gated = gated_windows(c);
+    const bool gated = gated_windows(c), gated_consistent = gated_consistent_windows(c);
     launch_ekf_win_one(sa, c->ekf, c->sp, cw, c->d_obs, c->d_enc, gated ? &c->slam_gate : nullptr, c->win_logger_parts, c->win_worker_publish,
-                       consistent_windows(c));
+                       consistent_windows(c) || gated_consistent);
     prof_end(c);
     if (gated) {                                                     // verdicts into records, counts, actions and the last-observed list
         prof_begin(c, P_EKF_WIN_GATE_FINISH, sa);
-        launch_ekf_win_gate_finish(sa, c->ekf, cw, c->slam_gate, c->d_obs);
+        launch_ekf_win_gate_finish(sa, c->ekf, cw, c->slam_gate, c->d_obs, gated_consistent);
         prof_end(c);
     }
 }
@@ -1347,8 +1356,8 @@ int schedule_ekf(aslam_ctx* c, int first, int count) {
         return ASLAM_OK;
     }
     // consistent innovations: the window chain's default form makes the reference's frozen-mean corrections, so no window
-    // is planned unless the consistent window is switched on and can run
-    if (!c->win_enabled || (c->consistent_on && !consistent_windows(c)) || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
+    // is planned unless the consistent window (gated: §37) is switched on and can run
+    if (!c->win_enabled || (c->consistent_on && !consistent_windows(c) && !gated_consistent_windows(c)) || (c->slam_gate_on && !gated_windows(c))) {  // every frame on the per-frame chain, enqueued at once
         r = finalize_pending(c);
         if (r) return r;
         // the SLAM gate: the window planner runs the "stationary" test on the host from a mirror of the last-observed
@@ -3330,6 +3339,22 @@ int aslam_set_consistent_windows(aslam_ctx* c, int on) {
 int aslam_get_consistent_windows(aslam_ctx* c, int* on) {
     if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
     *on = c->consistent_windows ? 1 : 0;
+    return ASLAM_OK;
+}
+
+// The SLAM gate on the running innovation inside EKF windows: one switch per context, in any mode, kept across mode changes
+int aslam_set_gated_consistent_windows(aslam_ctx* c, int on) {
+    if (!c) return ASLAM_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, ASLAM_E_INVALID, "on: 0 or 1");
+    // a batch still pending was submitted under the setting in force so far: it is enqueued first, and everything enqueued finishes
+    if (int r = sync_streams(c)) return r;
+    c->gated_consistent_windows = on == 1;
+    return ASLAM_OK;
+}
+
+int aslam_get_gated_consistent_windows(aslam_ctx* c, int* on) {
+    if (!c || !on) return fail(c, ASLAM_E_INVALID, "null argument");
+    *on = c->gated_consistent_windows ? 1 : 0;
     return ASLAM_OK;
 }
 

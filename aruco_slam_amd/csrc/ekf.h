@@ -328,8 +328,8 @@ inline int ekf_win_tiles(int nS) { return nS <= 20 ? 4 : nS <= 41 ? 8 : 12; }   
 // (nsteps == 0: none); obs / enc: the context's per-slot arrays.  launch_ekf_win_one: the whole window wd (K frames, nsteps steps,
 // epoch set) in one launch, the three roles following each other through in-launch counters
 // gate != nullptr: the gated instantiation, to be followed on the same stream by launch_ekf_win_gate_finish
-// consistent: the RunningMean instantiation (ungated, beside logger_parts = 3 and the width's default worker_publish,
-// whatever the two arguments say)
+// consistent: the RunningMean instantiation, one form per width whatever logger_parts and worker_publish say: ungated
+// beside logger_parts = 3, gated beside logger_parts = 1, both with the width's default worker_publish
 // logger_parts: what the chain's logger wave takes over from its prepare wave (bit 0: the log header's S^-1, bit 1: mu_S; the
 // results are the same to the bit whatever it is, 0 is the comparison path)
 // worker_publish: how the chain's worker waves publish the landmark rows of the step after next (bit 0: packed rows written 16
@@ -342,7 +342,8 @@ constexpr int win_worker_publish_default(int T) { return T == 4 ? 3 : T == 8 ? 1
 void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
                         const SlamGateArg* gate = nullptr, int logger_parts = 3, int worker_publish = -1, bool consistent = false);
 // behind a gated window: slot records and accepted counts of its K frames, the track record, the last frame's actions and last-observed list
-void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs);
+// consistent: behind the gated consistent window, whose headers carry e and, apart, ||ze|| for ref_flagged
+void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs, bool consistent = false);
 void launch_ekf_win_step(hipStream_t st, const EkfState& E, const SlamParams& sp, const WinDesc& wd, const ObsRaw* obs, const double* enc,
                          int s_piece, int s_log0, int s_nsteps, int q_piece, int q_log0, int q_nsteps, int worker_publish = -1);
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd);               // Y_0 = rows S of Sigma, position table

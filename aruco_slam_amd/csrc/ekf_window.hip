@@ -93,7 +93,8 @@ template <int NC> __device__ __forceinline__ void win_vmcnt_lag() {
 __host__ __device__ inline int win_log_stride(int T) { return 3 * 16 * T + kWinHdr; }
 __host__ __device__ inline int win_tlog_stride(int T) { return 8 * 16 * T; }
 // header of a logged step (doubles after the three operand rows)
-enum { WH_TYPE = 0, WH_POS = 1, WH_SI = 2, WH_ZE = 11, WH_C = 14, WH_S = 15, WH_G02 = 16, WH_G12 = 17, WH_A = 18, WH_B = 19, WH_D2 = 20, WH_ACC = 21 };
+enum { WH_TYPE = 0, WH_POS = 1, WH_SI = 2, WH_ZE = 11, WH_C = 14, WH_S = 15, WH_G02 = 16, WH_G12 = 17, WH_A = 18, WH_B = 19, WH_D2 = 20, WH_ACC = 21,
+       WH_ZN = 22 };   // WH_ZN: the gated consistent window only (below): ||ze|| at the frozen mean, while WH_ZE carries e
 // Gated window (aslam_set_slam_gate_windows): the one-launch step kernel is a template on a gate policy, as the solve
 // kernels of the per-frame chains are (ekf_slam_gate.h).  NoSlamGate is the default: every gated statement sits under `if constexpr`
 // and the policy is an empty base of the kernel's window argument, so the ungated kernels keep their arguments and their code.
@@ -110,6 +111,9 @@ static_assert(sizeof(WinArg<NoSlamGate>) == sizeof(WinDesc), "the ungated window
 // two waves that carry a copy of the mean (logger: every step; prepare: a frame's last correction, at the next predict) form e with
 // this one function from the same six differences, so that both copies keep the same bits.  d: mu_{j-1} - mu_0 at columns 0, 1, 2 and
 // lrow .. lrow + 2; ze comes in and e goes out in e0, e1, e2.
+// Gated consistent window (aslam_set_gated_consistent_windows): RunningMean with WinGate, in the LG = 1 form, where the
+// prepare wave carries the mean itself (lane = column) and so forms e in the step it judges: d2 = e^T S^-1 e, the selected mean update
+// adds K e, and lane 0 leaves e (WH_ZE) and ||ze|| of the frozen-mean ze (WH_ZN, for ref_flagged) in the step's header.
 __device__ __forceinline__ void win_running_innovation(double cth, double sth, double g02, double g12, const double (&d)[6], double& e0, double& e1,
                                                        double& e2) {
     e0 = e0 - ((-cth * d[0] - sth * d[1] + g02 * d[2]) + (cth * d[3] + sth * d[4]));
@@ -304,13 +308,15 @@ template <bool GATED, class LDS> __device__ __forceinline__ double win_header_en
 //   bit 1  the step table's entry a phase ahead: sPos[j + 3] is read with phase j's B operand and kept in a register, so that no
 //          LDS round trip stands between the MFMAs and the publication's switch (the step tables never change inside a window).
 // The prepare wave's steps and the values it reads do not depend on WP, and no floating-point operation moves.
-// IN: the innovation policy (FrozenMean, or RunningMean: the consistent window of DESIGN.md §33, beside LG = 3 and the ungated form only).
+// IN: the innovation policy (FrozenMean, or RunningMean: the consistent window of DESIGN.md §33, ungated beside LG = 3, or the gated
+// consistent window of DESIGN.md §37, WinGate beside LG = 1).
 template <int T, int RW, bool ONE, class G, int LG, int WP, class IN = FrozenMean>
 __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const WinDesc& wd, const G& gate, const ObsRaw* __restrict__ obs,
                                const double* __restrict__ enc, unsigned char* smem) {
     static_assert(ONE || !G::kOn, "only the one-launch window is gated");
     static_assert(ONE || LG == 0, "the piece schedule has no logger wave");
-    static_assert(!IN::kOn || (ONE && LG == 3 && !G::kOn), "the consistent window: one launch, the mean on the logger wave, ungated");
+    static_assert(!IN::kOn || (ONE && ((LG == 3 && !G::kOn) || (LG == 1 && G::kOn))),
+                  "the consistent window: one launch; ungated with the mean on the logger wave, gated with the mean on the prepare wave");
     constexpr bool LSI = (LG & 1) != 0, LMU = (LG & 2) != 0;
     constexpr bool PK = (WP & 1) != 0, AHEAD = (WP & 2) != 0;
     constexpr int SP = 16 * T, SPP = SP + 16, NC = SP / 64;       // SPP: operand rows lk and lk + 1 fall on opposite halves of the bank row
@@ -603,7 +609,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
 #pragma unroll
                     for (int c = 0; c < NC; c++) st_wt(log + k * SP + lane + 64 * c, av[k][c]);
                 if (!corr) { lcth = hC; lsth = hS; }
-                if constexpr (IN::kOn) {
+                if constexpr (IN::kOn && LMU) {
                     // ---- e = ze - H (mu_{j-1} - mu_0): six columns of this wave's own mean, by wave-uniform cross-lane reads ----
                     double dl[NC], d[6];
 #pragma unroll
@@ -616,7 +622,8 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 double hv = hb;
                 if (corr) {
                     if (hq >= 0) hv = hr;
-                    if constexpr (IN::kOn) hv = hq == 0 ? ze0 : hq == 1 ? ze1 : hq == 2 ? ze2 : hv;   // WH_ZE carries e: the replay's psi follows
+                    if constexpr (IN::kOn && LMU) hv = hq == 0 ? ze0 : hq == 1 ? ze1 : hq == 2 ? ze2 : hv;   // WH_ZE carries e: the replay's psi follows
+                    if constexpr (IN::kOn && !LMU) hv = hq >= 0 && hq < 3 ? hb : hv;   // ... formed by the prepare wave, which left it (and WH_ZN) in sHdr
                     if (!G::kOn && lane == WH_TYPE) hv = 1.0;
                     if (lane == WH_POS) hv = (double)pos;
                 }
@@ -878,6 +885,9 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                     if (lane == 0) mu[0] = np0;
                     if (lane == 1) mu[0] = np1;
                     if (lane == 2) mu[0] = th;
+                    // RunningMean on this wave: mu_0 of the frame is this pose and the landmark means in sMu, which stays as it is
+                    // until the next predict
+                    if constexpr (IN::kOn) { pn0 = np0; pn1 = np1; pth = th; }
                 }
                 // ---- the frame's records at the frozen mean (pose just predicted, landmarks as the previous frame left them) ----
                 if (lane < fm) {
@@ -917,7 +927,7 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
             } else {
                 // ---- correction a of the frame: c = H P, S = c H^T + R, Kt = S^-1 c ----
                 const int a = fa++;
-                const double ze0 = ASLAM_WAVE_BCAST(rze0, a), ze1 = ASLAM_WAVE_BCAST(rze1, a), ze2 = ASLAM_WAVE_BCAST(rze2, a);
+                double ze0 = ASLAM_WAVE_BCAST(rze0, a), ze1 = ASLAM_WAVE_BCAST(rze1, a), ze2 = ASLAM_WAVE_BCAST(rze2, a);   // (RunningMean on this wave: e from the verdict on)
                 const double R0 = ASLAM_WAVE_BCAST(rR0, a), R1 = ASLAM_WAVE_BCAST(rR1, a), R2 = ASLAM_WAVE_BCAST(rR2, a);
                 const double g02 = ASLAM_WAVE_BCAST(rg02, a), g12 = ASLAM_WAVE_BCAST(rg12, a);
                 // Gxm = [ -c -s g02  c  s 0 ;  s -c g12 -s  c 0 ;  0 0 -1  0 0 1 ]   (aruco_slam.cpp:140-143)
@@ -947,7 +957,18 @@ __device__ void win_chain_role(const EkfState& E, const SlamParams& sp, const Wi
                 // rounding to 1e-9 of max|P| within 150 frames.  inv3_fast of a symmetric S is symmetric bit for bit
                 Sm[3] = Sm[1]; Sm[6] = Sm[2]; Sm[7] = Sm[5];
                 inv3_fast(Sm, Si);
-                // gated: the verdict on this correction, from the S^-1 just formed and the frame's frozen-mean innovation (a NaN d2 rejects)
+                // RunningMean on this wave: from here on the correction is judged by and applied with e = ze - H (mu_{a-1} - mu_0),
+                // formed in place from this wave's own mean: six columns by wave-uniform cross-lane reads, less the frame's predicted pose
+                // and the landmark means its predict left in sMu.  A rejected step left mu alone, so the next e does not see it.  ||ze||,
+                // k_ekf_win_gate_finish's expression on the frozen-mean ze, is kept for the header
+                if constexpr (IN::kOn && !LMU) {
+                    const double d[6] = {ASLAM_WAVE_BCAST(mu[0], 0) - pn0, ASLAM_WAVE_BCAST(mu[0], 1) - pn1, ASLAM_WAVE_BCAST(mu[0], 2) - pth,
+                                         bcast_sel<NC>(mu, lrow) - sMu[lrow], bcast_sel<NC>(mu, lrow + 1) - sMu[lrow + 1], bcast_sel<NC>(mu, lrow + 2) - sMu[lrow + 2]};
+                    const double zn = sqrt(ze0 * ze0 + ze1 * ze1 + ze2 * ze2);
+                    win_running_innovation(cth, sth, g02, g12, d, ze0, ze1, ze2);
+                    if (lane == 0) { hdr[WH_ZE] = ze0; hdr[WH_ZE + 1] = ze1; hdr[WH_ZE + 2] = ze2; hdr[WH_ZN] = zn; }   // WH_ZE carries e: the replay's psi follows
+                }
+                // gated: the verdict on this correction, from the S^-1 just formed and the frame's frozen-mean innovation, or e (a NaN d2 rejects)
                 double d2 = 0.0;
                 bool rejected = false;
                 if constexpr (G::kOn) {
@@ -1312,8 +1333,11 @@ void k_ekf_win_step(EkfState E, SlamParams sp, WinArg<G> wa, WinReplay rs, WinRe
 // carries the filter's track record through the K frames in order (the integer streak rule), and wave 0 turns the rejected pops of
 // the window's LAST frame into action 3 and takes them out of the last-observed list the chain left behind (win_last_frame), so
 // that a device-planned frame that follows sees the exact list.  Fixed orders throughout, no floating-point atomics.
+// ZN (the gated consistent window): WH_ZE carries e there, which d2 and the verdict were formed from, and ref_flagged stays
+// the reference's test on the frozen-mean ze: its norm, formed by the prepare wave with the expression below, is read from WH_ZN.
 constexpr int kWinFinishThreads = 1024;
-__global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish(EkfState E, WinDesc wd, GateState gs, const ObsRaw* __restrict__ obs) {
+template <bool ZN>
+__device__ __forceinline__ void win_gate_finish(const EkfState& E, const WinDesc& wd, const GateState& gs, const ObsRaw* __restrict__ obs) {
     constexpr int NW = kWinFinishThreads / 64;
     __shared__ double sD2[NW][64];
     __shared__ int sKind[NW][64], sFlag[NW][64], sId[NW][64];   // kind 1: accepted, 2: rejected
@@ -1337,10 +1361,13 @@ __global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish(EkfSt
         const int m = min(fr.m, kWinCorrMax);
         if (lane < m) {
             const double* hd = hdr0 + (size_t)(sOff[k] + 1 + lane) * ls;
-            const double z0 = hd[WH_ZE], z1 = hd[WH_ZE + 1], z2 = hd[WH_ZE + 2];
             sD2[wave][lane] = hd[WH_D2];
             sKind[wave][lane] = hd[WH_ACC] == 0.0 ? 2 : 1;
-            sFlag[wave][lane] = sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 ? 1 : 0;   // the ||ze|| half of aruco_slam.cpp:156 (the chains never form K)
+            if constexpr (ZN) sFlag[wave][lane] = hd[WH_ZN] >= 1.0 ? 1 : 0;
+            else {
+                const double z0 = hd[WH_ZE], z1 = hd[WH_ZE + 1], z2 = hd[WH_ZE + 2];
+                sFlag[wave][lane] = sqrt(z0 * z0 + z1 * z1 + z2 * z2) >= 1.0 ? 1 : 0;   // the ||ze|| half of aruco_slam.cpp:156 (the chains never form K)
+            }
             sId[wave][lane] = obs[(size_t)slot * kMarkerMax + fr.cdet[lane]].id;
         }
         __builtin_amdgcn_wave_barrier();
@@ -1399,6 +1426,12 @@ __global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish(EkfSt
         if (keep) E.d_last[__popcll(bK & ((1ull << lane) - 1ull))] = lo;
         if (lane == 0) *E.d_nlast = __popcll(bK);
     }
+}
+__global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish(EkfState E, WinDesc wd, GateState gs, const ObsRaw* __restrict__ obs) {
+    win_gate_finish<false>(E, wd, gs, obs);
+}
+__global__ __launch_bounds__(kWinFinishThreads) void k_ekf_win_gate_finish_zn(EkfState E, WinDesc wd, GateState gs, const ObsRaw* __restrict__ obs) {
+    win_gate_finish<true>(E, wd, gs, obs);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1695,12 +1728,12 @@ template <int T, class G, class W> static void launch_win_one_lg(hipStream_t st,
                                                                           const ObsRaw* obs, const double* enc, bool consistent = false) {
     constexpr size_t lds = sizeof(WinChainLds<T, true>);
     constexpr int WD = win_worker_publish_default(T), NT = win_step_threads(T, 2, true);
-    if constexpr (!G::kOn) {
-        // the consistent window: built beside logger_parts = 3 and the width's default publication only
-        if (consistent) {
-            launch_step_kernel<T, true, 3, WD, RunningMean>(k_ekf_win_step<T, 2, true, G, 3, WD, RunningMean>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
-            return;
-        }
+    if (consistent) {
+        // the consistent window: one form per width, the width's default publication.  Ungated beside logger_parts = 3, the
+        // mean on the logger wave; gated beside logger_parts = 1, the mean on the prepare wave, which judges e
+        constexpr int LGC = G::kOn ? 1 : 3;
+        launch_step_kernel<T, true, LGC, WD, RunningMean>(k_ekf_win_step<T, 2, true, G, LGC, WD, RunningMean>, st, nb, NT, lds, E, sp, wa, r, r, obs, enc);
+        return;
     }
     if (lg == 3) {
         switch (wp < 0 ? WD : wp & kWinWorkerPublishAll) {
@@ -1721,14 +1754,15 @@ void launch_ekf_win_one(hipStream_t st, const EkfState& E, const SlamParams& sp,
     // (the chain role's waves: ceil(T / 2) workers, the prepare wave, the logger wave)
     if (gate) {                                                     // the gated instantiations: same grids, same blocks
         const WinArg<WinGate> wa{wd, WinGate{gate->g.gate_d2}};
-        with_win_width(wd.T, [&](auto T) { launch_win_one_lg<T(), WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc); });
+        with_win_width(wd.T, [&](auto T) { launch_win_one_lg<T(), WinGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent); });
         return;
     }
     const WinArg<NoSlamGate> wa{wd, {}};
     with_win_width(wd.T, [&](auto T) { launch_win_one_lg<T(), NoSlamGate>(st, nb, logger_parts, worker_publish, E, sp, wa, r, obs, enc, consistent); });
 }
-void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs) {
-    hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
+void launch_ekf_win_gate_finish(hipStream_t st, const EkfState& E, const WinDesc& wd, const SlamGateArg& gate, const ObsRaw* obs, bool consistent) {
+    if (consistent) hipLaunchKernelGGL(k_ekf_win_gate_finish_zn, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
+    else hipLaunchKernelGGL(k_ekf_win_gate_finish, dim3(1), dim3(kWinFinishThreads), 0, st, E, wd, gate.g, obs);
 }
 void launch_ekf_win_gather(hipStream_t st, const EkfState& E, const WinDesc& wd) {
     hipLaunchKernelGGL(k_ekf_win_gather, dim3((E.ld + 255) / 256, 16), dim3(256), 0, st, E, wd);       // y: rows of Y_0 in turn (one load in flight per thread otherwise)

@@ -853,7 +853,8 @@ int aslam_get_slot_obs_covariance(aslam_ctx* ctx, int slot, int max, int* n, asl
  * Dropped.  Relinearisation: H_i stays the Jacobian at mu_0, one meaning for every chain.  EKF windows: while the switch is on,
  * aslam_run_staged and the host-fed stream plan no windows, gated windows included, and every frame takes the per-frame chain
  * (aslam_get_plan_stats shows it); the window chain keeps the reference's frozen-mean corrections, unless
- * aslam_set_consistent_windows (the next section) is on as well.
+ * aslam_set_consistent_windows (the next section) is on as well.  With a SLAM gate set, windows come back only with
+ * aslam_set_gated_consistent_windows (the section after it) on top of both window switches.
  * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
  * pending batch and synchronises, as the other setters do. */
 int aslam_set_consistent_innovations(aslam_ctx* ctx, int on);
@@ -869,12 +870,39 @@ int aslam_get_consistent_innovations(aslam_ctx* ctx, int* on);
  * everything is as described above.
  * Where it runs.  SLAM and rig SLAM without a SLAM gate, in the one-launch window with the mean on the chain's logger wave (the
  * defaults; ASLAM_WIN_PIECE or ASLAM_WIN_LOGGER_PARTS other than 3 keep the per-frame chain).  A context with a SLAM gate keeps the
- * per-frame chain while consistent innovations are on, whatever aslam_set_slam_gate_windows says: the gated consistent window is
- * not built.  Localization, fleets and fleet SLAM have no windows and do not look at the switch.
+ * per-frame chain while consistent innovations are on, whatever aslam_set_slam_gate_windows says, unless the gated consistent
+ * window is switched on as well: aslam_set_gated_consistent_windows (the next section).  Localization, fleets and fleet SLAM have no
+ * windows and do not look at the switch.
  * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
  * pending batch and synchronises, as the other setters do. */
 int aslam_set_consistent_windows(aslam_ctx* ctx, int on);
 int aslam_get_consistent_windows(aslam_ctx* ctx, int* on);
+
+/* ---- the SLAM gate on the running innovation inside EKF windows (no reference counterpart) ------------------------------
+ * The robust filter is three switches together: an honest R (aslam_set_observation_covariance), consistent innovations and the SLAM
+ * gate.  With all three on, the two window switches above leave every frame on the per-frame chain.
+ * aslam_set_gated_consistent_windows(ctx, on), on = 0 or 1, lets aslam_run_staged, aslam_run_staged_rig and the host-fed stream plan
+ * EKF windows again, with the gated window's planner unchanged (a repeat of a sighting still unconfirmed closes the window; the tail
+ * of the batch takes the gated consistent per-frame chain, aslam_get_plan_stats entry [3]).
+ * Semantics.  The gated window's rules with the consistent window's innovation.  Correction i of a window frame, in pop order, with
+ * ze_i and H_i formed at the frame's predicted mean mu_0 as today and S_i from the live covariance:
+ *     e_i = ze_i - H_i (mu_{i-1} - mu_0)    d2 = e_i^T S_i^-1 e_i    rejected iff gate_d2 is finite and !(d2 <= gate_d2) (a NaN rejects)
+ * An accepted correction adds K_i e_i to the mean; a rejected one changes nothing, so mu_i = mu_{i-1} and the next e does not see
+ * it.  The records: nis_sum, d2_max, worst_id and the verdicts come from e_i; ref_flagged stays the reference's logged test
+ * ||ze_i|| >= 1 on the frozen-mean ze_i.  With gate_d2 = +inf the state is, bit for bit, the ungated consistent window's on the
+ * same plan.  Slot records, accepted counts, action 3 in the last frame's pop list, the last-observed list and the track record are
+ * the gated window's.
+ * Switch.  Off by default, settable in any mode, kept across aslam_localize_begin / _end and the fleet begins and ends.  It takes
+ * effect only when a SLAM gate is set and consistent innovations, aslam_set_slam_gate_windows and aslam_set_consistent_windows are all
+ * on, windows are enabled and the one-launch form is in use (no ASLAM_NO_WINDOWS, no ASLAM_WIN_PIECE).  In every other combination
+ * every launch, kernel and result is what it is with the switch off.  It allocates nothing.
+ * Where it runs.  SLAM and rig SLAM (EKF slots max_batch + step), in one form of the one-launch window per width, whatever
+ * ASLAM_WIN_LOGGER_PARTS and ASLAM_WIN_WORKER_PUBLISH say.  Localization, fleets and fleet SLAM have no windows and do not look at
+ * the switch.
+ * Errors.  ASLAM_E_INVALID: a null context or output, on outside {0, 1}.  A refused call changes nothing.  The setter first enqueues a
+ * pending batch and synchronises, as the other setters do. */
+int aslam_set_gated_consistent_windows(aslam_ctx* ctx, int on);
+int aslam_get_gated_consistent_windows(aslam_ctx* ctx, int* on);
 
 /* filter state (mu, sigma, landmark ids, armed flag) to / from a file; no counterpart in the reference (warm starts) */
 int aslam_save_state(aslam_ctx* ctx, const char* path);

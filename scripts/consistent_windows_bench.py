@@ -3,9 +3,11 @@
 fps: the headline workload (cfg2, 320 frames per step, one lap already mapped, 20 steps per leg, one process), the legs of
 scripts/consistent_bench.py --only fps with the consistent window between them:
     frozen windows | consistent per-frame | consistent windows | frozen windows again
-first without a SLAM gate, then the same four legs with the SLAM gate at its defaults and gated windows on.  The gated consistent window
-is not built (§33, Dropped), so the third gated leg shows the per-frame path again; its plan says so.  The consistent windowed rate is
-to be compared with the consistent per-frame rate of the same run, and the spread between the two frozen legs is the run's noise.
+first without a SLAM gate, then the same legs with the SLAM gate at its defaults and gated windows on.  In the gated half the
+consistent_windows leg documents the fallback (the gated consistent window has a switch of its own, so that leg shows the per-frame path
+again; its plan says so), and a fifth leg, consistent_gated_windows, follows it with aslam_set_gated_consistent_windows on (DESIGN.md
+§37).  A consistent windowed rate is to be compared with the consistent per-frame rate of the same run, and the spread between the two
+frozen legs is the run's noise: the gated consistent window passes if it beats consistent_per_frame by more than that spread.
 
 lap: §32's experiment (localization on the true map of the rendered ring of cfg2_sliding, observation covariance on, innovation gate
 at +inf, consistent innovations on) with the windows switch off and on.  Localization has no windows: the two rows must agree.
@@ -28,8 +30,8 @@ import bench  # noqa: E402
 import consistent_bench  # noqa: E402
 from aruco_slam_amd import capi, synth  # noqa: E402
 
-LEGS = (("frozen_windows", False, False), ("consistent_per_frame", True, False), ("consistent_windows", True, True),
-        ("frozen_windows_again", False, False))
+LEGS = (("frozen_windows", False, False, False), ("consistent_per_frame", True, False, False), ("consistent_windows", True, True, False),
+        ("consistent_gated_windows", True, True, True), ("frozen_windows_again", False, False, False))
 
 
 def fps(steps=20, warmup=3):
@@ -47,9 +49,12 @@ def fps(steps=20, warmup=3):
             ctx.set_slam_gate()
             ctx.set_slam_gate_windows(True)
         legs = {}
-        for name, consistent, windows in LEGS:
+        for name, consistent, windows, gated_consistent in LEGS:
+            if gated_consistent and not gated:
+                continue
             ctx.set_consistent_innovations(consistent)
             ctx.set_consistent_windows(windows)
+            ctx.set_gated_consistent_windows(gated_consistent)
             ctx.set_state(mu, S, ids)
             before = ctx.plan_stats()
             for k in range(warmup):
@@ -67,6 +72,13 @@ def fps(steps=20, warmup=3):
         legs["frozen_spread"] = round(abs(a - b), 1)
         legs["windows_over_per_frame"] = round(cw / pf, 3)
         legs["gap_to_frozen_windows"] = round(1.0 - cw / (0.5 * (a + b)), 4)
+        if gated:
+            gc = legs["consistent_gated_windows"]
+            gc["over_consistent_per_frame"] = round(gc["frames_per_s"] / pf, 3)
+            gc["gap_to_frozen_windows"] = round(1.0 - gc["frames_per_s"] / (0.5 * (a + b)), 4)
+            gc["every_frame_in_windows"] = (gc["plan"]["frames_per_frame_chain"] == 0 and gc["plan"]["frames_device_planned"] == 0
+                                            and gc["plan"]["frames_in_windows"] == (steps + warmup) * lap)
+            gc["beats_per_frame_by_more_than_the_spread"] = gc["frames_per_s"] - pf > legs["frozen_spread"]
         res["gated" if gated else "ungated"] = legs
     ctx.close()
     return res

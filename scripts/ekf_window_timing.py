@@ -1,6 +1,8 @@
 """development aid: the EKF alone (observations injected, no detector) on three scenes - cfg2 panels, cfg2 sliding ring, cfg3 panels -
-per-kernel HIP-event times per frame and the planner's window statistics.  usage: python scripts/ekf_window_timing.py [--consistent]
-[cfg2 cfg2_sliding cfg3]; --consistent: consistent innovations on, inside the windows too"""
+per-kernel HIP-event times per frame and the planner's window statistics.  usage: python scripts/ekf_window_timing.py [--consistent | --gated-consistent]
+[cfg2 cfg2_sliding cfg3]; --consistent: consistent innovations on, inside the windows too; --gated-consistent: every
+scene twice with the SLAM gate at its defaults and gated windows on, first frozen-mean, then with consistent innovations, consistent
+windows and gated consistent windows on"""
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -19,15 +21,19 @@ def observations(world, fr, rng):
     return np.array(out).reshape(-1, 3)
 
 
-def run(name, laps=2):
+def run(name, mode="", laps=2):
     cfg = synth.CONFIGS[name]
     w = synth.make_world(cfg)
     lap = w.lap_length()
     ctx = capi.Context(max_rows=64, max_cols=64, max_batch=lap, max_landmarks=w.L + 8, max_updates_per_frame=24 if w.M <= 24 else 64)
     ctx.set_camera(synth.camera_matrix(64, 64, 50.0), np.zeros(5))
-    if CONSISTENT:
+    if mode.startswith("gated"):
+        ctx.set_slam_gate()
+        ctx.set_slam_gate_windows(True)
+    if mode in ("consistent", "gated consistent"):
         ctx.set_consistent_innovations(True)
         ctx.set_consistent_windows(True)
+        ctx.set_gated_consistent_windows(mode == "gated consistent")
     rng = np.random.RandomState(3)
     frames = [w.frame(i) for i in range(lap)]
     turn = w.frame(lap)
@@ -54,11 +60,12 @@ def run(name, laps=2):
     prof = ctx.profile_get(); ps = ctx.plan_stats()
     mu, S = ctx.get_state()
     err = np.abs(mu[3:].reshape(-1, 3)[:, :2] - (w.world[:, :2] - np.array(frames[0].true_pose[:2]))).max()
-    print(f"{name}: N={N} lap {lap} frames: {dt / lap * 1e6:.1f} us/frame EKF-only ({lap / dt:.0f} fps); per frame us:",
+    print(f"{name}{' ' + mode if mode else ''}: N={N} lap {lap} frames: {dt / lap * 1e6:.1f} us/frame EKF-only ({lap / dt:.0f} fps); per frame us:",
           {k: round(v[1] / lap * 1e3, 2) for k, v in prof.items() if v[0]}, ps, f"map err {err:.3f} m sym {np.abs(S - S.T).max():.1e}", flush=True)
     ctx.close()
 
 
-CONSISTENT = "--consistent" in sys.argv[1:]
+MODES = ["gated frozen", "gated consistent"] if "--gated-consistent" in sys.argv[1:] else ["consistent" if "--consistent" in sys.argv[1:] else ""]
 for nm in ([a for a in sys.argv[1:] if not a.startswith("--")] or ["cfg2", "cfg2_sliding", "cfg3"]):
-    run(nm)
+    for md in MODES:
+        run(nm, md)
